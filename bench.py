@@ -14,7 +14,19 @@ driver's torchrun it just runs as one rank.  The 10 000 blocks are split across 
 configs[3]; `--scaling weak` gives every rank its own 10 000), no data-path collective, and every step ends
 with the path's one exchange: an RCCL all-gather of the per-sample maxima.
 
-With one GPU and no flags the same JSON line also carries further legs, each with a timed region of about three seconds
+A plain run (no --full) does only what the headline needs: it generates the workload, sets up the resident batch, runs W warm-up
+steps, times K steps, writes what the last timed step computed if --dump-outputs DIR is given, and prints the line.  Everything else
+below -- the stream measurements, the CPU baselines, the extra legs, weak scaling and the native driver's multi-GPU mode -- runs only
+with --full (and the full record is written only with --full or --full-json).
+
+  --dump-outputs DIR   after the timed steps: maxima.npy (float32 [blocks, samples], per-sample maxima), fits.npy (float32 [blocks, 4]:
+                       evd_rc or status, mu, lambda, samples above the best native score) and hss.npy (float64 [segments, 11]: block,
+                       strand as its character code, frame, start, end, startSite, endSite, startGenomic, endGenomic, score, p-value) of
+                       the last timed step; with N > 1 rank 0 writes the gathered maxima (or fit rows) and its own blocks' fits and HSS.
+                       At most 62 MB in all: a larger array is cut to a fixed, seeded sample of its rows, whose indices go to
+                       <name>_rows.npy (float64).
+
+With one GPU and --full the same JSON line also carries further legs, each with a timed region of about three seconds
 (`--no-extra` leaves them out): `end_to_end` -- the native driver rnacode_amd/rnacode_hip as a fresh process on a 10 000-block
 MAF file, wall time from exec to the last output byte, trees fitted on the GPU (no sidecar): SURVEY.md section 8d's metric with I/O
 included (RNAcode.c:115-228) -- and `end_to_end_100k`, the same on a 100 000-block file (what the fixed costs amortise to);
@@ -27,10 +39,10 @@ every leg, and `cpu_baseline_all_cores` runs one reference process per usable CP
 
 With N > 1 the line proves where the ranks sat (`n_ranks_seen`, `devices`: the UUIDs gathered from every rank), records RCCL's channel
 cap (`config.rccl_env`), and says which order of the exchange ran the timed region (`config.exchange_ab`: overlapped with the next
-step or waited for -- both are timed during the warm-up unless --overlap / --no-overlap forces one); `native_driver_multi_gpu` is the
-native driver's own `--gpus N` mode on the whole input file, run by rank 0 while the others wait on the host.
+step or waited for -- both are timed during the warm-up unless --overlap / --no-overlap forces one); with --full, `native_driver_multi_gpu`
+is the native driver's own `--gpus N` mode on the whole input file, run by rank 0 while the others wait on the host.
 
-A step is one pass of the hot path over this rank's blocks.  Two measurements per run, K steps each:
+A step is one pass of the hot path over this rank's blocks.  Two measurements, K steps each (the second only with --full):
   * resident (`value`, the contract's definition: inputs in HBM when the timed region starts): MT19937
     streams -> native scoring -> null sampling -> EVD fit on a resident batch, then the all-gather;
   * stream (`stream.value`): from host rc_block arrays to fitted results on the host -- block tables prepared
@@ -596,6 +608,36 @@ def compact_line(out):
     return line
 
 
+DUMP_BUDGET = {"maxima": 40_000_000, "fits": 8_000_000, "hss": 14_000_000}   # bytes per array, row indices included: 62 MB in all
+DUMP_SEED = 20261015
+
+
+def hss_rows(batch):
+    """The HSS tables of every block of `batch` as float64 rows [block, strand code, frame, start, end, startSite, endSite,
+    startGenomic, endGenomic, score, p-value], in the library's order."""
+    import numpy as np
+    rows = [(b, ord(h["strand"]), h["frame"], h["start"], h["end"], h["startSite"], h["endSite"], h["startGenomic"], h["endGenomic"],
+             h["score"], h["pvalue"]) for b, hs in enumerate(batch.scoreAln_all()) for h in hs]
+    return np.array(rows, dtype=np.float64).reshape(-1, 11)
+
+
+def dump_outputs(d, maxima, fits, hss):
+    """--dump-outputs: DIR/<name>.npy for each array.  An array over its DUMP_BUDGET is cut to a fixed, seeded sample of its rows
+    (in order), whose indices go to DIR/<name>_rows.npy as float64, so that two builds on the same arguments compare the same rows."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in (("maxima", maxima), ("fits", fits), ("hss", hss)):
+        rows_path = os.path.join(d, name + "_rows.npy")
+        if a.nbytes > DUMP_BUDGET[name]:
+            k = DUMP_BUDGET[name] // (a.nbytes // len(a) + 8)
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(len(a), size=k, replace=False))
+            np.save(rows_path, rows.astype(np.float64))
+            a = a[rows]
+        elif os.path.exists(rows_path):   # left over from a larger run into the same directory
+            os.remove(rows_path)
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -604,7 +646,12 @@ def free_port():
 
 def parse_args():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--full-json", default=None, help="where the full record goes (default gpurun_out/bench_full.json); the printed line is the compact one")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement besides the headline: stream, CPU baselines, extra legs, weak scaling, native multi-GPU")
+    ap.add_argument("--full-json", default=None,
+                    help="where the full record goes (with --full, default bench_out/bench_full.json; without --full, only if given); "
+                         "the printed line is the compact one")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (see the module docstring)")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=5)
@@ -750,7 +797,7 @@ def main():
     # one GPU, the default workload: the legs that start child processes run first, before this process touches a GPU
     single = world == 1 and not multi
     default_workload = (args.blocks, args.cols, args.seqs, args.samples) == CONFIGS[args.config][:4]
-    extras = single and not args.no_extra and default_workload and args.config == "c3"
+    extras = args.full and single and not args.no_extra and default_workload and args.config == "c3"
     cpu = None
     cpu_all = None
     legs = {}
@@ -769,7 +816,7 @@ def main():
         t0 = time.perf_counter()
         blocks5 = [b.upper() for b in synth_blocks(nb5, seqs5, cols5, seed=1)]
         gen5 = time.perf_counter() - t0
-    if single and not args.no_cpu_baseline:
+    if args.full and single and not args.no_cpu_baseline:
         cpu = cpu_baseline(blocks, args.samples, args.seed_base)
         if extras and "blocks" in cpu:
             try:   # the cgroup quota, where there is one (what rc_host_cpus reports as well)
@@ -873,13 +920,15 @@ def main():
         if multi:
             exchange(batch.fits() if args.exchange == "fits" else None)
 
-    # stream mode: the library's schedule (rc_stream_plan: small first sub-batch, then doubling, whole rounds of the chip) unless told otherwise
-    if args.sub_batches:
+    # stream mode (--full): the library's schedule (rc_stream_plan: small first sub-batch, then doubling, whole rounds of the chip) unless told otherwise
+    stream = None if args.no_stream or not args.full else api.Stream(ctx, params, args.depth)
+    if stream is None:
+        sub_sizes = []
+    elif args.sub_batches:
         sb = max(1, -(-len(blocks) // args.sub_batches))
         sub_sizes = [min(sb, len(blocks) - lo) for lo in range(0, len(blocks), sb)]
     else:
         sub_sizes = api.stream_plan(ctx, params, len(blocks), 1)
-    stream = None if args.no_stream else api.Stream(ctx, params, args.depth)
 
     def stream_step():
         nonlocal step_no
@@ -1004,6 +1053,15 @@ def main():
     elapsed, tk, nlaunch = timed(resident_step, True)
     if args.dump_gathered and rank == 0:
         np.save(args.dump_gathered, gathered.cpu().numpy() if multi else batch.maxScores_all())
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: with N > 1 the gathered array, and this rank's own fits and HSS
+        if multi and args.exchange == "maxima":
+            maxima, fits = gathered.cpu().numpy(), batch.fits()
+        elif multi:
+            maxima, fits = batch.maxScores_all(), gathered.cpu().numpy()
+        else:
+            maxima, fits = batch.maxScores_all(), batch.fits()
+        dump_outputs(args.dump_outputs, maxima, fits, hss_rows(batch))
     prep_host_ms, prep_kernels_ms, up_bytes = batch.prep_timing()
     s_elapsed = None
     c_elapsed = None
@@ -1067,7 +1125,7 @@ def main():
     # N > 1 under strong scaling: also the weak-scaling figure (every rank its own --blocks blocks, generator seed 1 + rank),
     # as an extra key: the per-GPU work then equals the N = 1 run's, which is what separates kernel scaling from shard size
     weak = None
-    if world > 1 and args.scaling == "strong" and not args.no_weak:
+    if args.full and world > 1 and args.scaling == "strong" and not args.no_weak:
         wblocks = [b.upper() for b in synth_blocks(args.blocks, args.seqs, args.cols, seed=1 + rank)]
         wm = api.Marshalled(wblocks)
         wm.set_trees()
@@ -1104,7 +1162,7 @@ def main():
     # theirs runs on the GPUs meanwhile).  A fresh process per run, wall time to the last output byte, as the one-GPU end_to_end leg.
     native_multi = None
     native_hook = bool(os.environ.get("RC_BENCH_TEST_NATIVE_MULTI"))   # test hook: this leg on a box with one GPU (every context on device 0), any workload
-    if world > 1 and args.scaling == "strong" and not args.no_extra and ((coll_dev != "cpu" and default_workload) or native_hook):
+    if args.full and world > 1 and args.scaling == "strong" and not args.no_extra and ((coll_dev != "cpu" and default_workload) or native_hook):
         # the other ranks wait at a barrier of a gloo group: on the host, with nothing of theirs spinning on a GPU meanwhile
         try:
             host_group = dist.new_group(backend="gloo")
@@ -1285,15 +1343,17 @@ def main():
             out[k] = v
         # The driver keeps the last 2000 characters of this process's output: the ONE line printed is therefore a compact one -- the
         # contract's keys, roofline, cpu_baseline and the numbers of every extra leg under short names (KEY below) -- and the full
-        # record with its prose goes to a file (gpurun_out/bench_full.json, or --full-json): what profiles/<round>/bench_default_run.json is.
-        full_path = args.full_json or os.path.join(ROOT, "gpurun_out", "bench_full.json")
-        try:
-            if os.path.dirname(full_path):   # (a bare file name has none: makedirs('') raises)
-                os.makedirs(os.path.dirname(full_path), exist_ok=True)
-            with open(full_path, "w") as fh:
-                json.dump(out, fh)
-        except OSError as e:
-            print(f"bench.py: the full record could not be written to {full_path}: {e}", file=sys.stderr)
+        # record with its prose goes to a file (with --full bench_out/bench_full.json unless --full-json says where; a plain run writes it
+        # only to an explicit --full-json): what profiles/<round>/bench_default_run.json is.
+        full_path = args.full_json or (os.path.join(ROOT, "bench_out", "bench_full.json") if args.full else None)
+        if full_path:
+            try:
+                if os.path.dirname(full_path):   # (a bare file name has none: makedirs('') raises)
+                    os.makedirs(os.path.dirname(full_path), exist_ok=True)
+                with open(full_path, "w") as fh:
+                    json.dump(out, fh)
+            except OSError as e:
+                print(f"bench.py: the full record could not be written to {full_path}: {e}", file=sys.stderr)
         print(json.dumps(compact_line(out), separators=(",", ":")))
     if stream is not None:
         stream.close()

@@ -391,7 +391,7 @@ def _bench(tmp_path, gpus, extra=(), env_extra=None):
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     args = ["--blocks", "50", "--samples", "192"] if "--blocks" not in extra else []
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), *args, "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--sub-batches", "3", "--dump-gathered", dump, "--full-json", full, *extra],
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--sub-batches", "3", "--dump-gathered", dump, "--full-json", full, *extra],
                        env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     return _bench_record(r.stdout, full), np.load(dump)
@@ -494,7 +494,7 @@ def test_bench_survives_a_failing_collective_library(tmp_path):
         dump = str(tmp_path / ("fail_%s.npy" % where))
         r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                             "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--blocks", "40", "--samples", "128",
-                            "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--sub-batches", "2", "--dump-gathered", dump,
+                            "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--sub-batches", "2", "--dump-gathered", dump,
                             "--full-json", dump + ".json"],
                            env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-3000:]
@@ -514,6 +514,40 @@ def test_bench_refuses_a_world_that_does_not_match_gpus(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--blocks", "8", "--samples", "64", "--steps", "1",
                         "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr
+
+
+def test_plain_bench_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and measures nothing besides the headline; --dump-outputs writes the last
+    step's maxima, fits and HSS, equal to --dump-gathered's maxima and the same on every run."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from conftest import ROOT
+
+    def run(steps, tag):
+        d = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--blocks", "40", "--samples", "128",
+                            "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(d), "--dump-gathered", str(tmp_path / (tag + "_g.npy"))],
+                           capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        line = json.loads(lines[0])
+        assert line["steps"] == steps and line["ms_per_step"] > 0 and line["value"] > 0 and line["legs"] == {}
+        assert "cpu_baseline" not in line
+        return d
+
+    a, b = run(3, "a"), run(2, "b")
+    assert sorted(os.listdir(a)) == ["fits.npy", "hss.npy", "maxima.npy"]
+    out = {n: np.load(a / (n + ".npy")) for n in ("maxima", "fits", "hss")}
+    assert out["maxima"].dtype == np.float32 and out["maxima"].shape == (40, 128)
+    assert out["fits"].dtype == np.float32 and out["fits"].shape == (40, 4) and (out["fits"][:, 0] == 1).all()
+    assert out["hss"].dtype == np.float64 and out["hss"].shape[1] == 11 and len(out["hss"]) > 0
+    np.testing.assert_array_equal(out["maxima"], np.load(tmp_path / "a_g.npy"))
+    for n, x in out.items():
+        np.testing.assert_array_equal(x, np.load(b / (n + ".npy")))
 
 
 def test_bench_under_torchrun_goes_through_rccl(tmp_path):
@@ -540,7 +574,7 @@ def test_bench_under_torchrun_goes_through_rccl(tmp_path):
         dump = str(tmp_path / ("rccl_%s.npy" % overlapped))
         r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                             "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--blocks", "40", "--samples", "128",
-                            "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--sub-batches", "2", "--dump-gathered", dump,
+                            "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--sub-batches", "2", "--dump-gathered", dump,
                             "--full-json", dump + ".json", *extra],
                            env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-3000:]
