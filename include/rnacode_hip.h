@@ -52,9 +52,31 @@ typedef struct rc_params {
   float cutoff;         /* --cutoff, only used by stop-early (score.c:992) */
   int32_t stopEarly;    /* --stop-early */
   uint32_t seed_base;
+  /* Genetic code (an addition: the reference always translates with the standard code).  "" = the standard code (what
+   * zero-initialised params and rc_default_params give); otherwise exactly 64 letters of "ACDEFGHIKLMNPQRSTVWY*" ('*' = stop, at
+   * least one sense codon) in NCBI's TCAG order -- the order NCBI prints a table's "AAs = FFLL..." line in: codon index
+   * 16 i(b1) + 4 i(b2) + i(b3) with T=0 C=1 A=2 G=3 -- then a NUL.  rc_genetic_code() fills it in for NCBI's table ids.
+   * rc_batch_create / rc_stream_create reject anything else with RC_ERR_ARG.  Last member, so that positional initialisers
+   * of the older layout keep working. */
+  char genetic_code[65];
 } rc_params;
 
-void rc_default_params(rc_params *p); /* RNAcode.c:68-85 */
+/* Binary compatibility.  genetic_code made rc_params longer (40 -> 105 bytes).  A program compiled against the older header passes
+ * the shorter struct, and the library must neither write nor read past it: the entry points that take an rc_params exist twice.
+ * The plain names (rc_default_params, rc_batch_create, rc_stream_create) are the older layout's -- they touch the members before
+ * genetic_code only and score with the standard code -- and this header maps those names to the _v2 entry points, which take the
+ * whole struct.  Source code keeps calling rc_default_params / rc_batch_create / rc_stream_create; recompiling it picks the _v2
+ * symbols.  (rc_stream_plan reads sampleN only and has one entry point.) */
+#define rc_default_params rc_default_params_v2
+#define rc_batch_create rc_batch_create_v2
+#define rc_stream_create rc_stream_create_v2
+
+void rc_default_params_v2(rc_params *p); /* RNAcode.c:68-85; genetic_code "" */
+
+/* The 64 letters of NCBI translation table `ncbi_id` (1-6, 9-14, 16, 21-26, 29, 30, 33) in the form rc_params.genetic_code
+ * takes, NUL-terminated.  Tables with context-dependent stops (27, 28, 31), table 32 and ids NCBI does not define return
+ * RC_ERR_ARG.  Host only: works without a GPU. */
+int rc_genetic_code(int32_t ncbi_id, char out[65]);
 
 /* One alignment block: `struct aln *[]` (src/rnaz_utils.h:12-20) flattened, plus what
  * treeML/string2tree hand to the scorer (RNAcode.c:153-158): Newick text and kappa. */
@@ -132,7 +154,7 @@ int rc_ctx_fit_exp_mode(const rc_ctx *ctx);
  * (no or malformed tree, names that do not match, too many rows) -- those are left out like the
  * reference's "Skipping alignment" (RNAcode.c:153-156), rc_batch_block_error() has the reason, and
  * the other blocks of the batch are scored normally. */
-int rc_batch_create(rc_ctx *ctx, const rc_block *blocks, int32_t n_blocks, const rc_params *par, rc_batch **out);
+int rc_batch_create_v2(rc_ctx *ctx, const rc_block *blocks, int32_t n_blocks, const rc_params *par, rc_batch **out);
 void rc_batch_destroy(rc_batch *b);
 const char *rc_batch_block_error(const rc_batch *b, int32_t blk);   /* "" if the block was accepted */
 int rc_batch_size(const rc_batch *b);
@@ -164,7 +186,7 @@ int rc_batch_wait(rc_batch *b);
  * reused by a later submit: the steady state allocates nothing) or keep it and rc_batch_destroy it.
  * The rc_block arrays only need to live during rc_stream_submit.  Submitting to a full stream is an error. */
 typedef struct rc_stream rc_stream;
-int rc_stream_create(rc_ctx *ctx, const rc_params *par, int32_t depth, rc_stream **out);
+int rc_stream_create_v2(rc_ctx *ctx, const rc_params *par, int32_t depth, rc_stream **out);
 int rc_stream_submit(rc_stream *s, const rc_block *blocks, int32_t n_blocks);
 /* the same, with this batch's per-sample maxima ([n_blocks][sampleN] floats) written into a caller-owned device
  * buffer (see rc_batch_bind_maxima): e.g. consecutive slices of the tensor a rank hands to the RCCL all-gather */
@@ -240,6 +262,9 @@ int rc_batch_backtrack(const rc_batch *b, int32_t blk, int32_t strand, int32_t o
  * read): pep_out[16a+4b+c] = amino-acid index 0..19 of codon (a,b,c) in A,C,G,T order or -1 for a stop;
  * matrix_out[20p+q] = BLOSUM entry of amino acids p,q.  blosum is 62 or 90. */
 int rc_code_tables(int32_t blosum, int32_t pep_out[64], int32_t matrix_out[400]);
+/* The same for the genetic code and matrix of a run's parameters (par->genetic_code, par->blosum): what a renderer of that run
+ * translates with.  RC_ERR_ARG for a code rc_batch_create would reject.  Host only. */
+int rc_code_tables_for(const rc_params *par, int32_t pep_out[64], int32_t matrix_out[400]);
 
 /* Tree + kappa for one block, the inputs treeML() hands to the scorer (src/treeML.c:35-152 via the
  * bundled PhyML): BIONJ topology from pairwise ML distances, HKY85 maximum-likelihood branch lengths

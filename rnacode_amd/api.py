@@ -18,7 +18,7 @@ import ctypes as C
 import os
 import subprocess
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -38,7 +38,8 @@ RC_OK, RC_ERR_ARG, RC_ERR_DEVICE, RC_ERR_UNSUPPORTED, RC_ERR_SKIP = 0, -1, -2, -
 class RcParams(C.Structure):
     _fields_ = [("Delta", C.c_float), ("Omega", C.c_float), ("omega", C.c_float),
                 ("stopPenalty_0", C.c_float), ("stopPenalty_k", C.c_float), ("blosum", C.c_int32),
-                ("sampleN", C.c_int32), ("cutoff", C.c_float), ("stopEarly", C.c_int32), ("seed_base", C.c_uint32)]
+                ("sampleN", C.c_int32), ("cutoff", C.c_float), ("stopEarly", C.c_int32), ("seed_base", C.c_uint32),
+                ("genetic_code", C.c_char * 65)]   # "" = standard code, else 64 letters in NCBI's TCAG order
 
 
 class RcBlock(C.Structure):
@@ -101,7 +102,7 @@ def lib():
         l.rc_ctx_destroy.argtypes = [C.c_void_p]
         l.rc_ctx_trim.argtypes = [C.c_void_p]
         l.rc_ctx_trim.restype = None
-        l.rc_batch_create.argtypes = [C.c_void_p, C.POINTER(RcBlock), C.c_int32, C.POINTER(RcParams), C.POINTER(C.c_void_p)]
+        l.rc_batch_create_v2.argtypes = [C.c_void_p, C.POINTER(RcBlock), C.c_int32, C.POINTER(RcParams), C.POINTER(C.c_void_p)]
         l.rc_batch_destroy.argtypes = [C.c_void_p]
         l.rc_batch_run.argtypes = [C.c_void_p]
         l.rc_batch_run_async.argtypes = [C.c_void_p]
@@ -113,7 +114,7 @@ def lib():
         l.rc_ctx_set_host_threads.argtypes = [C.c_void_p, C.c_int32]
         l.rc_ctx_host_threads.argtypes = [C.c_void_p]
         l.rc_ctx_fit_exp_mode.argtypes = [C.c_void_p]
-        l.rc_stream_create.argtypes = [C.c_void_p, C.POINTER(RcParams), C.c_int32, C.POINTER(C.c_void_p)]
+        l.rc_stream_create_v2.argtypes = [C.c_void_p, C.POINTER(RcParams), C.c_int32, C.POINTER(C.c_void_p)]
         l.rc_stream_submit.argtypes = [C.c_void_p, C.POINTER(RcBlock), C.c_int32]
         l.rc_stream_submit_bound.argtypes = [C.c_void_p, C.POINTER(RcBlock), C.c_int32, C.c_void_p]
         l.rc_stream_next.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -150,6 +151,8 @@ def lib():
         l.rc_fit_trees_device.argtypes = [C.c_void_p, C.POINTER(RcBlock), C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_float),
                                           C.POINTER(C.c_double)]
         l.rc_code_tables.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        l.rc_code_tables_for.argtypes = [C.POINTER(RcParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        l.rc_genetic_code.argtypes = [C.c_int32, C.c_char_p]
         l.rc_set_stream_cache.argtypes = [C.c_int]
         l.rc_set_stream_cache.restype = None
         _lib = l
@@ -157,13 +160,16 @@ def lib():
 
 
 EXPORTED_SYMBOLS = [
-    "rc_default_params", "rc_last_error", "rc_device_count", "rc_ctx_create", "rc_ctx_destroy", "rc_ctx_trim", "rc_batch_create",
+    "rc_default_params_v2", "rc_last_error", "rc_device_count", "rc_ctx_create", "rc_ctx_destroy", "rc_ctx_trim", "rc_batch_create_v2",
     "rc_batch_destroy", "rc_batch_bind_maxima", "rc_batch_run", "rc_batch_run_async", "rc_batch_wait", "rc_batch_size", "rc_batch_block_error",
-    "rc_batch_prep_timing", "rc_host_cpus", "rc_ctx_set_host_threads", "rc_ctx_host_threads", "rc_ctx_fit_exp_mode", "rc_stream_create", "rc_stream_submit", "rc_stream_submit_bound",
+    "rc_batch_prep_timing", "rc_host_cpus", "rc_ctx_set_host_threads", "rc_ctx_host_threads", "rc_ctx_fit_exp_mode", "rc_stream_create_v2", "rc_stream_submit", "rc_stream_submit_bound",
     "rc_stream_next", "rc_stream_recycle", "rc_stream_pending", "rc_stream_plan", "rc_stream_destroy", "rc_set_stream_cache", "rc_batch_work", "rc_batch_timing", "rc_batch_null_kernel", "rc_batch_status",
     "rc_batch_models", "rc_batch_maxima", "rc_batch_maxima_all", "rc_batch_fit", "rc_batch_fit_all", "rc_batch_hss", "rc_batch_hss_all", "rc_batch_clamped",
     "rc_batch_native_S", "rc_batch_backtrack", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
+    "rc_code_tables_for", "rc_genetic_code",
 ]
+# the entry points of the older rc_params layout (include/rnacode_hip.h, "Binary compatibility"): exported, no longer declared
+COMPAT_SYMBOLS = ["rc_default_params", "rc_batch_create", "rc_stream_create"]
 
 
 def _check(code: int) -> int:
@@ -172,13 +178,41 @@ def _check(code: int) -> int:
     return code
 
 
+def genetic_code(ncbi_id: int) -> str:
+    """The 64 letters of NCBI translation table `ncbi_id` in NCBI's TCAG order (rc_genetic_code; host only)."""
+    buf = C.create_string_buffer(65)
+    _check(lib().rc_genetic_code(int(ncbi_id), buf))
+    return buf.value.decode()
+
+
+def _code_letters(code: Union[int, str, None]) -> str:
+    """rc_params.genetic_code for an NCBI table id, a string of 64 letters (or an id written as digits), or None / "" (standard)."""
+    if code is None:
+        return ""
+    if isinstance(code, (int, np.integer)) and not isinstance(code, bool):
+        return genetic_code(int(code))
+    if isinstance(code, str):
+        if code.strip().isdigit():
+            return genetic_code(int(code))
+        return code
+    raise TypeError(f"genetic_code must be an NCBI table id or 64 letters, not {type(code).__name__}")
+
+
 def default_params(**kw) -> RcParams:
+    """rc_default_params with the given fields replaced.  genetic_code takes an NCBI table id (2) or 64 letters in NCBI's TCAG order;
+    a code the library would reject raises RnacodeError here."""
     p = RcParams()
-    lib().rc_default_params(C.byref(p))
+    lib().rc_default_params_v2(C.byref(p))
     for k, v in kw.items():
         if not hasattr(p, k):
             raise KeyError(k)
+        if k == "genetic_code":
+            v = _code_letters(v).encode()
+            if len(v) > 64:
+                raise RnacodeError(RC_ERR_ARG, "genetic_code must be empty or exactly 64 letters (NCBI TCAG order)")
         setattr(p, k, v)
+    if p.genetic_code:   # the same check rc_batch_create makes, now rather than when the first batch is made
+        code_tables(p.blosum, p.genetic_code.decode())
     return p
 
 
@@ -187,12 +221,20 @@ def pvalue(score: float, mu: float, lam: float) -> float:
     return float(lib().rc_pvalue(score, mu, lam))
 
 
-def code_tables(blosum: int = 62) -> Tuple[np.ndarray, np.ndarray]:
-    """(pep[64], matrix[20][20]) of rc_code_tables: genetic code (-1 = stop) and BLOSUM62/90 as the scorer uses them."""
+def code_tables(blosum: int = 62, genetic_code: Union[int, str, None] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """(pep[64], matrix[20][20]) of rc_code_tables_for: genetic code (-1 = stop; codon index 16 n1 + 4 n2 + n3 with A=0 C=1 G=2 T=3)
+    and BLOSUM62/90 as the scorer uses them.  genetic_code: as default_params takes it; None = the standard code."""
     pep = np.zeros(64, dtype=np.int32)
     mat = np.zeros((20, 20), dtype=np.int32)
     ip = C.POINTER(C.c_int32)
-    _check(lib().rc_code_tables(blosum, pep.ctypes.data_as(ip), mat.ctypes.data_as(ip)))
+    p = RcParams()
+    lib().rc_default_params_v2(C.byref(p))
+    p.blosum = blosum
+    letters = _code_letters(genetic_code).encode()
+    if len(letters) > 64:
+        raise RnacodeError(RC_ERR_ARG, "genetic_code must be empty or exactly 64 letters (NCBI TCAG order)")
+    p.genetic_code = letters
+    _check(lib().rc_code_tables_for(C.byref(p), pep.ctypes.data_as(ip), mat.ctypes.data_as(ip)))
     return pep, mat
 
 
@@ -353,7 +395,7 @@ class Batch:
         self.blocks = m.blocks
         n = len(self.blocks)
         self._h = C.c_void_p()
-        _check(lib().rc_batch_create(ctx._h, m.arr, n, C.byref(params), C.byref(self._h)))
+        _check(lib().rc_batch_create_v2(ctx._h, m.arr, n, C.byref(params), C.byref(self._h)))
         self.n = n
 
     @classmethod
@@ -512,7 +554,7 @@ class Stream:
         self.ctx, self.params, self.depth = ctx, params, depth
         self._h = C.c_void_p()
         self._blocks = []   # block lists of the batches in flight, oldest first
-        _check(lib().rc_stream_create(ctx._h, C.byref(params), depth, C.byref(self._h)))
+        _check(lib().rc_stream_create_v2(ctx._h, C.byref(params), depth, C.byref(self._h)))
 
     def submit(self, m: Marshalled, lo: int = 0, hi: Optional[int] = None, maxima_ptr: int = 0):
         """Submit blocks [lo, hi) of a Marshalled whose trees are set (set_trees).  maxima_ptr: device address that

@@ -67,6 +67,9 @@ def main(argv=None) -> int:
                     help="alignment blocks per sub-batch of the GPU stream (default: 2048, or 512 per distinct row count if that is more)")
     ap.add_argument("--seed-base", type=int, default=42)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--genetic-code", metavar="ID|LETTERS",
+                    help="genetic code: an NCBI translation table id (e.g. 2, vertebrate mitochondrial) or its 64 letters in NCBI's TCAG order "
+                         "(FFLLSSSS...); default: the standard code")
     a = ap.parse_args(argv)
 
     if a.blosum not in (62, 90):
@@ -77,7 +80,13 @@ def main(argv=None) -> int:
         vals = [float(x) for x in a.pars.split(",")]
         for key, v in zip(("Delta", "Omega", "omega", "stopPenalty_0"), vals):
             kw[key] = v
-    params = api.default_params(**kw)
+    if a.genetic_code is not None:
+        kw["genetic_code"] = a.genetic_code
+    try:
+        params = api.default_params(**kw)
+    except api.RnacodeError as e:   # a bad --genetic-code: before any context exists
+        print(f"ERROR: --genetic-code: {str(e).split(': ', 1)[-1]}", file=sys.stderr)
+        return 1
 
     if a.file:
         blocks = read_alignment_file(a.file)
@@ -142,7 +151,8 @@ def main(argv=None) -> int:
             if a.eps:   # misc.c:461-474: hss-<counter>.eps for every listed HSS with p below the plot cutoff
                 def hook(counter, h, i=i, b=b, batch=batch):
                     os.makedirs(a.eps_dir, exist_ok=True)
-                    text = eps.color_aln(b, h, lambda strand, lo, hi: batch.backtrack(i, 0 if strand == "+" else 1, lo, hi), a.blosum)
+                    text = eps.color_aln(b, h, lambda strand, lo, hi: batch.backtrack(i, 0 if strand == "+" else 1, lo, hi), a.blosum,
+                                          params.genetic_code.decode())
                     with open(os.path.join(a.eps_dir, f"hss-{counter}.eps"), "w") as fh:
                         fh.write(text)
             report.print_results(out, fmt, all_hss[i], b.rows[0].name, st, cutoff=a.cutoff, best_only=a.best_only,

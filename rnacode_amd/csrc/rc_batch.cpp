@@ -25,10 +25,12 @@ void rc_batch_destroy(rc_batch *b) {
 
 extern "C" void rc_batch_destroy(rc_batch *b);
 
-int batch_prepare(rc_batch *b, const rc_block *blocks, int32_t n_blocks, const rc_params *par) {
+int batch_prepare(rc_batch *b, const rc_block *blocks, int32_t n_blocks, const rc_params *par, const TableSet *set) {
   rc_ctx *ctx = b->ctx;
   if (par->blosum != 62 && par->blosum != 90) return fail(RC_ERR_ARG, "blosum must be 62 or 90");
   if (par->sampleN < 1) return fail(RC_ERR_ARG, "sampleN must be >= 1");
+  if (!set) RC_TRY(table_set(ctx, *par, &set));   // (a stream hands in the set it resolved when it was created)
+  b->tables = set;
   const auto t0 = std::chrono::steady_clock::now();
   b->par = *par; b->n = n_blocks;
   b->state = rc_batch::EMPTY;
@@ -37,7 +39,7 @@ int batch_prepare(rc_batch *b, const rc_block *blocks, int32_t n_blocks, const r
   b->errs.clear(); b->okBlocks.clear(); b->classes.clear();
   b->maxL = 0; b->maxDraws = 0; b->hssCap = 8;
   b->allExact = !params_in_fast_range(*par);
-  const PairTable &pt = (par->blosum == 90) ? ctx->pt90 : ctx->pt62;
+  const PairTable &pt = set->pt;
 
   // capacity of the two blob parts from the shapes alone, then one pinned buffer
   size_t hostSum = 0, devSum = 0;
@@ -160,7 +162,7 @@ int batch_upload(rc_batch *b) {
   HIP_TRY(hipMemsetAsync(b->dflags.p, 0, nn * sizeof(uint32_t), ps));
   HIP_TRY(hipMemsetAsync(b->dcounters.p, 0, kCntTotal * sizeof(uint32_t), ps));
   if (!b->okBlocks.empty()) {
-    const TablePtrs tp = table_ptrs(c, b->par.blosum);
+    const TablePtrs &tp = b->tables->ptrs;
     PrepArgs pa{};
     uint8_t *blob = b->dblob.as<uint8_t>();
     pa.blob = blob;
@@ -170,6 +172,7 @@ int batch_upload(rc_batch *b) {
     pa.modelPrefix = reinterpret_cast<const int *>(blob + b->oPrefix);
     pa.nModels = b->nModels;
     pa.pep = tp.pep; pa.blosum = tp.blosum; pa.codeInfo = tp.info;
+    pa.standardCode = tp.standard; pa.prepOff = tp.prepOff; pa.prepAb = tp.prepAb;
     pa.flags = b->dflags.as<uint32_t>();
     pa.exactList = b->dexact.as<int>();
     pa.exactCount = b->dcounters.as<int>() + kCntExact;
@@ -264,7 +267,7 @@ int batch_run_async(rc_batch *b, bool streaming) {
   // kernels queued beside it either wait for its tail or, worse, get in first and keep part of its workgroups out for their whole run
   if (wide) nativeFirst = true;
   const int nativeMode = c->serialNative ? 0 : nativeFirst ? 1 : 0;
-  const RunEnv R{b, c, cs, n, sampleN, groups, Spad, n * 6, table_ptrs(c, b->par.blosum), blob,
+  const RunEnv R{b, c, cs, n, sampleN, groups, Spad, n * 6, b->tables->ptrs, blob,
                  reinterpret_cast<const DevBlock *>(blob + b->oDblocks), reinterpret_cast<const int *>(blob + b->oOk),
                  reinterpret_cast<const int *>(blob + b->oClass), streaming, nativeFirst, nativeMode, fat};
   HIP_TRY(hipStreamWaitEvent(cs, b->evPrep, 0));   // upload + expected-score tables

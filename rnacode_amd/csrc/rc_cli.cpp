@@ -8,7 +8,11 @@
 // (which additionally draws the EPS plots):
 //
 //   rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]
-//               [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B] [FILE]
+//               [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]
+//               [--genetic-code ID|LETTERS] [FILE]
+//
+// --genetic-code (not in the reference, which always uses the standard code): an NCBI table id or 64 letters in NCBI's TCAG order
+// (rc_params.genetic_code); checked while the options are parsed, before any context exists; every context of --gpus gets it.
 //
 // --gpus N (SURVEY.md section 8e inside ONE process, no collective library needed): N contexts on N host threads, each with
 // usable CPUs / N block-preparation threads.  Many blocks: the sub-batches of the stream are dealt to the GPUs in turn, every GPU
@@ -364,7 +368,9 @@ struct Listing {
 void usage() {
   std::fprintf(stderr, "usage: rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]\n"
                        "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]\n"
-                       "                   [--dump-blocks] [FILE]\n");
+                       "                   [--genetic-code ID|LETTERS] [--dump-blocks] [FILE]\n"
+                       "  --genetic-code ID|LETTERS  an NCBI translation table id (e.g. 2, vertebrate mitochondrial) or its 64 letters in\n"
+                       "                             NCBI's TCAG order (FFLLSSSS...); default: the standard code\n");
 }
 
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -725,6 +731,14 @@ int main(int argc, char **argv) {
     else if (o == "--devices") devicesArg = val();
     else if (o == "--sub-blocks") subBlocks = std::max(1, std::atoi(val()));
     else if (o == "--dump-blocks") dumpBlocks = true;
+    else if (o == "--genetic-code") {
+      const std::string v = val();
+      if (!v.empty() && v.find_first_not_of("0123456789") == std::string::npos) {
+        if (v.size() > 9) die("--genetic-code: unknown genetic code id " + v);
+        if (rc_genetic_code(std::atoi(v.c_str()), par.genetic_code) != RC_OK) die("--genetic-code: " + std::string(rc_last_error()));
+      } else if (v.size() > 64) die("--genetic-code: the letters must be exactly 64 (NCBI TCAG order)");
+      else std::snprintf(par.genetic_code, sizeof par.genetic_code, "%s", v.c_str());
+    }
     else if (o == "-h" || o == "--help") { usage(); return 0; }
     else if (o == "-e" || o == "--eps") list.eps = true;
     else if (o == "-i" || o == "--eps-cutoff") list.epsCutoff = static_cast<float>(std::atof(val()));
@@ -733,6 +747,10 @@ int main(int argc, char **argv) {
     else file = o;
   }
   if (par.blosum != 62 && par.blosum != 90) die("Currently only BLOSUM62 and BLOSUM90 are supported.");
+  {   // the genetic code is checked (host only) before any context exists
+    int32_t pep[64], matrix[400];
+    if (rc_code_tables_for(&par, pep, matrix) != RC_OK) die("--genetic-code: " + std::string(rc_last_error()));
+  }
   list.cutoff = par.cutoff;
   std::vector<int> devices;
   if (!devicesArg.empty()) {
@@ -828,7 +846,7 @@ int main(int argc, char **argv) {
   }
 
   if (!outfile.empty()) { list.out = std::fopen(outfile.c_str(), "w"); if (!list.out) die("Could not open " + outfile); }
-  if (list.eps && rc_code_tables(par.blosum, R.tables.pep, R.tables.matrix) != RC_OK) die(rc_last_error());
+  if (list.eps && rc_code_tables_for(&par, R.tables.pep, R.tables.matrix) != RC_OK) die(rc_last_error());
   tRead = now() - tRead;
   if (ctxThread.joinable()) ctxThread.join();
   for (int g = 0; g < gpus; g++) if (ctxRc[g] != RC_OK) die(ctxErr[g]);

@@ -1,5 +1,7 @@
 // rc_context.cpp -- contexts of the C-ABI (include/rnacode_hip.h): device, streams, constant tables, host threads.
 // No CPU implementation of the hot path lives in this library: without a HIP device rc_ctx_create fails with RC_ERR_DEVICE.
+#include <cstddef>
+
 #include "rc_runtime.h"
 
 extern "C" {
@@ -10,6 +12,7 @@ void rc_default_params(rc_params *p) {
   p->Delta = -10.0f; p->Omega = -4.0f; p->omega = -2.0f;
   p->stopPenalty_0 = -9999.0f; p->stopPenalty_k = -8.0f;
   p->blosum = 62; p->sampleN = 100; p->cutoff = 1.0f; p->stopEarly = 0; p->seed_base = 42;
+  std::memset(p->genetic_code, 0, sizeof p->genetic_code);   // the standard code
 }
 
 // A batch with several row-count classes puts its class launches on separate streams, and a stream of sub-batches keeps two batches in
@@ -19,6 +22,56 @@ void rc_default_params(rc_params *p) {
 }  // extern "C"
 
 void want_hw_queues() { (void)setenv("GPU_MAX_HW_QUEUES", "8", 0); }
+
+// A run's tables are found by (code, matrix) among the context's sets; a new pair is built and uploaded here, once (a synchronous copy
+// of ~16 KB: queued batches do not read it, they hold sets of their own).  The lists k_prep_models_few_rt walks are calculateBG's loops
+// (score.c:107-193) under this code: pairs with a stop codon, then the sense pairs of Hamming class 0, 1, 2, 3, each a outer, b inner.
+int table_set(rc_ctx *c, const rc_params &par, const TableSet **out) {
+  char code[64];
+  const char *why = nullptr;
+  if (!parse_genetic_code(par.genetic_code, code, &why)) return fail(RC_ERR_ARG, why);
+  if (par.blosum != 62 && par.blosum != 90) return fail(RC_ERR_ARG, "blosum must be 62 or 90");
+  std::lock_guard<std::mutex> lk(c->setMutex);
+  for (const auto &t : c->sets)
+    if (t->blosum == par.blosum && std::memcmp(t->code, code, 64) == 0) { *out = t.get(); return RC_OK; }
+  auto t = std::make_unique<TableSet>(code, par.blosum);
+  t->pt.build(t->ct);
+  const size_t oPair = 0, oBlosum = al256(4096), oInfo = oBlosum + al256(400 * sizeof(int)), oPep = oInfo + al256(64 * sizeof(CodeInfo)),
+               oOff = oPep + al256(64 * sizeof(int)), oAb = oOff + al256(6 * sizeof(int)), total = oAb + al256(4096 * sizeof(uint16_t));
+  std::vector<uint8_t> h(total, 0);
+  std::memcpy(h.data() + oPair, t->pt.pair, 4096);
+  int *bl = reinterpret_cast<int *>(h.data() + oBlosum);
+  for (int p = 0; p < 20; p++) for (int q = 0; q < 20; q++) bl[20 * p + q] = t->ct.blosum[p][q];
+  std::memcpy(h.data() + oInfo, t->pt.info, 64 * sizeof(CodeInfo));
+  int *pep = reinterpret_cast<int *>(h.data() + oPep);
+  for (int i = 0; i < 64; i++) pep[i] = t->ct.pep[i];
+  int *off = reinterpret_cast<int *>(h.data() + oOff);
+  uint16_t *ab = reinterpret_cast<uint16_t *>(h.data() + oAb);
+  int n = 0;
+  off[0] = 0;
+  for (int a = 0; a < 64; a++) for (int b = 0; b < 64; b++) if (pep[a] == -1 || pep[b] == -1) ab[n++] = static_cast<uint16_t>(a << 6 | b);
+  for (int hq = 0; hq < 4; hq++) {
+    off[1 + hq] = n;
+    for (int a = 0; a < 64; a++) for (int b = 0; b < 64; b++) {
+      if (pep[a] == -1 || pep[b] == -1) continue;
+      const int x = a ^ b;
+      if (((x & 48) != 0) + ((x & 12) != 0) + ((x & 3) != 0) == hq) ab[n++] = static_cast<uint16_t>(a << 6 | b);
+    }
+  }
+  off[5] = n;
+  t->d.retired = c->retired.get();
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(t->d.ensure(total));
+  HIP_TRY(hipMemcpy(t->d.p, h.data(), total, hipMemcpyHostToDevice));
+  const uint8_t *d = t->d.as<uint8_t>();
+  const CodeTables standard(par.blosum);
+  t->ptrs = TablePtrs{d + oPair, reinterpret_cast<const int *>(d + oPep), reinterpret_cast<const int *>(d + oBlosum),
+                      reinterpret_cast<const CodeInfo *>(d + oInfo), reinterpret_cast<const int *>(d + oOff),
+                      reinterpret_cast<const uint16_t *>(d + oAb), std::memcmp(standard.pep, t->ct.pep, sizeof standard.pep) == 0};
+  *out = t.get();
+  c->sets.push_back(std::move(t));
+  return RC_OK;
+}
 
 extern "C" {
 
@@ -101,7 +154,7 @@ int rc_ctx_create(int device, rc_ctx **out) {
     else if (v == "device" || v == "0") c->expMode = 0;
     else return fail(RC_ERR_ARG, "RC_FIT_EXP must be generic, fused or device");
   }
-  for (DevBuf *d : {&c->treeJobs, &c->treeIn, &c->treeWork, &c->treeRes, &c->d_tables, &c->d_cellStats}) d->retired = c->retired.get();
+  for (DevBuf *d : {&c->treeJobs, &c->treeIn, &c->treeWork, &c->treeRes, &c->d_cellStats}) d->retired = c->retired.get();
   for (PinBuf *h : {&c->treeInPin, &c->treeResPin}) h->retired = c->retired.get();
   c->genericScratchWords = std::max<size_t>(static_cast<size_t>(1) << 30, prop.totalGlobalMem / 12 / sizeof(uint32_t));
   c->togetherWords = std::max<size_t>(static_cast<size_t>(1) << 30, prop.totalGlobalMem / 36 / sizeof(uint32_t));   // 8 GB of 288: allocating more costs a short run more than it gains (tools/cli_mixed_sweep.sh)
@@ -144,24 +197,13 @@ int rc_ctx_create(int device, rc_ctx **out) {
   if (const char *e = std::getenv("RC_TILED_WIDE_MAX_L")) c->rule.tiledWideMaxL = std::max(0, std::atoi(e));
   if (const char *e = std::getenv("RC_TILED_ANY_L_MIN_ROWS")) c->rule.tiledAnyLMinRows = std::max(kTemplRows + 1, std::atoi(e));
   if (const char *e = std::getenv("RC_STOP_ROUNDS")) c->stopRounds = std::max(2, std::min(kMaxRounds, std::atoi(e)));
-  c->pt62.build(c->ct62);
-  c->pt90.build(c->ct90);
-  {   // constant tables: genetic code, then per matrix: pair table, BLOSUM, code infos
-    const size_t per = 4096 + 400 * sizeof(int) + 64 * sizeof(CodeInfo);
-    std::vector<uint8_t> h(64 * sizeof(int) + 2 * per);
-    int *pep = reinterpret_cast<int *>(h.data());
-    for (int i = 0; i < 64; i++) pep[i] = c->ct62.pep[i];
-    for (int w = 0; w < 2; w++) {
-      const PairTable &pt = w ? c->pt90 : c->pt62;
-      const CodeTables &ct = w ? c->ct90 : c->ct62;
-      uint8_t *m = h.data() + 64 * sizeof(int) + w * per;
-      std::memcpy(m, pt.pair, 4096);
-      int *bl = reinterpret_cast<int *>(m + 4096);
-      for (int p = 0; p < 20; p++) for (int q = 0; q < 20; q++) bl[20 * p + q] = ct.blosum[p][q];
-      std::memcpy(m + 4096 + 400 * sizeof(int), pt.info, 64 * sizeof(CodeInfo));
-    }
-    HIP_TRY(c->d_tables.ensure(h.size()));
-    HIP_TRY(hipMemcpy(c->d_tables.p, h.data(), h.size(), hipMemcpyHostToDevice));
+  {   // the standard code's tables for both matrices: every run without a genetic code of its own
+    rc_params std{};
+    std.blosum = 62;
+    const TableSet *unused = nullptr;
+    RC_TRY(table_set(c, std, &unused));
+    std.blosum = 90;
+    RC_TRY(table_set(c, std, &unused));
   }
   trace("ctx: tables", nullptr);
   c->tieThr = float_threshold_lt(0.0001);
@@ -179,6 +221,16 @@ int rc_ctx_create(int device, rc_ctx **out) {
   return RC_OK;
 }
 
+int rc_genetic_code(int32_t ncbi_id, char out[65]) {
+  if (!out) return fail(RC_ERR_ARG, "null out pointer");
+  const char *aas = ncbi_code(ncbi_id);
+  if (!aas) return fail(RC_ERR_ARG, "unknown genetic code id " + std::to_string(ncbi_id) +
+                                    " (built in: 1-6, 9-14, 16, 21-26, 29, 30, 33; 27, 28, 31 and 32 are not supported)");
+  std::memcpy(out, aas, 64);
+  out[64] = '\0';
+  return RC_OK;
+}
+
 int rc_ctx_set_host_threads(rc_ctx *c, int32_t threads) {
   if (!c || threads < 1) return fail(RC_ERR_ARG, "bad argument");
   if (c->inflight.load() != 0) return fail(RC_ERR_ARG, "batches are in flight");
@@ -190,5 +242,41 @@ int rc_ctx_set_host_threads(rc_ctx *c, int32_t threads) {
 int rc_ctx_host_threads(const rc_ctx *c) { return c ? c->hostThreads : 0; }
 
 int rc_ctx_fit_exp_mode(const rc_ctx *c) { return c ? c->expMode : RC_ERR_ARG; }
+
+}  // extern "C"
+
+// The entry points of the older rc_params layout (include/rnacode_hip.h, "Binary compatibility"): a program compiled against the header
+// of before genetic_code hands in 40 bytes.  These read and write exactly those and run the _v2 entry points with the standard code.
+#undef rc_default_params
+#undef rc_batch_create
+#undef rc_stream_create
+static constexpr size_t kParamsV1Bytes = offsetof(rc_params, genetic_code);
+static_assert(kParamsV1Bytes == 40, "the members of the older rc_params layout");
+static rc_params params_v1(const rc_params *old) {   // old: kParamsV1Bytes readable bytes
+  rc_params p;
+  std::memset(&p, 0, sizeof p);
+  std::memcpy(&p, old, kParamsV1Bytes);
+  return p;
+}
+
+extern "C" {
+
+void rc_default_params(rc_params *p) {
+  rc_params q;
+  rc_default_params_v2(&q);
+  std::memcpy(p, &q, kParamsV1Bytes);
+}
+
+int rc_batch_create(rc_ctx *ctx, const rc_block *blocks, int32_t n_blocks, const rc_params *par, rc_batch **out) {
+  if (!par) return rc_batch_create_v2(ctx, blocks, n_blocks, par, out);
+  const rc_params p = params_v1(par);
+  return rc_batch_create_v2(ctx, blocks, n_blocks, &p, out);
+}
+
+int rc_stream_create(rc_ctx *ctx, const rc_params *par, int32_t depth, rc_stream **out) {
+  if (!par) return rc_stream_create_v2(ctx, par, depth, out);
+  const rc_params p = params_v1(par);
+  return rc_stream_create_v2(ctx, &p, depth, out);
+}
 
 }  // extern "C"

@@ -5,7 +5,8 @@
 // sequence (extendRegion, src/misc.c:555-626) -- colored codon by codon from the backtracked state path (rc_batch_backtrack,
 // score.c:558-797).  Same layout code as rnacode_amd/eps.py (which tests/test_eps_cpu.py pins to EPS files the reference wrote);
 // tests/test_gpu_dropin.py compares the two drivers' files byte for byte.  Plain C++ on the public C-ABI only: the genetic code and
-// the BLOSUM matrix come from rc_code_tables.
+// the BLOSUM matrix come from rc_code_tables_for (the run's rc_params: its genetic code decides the translated letters and where
+// extend_region's walk to the next stop ends).
 #pragma once
 #include <cmath>
 #include <cstdarg>

@@ -2,6 +2,7 @@
 //
 //   k_mt_stream       MT19937 output streams, one wavefront per seed          (seqgen/twister.c:73-152)
 //   k_prep_models     calculateBG's two 4096-term accumulations per (block, strand, row)  (score.c:107-193)
+//                     (k_prep_models_few for few models; k_prep_models_rt / _few_rt for a genetic code other than the standard one)
 //   k_prep_lut        sigma value of every codon-pair code per (block, strand, k)         (score.c:406-425)
 //   k_prep_gaps       reverse-complement rows, codon windows and z of every reference position    (rnaz_utils.c:316-348, misc.c:186-289)
 //   k_null<NK>        simulate -> codon-pair codes -> 3-state DP -> HSS scan -> per-sample maximum,
@@ -241,6 +242,138 @@ __global__ __launch_bounds__(64) void k_prep_models_few(PrepArgs A) {
   }
 }
 
+// The two preparation kernels for a genetic code given at run time (rc_params.genetic_code, when it is not the standard code; the standard
+// code -- tables 1 and 11 -- keeps the kernels above, which have it compiled in).  Same terms, same chains, same order of additions.
+//
+// Many models: k_prep_models with kPepOf(b) replaced by pep[b].  Lane c holds pep[c]; v_readlane hands the wavefront pep[b] as a scalar,
+// so whether b is a stop and its amino acid stay wave-uniform (scalar branches), one Hamming class per wavefront as before; b stays
+// unrolled, which keeps the HKY85 rows r1..r3 in registers (indexed by b's bases at compile time).  No LDS, no scratch.
+__global__ __launch_bounds__(64) void k_prep_models_rt(PrepArgs A) {
+  __builtin_amdgcn_s_setprio(3);
+  const int lane = threadIdx.x;
+  const int pepLane = A.pep[lane];   // amino acid of codon `lane` (one wavefront of 64 lanes: every codon)
+  const int hq = blockIdx.x & 3;
+  int t = (blockIdx.x >> 2) * kWave + lane;
+  const bool active = t < A.nModels;
+  if (!active) t = A.nModels - 1;
+  int lo = 0, hi = A.nBlocks;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (A.modelPrefix[mid] <= t) lo = mid; else hi = mid;
+  }
+  const DevBlock *db = A.dblocks + A.blocks[lo];
+  ModelRec *m = reinterpret_cast<ModelRec *>(A.blob + db->off_models) + (t - A.modelPrefix[lo]);
+  const float *__restrict__ P = m->P;
+  const float f0 = m->freqs[0], f1 = m->freqs[1], f2 = m->freqs[2], f3 = m->freqs[3];
+  const int *__restrict__ blosum = A.blosum;
+  auto freq = [&](int x) { return x == 0 ? f0 : x == 1 ? f1 : x == 2 ? f2 : f3; };   // x is wave-uniform
+  float probStop = 0.0f;
+  for (int a = 0; a < 64; a++) {
+    const int a1 = a >> 4, a2 = (a >> 2) & 3, a3 = a & 3;
+    const bool stopA = __builtin_amdgcn_readlane(pepLane, a) == -1;
+    const float fa = freq(a1) * freq(a2) * freq(a3);
+    float r1[4], r2[4], r3[4];
+#pragma unroll
+    for (int x = 0; x < 4; x++) { r1[x] = P[a1 * 4 + x]; r2[x] = P[a2 * 4 + x]; r3[x] = P[a3 * 4 + x]; }
+    for_codon_b<0>([&](auto bc) {
+      constexpr int b = decltype(bc)::value;
+      const bool stopB = __builtin_amdgcn_readlane(pepLane, b) == -1;
+      if (stopA || stopB) {   // wave-uniform
+        float pAB = r1[b >> 4] * r2[(b >> 2) & 3] * r3[b & 3];
+        pAB = pAB * fa;
+        probStop = probStop + pAB;
+      }
+    });
+  }
+  float cq = 0.0f, sq = 0.0f;
+  const float keep = 1.0f - probStop;
+  for (int a = 0; a < 64; a++) {
+    const int pa = __builtin_amdgcn_readlane(pepLane, a);
+    if (pa == -1) continue;
+    const int a1 = a >> 4, a2 = (a >> 2) & 3, a3 = a & 3;
+    const float fa = freq(a1) * freq(a2) * freq(a3);
+    float r1[4], r2[4], r3[4];
+#pragma unroll
+    for (int x = 0; x < 4; x++) { r1[x] = P[a1 * 4 + x]; r2[x] = P[a2 * 4 + x]; r3[x] = P[a3 * 4 + x]; }
+    for_codon_b<0>([&](auto bc) {
+      constexpr int b = decltype(bc)::value;
+      const int pb = __builtin_amdgcn_readlane(pepLane, b);
+      const int x = a ^ b;
+      const int h = ((x & 48) != 0) + ((x & 12) != 0) + ((x & 3) != 0);
+      if (pb != -1 && h == hq) {   // wave-uniform
+        float pAB = r1[b >> 4] * r2[(b >> 2) & 3] * r3[b & 3];
+        pAB = pAB * fa;
+        pAB = pAB / keep;
+        const float sc = static_cast<float>(blosum[pa * 20 + pb]);
+        cq = cq + pAB;
+        sq = sq + sc * pAB;
+      }
+    });
+  }
+  if (active) {
+    m->scores[hq] = sq / cq;
+    m->probs[hq] = cq;
+  }
+}
+
+// Few models: k_prep_models_few with its lists built by the host for this code (rc_context.cpp, table_set) and read from global memory.
+__global__ __launch_bounds__(64) void k_prep_models_few_rt(PrepArgs A) {
+  __builtin_amdgcn_s_setprio(3);
+  const int lane = threadIdx.x;
+  const int hq = blockIdx.x & 3, t = blockIdx.x >> 2;   // the grid is 4 x nModels
+  int lo = 0, hi = A.nBlocks;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (A.modelPrefix[mid] <= t) lo = mid; else hi = mid;
+  }
+  const DevBlock *db = A.dblocks + A.blocks[lo];
+  ModelRec *m = reinterpret_cast<ModelRec *>(A.blob + db->off_models) + (t - A.modelPrefix[lo]);
+  const float *__restrict__ P = m->P;
+  const float f0 = m->freqs[0], f1 = m->freqs[1], f2 = m->freqs[2], f3 = m->freqs[3];
+  const int *__restrict__ off = A.prepOff;
+  const uint16_t *__restrict__ abList = A.prepAb;
+  auto freq = [&](int x) { return x == 0 ? f0 : x == 1 ? f1 : x == 2 ? f2 : f3; };
+  auto term = [&](int ab) {   // P(a -> b) x f(a), the products in calculateBG's order
+    const int a = ab >> 6, b = ab & 63;
+    const int a1 = a >> 4, a2 = (a >> 2) & 3, a3 = a & 3;
+    const float fa = freq(a1) * freq(a2) * freq(a3);
+    float pAB = P[a1 * 4 + (b >> 4)] * P[a2 * 4 + ((b >> 2) & 3)] * P[a3 * 4 + (b & 3)];
+    pAB = pAB * fa;
+    return pAB;
+  };
+  auto add_in_order = [&](float &acc, float v, int cnt) {   // acc += v of lane 0, 1, ..., cnt - 1
+    for (int l = 0; l < cnt; l++) acc = acc + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+  };
+  const int s0 = off[0], s1 = off[1], c0 = off[1 + hq], c1 = off[2 + hq];
+  float probStop = 0.0f;
+  for (int base = s0; base < s1; base += kWave) {
+    const int cnt = s1 - base < kWave ? s1 - base : kWave;
+    const float v = lane < cnt ? term(abList[base + lane]) : 0.0f;
+    add_in_order(probStop, v, cnt);
+  }
+  const float keep = 1.0f - probStop;
+  float cq = 0.0f, sq = 0.0f;
+  for (int base = c0; base < c1; base += kWave) {
+    const int cnt = c1 - base < kWave ? c1 - base : kWave;
+    float pAB = 0.0f, sp = 0.0f;
+    if (lane < cnt) {
+      const int ab = abList[base + lane];
+      pAB = term(ab);
+      pAB = pAB / keep;
+      const float sc = static_cast<float>(A.blosum[A.pep[ab >> 6] * 20 + A.pep[ab & 63]]);
+      sp = sc * pAB;
+    }
+    for (int l = 0; l < cnt; l++) {
+      cq = cq + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pAB), l));
+      sq = sq + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sp), l));
+    }
+  }
+  if (lane == 0) {
+    m->scores[hq] = sq / cq;
+    m->probs[hq] = cq;
+  }
+}
+
 // same test as rc_host.cpp in_div_range: 0, or 2^-76 <= |v| < 2^40
 __device__ __forceinline__ bool in_div_range_dev(float v) {
   const float a = fabsf(v);
@@ -371,8 +504,10 @@ __global__ __launch_bounds__(64) void k_prep_gaps(PrepArgs A) {
 void launch_prep(const PrepArgs &a, hipStream_t stream) {
   if (a.nBlocks <= 0) return;
   hipLaunchKernelGGL(k_prep_gaps, dim3(2 * a.nBlocks), dim3(kWave), 0, stream, a);
-  if (a.nModels <= 2048) hipLaunchKernelGGL(k_prep_models_few, dim3(4 * a.nModels), dim3(kWave), 0, stream, a);
-  else hipLaunchKernelGGL(k_prep_models, dim3(4 * ((a.nModels + kWave - 1) / kWave)), dim3(kWave), 0, stream, a);
+  const bool few = a.nModels <= 2048;
+  const dim3 grid(few ? 4 * a.nModels : 4 * ((a.nModels + kWave - 1) / kWave));
+  if (a.standardCode) hipLaunchKernelGGL(few ? k_prep_models_few : k_prep_models, grid, dim3(kWave), 0, stream, a);
+  else hipLaunchKernelGGL(few ? k_prep_models_few_rt : k_prep_models_rt, grid, dim3(kWave), 0, stream, a);
   hipLaunchKernelGGL(k_prep_lut, dim3(a.nBlocks), dim3(kWave), 0, stream, a);
 }
 

@@ -83,6 +83,9 @@ struct PrepArgs {
   const int *modelPrefix;     // [nBlocks + 1] running sum of 2 N over `blocks`: model t belongs to the block whose range holds t
   int nModels;
   const int *pep;             // [64] amino-acid index per codon, -1 = stop
+  bool standardCode;          // pep is the standard code (k_prep_models / k_prep_models_few have it compiled in); else the _rt variants read pep
+  const int *prepOff;         // k_prep_models_few_rt: [6] list offsets (stop pairs, Hamming classes 0..3) into ...
+  const uint16_t *prepAb;     //   ... [4096] (a << 6 | b) in calculateBG's order under pep (rc_context.cpp, table_set)
   const int *blosum;          // [20][20]
   const CodeInfo *codeInfo;   // [64]
   uint32_t *flags;            // per batch index
@@ -172,7 +175,7 @@ int tree_fit_register_occupancy();   // workgroups per CU the kernel's registers
 bool launch_tree_fit(const TreeJob *jobs, int njobs, bool big, size_t ldsBytes, const uint8_t *in, double *scratch, double *results, hipStream_t stream);
 
 void launch_mt_stream(uint32_t seedBase, int Spad, int D, uint32_t *U, hipStream_t stream);
-void launch_prep(const PrepArgs &a, hipStream_t stream);   // k_prep_models, then k_prep_lut
+void launch_prep(const PrepArgs &a, hipStream_t stream);   // k_prep_gaps, k_prep_models (or a variant), then k_prep_lut
 int null_occupancy(int NK, size_t ldsBytes);   // resident workgroups per CU (0 = cannot launch)
 int null_occupancy_plain(int NK, size_t dynLds, int hiOcc);   // the same for a launch that reads its codes from L2 with dynLds bytes of LDS; hiOcc: k_null_occ (0 if N-1 has none)
 bool launch_null(int NK, const NullArgs &a, int grid, size_t ldsBytes, bool exact, hipStream_t stream);

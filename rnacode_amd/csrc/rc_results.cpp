@@ -307,4 +307,15 @@ int rc_code_tables(int32_t blosum, int32_t pep_out[64], int32_t matrix_out[400])
   return RC_OK;
 }
 
+int rc_code_tables_for(const rc_params *par, int32_t pep_out[64], int32_t matrix_out[400]) {
+  if (!par || (par->blosum != 62 && par->blosum != 90) || !pep_out || !matrix_out) return fail(RC_ERR_ARG, "bad argument");
+  char code[64];
+  const char *why = nullptr;
+  if (!parse_genetic_code(par->genetic_code, code, &why)) return fail(RC_ERR_ARG, why);
+  const CodeTables ct(par->blosum, code);
+  for (int c = 0; c < 64; c++) pep_out[c] = ct.pep[c];
+  for (int p = 0; p < 20; p++) for (int q = 0; q < 20; q++) matrix_out[20 * p + q] = ct.blosum[p][q];
+  return RC_OK;
+}
+
 }  // extern "C"

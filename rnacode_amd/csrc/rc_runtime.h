@@ -292,6 +292,8 @@ class Pool {
 inline size_t al256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
 
+struct TableSet;
+
 struct rc_ctx {
   int device = 0;
   int numCU = 0;
@@ -322,9 +324,8 @@ struct rc_ctx {
   std::vector<hipStream_t> classStreams;   // k_null launches of different row-count classes, when a batch has several: these beside the run's own stream
   int classStreamCount = 3;                // ... that many in all (RC_CLASS_STREAMS)
   unsigned seq = 0;
-  CodeTables ct62{62}, ct90{90};
-  PairTable pt62, pt90;
-  DevBuf d_tables;                 // pair tables, genetic code, BLOSUM matrices, code infos (see table_ptrs)
+  std::mutex setMutex;             // table_set
+  std::vector<std::unique_ptr<TableSet>> sets;   // per (genetic code, BLOSUM) in use: built and uploaded on first use (the two standard ones with the context)
   // MT19937 stream cache
   uint32_t *d_U = nullptr;
   size_t U_cap = 0;
@@ -383,16 +384,25 @@ inline hipStream_t stream_tree2(rc_ctx *c) { return ctx_stream(c, 7); }
   hipStream_t var = (expr);                                                                    \
   if (!var) return fail(RC_ERR_DEVICE, "hipStreamCreateWithPriority failed")
 
-// layout of rc_ctx::d_tables
-struct TablePtrs { const uint8_t *pair; const int *pep; const int *blosum; const CodeInfo *info; };
-inline TablePtrs table_ptrs(const rc_ctx *c, int blosum) {
-  const uint8_t *base = c->d_tables.as<uint8_t>();
-  const size_t per = 4096 + 400 * sizeof(int) + 64 * sizeof(CodeInfo);
-  const uint8_t *m = base + 64 * sizeof(int) + (blosum == 90 ? per : 0);
-  return TablePtrs{m, reinterpret_cast<const int *>(base), reinterpret_cast<const int *>(m + 4096),
-                   reinterpret_cast<const CodeInfo *>(m + 4096 + 400 * sizeof(int))};
-}
+// One (genetic code, BLOSUM) pair's tables (rc_context.cpp, table_set): the host copies prepare_block reads and their device copy.
+// Device layout, each part 256-aligned: pair table [4096] | BLOSUM int [400] | CodeInfo [64] | pep int [64] | the few-model preparation
+// lists of a run-time code (k_prep_models_few_rt): off int [6], then (a << 6 | b) uint16 [4096].  About 16 KB; kept until rc_ctx_destroy.
+struct TablePtrs {
+  const uint8_t *pair; const int *pep; const int *blosum; const CodeInfo *info;
+  const int *prepOff; const uint16_t *prepAb;
+  bool standard;   // pep is the standard code's: the preparation kernels with the code compiled in (k_prep_models, k_prep_models_few)
+};
+struct TableSet {
+  char code[64];   // genetic code in the library's codon order (kGeneticCode's form)
+  int blosum;
+  CodeTables ct;
+  PairTable pt;
+  DevBuf d;
+  TablePtrs ptrs{};
+  TableSet(const char *c, int which) : blosum(which), ct(which, c) { std::memcpy(code, c, 64); }
+};
 
+struct rc_stream;
 struct rc_stream;
 
 struct rc_batch {
@@ -403,6 +413,7 @@ struct rc_batch {
   rc_ctx *ctx = nullptr;
   int device = 0;
   rc_params par{};
+  const TableSet *tables = nullptr;   // the context's tables for par's genetic code and matrix
   int n = 0;
   enum State { EMPTY, READY, RUNNING, DONE } state = EMPTY;
   std::vector<BlockMeta> meta;
@@ -455,6 +466,7 @@ struct rc_batch {
 struct rc_stream {
   rc_ctx *ctx = nullptr;
   rc_params par{};
+  const TableSet *tables = nullptr;   // resolved at create: a submit looks nothing up and builds nothing
   int depth = 2;
   std::deque<rc_batch *> inflight;
   std::vector<rc_batch *> spare;
@@ -486,7 +498,9 @@ struct RunEnv {
 
 // functions that cross unit boundaries
 void want_hw_queues();
-int batch_prepare(rc_batch *b, const rc_block *blocks, int32_t n_blocks, const rc_params *par);   // rc_batch.cpp
+// the context's tables for par's genetic code and BLOSUM, built and uploaded on first use; RC_ERR_ARG for a code parse_genetic_code rejects
+int table_set(rc_ctx *c, const rc_params &par, const TableSet **out);                               // rc_context.cpp
+int batch_prepare(rc_batch *b, const rc_block *blocks, int32_t n_blocks, const rc_params *par, const TableSet *set = nullptr);   // rc_batch.cpp
 int batch_upload(rc_batch *b);
 int batch_run_async(rc_batch *b, bool streaming = false);
 int batch_wait(rc_batch *b);

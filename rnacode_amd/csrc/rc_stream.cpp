@@ -9,8 +9,10 @@ int rc_stream_create(rc_ctx *ctx, const rc_params *par, int32_t depth, rc_stream
   if (!ctx || !par || !out || depth < 1 || depth > 16) return fail(RC_ERR_ARG, "bad argument");
   if (par->blosum != 62 && par->blosum != 90) return fail(RC_ERR_ARG, "blosum must be 62 or 90");
   if (par->sampleN < 1) return fail(RC_ERR_ARG, "sampleN must be >= 1");
+  const TableSet *set = nullptr;
+  RC_TRY(table_set(ctx, *par, &set));   // the genetic code is checked here, and its tables are uploaded now rather than by a submit
   rc_stream *s = new rc_stream();
-  s->ctx = ctx; s->par = *par; s->depth = depth;
+  s->ctx = ctx; s->par = *par; s->depth = depth; s->tables = set;
   // the HIP streams its sub-batches will use, now rather than inside the first submits (10 ms each): a driver creates its rc_stream
   // while something else is still on the way (the stand-alone driver: the first chunk of tree fits)
   (void)stream_copy(ctx);
@@ -73,7 +75,7 @@ int rc_stream_submit_bound(rc_stream *s, const rc_block *blocks, int32_t n_block
   if (maxima_device_ptr) { b->dmaxima.release(); b->maxPtr = static_cast<float *>(maxima_device_ptr); b->maximaExternal = true; }
   else if (b->maximaExternal) { b->maxPtr = nullptr; b->maximaExternal = false; }
   trace("submit", b);
-  int r = batch_prepare(b, blocks, n_blocks, &s->par);
+  int r = batch_prepare(b, blocks, n_blocks, &s->par, s->tables);
   trace("prepared", b);
   if (r == RC_OK) r = batch_upload(b);
   trace("uploaded", b);

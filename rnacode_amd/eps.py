@@ -126,13 +126,14 @@ def consensus(rows: Sequence[str]) -> str:
 
 
 class _Tables:
-    _cache: Dict[int, Tuple[np.ndarray, np.ndarray]] = {}
+    _cache: Dict[Tuple[int, str], Tuple[np.ndarray, np.ndarray]] = {}
 
     @classmethod
-    def get(cls, blosum: int):
-        if blosum not in cls._cache:
-            cls._cache[blosum] = api.code_tables(blosum)
-        return cls._cache[blosum]
+    def get(cls, blosum: int, genetic_code: str = ""):
+        key = (blosum, genetic_code)
+        if key not in cls._cache:
+            cls._cache[key] = api.code_tables(blosum, genetic_code)
+        return cls._cache[key]
 
 
 def _pep(pep: np.ndarray, codon: str) -> int:
@@ -282,12 +283,13 @@ def _color_hss(out: List[str], rows: Sequence[str], bt, label: str, b: int, i: i
                 out.append("0 setgray\n")
 
 
-def color_aln(block: AlnBlock, hss: dict, backtrack: Backtrack, blosum: int = 62) -> str:
+def color_aln(block: AlnBlock, hss: dict, backtrack: Backtrack, blosum: int = 62, genetic_code: str = "") -> str:
     """EPS text for one high-scoring segment of `block` (colorAln, postscript.c:38-332).
 
+    genetic_code: the run's rc_params.genetic_code ("" = standard): the letters drawn and where extendRegion's walk stops.
     hss: a record of scoreAln (strand, frame, start, end, pvalue).  backtrack(strand, b, i) returns the
     (states, z, transitions) arrays of rc_batch_backtrack for that strand."""
-    pep, matrix = _Tables.get(blosum)
+    pep, matrix = _Tables.get(blosum, genetic_code)
     rows = [r.seq for r in block.rows]
     names = [r.name for r in block.rows]
     N = len(rows)
