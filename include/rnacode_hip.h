@@ -288,6 +288,41 @@ int rc_fit_trees_device(rc_ctx *ctx, const rc_block *blocks, int32_t n_blocks, c
  * handling (diagnostic: compares a tree from elsewhere with rc_fit_tree's on equal terms). */
 int rc_tree_lnl(const rc_block *blk, double *lnl_out);
 
+/* A species tree given once per run (--species-tree; not in the reference, whose trees are always fitted per block).  Newick with a
+ * branch length on every tip and unique tip labels; below the root a node has at most two children, the root at most three
+ * (polytomies are refused).  rc_species_tree_create parses it (host only; RC_ERR_ARG and rc_last_error() say why not).
+ * A block's rows are matched to tips: a row matches the tip whose label is its whole name, else the tip whose label is the part
+ * of its name before the first '.' (UCSC's species.chrom: "ec_K12.chr" -> "ec_K12").  A row that matches no tip, or two rows that
+ * match one tip, refuse the block (that block only; the reason names the species).  The tree is then pruned to the matched tips:
+ * nodes left with one child are spliced out (lengths summed), a root left with two children is folded into its first internal
+ * child (the other child hangs below it with the two root branches summed), children keep the species tree's order, tips are
+ * labelled with the row names -- 2N - 2 nodes, like a fitted tree. */
+typedef struct rc_species_tree rc_species_tree;
+enum { RC_SPECIES_FIXED = 0, RC_SPECIES_SCALE = 1, RC_SPECIES_BRANCHES = 2 };
+int rc_species_tree_create(const char *newick, rc_species_tree **out);
+void rc_species_tree_destroy(rc_species_tree *t);
+int rc_species_tree_tips(const rc_species_tree *t);
+/* The pruned tree of one block as Newick ("%f" lengths, none on the root) into newick_out[cap]; RC_ERR_ARG with the reason if the
+ * block is refused. */
+int rc_species_tree_prune(const rc_species_tree *t, const rc_block *blk, char *newick_out, int32_t cap);
+/* Trees + kappas on the pruned species tree, one fit per block; no distances and no BIONJ, kappa starts at 4.0 as in rc_fit_trees:
+ *   RC_SPECIES_FIXED     the lengths as given, ML kappa only;
+ *   RC_SPECIES_SCALE     ML kappa and one factor s in [1e-3, 1e3] on every length (lengths floored at 1e-6);
+ *   RC_SPECIES_BRANCHES  every length and kappa by ML, starting from the species tree's lengths.
+ * The Newick text carries the fitted (in SCALE: scaled) lengths, so that it reproduces what is scored.  Output as rc_fit_trees:
+ * blocks that are skipped or refused get an empty string and kappa 0; scale_out (may be NULL) receives s (1 in the other modes, 0
+ * for blocks without a tree).  rc_fit_species_trees runs on `threads` host threads (0 = the CPUs this process may use); returns
+ * the number of fitted blocks. */
+int rc_fit_species_trees(const rc_species_tree *t, int32_t mode, const rc_block *blocks, int32_t n_blocks, char *newick_out, int32_t cap,
+                         float *kappa_out, double *scale_out, int32_t threads);
+/* The same fits on the GPU of `ctx`, one wavefront per block for every block the species tree covers, up to RC_MAX_ROWS rows (a given
+ * topology needs none of BIONJ's tables, which hold rc_fit_trees_device's kernel to 64).  lnl_out, scale_out and on_device_out
+ * (each may be NULL) receive per block the log-likelihood, s, and 1 if the block was fitted on the device (0 if it was not fitted).
+ * Returns the number of fitted blocks or a negative error code. */
+int rc_fit_species_trees_device(rc_ctx *ctx, const rc_species_tree *t, int32_t mode, const rc_block *blocks, int32_t n_blocks,
+                                char *newick_out, int32_t cap, float *kappa_out, double *lnl_out, double *scale_out,
+                                int32_t *on_device_out);
+
 /* EVDMaxLikelyFit (src/extreme_fit.c:157-251) on the device for n doubles; returns 1 / 0. */
 int rc_evd_fit(rc_ctx *ctx, const double *x, int32_t n, double *mu, double *lambda);
 /* p = 1 - exp(-exp(-lambda (score - mu))) with RNAcode.c:182's float/double promotions (host arithmetic): for callers

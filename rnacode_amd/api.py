@@ -150,6 +150,15 @@ def lib():
         l.rc_tree_lnl.argtypes = [C.POINTER(RcBlock), C.POINTER(C.c_double)]
         l.rc_fit_trees_device.argtypes = [C.c_void_p, C.POINTER(RcBlock), C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_float),
                                           C.POINTER(C.c_double)]
+        l.rc_species_tree_create.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+        l.rc_species_tree_destroy.argtypes = [C.c_void_p]
+        l.rc_species_tree_destroy.restype = None
+        l.rc_species_tree_tips.argtypes = [C.c_void_p]
+        l.rc_species_tree_prune.argtypes = [C.c_void_p, C.POINTER(RcBlock), C.c_char_p, C.c_int32]
+        l.rc_fit_species_trees.argtypes = [C.c_void_p, C.c_int32, C.POINTER(RcBlock), C.c_int32, C.c_char_p, C.c_int32,
+                                           C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_int32]
+        l.rc_fit_species_trees_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(RcBlock), C.c_int32, C.c_char_p, C.c_int32,
+                                                  C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         l.rc_code_tables.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.rc_code_tables_for.argtypes = [C.POINTER(RcParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.rc_genetic_code.argtypes = [C.c_int32, C.c_char_p]
@@ -166,7 +175,8 @@ EXPORTED_SYMBOLS = [
     "rc_stream_next", "rc_stream_recycle", "rc_stream_pending", "rc_stream_plan", "rc_stream_destroy", "rc_set_stream_cache", "rc_batch_work", "rc_batch_timing", "rc_batch_null_kernel", "rc_batch_status",
     "rc_batch_models", "rc_batch_maxima", "rc_batch_maxima_all", "rc_batch_fit", "rc_batch_fit_all", "rc_batch_hss", "rc_batch_hss_all", "rc_batch_clamped",
     "rc_batch_native_S", "rc_batch_backtrack", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
-    "rc_code_tables_for", "rc_genetic_code",
+    "rc_code_tables_for", "rc_genetic_code", "rc_species_tree_create", "rc_species_tree_destroy", "rc_species_tree_tips", "rc_species_tree_prune",
+    "rc_fit_species_trees", "rc_fit_species_trees_device",
 ]
 # the entry points of the older rc_params layout (include/rnacode_hip.h, "Binary compatibility"): exported, no longer declared
 COMPAT_SYMBOLS = ["rc_default_params", "rc_batch_create", "rc_stream_create"]
@@ -304,6 +314,84 @@ def fit_trees(blocks, threads: int = 0, cap: int = 0, ctx: "Optional[Context]" =
         _check(lib().rc_fit_trees(arr, n, buf, cap, kap, threads))
     out = []
     raw = buf.raw   # one copy (buf.raw copies the whole buffer on every access)
+    for i in range(n):
+        s = raw[i * cap:(i + 1) * cap].split(b"\0", 1)[0].decode()
+        out.append((s, float(kap[i])) if s else None)
+    return out
+
+
+SPECIES_MODES = {"fixed": 0, "scale": 1, "branches": 2}   # RC_SPECIES_FIXED / _SCALE / _BRANCHES
+
+
+def _one_block(block: AlnBlock, newick: Optional[str] = None, kappa: float = 0.0):
+    rows = (C.c_char_p * block.n)(*[r.seq.encode() for r in block.rows])
+    names = (C.c_char_p * block.n)(*[r.name.encode() for r in block.rows])
+    keep = newick.encode() if newick is not None else None
+    return RcBlock(block.n, block.cols, rows, names, block.rows[0].start, block.rows[0].length, keep, kappa), (rows, names, keep)
+
+
+class SpeciesTree:
+    """A species tree given once per run (rc_species_tree): Newick with a length on every tip and unique labels, no polytomies.
+    Raises RnacodeError (RC_ERR_ARG) with the reason otherwise."""
+
+    def __init__(self, newick: str):
+        self._h = C.c_void_p()
+        _check(lib().rc_species_tree_create(newick.encode(), C.byref(self._h)))
+
+    @property
+    def tips(self) -> int:
+        return _check(lib().rc_species_tree_tips(self._h))
+
+    def prune(self, block: AlnBlock) -> str:
+        """The tree pruned to the block's rows, tips labelled with the row names (Newick, "%f" lengths).  RnacodeError names the
+        species if a row matches no tip or two rows match one."""
+        blk, _keep = _one_block(block)
+        buf = C.create_string_buffer(max(1 << 14, 96 * block.n))
+        _check(lib().rc_species_tree_prune(self._h, C.byref(blk), buf, len(buf)))
+        return buf.value.decode()
+
+    def close(self):
+        if self._h:
+            lib().rc_species_tree_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def fit_species_trees(blocks, tree: SpeciesTree, mode: str = "scale", ctx: "Optional[Context]" = None, threads: int = 0,
+                      lnl: Optional[list] = None, scale: Optional[list] = None, cap: int = 0,
+                      on_device: Optional[list] = None) -> List[Optional[Tuple[str, float]]]:
+    """Trees + kappas on `tree` pruned to every block's rows (a sequence of AlnBlocks or a Marshalled), fitted in `mode`
+    ("fixed", "scale" or "branches"); None for blocks skipped or refused.  With ctx: rc_fit_species_trees_device on that context's
+    GPU (`lnl` and `on_device`, if lists, receive the log-likelihoods and 1 per block fitted on the device); without: host threads.
+    `scale`, if a list, receives the factor on the lengths (1 outside "scale", 0 for blocks without a tree)."""
+    if mode not in SPECIES_MODES:
+        raise ValueError(f"species tree fit mode must be one of {', '.join(SPECIES_MODES)}")
+    m = blocks if isinstance(blocks, Marshalled) else Marshalled(blocks)
+    n = len(m.blocks)
+    if cap <= 0:
+        cap = max(1 << 14, 96 * max((b.n for b in m.blocks), default=0))
+    buf = C.create_string_buffer(max(n, 1) * cap)
+    kap = (C.c_float * max(n, 1))()
+    sc = (C.c_double * max(n, 1))()
+    if ctx is not None:
+        ll = (C.c_double * max(n, 1))()
+        dev = (C.c_int32 * max(n, 1))()
+        _check(lib().rc_fit_species_trees_device(ctx._h, tree._h, SPECIES_MODES[mode], m.arr, n, buf, cap, kap, ll, sc, dev))
+        if lnl is not None:
+            lnl[:] = [float(x) for x in ll[:n]]
+        if on_device is not None:
+            on_device[:] = [int(x) for x in dev[:n]]
+    else:
+        _check(lib().rc_fit_species_trees(tree._h, SPECIES_MODES[mode], m.arr, n, buf, cap, kap, sc, threads))
+    if scale is not None:
+        scale[:] = [float(x) for x in sc[:n]]
+    out = []
+    raw = buf.raw
     for i in range(n):
         s = raw[i * cap:(i + 1) * cap].split(b"\0", 1)[0].decode()
         out.append((s, float(kap[i])) if s else None)

@@ -4,12 +4,16 @@ Mirrors the reference's command line (src/cmdline.ggo:6-20, src/RNAcode.c:236-37
 options that concern the scoring path and the listings:
 
     python -m rnacode_amd.cli [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S]
-                              [-e [-i CUTOFF] [-d DIR]] [-o OUT] [--trees SIDECAR] [FILE]
+                              [-e [-i CUTOFF] [-d DIR]] [-o OUT] [--trees SIDECAR | --species-tree NEWICK
+                              [--species-tree-fit fixed|scale|branches]] [--write-trees SIDECAR] [FILE]
 
 Tree + kappa per block (PhyML in the reference, RNAcode.c:153) come either from a sidecar
 (`--trees`: one `<newick> TAB <kappa>` line per alignment block, in file order; `-` for blocks the
 driver skips) or, without it, from the built-in estimator (rc_fit_trees_device, one wavefront per
-block).  The blocks are scored on the GPU as a stream of sub-batches (--sub-blocks, rc_stream_*).  -e writes the reference's colored
+block), or from one species tree for the whole run (`--species-tree`: pruned to each block's rows and fitted on the GPU in
+the mode --species-tree-fit names, rc_fit_species_trees_device; a block whose rows the tree does not cover is skipped with a line
+on stderr).  `--write-trees` writes the trees a run scored with as a sidecar (one line per block read, kappa as %.9g so that the
+float round-trips).  The blocks are scored on the GPU as a stream of sub-batches (--sub-blocks, rc_stream_*).  -e writes the reference's colored
 alignment plots (src/postscript.c) as <DIR>/hss-<n>.eps.
 Quirk kept from the reference: the 4th value of --pars goes to stopPenalty_0 (RNAcode.c:318)."""
 from __future__ import annotations
@@ -39,6 +43,32 @@ def read_sidecar(path: str) -> List[Optional[tuple]]:
     return out
 
 
+def write_sidecar(path: str, n_read: int, read_index: List[int], trees: List[Optional[tuple]]) -> None:
+    """The sidecar --trees reads: one '<newick>\\t<kappa>' line per block read ('-' for blocks without a tree or dropped by --limit);
+    %.9g prints the float kappa so that it reads back as the same float."""
+    lines = ["-"] * n_read
+    for at, t in zip(read_index, trees):
+        if t is not None:
+            lines[at] = "%s\t%.9g" % (t[0], t[1])
+    with open(path, "w") as fh:
+        fh.write("".join(x + "\n" for x in lines))
+
+
+def apply_limit(blocks: List[AlnBlock], limit: str):
+    """pruneAln (rnaz_utils.c:724-752, called at RNAcode.c:130-132): the rows whose name starts with one of the comma-separated
+    strings stay, the columns stay.  Returns the kept blocks and their positions in `blocks`."""
+    keep = [x for x in limit.split(",") if x]
+    kept, where = [], []
+    for at, b in enumerate(blocks):
+        rows = [r for r in b.rows if any(r.name.startswith(x) for x in keep)]
+        if not rows:   # (the reference dereferences the missing first row here)
+            print("Skipping alignment. There must be at least three sequences in the alignment.", file=sys.stderr)
+            continue
+        kept.append(AlnBlock(rows, b.block_id, b.tree, b.kappa))
+        where.append(at)
+    return kept, where
+
+
 def fit_trees(blocks, threads: int = 0, ctx: "Optional[api.Context]" = None) -> List[Optional[tuple]]:
     """Trees + kappas for every block the driver will score: on ctx's GPU (rc_fit_trees_device) when a
     context is given, else on host threads (rc_fit_trees)."""
@@ -63,6 +93,12 @@ def main(argv=None) -> int:
     ap.add_argument("-d", "--eps-dir", default="eps", help="Directory to put eps-files")
     ap.add_argument("-l", "--limit", help="limit to species: keep the rows whose name starts with one of these comma-separated strings")
     ap.add_argument("--trees", help="sidecar: one '<newick>\\t<kappa>' line per block (default: fit them)")
+    ap.add_argument("--species-tree", metavar="NEWICK_FILE",
+                    help="one species tree for every block (not with --trees): pruned to each block's rows -- a row matches the tip "
+                         "named like it, or like its name before the first '.' -- and fitted on the GPU")
+    ap.add_argument("--species-tree-fit", choices=sorted(api.SPECIES_MODES), default="scale",
+                    help="fixed: kappa only; scale (default): kappa and one factor on all lengths; branches: kappa and every length")
+    ap.add_argument("--write-trees", metavar="SIDECAR", help="write the trees the run scored with, in the form --trees reads")
     ap.add_argument("--sub-blocks", type=int, default=0,
                     help="alignment blocks per sub-batch of the GPU stream (default: 2048, or 512 per distinct row count if that is more)")
     ap.add_argument("--seed-base", type=int, default=42)
@@ -87,6 +123,17 @@ def main(argv=None) -> int:
     except api.RnacodeError as e:   # a bad --genetic-code: before any context exists
         print(f"ERROR: --genetic-code: {str(e).split(': ', 1)[-1]}", file=sys.stderr)
         return 1
+    species = None
+    if a.species_tree:   # parsed before any context exists
+        if a.trees:
+            print("ERROR: --species-tree and --trees cannot be used together", file=sys.stderr)
+            return 1
+        try:
+            with open(a.species_tree) as fh:
+                species = api.SpeciesTree(fh.read())
+        except (OSError, api.RnacodeError) as e:
+            print(f"ERROR: --species-tree: {str(e).split(': ', 1)[-1]}", file=sys.stderr)
+            return 1
 
     if a.file:
         blocks = read_alignment_file(a.file)
@@ -97,26 +144,32 @@ def main(argv=None) -> int:
         blocks = read_alignment_file(fh.name)
     blocks = [b.upper() for b in blocks]
     n_read = len(blocks)
+    read_index = list(range(n_read))
     if a.limit:   # pruneAln (rnaz_utils.c:724-752, called at RNAcode.c:130-132): rows only, the columns stay
-        keep = [x for x in a.limit.split(",") if x]
-        kept = []
-        for b in blocks:
-            rows = [r for r in b.rows if any(r.name.startswith(x) for x in keep)]
-            if not rows:   # (the reference dereferences the missing first row here)
-                print("Skipping alignment. There must be at least three sequences in the alignment.", file=sys.stderr)
-                continue
-            kept.append(AlnBlock(rows, b.block_id, b.tree, b.kappa))
-        blocks = kept
+        blocks, read_index = apply_limit(blocks, a.limit)
     ctx = api.Context(a.device)
     marshalled = api.Marshalled(blocks)   # one rc_block array for the tree fit and the batch
+    refused = {}   # --species-tree: block -> why its rows do not match the tree
     if a.trees:
         side = read_sidecar(a.trees)
+        if len(side) == n_read and len(blocks) != n_read:   # one entry per block read (--write-trees): the kept blocks' entries
+            side = [side[at] for at in read_index]
         if len(side) != len(blocks):
             print(f"ERROR: {len(blocks)} alignment blocks but {len(side)} sidecar entries", file=sys.stderr)
             ctx.close()
             return 1
+    elif species is not None:
+        side = api.fit_species_trees(marshalled, species, a.species_tree_fit, ctx=ctx)
+        for i, (b, s) in enumerate(zip(blocks, side)):
+            if s is None and b.n >= 3:
+                try:
+                    species.prune(b)
+                except api.RnacodeError as e:
+                    refused[i] = str(e).split(": ", 1)[-1]
     else:
         side = fit_trees(marshalled, ctx=ctx)
+    if a.write_trees:
+        write_sidecar(a.write_trees, n_read, read_index, side)
     prepared: List[AlnBlock] = []
     for b, s in zip(blocks, side):
         # no tree: either a block the driver skips anyway (N <= 2, too short) or one whose tree could not be built;
@@ -140,6 +193,9 @@ def main(argv=None) -> int:
         for i in range(batch.n):
             b = prepared[base + i]
             code = batch.status(i)
+            if base + i in refused:   # the species tree does not cover the block's rows
+                print(f"Skipping alignment {read_index[base + i] + 1} ({b.rows[0].name}). {refused[base + i]}", file=sys.stderr)
+                continue
             if code == api.RC_ERR_SKIP:   # RNAcode.c:142-150
                 msg = "There must be at least three sequences in the alignment." if b.n <= 2 else "Too short."
                 print(f"Skipping alignment. {msg}", file=sys.stderr)

@@ -9,7 +9,13 @@
 //
 //   rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]
 //               [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]
-//               [--genetic-code ID|LETTERS] [FILE]
+//               [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]
+//               [--write-trees SIDECAR] [FILE]
+//
+// --species-tree (not in the reference, which fits a tree per block): one species tree for the run, parsed before any context
+// exists, pruned to each block's rows and fitted on the GPU (rc_fit_species_trees_device) where rc_fit_trees_device would run; a
+// block the tree does not cover is skipped with a line naming it and the species.  --write-trees: the trees the run scored with,
+// one '<newick> TAB <kappa>' line per block read ('-' for none), kappa as %.9g -- what --trees reads back to the same floats.
 //
 // --genetic-code (not in the reference, which always uses the standard code): an NCBI table id or 64 letters in NCBI's TCAG order
 // (rc_params.genetic_code); checked while the options are parsed, before any context exists; every context of --gpus gets it.
@@ -63,6 +69,7 @@ struct Block {
   std::string tree;     // empty: none
   float kappa = 0.0f;
   int index = 0;        // position in the input file (the --trees sidecar has one entry per block READ, before --limit drops any)
+  std::string refused;  // --species-tree: why the block's rows do not match the species tree (the block is skipped)
 };
 
 double now();
@@ -368,9 +375,15 @@ struct Listing {
 void usage() {
   std::fprintf(stderr, "usage: rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]\n"
                        "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]\n"
-                       "                   [--genetic-code ID|LETTERS] [--dump-blocks] [FILE]\n"
+                       "                   [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]\n"
+                       "                   [--write-trees SIDECAR] [--dump-blocks] [FILE]\n"
                        "  --genetic-code ID|LETTERS  an NCBI translation table id (e.g. 2, vertebrate mitochondrial) or its 64 letters in\n"
-                       "                             NCBI's TCAG order (FFLLSSSS...); default: the standard code\n");
+                       "                             NCBI's TCAG order (FFLLSSSS...); default: the standard code\n"
+                       "  --species-tree FILE        one species tree for every block (not with --trees): pruned to each block's rows (a row\n"
+                       "                             matches the tip named like it, or like its name before the first '.') and fitted:\n"
+                       "  --species-tree-fit MODE    fixed: kappa only; scale (default): kappa and one factor on all lengths; branches:\n"
+                       "                             kappa and every length\n"
+                       "  --write-trees FILE         write the trees the run scored with, in the form --trees reads\n");
 }
 
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -394,6 +407,9 @@ struct Run {
   std::vector<rc_block> rb;          // rc_block views of `blocks` (newick / kappa filled in when the trees are there)
   int cap = 64;                      // room for a Newick text
   bool haveSidecar = false;
+  rc_species_tree *species = nullptr;   // --species-tree
+  int speciesMode = RC_SPECIES_SCALE;
+  bool keepTrees = false;            // --write-trees: the fitted trees go back into `blocks`
   rceps::Tables tables;
   // the writer: one thread, jobs in input order
   std::mutex jm;
@@ -430,6 +446,10 @@ void writer_thread(Run &R) {
       const Block &blk = R.blocks[j->blockIdx[i]];
       if (st == RC_ERR_SKIP) {   // RNAcode.c:142-150
         std::fprintf(stderr, "Skipping alignment. %s\n", blk.rows.size() <= 2 ? "There must be at least three sequences in the alignment." : "Too short.");
+        continue;
+      }
+      if (!blk.refused.empty()) {   // --species-tree: the block's rows do not match the species tree
+        std::fprintf(stderr, "Skipping alignment %d (%s). %s\n", blk.index + 1, std::string(blk.rows[0].name).c_str(), blk.refused.c_str());
         continue;
       }
       if (st != RC_OK) {         // RNAcode.c:153-156
@@ -504,6 +524,21 @@ std::unique_ptr<Job> collect(const Run &R, rc_batch *b, int seq, const std::vect
 
 struct Times { double ctx = 0, trees = 0, treeWait = 0, submit = 0, wait = 0, fetch = 0; };
 
+// the trees of n blocks (their positions in R.blocks: idx) on one GPU: the built-in estimator, or the species tree pruned to each
+// block; a block the species tree refuses gets its reason (the writer names it when it skips the block)
+int fit_chunk(Run &R, rc_ctx *ctx, const rc_block *rb, int n, char *nwk, float *kap, const int *idx) {
+  if (!R.species) return rc_fit_trees_device(ctx, rb, n, nwk, R.cap, kap, nullptr);
+  const int r = rc_fit_species_trees_device(ctx, R.species, R.speciesMode, rb, n, nwk, R.cap, kap, nullptr, nullptr, nullptr);
+  if (r < 0) return r;
+  for (int i = 0; i < n; i++) {
+    char *dst = nwk + static_cast<size_t>(i) * R.cap;
+    if (dst[0] || rb[i].n_rows < 3) continue;   // fitted, or a block the scorer skips for its shape
+    if (rc_species_tree_prune(R.species, &rb[i], dst, R.cap) != RC_OK) R.blocks[idx[i]].refused = rc_last_error();
+    dst[0] = 0;
+  }
+  return r;
+}
+
 // One GPU's share of a many-block input: its sub-batches (ranges of the input, in input order), trees fitted on this GPU in chunks
 // that run ahead of the scoring on a thread of their own, scoring as a stream, results to the writer.
 struct Worker {
@@ -543,10 +578,13 @@ void run_worker(Run &R, Worker &W, int subBlocks) {
       nwk.assign(static_cast<size_t>(mf) * R.cap, 0);
       kap.assign(mf, 0.0f);
       const double t0 = now();
-      const int r = rc_fit_trees_device(W.ctx, rb.data() + at, mf, nwk.data(), R.cap, kap.data(), nullptr);
+      const int r = fit_chunk(R, W.ctx, rb.data() + at, mf, nwk.data(), kap.data(), idx.data() + at);
       W.t.trees += now() - t0;
       if (r >= 0)
-        for (int i = 0; i < mf; i++) { tree[at + i] = nwk.data() + static_cast<size_t>(i) * R.cap; kappa[at + i] = kap[i]; }
+        for (int i = 0; i < mf; i++) {
+          tree[at + i] = nwk.data() + static_cast<size_t>(i) * R.cap; kappa[at + i] = kap[i];
+          if (R.keepTrees) { R.blocks[idx[at + i]].tree = tree[at + i]; R.blocks[idx[at + i]].kappa = kap[i]; }
+        }
       {
         std::lock_guard<std::mutex> lk(tm);
         if (r < 0) { treeErr = rc_last_error(); fitted = n; }
@@ -625,7 +663,9 @@ bool run_sample_split(Run &R, std::vector<Worker> &W, std::string &err) {
   if (!R.haveSidecar) {
     nwk.assign(static_cast<size_t>(n) * R.cap, 0);
     const double t0 = now();
-    if (rc_fit_trees_device(W[0].ctx, R.rb.data(), n, nwk.data(), R.cap, kap.data(), nullptr) < 0) { err = rc_last_error(); return false; }
+    std::vector<int> all(n);
+    for (int i = 0; i < n; i++) all[i] = i;
+    if (fit_chunk(R, W[0].ctx, R.rb.data(), n, nwk.data(), kap.data(), all.data()) < 0) { err = rc_last_error(); return false; }
     W[0].t.trees += now() - t0;
     for (int i = 0; i < n; i++) { R.blocks[i].tree = nwk.data() + static_cast<size_t>(i) * R.cap; R.blocks[i].kappa = kap[i]; }
   }
@@ -703,7 +743,7 @@ int main(int argc, char **argv) {
   rc_default_params(&R.par);
   rc_params &par = R.par;
   Listing &list = R.list;
-  std::string file, outfile, trees, limit, devicesArg;
+  std::string file, outfile, trees, limit, devicesArg, speciesFile, writeTrees;
   int device = 0, subBlocks = 0, gpus = 1;   // subBlocks 0: the library's schedule
   bool dumpBlocks = false;
   for (int a = 1; a < argc; a++) {
@@ -725,6 +765,14 @@ int main(int argc, char **argv) {
       for (int i = 0; i < 4 && std::getline(ss, item, ','); i++) *dst[i] = static_cast<float>(std::atof(item.c_str()));
     } else if (o == "-l" || o == "--limit") limit = val();
     else if (o == "--trees") trees = val();
+    else if (o == "--species-tree") speciesFile = val();
+    else if (o == "--species-tree-fit") {
+      const std::string v = val();
+      if (v == "fixed") R.speciesMode = RC_SPECIES_FIXED;
+      else if (v == "scale") R.speciesMode = RC_SPECIES_SCALE;
+      else if (v == "branches") R.speciesMode = RC_SPECIES_BRANCHES;
+      else die("--species-tree-fit must be fixed, scale or branches");
+    } else if (o == "--write-trees") writeTrees = val();
     else if (o == "--seed-base") par.seed_base = static_cast<uint32_t>(std::strtoul(val(), nullptr, 10));
     else if (o == "--device") device = std::atoi(val());
     else if (o == "--gpus") gpus = std::max(1, std::atoi(val()));
@@ -751,6 +799,15 @@ int main(int argc, char **argv) {
     int32_t pep[64], matrix[400];
     if (rc_code_tables_for(&par, pep, matrix) != RC_OK) die("--genetic-code: " + std::string(rc_last_error()));
   }
+  if (!speciesFile.empty()) {   // parsed (host only) before any context exists
+    if (!trees.empty()) die("--species-tree and --trees cannot be used together");
+    std::ifstream in(speciesFile);
+    if (!in) die("Could not open " + speciesFile);
+    std::stringstream ss;
+    ss << in.rdbuf();
+    if (rc_species_tree_create(ss.str().c_str(), &R.species) != RC_OK) die("--species-tree: " + std::string(rc_last_error()));
+  }
+  R.keepTrees = !writeTrees.empty();
   list.cutoff = par.cutoff;
   std::vector<int> devices;
   if (!devicesArg.empty()) {
@@ -930,6 +987,17 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "[rnacode_hip] read %.3f s, context (beside the reading) %.3f s, trees (their own thread) %.3f s of which the scoring waited %.3f s, submit %.3f s, wait %.3f s, results %.3f s, listing (its own thread) %.3f s, main() so far %.3f s%s\n",
                  tRead, s.ctx, s.trees, s.treeWait, s.submit, s.wait, s.fetch, R.tList, now() - tMain,
                  gpus > 1 ? (", " + std::to_string(gpus) + " GPUs (sums over them): " + mode).c_str() : "");
+  }
+  if (!writeTrees.empty()) {   // the sidecar --trees reads: one line per block READ, '-' for blocks without a tree
+    FILE *f = std::fopen(writeTrees.c_str(), "w");
+    if (!f) die("Could not open " + writeTrees);
+    std::vector<int> at(nRead, -1);
+    for (int i = 0; i < n; i++) at[blocks[i].index] = i;
+    for (int i = 0; i < nRead; i++) {
+      if (at[i] < 0 || blocks[at[i]].tree.empty()) std::fputs("-\n", f);
+      else std::fprintf(f, "%s\t%.9g\n", blocks[at[i]].tree.c_str(), static_cast<double>(blocks[at[i]].kappa));   // %.9g: the float round-trips
+    }
+    if (std::fclose(f) != 0) die("Could not write " + writeTrees);
   }
   if (list.fmt == 0) {   // RNAcode.c:223-228
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

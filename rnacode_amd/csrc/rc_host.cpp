@@ -61,6 +61,7 @@ struct NwParser {
     t->parent.push_back(parent < 0 ? 0 : parent);
     t->length.push_back(0.0);
     t->tip.push_back(-1);
+    t->haslen.push_back(0);
     return q;
   }
   // subtree := '(' subtree ',' subtree [',' subtree]? ')' [label] | name ;  then [':' length ['[' param ']']]
@@ -111,6 +112,7 @@ struct NwParser {
         pos = static_cast<size_t>(end - s);
       }
       t->length[q] = len;
+      t->haslen[q] = 1;
       ws();
       if (s[pos] == '[') { while (s[pos] && s[pos] != ']') pos++; if (s[pos]) pos++; }
     }
@@ -122,7 +124,7 @@ struct NwParser {
 
 void Tree::clear() {
   nnodes = 0; rooted = false;
-  parent.clear(); length.clear(); tip.clear(); namepool.clear(); nameOff.clear(); nameLen.clear(); tipnode.clear();
+  parent.clear(); length.clear(); haslen.clear(); tip.clear(); namepool.clear(); nameOff.clear(); nameLen.clear(); tipnode.clear();
 }
 
 bool Tree::tip_is(int k, const char *name) const {

@@ -3,6 +3,7 @@
 #include <atomic>
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/rnacode_hip.h"
@@ -17,6 +18,7 @@ struct Tree {
   bool rooted = false;
   std::vector<int> parent;          // parent[q] < q, parent[0] = 0
   std::vector<double> length;       // branch to parent as read by "%lf" (treefile.c:431)
+  std::vector<uint8_t> haslen;      // 1 where the text gave the node a length (a species tree needs one on every tip)
   std::vector<int> tip;             // tip number in order of appearance, -1 for internal
   std::vector<char> namepool;       // tip labels back to back (white space removed, as the reference's reader does)
   std::vector<int> nameOff, nameLen;   // by tip number: where its label sits in namepool
@@ -85,6 +87,31 @@ bool fit_tree(const std::vector<std::string> &rows, const std::vector<std::strin
 
 bool tree_lnl(const std::vector<std::string> &rows, const std::vector<std::string> &names, const char *newick, float kappa,
               double *lnl_out, std::string &err);
+
+// a topology in the estimator's numbering (rc_tree_core.h, Work): tips 0..N-1 = the block's rows, internal nodes N..nn-1 with the root
+// last (nn = 2N - 2, the root has three children), child[3 v + c], a pre-order, lengths by node (the root's unused)
+struct Topology {
+  int N = 0, root = 0;
+  std::vector<int> parent, nchild, child, preorder;
+  std::vector<double> len;
+  int nn() const { return 2 * N - 2; }
+};
+
+// --species-tree (rc_species.cpp): a Newick species tree parsed once, pruned to each block's rows
+struct SpeciesTree {
+  Tree t;
+  std::vector<int> kidOff, kids;                // children of node q: kids[kidOff[q] .. kidOff[q + 1]), in the text's order
+  std::vector<std::pair<std::string, int>> byLabel;   // (tip label, node), sorted by label
+  int find(const std::string &label) const;     // node of the tip with this label, -1 if none
+};
+bool species_tree_parse(const char *newick, SpeciesTree &st, std::string &err);
+// match the rows to tips (whole name, else the name before its first '.') and prune: unmatched tips dropped, one-child nodes spliced
+// out (lengths summed), a two-child root folded into its first internal child.  Tips are the rows.  false + reason: a row that matches
+// no tip, two rows that match one tip, fewer than three rows.
+bool species_prune(const SpeciesTree &st, int N, const char *const *names, Topology &out, std::string &err);
+// the estimator on a given topology (rc_tree_core.h, fit_given); mode: treefit::kFitBranches / kFitFixed / kFitScale
+bool fit_given_tree(const PatternSet &ps, const Topology &topo, int mode, const std::vector<std::string> &names, std::string &newick,
+                    float &kappa, double *lnl_out, double *scale_out, std::string &err);
 
 // extreme_fit.c / RNAcode.c:182 pieces that stay on the host
 float pvalue_of(float score, float mu, float lambda);

@@ -124,34 +124,47 @@ struct TreeJob {
   uint64_t off_w;             // bytes into the input blob (8-aligned): [P] pattern weights
   uint64_t off_work;          // doubles into the scratch: tree_work_doubles(N, P) -- only jobs of the big-block launches have one
   uint64_t off_out;           // doubles into the result buffer: the job's TreeResult record (tree_result_doubles(N) doubles)
+  int mode;                   // -1: the full fit (distances, BIONJ); else a given topology (species tree) fitted in treefit::kFit* mode
+  int pad_;
+  uint64_t off_topo;          // mode >= 0: bytes into the input blob (8-aligned): the topology, tree_topo_bytes(N)
 };
+// A given topology in the input blob, nn = 2N - 2: ints {root, parent[nn], nchild[nn], child[3 nn], preorder[nn]}, then at
+// tree_topo_len_at(N) (8-aligned) the starting lengths, doubles len[nn]
+__host__ __device__ inline size_t tree_topo_len_at(int N) { const size_t nn = 2 * static_cast<size_t>(N) - 2; return (sizeof(int) * (1 + 6 * nn) + 7) & ~static_cast<size_t>(7); }
+__host__ __device__ inline size_t tree_topo_bytes(int N) { return tree_topo_len_at(N) + sizeof(double) * (2 * static_cast<size_t>(N) - 2); }
 #ifdef RC_TREE_PROFILE
 constexpr int kTreeProfDoubles = 12;   // profiling builds: cycles of phases 0..8 and counters 9..11 behind every record
 #else
 constexpr int kTreeProfDoubles = 0;
 #endif
 // What travels back to the host per job, nn = 2N - 2 nodes: doubles {kappa, lnl, len[nn]} then ints {root, nchild[nn], child[3 nn]}
-// (260 bytes for six rows)
+// (260 bytes for six rows); a job with a given topology has one double more behind that, the scale (kFitScale's s, else 1)
 __host__ __device__ inline size_t tree_result_doubles(int N) { const size_t nn = 2 * static_cast<size_t>(N) - 2; return 2 + nn + (1 + 4 * nn + 1) / 2 + kTreeProfDoubles; }
 // A fit's working set, as offsets (in doubles) into the workgroup's LDS.  Always there: branch lengths, the five transfer constants
 // and three exponentials per branch, BIONJ's D and V and its temporaries, the tree as integer arrays.  With cols: the pattern weights,
 // the conditional-likelihood columns -- dn and up of the N - 3 internal nodes below the root, [4][P] each, and the four Newton
 // constants per pattern -- and the masks; a block whose columns do not fit keeps those three in global memory (big).
-struct TreeLdsLayout { uint32_t len, coef, e3, D, V, tmpD, opt, ints, w, cols, mask, total; };
+// A job with a given topology (given) has no distance matrices and no BIONJ tables; it keeps its starting lengths (len0) instead.
+struct TreeLdsLayout { uint32_t len, coef, e3, D, V, tmpD, len0, opt, ints, w, cols, mask, total; };
 constexpr uint32_t kTreeOptDoubles = 32 + kTreeProfDoubles;   // room for treefit::OptState (rc_tree_kernel.hip asserts it), profiling builds: and the phase counters
 __host__ __device__ inline size_t tree_col_doubles(int N, int P) { return (static_cast<size_t>(2) * (N > 3 ? N - 3 : 0) * 4 + 4) * static_cast<size_t>(P); }
-__host__ __device__ inline TreeLdsLayout tree_lds_layout(int N, int P, bool big) {
+__host__ __device__ inline TreeLdsLayout tree_lds_layout(int N, int P, bool big, bool given = false) {
   const uint32_t n = static_cast<uint32_t>(N), nn = 2 * n - 2, p = static_cast<uint32_t>(P);
   TreeLdsLayout l{};
   uint32_t at = 0;
   l.len = at; at += nn;
   l.coef = at; at += 5 * nn;
   l.e3 = at; at += 3 * nn;
-  l.D = at; at += n * n;
-  l.V = at; at += n * n;
-  l.tmpD = at; at += n;
+  l.D = l.V = l.tmpD = l.len0 = at;
+  if (given) {
+    l.len0 = at; at += nn;
+  } else {
+    l.D = at; at += n * n;
+    l.V = at; at += n * n;
+    l.tmpD = at; at += n;
+  }
   l.opt = at; at += kTreeOptDoubles;
-  l.ints = at; at += (7 * nn + 2 * n + 1) / 2;   // parent, nchild, child[3], preorder, then bionj's 2 N + nn
+  l.ints = at; at += given ? (6 * nn + 1) / 2 : (7 * nn + 2 * n + 1) / 2;   // parent, nchild, child[3], preorder, then bionj's 2 N + nn
   l.w = l.cols = l.mask = at;
   if (!big) {
     l.w = at; at += p;
@@ -161,9 +174,9 @@ __host__ __device__ inline TreeLdsLayout tree_lds_layout(int N, int P, bool big)
   l.total = at;
   return l;
 }
-inline size_t tree_fit_lds_bytes(int N, int P, bool big) {   // (64-bit: a block that cannot fit must not wrap round to a small number)
+inline size_t tree_fit_lds_bytes(int N, int P, bool big, bool given = false) {   // (64-bit: a block that cannot fit must not wrap round to a small number)
   const size_t n = static_cast<size_t>(N), nn = 2 * n - 2, p = static_cast<size_t>(P);
-  size_t at = 9 * nn + 2 * n * n + n + kTreeOptDoubles + (7 * nn + 2 * n + 1) / 2;
+  size_t at = given ? 10 * nn + kTreeOptDoubles + (6 * nn + 1) / 2 : 9 * nn + 2 * n * n + n + kTreeOptDoubles + (7 * nn + 2 * n + 1) / 2;
   if (!big) at += p + tree_col_doubles(N, P) + (n * p + 7) / 8;
   return at * sizeof(double);
 }

@@ -39,7 +39,7 @@ struct SerialExec {
 struct Fitter {
   treefit::Work k{};
   std::vector<uint8_t> mask;
-  std::vector<double> w, D, V, len, e3, dnI, upI, kc, tmpD;
+  std::vector<double> w, D, V, len, len0, e3, dnI, upI, kc, tmpD;
   std::vector<treefit::Coef> coef;
   treefit::OptState opt{};
   std::vector<int> parent, nchild, child, preorder, tmpI;
@@ -48,10 +48,10 @@ struct Fitter {
     mask = ps.mask; w = ps.w;
     k.N = ps.N; k.P = ps.P;
   }
-  void allocate(int nn) {
+  void allocate(int nn, bool bionj = true) {   // bionj = false: a given topology, no distance matrices
     k.nn = nn;
     const int N = k.N;
-    D.assign(static_cast<size_t>(N) * N, 0.0); V = D;
+    if (bionj) { D.assign(static_cast<size_t>(N) * N, 0.0); V = D; }
     len.assign(nn, kBlMin); parent.assign(nn, -1); nchild.assign(nn, 0); child.assign(static_cast<size_t>(nn) * 3, -1); preorder.assign(nn, 0);
     const size_t sz = static_cast<size_t>(std::max(nn - N, 1)) * 4 * k.P;   // columns of the internal nodes only
     dnI.assign(sz, 0.0); upI.assign(sz, 0.0); kc.assign(static_cast<size_t>(4) * k.P, 0.0);
@@ -65,6 +65,29 @@ struct Fitter {
 };
 
 }  // namespace
+
+bool fit_given_tree(const PatternSet &ps, const Topology &topo, int mode, const std::vector<std::string> &names, std::string &newick,
+                    float &kappa, double *lnl_out, double *scale_out, std::string &err) {
+  if (topo.N != ps.N) { err = "tree and alignment differ in the number of sequences"; return false; }
+  const int nn = topo.nn();
+  Fitter f;
+  f.load(ps);
+  f.allocate(nn, false);
+  f.k.root = topo.root;
+  f.parent = topo.parent; f.nchild = topo.nchild; f.child = topo.child; f.preorder = topo.preorder;
+  for (int v = 0; v < nn; v++) f.len[v] = std::max(topo.len[v], kBlMin);
+  f.len0 = f.len;
+  f.k.parent = f.parent.data(); f.k.nchild = f.nchild.data(); f.k.child = f.child.data(); f.k.preorder = f.preorder.data();
+  f.k.len = f.len.data(); f.k.len0 = f.len0.data();
+  f.k.mode = mode;
+  SerialExec ex;
+  const double l = treefit::fit_given(f.k, ex);
+  newick = newick_of(ps.N, f.k.root, f.k.nchild, f.k.child, f.k.len, names);
+  kappa = static_cast<float>(f.k.mod.kappa);
+  if (lnl_out) *lnl_out = l;
+  if (scale_out) *scale_out = mode == treefit::kFitScale ? f.opt.scale : 1.0;
+  return true;
+}
 
 // distinct alignment columns (as allowed-state masks) in the order of their first appearance, with their multiplicities
 bool compress_patterns(const char *const *rows, int N, int cols, PatternSet &ps, std::string &err) {

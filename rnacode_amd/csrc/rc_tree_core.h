@@ -198,8 +198,14 @@ struct LocalMin {
 struct OptState {
   LocalMin lm;
   double prev, kap, h, f0, f1;
+  double scale;          // kFitScale: the factor on every starting length
   int what, round, probe;
+  int param;             // what the probes and the search move: 0 kappa, 1 the scale
 };
+
+// what optimise() estimates besides kappa: every branch length (the full fit; a given topology from its starting lengths), nothing
+// (the lengths as given), or one factor on all the starting lengths in len0
+enum { kFitBranches = 0, kFitFixed = 1, kFitScale = 2 };
 
 // everything one fit works on; the arrays are provided by the caller (host vectors / the kernel's LDS and, for long blocks, global scratch)
 struct Work {
@@ -225,6 +231,8 @@ struct Work {
   double *dnI, *upI;     // [nn - N][4][P]
   double *kc;            // [4][P]
   OptState *opt;         // optimise()'s state
+  int mode;              // kFitBranches / kFitFixed / kFitScale
+  const double *len0;    // [nn] kFitScale: the starting lengths the scale multiplies
 };
 
 // empirical base frequencies; ambiguous characters are shared out by the current estimate (8 rounds,
@@ -567,6 +575,18 @@ RC_HD void branch_pass(Work &k, Exec &ex) {
   ex.mark(7);
 }
 
+// kFitScale's parameter: every length the starting one times s, floored at kBlMin (as tree_lnl floors a given length).  A starting
+// length at the floor is a zero-length branch and stays one (a scaled 1e-6 would print as "%f" rounds it, not as it was fitted).
+template <typename Exec>
+RC_HD void scale_lengths(Work &k, Exec &ex, double s) {
+  for (int v = ex.lane(); v < k.nn; v += ex.nlanes()) { const double l = k.len0[v] > kBlMin ? k.len0[v] * s : kBlMin; k.len[v] = l > kBlMin ? l : kBlMin; }
+}
+template <typename Exec>
+RC_HD void set_param(Work &k, Exec &ex, int param, double x) {
+  if (param) scale_lengths(k, ex, x);
+  else k.mod.set(k.pi, x);
+}
+
 // coordinate-wise ML: every branch, then kappa, until the log-likelihood moves by less than 1e-4
 // (PhyML's Round_Optimize stops at 1e-3, phyml/utilities.c:5207).  Branch lengths by Newton's method (edge_newton).  kappa, whose
 // every evaluation is a pass over the whole tree: a Newton step from three likelihood values one per cent apart (the round's closing
@@ -574,12 +594,16 @@ RC_HD void branch_pass(Work &k, Exec &ex) {
 // double or halve kappa, the bracketing minimiser on a bracket around the current value instead (a factor 4 either way in the first
 // round, 2 later).  Written as one loop around ONE evaluation of the likelihood -- what the value is for is a small state -- so that
 // the code of the tree pass exists once (the kernel's instruction stream has to fit the instruction cache).
+// The modes of a given topology (fit_given) are states of the same loop: kFitFixed leaves out the branch pass; kFitScale leaves it out
+// too and puts a search for the scale s in [1e-3, 1e3] before kappa's, by the same three probes, Newton step and LocalMin fallback
+// (st.kap / st.h / st.lm hold whichever parameter is being searched, st.param says which).
 template <typename Exec>
 RC_HD double optimise(Work &k, Exec &ex) {
   enum { kClose, kProbe, kSearch };   // the value is: the round's closing likelihood / one of the three probes / an evaluation of the search
   OptState &st = *k.opt;
   st.what = kClose; st.round = -1; st.probe = 0;
   st.prev = 0; st.kap = k.mod.kappa; st.h = 0; st.f0 = 0; st.f1 = 0;
+  st.scale = 1.0; st.param = 0;
   for (;;) {
     ex.sync();
     ex.mark(8);
@@ -590,38 +614,46 @@ RC_HD double optimise(Work &k, Exec &ex) {
       if (st.round >= 0 && fabs(lnl - st.prev) < 1e-4) return lnl;
       st.prev = lnl;
       if (++st.round >= 60) return lnl;
-      ex.sync();
-      ex.count(11);
-      branch_pass(k, ex);
-      st.kap = k.mod.kappa; st.h = 0.01 * st.kap;
+      if (k.mode == kFitBranches) {
+        ex.sync();
+        ex.count(11);
+        branch_pass(k, ex);
+      }
+      st.param = k.mode == kFitScale ? 1 : 0;
+      st.kap = st.param ? st.scale : k.mod.kappa; st.h = 0.01 * st.kap;
       st.what = kProbe; st.probe = 0;
-      k.mod.set(k.pi, st.kap - st.h);
+      set_param(k, ex, st.param, st.kap - st.h);
     } else if (st.what == kProbe) {
       const double f = -lnl;
-      if (st.probe == 0) { st.f0 = f; st.probe = 1; k.mod.set(k.pi, st.kap); }
-      else if (st.probe == 1) { st.f1 = f; st.probe = 2; k.mod.set(k.pi, st.kap + st.h); }
+      if (st.probe == 0) { st.f0 = f; st.probe = 1; set_param(k, ex, st.param, st.kap); }
+      else if (st.probe == 1) { st.f1 = f; st.probe = 2; set_param(k, ex, st.param, st.kap + st.h); }
       else {
+        const double lo = st.param ? 1e-3 : 0.1, hi = st.param ? 1e3 : 100.0;
         const double kap = st.kap, h = st.h, f0 = st.f0, f1 = st.f1;
         const double c = f0 - 2 * f1 + f;
         const double kn = c > 0 ? kap + 0.5 * h * (f0 - f) / c : 0.0;
-        if (c > 0 && kn > 0.5 * kap && kn < 2.0 * kap && kn > 0.1 && kn < 100.0) { st.kap = kn; close = true; }
-        else { st.lm.start(0.1, 100.0, kap, st.round == 0 ? 4.0 : 2.0, 1e-5, 60); st.what = kSearch; k.mod.set(k.pi, st.lm.u); }
+        if (c > 0 && kn > 0.5 * kap && kn < 2.0 * kap && kn > lo && kn < hi) { st.kap = kn; close = true; }
+        else { st.lm.start(lo, hi, kap, st.round == 0 ? 4.0 : 2.0, 1e-5, 60); st.what = kSearch; set_param(k, ex, st.param, st.lm.u); }
       }
     } else {
-      if (st.lm.feed(-lnl)) k.mod.set(k.pi, st.lm.u);
+      if (st.lm.feed(-lnl)) set_param(k, ex, st.param, st.lm.u);
       else { st.kap = st.lm.x; close = true; }
     }
-    if (close) { k.mod.set(k.pi, st.kap); st.what = kClose; }
+    if (close) {
+      set_param(k, ex, st.param, st.kap);
+      if (st.param) {   // the scale is done: kappa's probes next, on the scaled lengths
+        st.scale = st.kap; st.param = 0;
+        st.kap = k.mod.kappa; st.h = 0.01 * st.kap;
+        st.what = kProbe; st.probe = 0;
+        set_param(k, ex, 0, st.kap - st.h);
+      } else st.what = kClose;
+    }
   }
 }
 
-// the whole fit; D must hold no data yet.  Returns the log-likelihood.
+// the starting tree of the full fit: pairwise distances under the model at kappa 4, then BIONJ; D must hold no data yet
 template <typename Exec>
-RC_HD double fit(Work &k, Exec &ex) {
-  ex.mark(0);
-  base_freqs(k, ex);
-  ex.mark(1);
-  k.mod.set(k.pi, 4.0);   // treeML.c:75
+RC_HD void bionj_start(Work &k, Exec &ex) {
   const int N = k.N, npairs = N * (N - 1) / 2;
   for (int q = ex.lane(); q < npairs; q += ex.nlanes()) {   // pair q -> (i, j), i < j
     int i = 0, rem = q;
@@ -640,9 +672,27 @@ RC_HD double fit(Work &k, Exec &ex) {
   }
   ex.sync();
   k.root = ex.broadcast_root(k.root);
+}
+
+// The whole fit.  given = false: the full fit (bionj_start's tree).  given = true: the fit on a GIVEN topology (a species tree
+// pruned to the block's rows, rc_species.cpp) -- the caller has filled root, parent, nchild, child, preorder, the starting lengths in
+// len and len0, and mode; no distances, no BIONJ.  Either way kappa starts at 4.0, and optimise() is called at this one place (the
+// kernel calls fit_any, not fit and fit_given: one copy of the tree pass).  Returns the log-likelihood; kFitScale's factor is
+// opt->scale.
+template <typename Exec>
+RC_HD double fit_any(Work &k, Exec &ex, bool given) {
+  ex.mark(0);
+  base_freqs(k, ex);
+  ex.mark(1);
+  k.mod.set(k.pi, 4.0);   // treeML.c:75
+  if (!given) bionj_start(k, ex);
   ex.mark(3);
   return optimise(k, ex);
 }
+template <typename Exec>
+RC_HD double fit(Work &k, Exec &ex) { return fit_any(k, ex, false); }
+template <typename Exec>
+RC_HD double fit_given(Work &k, Exec &ex) { return fit_any(k, ex, true); }
 
 }  // namespace treefit
 }  // namespace rc

@@ -85,16 +85,33 @@ template <bool BIG>
 __device__ __forceinline__ void tree_fit_body(const TreeJob *jobs, const uint8_t *in, double *scratch, double *results) {
   const TreeJob j = jobs[blockIdx.x];
   treefit::Work k;
-  const int N = j.N, P = j.P, nn = 2 * N - 2, nI = N > 3 ? N - 3 : 0;   // column slots: the internal nodes below the root (bionj numbers the root last)
+  // column slots: the internal nodes below the root (bionj numbers the root last, and so does a given topology, rc_species.cpp)
+  const int N = j.N, P = j.P, nn = 2 * N - 2, nI = N > 3 ? N - 3 : 0;
+  const bool given = j.mode >= 0;   // a species tree's topology travels in the job (no distances, no BIONJ, no 64-tip bound)
   k.N = N; k.P = P; k.nn = nn; k.root = 0;
-  const TreeLdsLayout lay = tree_lds_layout(N, P, BIG);
+  k.mode = given ? j.mode : treefit::kFitBranches;
+  const TreeLdsLayout lay = tree_lds_layout(N, P, BIG, given);
   double *d = tree_lds;
   k.len = d + lay.len; k.coef = reinterpret_cast<treefit::Coef *>(d + lay.coef); k.e3 = d + lay.e3;
-  k.D = d + lay.D; k.V = d + lay.V; k.tmpD = d + lay.tmpD;
+  k.D = d + lay.D; k.V = d + lay.V; k.tmpD = d + lay.tmpD; k.len0 = d + lay.len0;
   static_assert(sizeof(treefit::OptState) <= kTreeOptDoubles * sizeof(double), "OptState outgrew its LDS slot");
   k.opt = reinterpret_cast<treefit::OptState *>(d + lay.opt);
   int *ib = reinterpret_cast<int *>(d + lay.ints);
   k.parent = ib; k.nchild = ib + nn; k.child = ib + 2 * nn; k.preorder = ib + 5 * nn; k.tmpI = ib + 6 * nn;
+  if (given) {   // the topology and starting lengths into the LDS arrays BIONJ would fill (rc_launch.h, tree_topo_len_at)
+    const int *ti = reinterpret_cast<const int *>(in + j.off_topo);
+    const double *tl = reinterpret_cast<const double *>(in + j.off_topo + tree_topo_len_at(N));
+    for (int v = threadIdx.x; v < nn; v += kWave) {
+      k.parent[v] = ti[1 + v];
+      k.nchild[v] = ti[1 + nn + v];
+      for (int c = 0; c < 3; c++) k.child[3 * v + c] = ti[1 + 2 * nn + 3 * v + c];
+      k.preorder[v] = ti[1 + 5 * nn + v];
+      const double l = tl[v] > treefit::kBlMin ? tl[v] : treefit::kBlMin;   // floored as tree_lnl and the host fit do
+      k.len[v] = l;
+      d[lay.len0 + v] = l;
+    }
+    k.root = __builtin_amdgcn_readfirstlane(ti[0]);
+  }
   const uint8_t *gmask = in + j.off_mask;
   const double *gw = reinterpret_cast<const double *>(in + j.off_w);
   if constexpr (BIG) {
@@ -120,12 +137,14 @@ __device__ __forceinline__ void tree_fit_body(const TreeJob *jobs, const uint8_t
     __syncthreads();
     ex.last = clock64();
   }
-  const double lnl = treefit::fit(k, ex);
+  __syncthreads();
+  const double lnl = treefit::fit_any(k, ex, given);
   if constexpr (kTreeProfile) ex.mark(8);
   // the compact result record (rc_launch.h, tree_result_doubles)
   double *rd = results + j.off_out;
   int *ri = reinterpret_cast<int *>(rd + 2 + nn);
   if (threadIdx.x == 0) { rd[0] = k.mod.kappa; rd[1] = lnl; ri[0] = k.root; }
+  if (given && threadIdx.x == 0) rd[tree_result_doubles(N)] = k.opt->scale;
   for (int v = threadIdx.x; v < nn; v += kWave) {
     rd[2 + v] = k.len[v];
     ri[1 + v] = k.nchild[v];

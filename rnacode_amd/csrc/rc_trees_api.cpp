@@ -1,6 +1,7 @@
 // rc_trees_api.cpp -- the tree estimator's entry points (rc_fit_tree, rc_fit_trees, rc_fit_trees_device, rc_tree_lnl), the stand-alone
 // EVD fit, p-values and the MT19937 accessor.
 #include "rc_runtime.h"
+#include "rc_tree_core.h"
 
 extern "C" {
 
@@ -50,16 +51,27 @@ int rc_fit_trees(const rc_block *blocks, int32_t n_blocks, char *newick_out, int
   return done.load();
 }
 
+}  // extern "C"
+
+struct rc_species_tree { rc::SpeciesTree st; };
+
 // The same fits on the GPU, one wavefront per block (rc_tree_kernel.hip).  Host work: pattern
 // compression (threads) and writing the Newick text.
 static constexpr int kTreeDeviceTips = 64;   // treefit::kMaxTipsDevice (rc_tree_core.h)
 
-int rc_fit_trees_device(rc_ctx *c, const rc_block *blocks, int32_t n_blocks, char *newick_out, int32_t cap, float *kappa_out,
-                        double *lnl_out) {
-  if (!c || !blocks || !newick_out || !kappa_out || n_blocks < 0 || cap < 8) return fail(RC_ERR_ARG, "bad argument");
+// rc_species_tree's modes -> rc_tree_core.h's
+static int fit_mode_of(int32_t mode) {
+  return mode == RC_SPECIES_FIXED ? treefit::kFitFixed : (mode == RC_SPECIES_SCALE ? treefit::kFitScale : treefit::kFitBranches);
+}
+
+// sp == nullptr: the full fit (rc_fit_trees_device); else every block on sp pruned to its rows, fitted in `mode` (rc_tree_core.h) --
+// on the device up to the host estimator's 512 tips, the topology travelling in the job
+static int fit_trees_device(rc_ctx *c, const SpeciesTree *sp, int mode, const rc_block *blocks, int32_t n_blocks, char *newick_out,
+                            int32_t cap, float *kappa_out, double *lnl_out, double *scale_out, int32_t *on_device_out) {
   HIP_TRY(hipSetDevice(c->device));
   trace("trees: call", blocks);
   std::vector<PatternSet> ps(n_blocks);
+  std::vector<Topology> topo(sp ? n_blocks : 0);
   std::vector<char> ok(n_blocks, 0);
   {
     std::atomic<int> next{0};
@@ -73,7 +85,11 @@ int rc_fit_trees_device(rc_ctx *c, const rc_block *blocks, int32_t n_blocks, cha
         int L = 0;
         for (const char *p = b.rows[0]; *p; p++) L += (*p != '-');
         if (L < 3) continue;
-        if (b.n_rows > kTreeDeviceTips) {   // more tips than the kernel's per-lane tables hold: the host estimator, here on this thread
+        if (sp) {
+          std::string err;
+          ok[i] = species_prune(*sp, b.n_rows, b.names, topo[i], err) ? 1 : 0;
+          if (!ok[i]) continue;
+        } else if (b.n_rows > kTreeDeviceTips) {   // more tips than the kernel's per-lane tables hold: the host estimator, here on this thread
           std::vector<std::string> rows(b.n_rows), names(b.n_rows);
           for (int r = 0; r < b.n_rows; r++) { rows[r] = b.rows[r]; names[r] = b.names[r]; }
           std::string nwk, err;
@@ -125,11 +141,13 @@ int rc_fit_trees_device(rc_ctx *c, const rc_block *blocks, int32_t n_blocks, cha
     if (ok[i] == 2) { hostDone++; continue; }   // fitted on the host above
     newick_out[static_cast<size_t>(i) * cap] = 0; kappa_out[i] = 0.0f;
     if (lnl_out) lnl_out[i] = 0.0;
+    if (scale_out) scale_out[i] = 0.0;
+    if (on_device_out) on_device_out[i] = 0;
     if (!ok[i]) continue;
-    const size_t need = tree_fit_lds_bytes(ps[i].N, ps[i].P, false);
+    const size_t need = tree_fit_lds_bytes(ps[i].N, ps[i].P, false, sp != nullptr);
     if (need > ldsMax) {
       launches[0].blocks.push_back(i);
-      launches[0].lds = std::max(launches[0].lds, tree_fit_lds_bytes(ps[i].N, ps[i].P, true));
+      launches[0].lds = std::max(launches[0].lds, tree_fit_lds_bytes(ps[i].N, ps[i].P, true, sp != nullptr));
       continue;
     }
     const int occ = static_cast<int>(std::min<size_t>(static_cast<size_t>(occReg), c->ldsPerCU / std::max<size_t>(need, 1)));
@@ -147,14 +165,16 @@ int rc_fit_trees_device(rc_ctx *c, const rc_block *blocks, int32_t n_blocks, cha
     for (int i : L.blocks) {
       TreeJob j{};
       j.N = ps[i].N; j.P = ps[i].P;
+      j.mode = sp ? mode : -1;
       j.off_mask = in_bytes;
       in_bytes = (in_bytes + ps[i].mask.size() + 7) & ~static_cast<size_t>(7);
       j.off_w = in_bytes;
       in_bytes += sizeof(double) * ps[i].P;
+      if (sp) { j.off_topo = in_bytes; in_bytes += tree_topo_bytes(j.N); }
       j.off_work = work_doubles;
       if (L.big) work_doubles += tree_work_doubles(j.N, j.P);
       j.off_out = res_doubles;
-      res_doubles += tree_result_doubles(j.N);
+      res_doubles += tree_result_doubles(j.N) + (sp ? 1 : 0);
       jobs.push_back(j);
       owner.push_back(i);
     }
@@ -202,6 +222,17 @@ int rc_fit_trees_device(rc_ctx *c, const rc_block *blocks, int32_t n_blocks, cha
         const PatternSet &p = ps[owner[q]];
         std::memcpy(in + jobs[q].off_mask, p.mask.data(), p.mask.size());
         std::memcpy(in + jobs[q].off_w, p.w.data(), sizeof(double) * p.P);
+        if (sp) {
+          const Topology &t = topo[owner[q]];
+          const size_t nn = static_cast<size_t>(t.nn());
+          int *ti = reinterpret_cast<int *>(in + jobs[q].off_topo);
+          ti[0] = t.root;
+          std::memcpy(ti + 1, t.parent.data(), sizeof(int) * nn);
+          std::memcpy(ti + 1 + nn, t.nchild.data(), sizeof(int) * nn);
+          std::memcpy(ti + 1 + 2 * nn, t.child.data(), sizeof(int) * 3 * nn);
+          std::memcpy(ti + 1 + 5 * nn, t.preorder.data(), sizeof(int) * nn);
+          std::memcpy(in + jobs[q].off_topo + tree_topo_len_at(t.N), t.len.data(), sizeof(double) * nn);
+        }
       }
     };
     std::vector<std::thread> th;
@@ -283,6 +314,8 @@ int rc_fit_trees_device(rc_ctx *c, const rc_block *blocks, int32_t n_blocks, cha
         std::memcpy(newick_out + static_cast<size_t>(i) * cap, nwk.c_str(), nwk.size() + 1);
         kappa_out[i] = static_cast<float>(rd[0]);
         if (lnl_out) lnl_out[i] = rd[1];
+        if (scale_out) scale_out[i] = sp ? rd[tree_result_doubles(jobs[q].N)] : 1.0;
+        if (on_device_out) on_device_out[i] = 1;
         done.fetch_add(1);
       }
     };
@@ -293,6 +326,92 @@ int rc_fit_trees_device(rc_ctx *c, const rc_block *blocks, int32_t n_blocks, cha
   }
   trace("trees: newick", blocks);
   return done.load() + hostDone;
+}
+
+extern "C" {
+
+int rc_fit_trees_device(rc_ctx *c, const rc_block *blocks, int32_t n_blocks, char *newick_out, int32_t cap, float *kappa_out,
+                        double *lnl_out) {
+  if (!c || !blocks || !newick_out || !kappa_out || n_blocks < 0 || cap < 8) return fail(RC_ERR_ARG, "bad argument");
+  return fit_trees_device(c, nullptr, 0, blocks, n_blocks, newick_out, cap, kappa_out, lnl_out, nullptr, nullptr);
+}
+
+int rc_species_tree_create(const char *newick, rc_species_tree **out) {
+  if (!newick || !out) return fail(RC_ERR_ARG, "bad argument");
+  *out = nullptr;
+  auto *t = new rc_species_tree;
+  std::string err;
+  if (!species_tree_parse(newick, t->st, err)) { delete t; return fail(RC_ERR_ARG, err); }
+  *out = t;
+  return RC_OK;
+}
+
+void rc_species_tree_destroy(rc_species_tree *t) { delete t; }
+
+int rc_species_tree_tips(const rc_species_tree *t) {
+  if (!t) return fail(RC_ERR_ARG, "bad argument");
+  return t->st.t.ntips();
+}
+
+int rc_species_tree_prune(const rc_species_tree *t, const rc_block *blk, char *newick_out, int32_t cap) {
+  if (!t || !blk || !blk->names || !newick_out || cap < 8) return fail(RC_ERR_ARG, "bad argument");
+  Topology topo;
+  std::string err;
+  if (!species_prune(t->st, blk->n_rows, blk->names, topo, err)) return fail(RC_ERR_ARG, err);
+  std::vector<std::string> names(blk->names, blk->names + blk->n_rows);
+  const std::string nwk = newick_of(topo.N, topo.root, topo.nchild.data(), topo.child.data(), topo.len.data(), names);
+  if (static_cast<int>(nwk.size()) + 1 > cap) return fail(RC_ERR_ARG, "newick buffer too small");
+  std::memcpy(newick_out, nwk.c_str(), nwk.size() + 1);
+  return RC_OK;
+}
+
+static bool species_mode_ok(int32_t mode) { return mode == RC_SPECIES_FIXED || mode == RC_SPECIES_SCALE || mode == RC_SPECIES_BRANCHES; }
+
+int rc_fit_species_trees(const rc_species_tree *t, int32_t mode, const rc_block *blocks, int32_t n_blocks, char *newick_out, int32_t cap,
+                         float *kappa_out, double *scale_out, int32_t threads) {
+  if (!t || !species_mode_ok(mode) || !blocks || !newick_out || !kappa_out || n_blocks < 0 || cap < 8) return fail(RC_ERR_ARG, "bad argument");
+  std::atomic<int> next{0}, done{0};
+  unsigned nt = threads > 0 ? static_cast<unsigned>(threads) : static_cast<unsigned>(std::min(effective_cpus(), 32));
+  nt = std::min<unsigned>(nt, static_cast<unsigned>(std::max(1, n_blocks)));
+  auto work = [&]() {
+    for (;;) {
+      const int i = next.fetch_add(1);
+      if (i >= n_blocks) break;
+      char *dst = newick_out + static_cast<size_t>(i) * cap;
+      dst[0] = 0; kappa_out[i] = 0.0f;
+      if (scale_out) scale_out[i] = 0.0;
+      const rc_block &b = blocks[i];
+      if (!b.rows || !b.names || b.n_rows <= 2) continue;
+      int L = 0;
+      for (const char *p = b.rows[0]; *p; p++) L += (*p != '-');
+      if (L < 3) continue;
+      Topology topo;
+      PatternSet ps;
+      std::string nwk, err;
+      if (!species_prune(t->st, b.n_rows, b.names, topo, err)) continue;
+      std::vector<std::string> rows(b.rows, b.rows + b.n_rows), names(b.names, b.names + b.n_rows);
+      if (!compress_patterns(rows, ps, err)) continue;
+      float kappa = 0;
+      double s = 1.0;
+      if (!fit_given_tree(ps, topo, fit_mode_of(mode), names, nwk, kappa, nullptr, &s, err) || static_cast<int>(nwk.size()) + 1 > cap) continue;
+      std::memcpy(dst, nwk.c_str(), nwk.size() + 1);
+      kappa_out[i] = kappa;
+      if (scale_out) scale_out[i] = s;
+      done.fetch_add(1);
+    }
+  };
+  std::vector<std::thread> th;
+  for (unsigned k = 1; k < nt; k++) th.emplace_back(work);
+  work();
+  for (auto &x : th) x.join();
+  return done.load();
+}
+
+int rc_fit_species_trees_device(rc_ctx *c, const rc_species_tree *t, int32_t mode, const rc_block *blocks, int32_t n_blocks,
+                                char *newick_out, int32_t cap, float *kappa_out, double *lnl_out, double *scale_out,
+                                int32_t *on_device_out) {
+  if (!c || !t || !species_mode_ok(mode) || !blocks || !newick_out || !kappa_out || n_blocks < 0 || cap < 8) return fail(RC_ERR_ARG, "bad argument");
+  return fit_trees_device(c, &t->st, fit_mode_of(mode), blocks, n_blocks, newick_out, cap, kappa_out, lnl_out, scale_out, on_device_out);
 }
 
 int rc_tree_lnl(const rc_block *blk, double *lnl_out) {
