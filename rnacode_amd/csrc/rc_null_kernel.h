@@ -196,6 +196,13 @@ __device__ __forceinline__ void sample_scan_last(const SampleScan &st, float &be
 // one ROW RANGE of one strand x frame part from those codes, its S values going to a buffer instead of through the scan;
 // k_null_rowscan folds them afterwards.  MODE 0: the whole item (or one strand x frame part of it) in one workgroup.
 struct DeepFetch {};   // `kind` of a cell in the span loops that fetch TWO cells ahead (see "two cells of distance" in null_body)
+// the next site of a cell in a group of the two-row loop (codes staged in LDS): its words lie OFF bytes behind the group's base address `at`
+template <int OFF> struct StagedSite { uint32_t at; };
+template <typename T> struct IsStagedSite : std::false_type {};
+template <int OFF> struct IsStagedSite<StagedSite<OFF>> : std::true_type {};
+template <int OFF> constexpr int staged_off(StagedSite<OFF>) { return OFF; }
+__device__ __forceinline__ int site_index(int j) { return j; }
+template <int OFF> __device__ __forceinline__ int site_index(StagedSite<OFF>) { return 0; }   // (only the L2 path uses the index itself)
 
 template <int NK, bool LDSC, bool EXACT, bool DUAL, int MODE = 0>
 __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__restrict__ blob,
@@ -601,6 +608,19 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
 #endif
           }
         };
+        auto fetch_staged_at = [&](uint32_t (&w)[NCW], auto site) {  // the same at a group's base address and a constant offset
+          constexpr int off = staged_off(decltype(site){});
+          static_assert(off + NCW * kWave * 4 <= 65536, "ds_read offset: 16 bits");
+          const uint32_t at = site.at;
+#pragma unroll
+          for (int x = 0; x < NCW; x++) {
+#ifdef RC_PLAIN_FETCH
+            w[x] = *reinterpret_cast<const uint32_t *>(ldsBytesAll + at + off + x * kWave * 4);
+#else
+            asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(w[x]) : "v"(at), "n"(off + x * kWave * 4));
+#endif
+          }
+        };
         auto fetch_cached = [&](uint32_t (&w)[NCW], int j) {        // suffix cache: site j >= jc, the scratch's layout
           const uint32_t off = static_cast<uint32_t>(j - jc) * kCacheSiteBytes;
 #ifdef RC_PLAIN_FETCH
@@ -671,14 +691,14 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
         // latency.  (As plain C++ loads into a second register set the compiler's own wait-count placement waited for them twenty
         // instructions after they had been issued: its analysis merges the loop-entry state, where the first words are still on
         // their way, into the loop.)
-        auto lookup = [&](uint32_t (&w)[NCW], float (&sig)[NK], int jn, auto scalarLoadsNearby, auto kind) {   // (kind: unused)
+        auto lookup = [&](uint32_t (&w)[NCW], float (&sig)[NK], auto jn, auto scalarLoadsNearby, auto kind) {   // (kind: unused)
           if constexpr (LDSC) {
 #pragma unroll
             for (int x = 0; x < NCW; x++) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(w[x]));
           }
           // the global fetch's scalar base, settled HERE: a VMEM instruction must not read an SGPR within five wait states of the scalar
           // instruction that wrote it, and the compiler's hazard recognizer does not look inside inline asm -- the look-ups below lie between
-          const uint32_t *pnext = sbase + static_cast<size_t>(jn) * kSiteWords;
+          const uint32_t *pnext = sbase + static_cast<size_t>(site_index(jn)) * kSiteWords;
           if constexpr (!LDSC && !EXACT) asm volatile("" : "+s"(pnext));
           static_for<NK>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
@@ -727,7 +747,8 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
             });
           };
           if constexpr (LDSC) {
-            fetch_staged(w, jn);
+            if constexpr (IsStagedSite<std::decay_t<decltype(jn)>>::value) fetch_staged_at(w, jn);
+            else fetch_staged(w, jn);
             wait_lookups(std::integral_constant<int, NCW>{});
           } else if constexpr (!EXACT) {
             // the fetch goes out as early as it can (the look-ups have read w when they were issued): the next call waits for it, and
@@ -882,9 +903,10 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
           // rows below it; other rows go alone.
           typedef float RowBuf __attribute__((ext_vector_type(32)));
           constexpr int kBuf = 32;
+          constexpr int kGroup = 4;   // cells per group in the span loops (codes staged in LDS)
           RowBuf buf = {};
           Regs RB;   // row a + 1 (its lut members are not used)
-          auto pristine2 = [&](uint32_t (&w)[NCW], float &wvA, float &wvB, int jn, float &vB, auto kd) -> float {
+          auto pristine2 = [&](uint32_t (&w)[NCW], float &wvA, float &wvB, auto jn, float &vB, auto kd) -> float {
             float sig[NK];
             lookup(w, sig, jn, std::false_type{}, kd);
             wvA = wvA + omega_v;
@@ -904,7 +926,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
             vB = finish(sumB);
             return finish(sumA);
           };
-          auto fast2 = [&](uint32_t (&w)[NCW], int jn, float &vB, auto kd) -> float {
+          auto fast2 = [&](uint32_t (&w)[NCW], auto jn, float &vB, auto kd) -> float {
             float sig[NK];
             lookup(w, sig, jn, std::false_type{}, kd);
             float sumA = 0.0f, sumB = 0.0f;
@@ -926,7 +948,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
             vB = finish(sumB);
             return finish(sumA);
           };
-          auto tail2 = [&](uint32_t (&w)[NCW], int jn, float &vB, auto kd) -> float {
+          auto tail2 = [&](uint32_t (&w)[NCW], auto jn, float &vB, auto kd) -> float {
             float sig[NK];
             lookup(w, sig, jn, std::false_type{}, kd);
             float sumA = 0.0f, sumB = 0.0f;
@@ -1029,10 +1051,49 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                     for (int x = 0; x < NCW; x++) asm volatile("s_waitcnt vmcnt(0)" : "+v"(wB[x]));   // (pending registers are not given away)
                   }
                 }
+                if constexpr (LDSC) {
+                  // Codes staged in LDS: the cells go in GROUPS of kGroup, one loop test, one buffer index and one s_set_gpr_idx window per
+                  // group; the next sites' words come from one base address plus a constant offset per cell.  The cells whose row a + 1 values
+                  // are thrown away (in front of b0) go first, without a buffer write; a group never reaches the frame's final site (whose
+                  // cell fetches no further site), so no cell of a group needs the clamp of the next site.  The rest: one cell at a time.
+                  for (const int pe = e < b0 ? e : b0; j < pe; j++) {   // (j < b0 <= sites - 1: the next site exists)
+                    float vB;
+                    const float v = fn(wcur, j + 1, vB, std::true_type{});
+                    sample_scan_step(st, v, j2f, negTie);
+                    const float two_c = two_v;
+                    asm volatile("v_add_f32 %0, %1, %0" : "+v"(j2f) : "v"(two_c));
+                  }
+                  const int ge = e < sites - 1 ? e : sites - 1;
+                  for (; j + kGroup <= ge; j += kGroup) {
+                    const uint32_t at = ldsLane + static_cast<uint32_t>(j + 1) * (NCW * kWave * 4u);
+                    float vB[kGroup];
+                    static_for<kGroup>([&](auto uc) {
+                      constexpr int u = decltype(uc)::value;
+                      const float v = fn(wcur, StagedSite<u * NCW * kWave * 4>{at}, vB[u], std::true_type{});
+                      sample_scan_step(st, v, j2f, negTie);
+                      const float two_c = two_v;
+                      asm volatile("v_add_f32 %0, %1, %0" : "+v"(j2f) : "v"(two_c));
+                    });
+                    // the group's values into entries idx .. idx + kGroup - 1 (idx >= 0: j >= b0), one index for all: the scheduling
+                    // barriers keep the indexed moves side by side, where one s_set_gpr_idx_on .. off window takes them all
+                    // (the index settled in an SGPR of its own and known not to be negative -- the mask changes no value, 0 <= idx <= kBuf - kGroup
+                    // - 1 -- lets u fold into the moves' register operand: on a base that might be negative the compiler adds each index anew,
+                    // and the windows stay apart)
+                    int idxRaw = j - b0;
+                    asm volatile("" : "+s"(idxRaw));
+                    const int idx = idxRaw & (kBuf - 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                    static_for<kGroup>([&](auto uc) {
+                      constexpr int u = decltype(uc)::value;
+                      buf[idx + u] = vB[u];
+                    });
+                    __builtin_amdgcn_sched_barrier(0);
+                  }
+                }
                 for (; j < e; j++) pair_cell(wcur, j, j + 1 < sites ? j + 1 : j, std::true_type{}, fn);
               };
               {
-                dspan(next_event(j, sites), [&](uint32_t (&w)[NCW], int jn, float &vB, auto kd) { return pristine2(w, wvA, wvB, jn, vB, kd); });
+                dspan(next_event(j, sites), [&](uint32_t (&w)[NCW], auto jn, float &vB, auto kd) { return pristine2(w, wvA, wvB, jn, vB, kd); });
                 static_for<NK>([&](auto kc) {
                   constexpr int k = decltype(kc)::value;
                   auto &r = R.template at<k>();
@@ -1056,9 +1117,9 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                     auto &rb = RB.template at<k>();
                     rb.s1 = fmaxf(rb.s1, rb.s2);
                   });
-                  dspan(e, [&](uint32_t (&w)[NCW], int jn, float &vB, auto kd) { return tail2(w, jn, vB, kd); });
+                  dspan(e, [&](uint32_t (&w)[NCW], auto jn, float &vB, auto kd) { return tail2(w, jn, vB, kd); });
                 }
-                dspan(e, [&](uint32_t (&w)[NCW], int jn, float &vB, auto kd) { return fast2(w, jn, vB, kd); });
+                dspan(e, [&](uint32_t (&w)[NCW], auto jn, float &vB, auto kd) { return fast2(w, jn, vB, kd); });
               }
 #pragma unroll
               for (int x = 0; x < NCW; x++) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wcur[x]));
@@ -1337,7 +1398,9 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
 // register copied).  profiles/r06/rows_sweep_before.txt, rows_sweep_forced_occupancy.txt, rows_sweep_after.txt.
 // 7, 10 and 11 rows: the second register set of the two-cell fetch distance cost these three a wavefront (78 -> 83, 90 -> 97, 95 -> 103 VGPRs); told
 // what to aim for, the register allocator fits them into 78 / 89 / 94 again without a single spill.
-constexpr int null_min_waves(int NK, bool EXACT, bool DUAL, int MODE) { return (EXACT || DUAL || MODE != 0) ? 1 : NK == 6 ? 6 : (NK == 9 || NK == 10) ? 5 : (NK >= 16 && NK <= 21) ? 4 : (NK >= 24 && NK <= 29) ? 3 : 1; }
+// Two rows per pass: four wavefronts per SIMD (16 per CU is what the staged codes' LDS allows).  The cell groups of the span loops took
+// k_null<5, true, false, true> from 127 to 129 VGPRs on their own; held to four, it fits 128 with nothing spilled.
+constexpr int null_min_waves(int NK, bool EXACT, bool DUAL, int MODE) { return DUAL ? 4 : (EXACT || MODE != 0) ? 1 : NK == 6 ? 6 : (NK == 9 || NK == 10) ? 5 : (NK >= 16 && NK <= 21) ? 4 : (NK >= 24 && NK <= 29) ? 3 : 1; }
 template <int NK, bool LDSC, bool EXACT, bool DUAL = false, int MODE = 0>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(null_min_waves(NK, EXACT, DUAL, MODE))))
 void k_null(NullArgs A, const uint8_t *__restrict__ blob,
