@@ -23,10 +23,12 @@ extern "C" {
 #define RC_ERR_UNSUPPORTED (-3) /* shape outside the built kernels (N > RC_MAX_ROWS, more than RC_MAX_COLS columns) */
 #define RC_ERR_SKIP (-4)        /* block the reference driver skips (RNAcode.c:142-150) */
 
-#define RC_MAX_ROWS 500         /* rows per block, the reference's own limit (MAX_NUM_NAMES, rnaz_utils.h:7).  N <= 32 runs the
-                                   register-resident kernels, 33..64 a slower instantiation of the same code, 65..500 generic kernels
-                                   (sequence-by-sequence over register-tiled rows, codes in a global scratch); the built-in tree estimator
-                                   runs on the GPU for up to 64 rows and on host threads for wider blocks */
+#define RC_MAX_ROWS 500         /* rows per block, the reference's own limit (MAX_NUM_NAMES, rnaz_utils.h:7).  By default up to 31 rows
+                                   run the register-resident kernels; from 32 rows on, blocks short enough (200 reference residues, 250
+                                   at 37..64 rows, any length from 112 rows) a kernel that scores the sequences in tiles, the others a
+                                   slower instantiation of the register-resident code up to 36 rows and generic kernels (sequence by
+                                   sequence, codes in a global scratch) from 37 (RC_GENERIC_MIN_ROWS, RC_TILED_*); the built-in tree
+                                   estimator runs on the GPU for up to 64 rows and on host threads for wider blocks */
 #define RC_MAX_COLS 65535       /* alignment columns per block (16-bit column indices); longer blocks get the status RC_ERR_UNSUPPORTED --
                                    the reference's breakMAF.pl (python -m rnacode_amd.breakmaf) splits them first, as its README asks */
 /* Two further bounds on a block's size.  (1) Device memory: the MT19937 streams of a block take 4 bytes x (2 rows - 1) x columns x
@@ -216,7 +218,7 @@ int rc_batch_work(const rc_batch *b, int64_t *sample_alignments, int64_t *column
  * t[3] native scoring kernels, t[4] EVD fit kernel.  n_launch[i] = launches behind t[i]. */
 int rc_batch_timing(const rc_batch *b, float t[5], int32_t n_launch[5]);
 /* The null-sampling kernel instantiation that did most of the last run's work, spelled as a profiler prints it
- * ("rc::k_null<5, true, false>"): lets a benchmark check that counter data it quotes belongs to the kernel it timed. */
+ * ("rc::k_null<5, true, false, true, 0>"): lets a benchmark check that counter data it quotes belongs to the kernel it timed. */
 const char *rc_batch_null_kernel(const rc_batch *b);
 /* Preparation of the batch: wall time of the host part (ms), duration of the device kernels that make the
  * expected-score tables (ms, known after a run), bytes copied to the device. */

@@ -292,13 +292,14 @@ int batch_run_async(rc_batch *b, bool streaming) {
     if (b->par.stopEarly && fa.stopCutoff >= 0 && fa.stopCutoff < sampleN && static_cast<long long>(b->okBlocks.size()) * groups >= c->stopTwoRoundsMinItems)
       g1 = std::min(groups, (fa.stopCutoff + 1 + kWave + kWave - 1) / kWave);
     {   // one staging scratch for all rounds
-      size_t need = 0, most = 0;
+      size_t most = 0;
       int r = 0;
       b->sbufNeed = 0;
       for (int lo = 0, hi = g1; lo < groups; r++) {
         if (r == c->stopRounds - 1) hi = groups;
-        RC_TRY(launch_null_groups(R, lo, hi, r, 0, &need));
-        most = std::max(most, need);
+        size_t sbuf = 0;
+        most = std::max(most, null_round_need(R, lo, hi, &sbuf));
+        b->sbufNeed = std::max(b->sbufNeed, sbuf);
         lo = hi; hi = std::min(groups, hi * 2);
       }
       HIP_TRY(b->dscratch.ensure(most * sizeof(uint32_t)));

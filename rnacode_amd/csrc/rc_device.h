@@ -15,15 +15,15 @@ namespace rc {
 constexpr int kMaxRows = 500;     // N <= 500 (RC_MAX_ROWS, the reference's MAX_NUM_NAMES, rnaz_utils.h:7)
 constexpr int kTemplRows = 64;    // N <= 64: kernels instantiated per N-1 (k_null<N-1>, k_native_dp<N-1>); above: k_generic_sim + k_generic_dp
 constexpr int kFastRows = 32;     // N <= 32: register-resident fast instantiations; 33..64 the EXACT instantiation only
-constexpr int kGenericDefaultMinRows = 37;   // rc_ctx::genericMinRows: from this many rows on the generic kernels are the faster ones (RC_GENERIC_MIN_ROWS overrides, 65 = never below 65)
+constexpr int kGenericDefaultMinRows = 37;   // ClassRule::genericMinRows: from this many rows on the generic kernels are the faster ones (RC_GENERIC_MIN_ROWS overrides, 65 = never below 65)
 constexpr int kGenericClass = kTemplRows;   // row-count classes are indexed by N-1 (2..63); all wider blocks share this one
 // k_tiled_dp<KT> (rc_null_tiled.h): blocks of kTiledMinRows rows and more whose sequences besides the reference are scored in T tiles of KT (12..15)
 // with the running sum of a cell carried from tile to tile -- one class per tile size behind the generic one
 constexpr int kTiledMinKT = 12, kTiledMaxKT = 15;
 constexpr int kTiledClass0 = kGenericClass + 1;                                   // class of KT = kTiledMinKT
 constexpr int kClassSlots = kTiledClass0 + (kTiledMaxKT - kTiledMinKT + 1);
-constexpr int kTiledDefaultMinRows = 32;     // rc_ctx::tiledMinRows (RC_TILED_MIN_ROWS; 65 = never)
-constexpr int kTiledDefaultMaxL = 250;       // rc_ctx::tiledMaxL (RC_TILED_MAX_L): ... and only blocks of at most this many reference residues (200 below 37 rows)
+constexpr int kTiledDefaultMinRows = 32;     // ClassRule::tiledMinRows (RC_TILED_MIN_ROWS; 65 = never)
+constexpr int kTiledDefaultMaxL = 250;       // ClassRule::tiledMaxL (RC_TILED_MAX_L): ... and only blocks of at most this many reference residues (200 below 37 rows)
 // Tile size for N-1 sequences: the one that costs least by T (9 KT + 20) -- about nine instructions per sequence and cell, twenty per cell and
 // pass (the carried sum in and out, the code words, the loop), padded sequences (T KT - (N-1) of them, scored as zeros) included.
 constexpr int tiled_kt(int NK) {

@@ -1038,31 +1038,23 @@ void launch_mt_stream(uint32_t seedBase, int Spad, int D, uint32_t *U, hipStream
 }
 
 // k_null is instantiated in eight units (rc_null_a..h.hip), one per range of N-1; e..h hold the wide blocks (N-1 >= 32)
-#define RC_NULL_UNIT(S) int null_occupancy_##S(int, size_t); int null_occupancy_plain_##S(int, size_t, int); bool launch_null_##S(int, const NullArgs &, int, size_t, bool, hipStream_t);
+#define RC_NULL_UNIT(S) int null_occupancy_##S(int, NullKind, size_t); bool launch_null_##S(int, NullKind, const NullArgs &, int, size_t, hipStream_t);
 RC_NULL_UNIT(a) RC_NULL_UNIT(b) RC_NULL_UNIT(c) RC_NULL_UNIT(d) RC_NULL_UNIT(e) RC_NULL_UNIT(f) RC_NULL_UNIT(g) RC_NULL_UNIT(h)
 #undef RC_NULL_UNIT
-
-int null_occupancy(int NK, size_t ldsBytes) {
-  if (NK < 2 || NK > kTemplRows - 1) return 0;
-  return NK <= 6 ? null_occupancy_a(NK, ldsBytes) : NK <= 12 ? null_occupancy_b(NK, ldsBytes)
-       : NK <= 21 ? null_occupancy_c(NK, ldsBytes) : NK <= 31 ? null_occupancy_d(NK, ldsBytes)
-       : NK <= 39 ? null_occupancy_e(NK, ldsBytes) : NK <= 47 ? null_occupancy_f(NK, ldsBytes)
-       : NK <= 55 ? null_occupancy_g(NK, ldsBytes) : null_occupancy_h(NK, ldsBytes);
+struct NullUnit { int maxNK; int (*occupancy)(int, NullKind, size_t); bool (*launch)(int, NullKind, const NullArgs &, int, size_t, hipStream_t); };
+static const NullUnit *null_unit(int NK) {
+  static const NullUnit units[] = {{6, null_occupancy_a, launch_null_a}, {12, null_occupancy_b, launch_null_b}, {21, null_occupancy_c, launch_null_c},
+                                   {31, null_occupancy_d, launch_null_d}, {39, null_occupancy_e, launch_null_e}, {47, null_occupancy_f, launch_null_f},
+                                   {55, null_occupancy_g, launch_null_g}, {kTemplRows - 1, null_occupancy_h, launch_null_h}};
+  if (NK < 2) return nullptr;
+  for (const NullUnit &u : units) if (NK <= u.maxNK) return &u;
+  return nullptr;
 }
 
-int null_occupancy_plain(int NK, size_t dynLds, int hiOcc) {
-  if (NK < 2 || NK >= kFastRows) return 0;
-  return NK <= 6 ? null_occupancy_plain_a(NK, dynLds, hiOcc) : NK <= 12 ? null_occupancy_plain_b(NK, dynLds, hiOcc)
-       : NK <= 21 ? null_occupancy_plain_c(NK, dynLds, hiOcc) : null_occupancy_plain_d(NK, dynLds, hiOcc);
-}
-
-// N-1 >= 32: only the EXACT instantiation without code staging exists (ldsBytes and exact are ignored)
-bool launch_null(int NK, const NullArgs &a, int grid, size_t ldsBytes, bool exact, hipStream_t stream) {
-  if (NK < 2 || NK > kTemplRows - 1) return false;
-  return NK <= 6 ? launch_null_a(NK, a, grid, ldsBytes, exact, stream) : NK <= 12 ? launch_null_b(NK, a, grid, ldsBytes, exact, stream)
-       : NK <= 21 ? launch_null_c(NK, a, grid, ldsBytes, exact, stream) : NK <= 31 ? launch_null_d(NK, a, grid, ldsBytes, exact, stream)
-       : NK <= 39 ? launch_null_e(NK, a, grid, ldsBytes, exact, stream) : NK <= 47 ? launch_null_f(NK, a, grid, ldsBytes, exact, stream)
-       : NK <= 55 ? launch_null_g(NK, a, grid, ldsBytes, exact, stream) : launch_null_h(NK, a, grid, ldsBytes, exact, stream);
+int null_occupancy(int NK, NullKind kind, size_t ldsBytes) { const NullUnit *u = null_unit(NK); return u ? u->occupancy(NK, kind, ldsBytes) : 0; }
+bool launch_null(int NK, NullKind kind, const NullArgs &a, int grid, size_t ldsBytes, hipStream_t stream) {
+  const NullUnit *u = null_unit(NK);
+  return u && u->launch(NK, kind, a, grid, ldsBytes, stream);
 }
 
 #define RC_FOR_NK(X) \
@@ -1140,27 +1132,25 @@ size_t null_generic_lds_bytes(int N, int nnodes) { return generic_lds_bytes(N, n
 
 size_t null_generic_codes_bytes(int N, int L, int nnodes) { return generic_codes_bytes(N, L, nnodes); }
 size_t null_generic_state_bytes(int N, int L, int nnodes) { return generic_state_bytes(N, L, nnodes); }
-int generic_sim_occupancy(size_t ldsBytes) {
+int generic_occupancy(NullKind kind, size_t ldsBytes) {
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_generic_sim<false>, 64, ldsBytes) != hipSuccess) return 0;
-  return nb;
-}
-int generic_dp_occupancy(size_t ldsBytes) {
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_generic_dp, 64, ldsBytes) != hipSuccess) return 0;
-  return nb;
-}
-void launch_generic_sim(const NullArgs &a, int grid, size_t ldsBytes, hipStream_t stream, bool tiled) {
-  if (tiled) {
-    hipLaunchKernelGGL(k_generic_sim<true>, dim3(grid), dim3(64), ldsBytes, stream, a, a.blob, a.dblocks, a.classBlocks, a.flags, a.U, a.pair, static_cast<uint8_t *>(nullptr), a.maxima);
-    return;
+  hipError_t e = hipErrorInvalidValue;
+  switch (kind) {
+    case NullKind::GenericSim: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_generic_sim<false>, 64, ldsBytes); break;
+    case NullKind::TiledSim: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_generic_sim<true>, 64, ldsBytes); break;
+    case NullKind::GenericDp: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_generic_dp, 64, ldsBytes); break;
+    default: break;
   }
-  hipLaunchKernelGGL(k_generic_sim<false>, dim3(grid), dim3(64), ldsBytes, stream, a, a.blob, a.dblocks, a.classBlocks, a.flags, a.U, a.pair, static_cast<uint8_t *>(nullptr), a.maxima);
+  return e == hipSuccess ? nb : 0;
 }
-void launch_generic_dp(const NullArgs &a, int grid, size_t ldsBytes, uint8_t *scratchBytes, hipStream_t stream) {
-  hipLaunchKernelGGL(k_generic_dp, dim3(grid), dim3(64), ldsBytes, stream, a, a.blob, a.dblocks, a.classBlocks, a.flags, a.U, a.pair, scratchBytes, a.maxima);
+void launch_generic(NullKind kind, const NullArgs &a, int grid, size_t ldsBytes, uint8_t *scratchBytes, hipStream_t stream) {
+  if (kind == NullKind::GenericDp)
+    hipLaunchKernelGGL(k_generic_dp, dim3(grid), dim3(64), ldsBytes, stream, a, a.blob, a.dblocks, a.classBlocks, a.flags, a.U, a.pair, scratchBytes, a.maxima);
+  else if (kind == NullKind::TiledSim)
+    hipLaunchKernelGGL(k_generic_sim<true>, dim3(grid), dim3(64), ldsBytes, stream, a, a.blob, a.dblocks, a.classBlocks, a.flags, a.U, a.pair, scratchBytes, a.maxima);
+  else
+    hipLaunchKernelGGL(k_generic_sim<false>, dim3(grid), dim3(64), ldsBytes, stream, a, a.blob, a.dblocks, a.classBlocks, a.flags, a.U, a.pair, scratchBytes, a.maxima);
 }
-
 void launch_native_dp_generic(const NativeArgs &a, int nblocks, float *scratch, size_t scratchStride, hipStream_t stream) {
   hipLaunchKernelGGL(k_native_dp_generic, dim3(nblocks * 6), dim3(64), 0, stream, a, scratch, scratchStride);
 }

@@ -4,6 +4,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <string>
 
 #include "rc_device.h"
 
@@ -43,9 +44,7 @@ struct NullArgs {
   uint8_t *codesAll;          // k_generic_sim / k_generic_dp: the codes of every item of the launch pair, item u at u * codesStride
   size_t codesStride;
   int cacheSites;             // codes from L2: the words of the last cacheSites sites of a strand x frame are kept in LDS (0: none)
-  int plainLds;               // host only: dynamic LDS bytes of a launch that reads its codes from L2 (phase A's tables, then the suffix cache); 0: the default
-  int hiOcc;                  // host only: 1 = launch k_null_occ (one more wavefront per SIMD), where this N-1 has one
-  int dual;                   // 1: the instantiation that walks two rows of S per pass (N-1 <= kDualRowsMaxNK, codes staged in LDS)
+  int reserved[3];            // unused, zero: keeps the offsets of the fields below (the launch's instantiation is a NullKind, below)
   int stealWait;              // 1: a workgroup without work waits for owners that are still simulating a late item; 0: it leaves at once (a stream: the next sub-batch's workgroups want its place)
   int simParts, simGrid;      // rows split over workgroups: an item's simulation is cut into simParts site ranges, simGrid workgroups take them (k_null<.., 2>)
   unsigned int *simCounter;   // ... from queues of their own [8]
@@ -189,9 +188,44 @@ bool launch_tree_fit(const TreeJob *jobs, int njobs, bool big, size_t ldsBytes, 
 
 void launch_mt_stream(uint32_t seedBase, int Spad, int D, uint32_t *U, hipStream_t stream);
 void launch_prep(const PrepArgs &a, hipStream_t stream);   // k_prep_gaps, k_prep_models (or a variant), then k_prep_lut
-int null_occupancy(int NK, size_t ldsBytes);   // resident workgroups per CU (0 = cannot launch)
-int null_occupancy_plain(int NK, size_t dynLds, int hiOcc);   // the same for a launch that reads its codes from L2 with dynLds bytes of LDS; hiOcc: k_null_occ (0 if N-1 has none)
-bool launch_null(int NK, const NullArgs &a, int grid, size_t ldsBytes, bool exact, hipStream_t stream);
+// Every instantiation a sampling launch can run (rc_schedule.cpp plans which), apart from its N-1 or tile size: k_null's, then the wide
+// classes' (rc_schedule.cpp, occupancy, relies on that order)
+enum class NullKind {
+  Exact,          // k_null<NK, false, true>: codes from L2, the written-out recurrence (blocks flagged by k_prep_lut; N-1 >= 32: the only one)
+  Staged,         // k_null<NK, true, false>: codes staged in LDS
+  StagedTwoRow,   // k_null<NK, true, false, true>: the same, two rows of S per pass (N-1 <= kDualRowsMaxNK)
+  L2,             // k_null<NK, false, false>: codes from L2 (dynamic LDS: phase A's tables, then the suffix cache)
+  L2Occ,          // k_null_occ<NK>: the same, compiled for one more wavefront per SIMD (where N-1 has one)
+  L2TwoRow,       // k_null<NK, false, false, true>: codes from L2, two rows per pass (3 <= N-1 <= kDualRowsMaxNK)
+  RowSplit,       // k_null<NK, false, false, false, 2> on a.simGrid, then <.., 1>: a part's rows over workgroups (k_null_rowscan follows)
+  GenericSim,     // k_generic_sim<false>: the simulation of the blocks of more than 64 rows
+  TiledSim,       // k_generic_sim<true>: ... of a tiled class, its codes in k_tiled_dp's layout
+  GenericDp,      // k_generic_dp
+  TiledDp,        // k_tiled_dp<KT, false>
+  TiledDpNan,     // k_tiled_dp<KT, true>: the reference's NaN-order-dependent maxima
+};
+// the kind's kernel as rocprofv3 prints it (rc_batch_null_kernel); n: N-1 or the tile size
+inline std::string null_kernel_name(NullKind kind, int n) {
+  const std::string k = std::to_string(n);
+  switch (kind) {
+    case NullKind::Exact: return "rc::k_null<" + k + ", false, true, false, 0>";
+    case NullKind::Staged: return "rc::k_null<" + k + ", true, false, false, 0>";
+    case NullKind::StagedTwoRow: return "rc::k_null<" + k + ", true, false, true, 0>";
+    case NullKind::L2: return "rc::k_null<" + k + ", false, false, false, 0>";
+    case NullKind::L2Occ: return "rc::k_null_occ<" + k + ">";
+    case NullKind::L2TwoRow: return "rc::k_null<" + k + ", false, false, true, 0>";
+    case NullKind::RowSplit: return "rc::k_null<" + k + ", false, false, false, 1>";
+    case NullKind::GenericSim: return "rc::k_generic_sim<false>";
+    case NullKind::TiledSim: return "rc::k_generic_sim<true>";
+    case NullKind::GenericDp: return "rc::k_generic_dp";
+    case NullKind::TiledDp: return "rc::k_tiled_dp<" + k + ", false>";
+    case NullKind::TiledDpNan: return "rc::k_tiled_dp<" + k + ", true>";
+  }
+  return "";
+}
+// resident workgroups per CU of a kind's kernel with ldsBytes of dynamic LDS (0: N-1 has no such kernel); launch: false if it has none
+int null_occupancy(int NK, NullKind kind, size_t ldsBytes);
+bool launch_null(int NK, NullKind kind, const NullArgs &a, int grid, size_t ldsBytes, hipStream_t stream);
 void launch_null_rowscan(const NullArgs &a, int items, hipStream_t stream);   // getHSS over the buffers a ROWS launch of k_null left: one wavefront per (item, strand x frame)
 void launch_native_sigma(const NativeArgs &a, int nblocks, hipStream_t stream);
 bool launch_native_dp(int NK, const NativeArgs &a, int grid, hipStream_t stream);   // a.nItems items over `grid` persistent workgroups
@@ -213,15 +247,15 @@ size_t null_generic_lds_bytes(int N, int nnodes);   // packed node states + codo
 // the same in two launches (simulation with many light wavefronts, then the DP): bytes of an item's codes / of a DP workgroup's states
 size_t null_generic_codes_bytes(int N, int L, int nnodes);
 size_t null_generic_state_bytes(int N, int L, int nnodes);
-int generic_sim_occupancy(size_t ldsBytes);
-int generic_dp_occupancy(size_t ldsBytes);
-void launch_generic_sim(const NullArgs &a, int grid, size_t ldsBytes, hipStream_t stream, bool tiled = false);   // tiled: the codes in k_tiled_dp's layout
-// blocks of 28..64 rows in tiles of KT sequences (rc_null_tiled.h): bytes of an item's codes / of a DP workgroup's row buffer, occupancy, launch
+// k_generic_sim<false / true> and k_generic_dp (GenericSim, TiledSim, GenericDp): occupancy, launch (the DP reads the codes at scratchBytes)
+int generic_occupancy(NullKind kind, size_t ldsBytes);
+void launch_generic(NullKind kind, const NullArgs &a, int grid, size_t ldsBytes, uint8_t *scratchBytes, hipStream_t stream);
+// blocks of 32 rows and more that are short enough (rc_device.h, block_class) in tiles of KT sequences (rc_null_tiled.h): bytes of an item's
+// codes / of a DP workgroup's row buffer; occupancy and launch of k_tiled_dp<KT, ..> (TiledDp, TiledDpNan)
 size_t null_tiled_codes_bytes(int NK, int KT, int L);
 size_t null_tiled_state_bytes(int L);
-int tiled_dp_occupancy(int KT, size_t ldsBytes);
-bool launch_tiled_dp(int KT, bool nanSem, const NullArgs &a, int grid, size_t ldsBytes, uint8_t *scratchBytes, hipStream_t stream);
-void launch_generic_dp(const NullArgs &a, int grid, size_t ldsBytes, uint8_t *scratchBytes, hipStream_t stream);
+int tiled_dp_occupancy(int KT, NullKind kind, size_t ldsBytes);
+bool launch_tiled_dp(int KT, NullKind kind, const NullArgs &a, int grid, size_t ldsBytes, uint8_t *scratchBytes, hipStream_t stream);
 void launch_native_dp_generic(const NativeArgs &a, int nblocks, float *scratch, size_t scratchStride, hipStream_t stream);
 void launch_stop_mark(const FitArgs &a, int nblocks, hipStream_t stream);
 void launch_evd_fit(const FitArgs &a, int nblocks, bool latency, hipStream_t stream);   // latency: no other batch is in flight

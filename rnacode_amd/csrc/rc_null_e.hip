@@ -2,5 +2,5 @@
 #include "rc_null_kernel.h"
 
 namespace rc {
-RC_DEFINE_NULL_WIDE_RANGE(e, 32, 39)
+RC_DEFINE_NULL_RANGE(e, 32, 39)
 }  // namespace rc

@@ -2,5 +2,5 @@
 #include "rc_null_kernel.h"
 
 namespace rc {
-RC_DEFINE_NULL_WIDE_RANGE(f, 40, 47)
+RC_DEFINE_NULL_RANGE(f, 40, 47)
 }  // namespace rc

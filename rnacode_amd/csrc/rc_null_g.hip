@@ -2,5 +2,5 @@
 #include "rc_null_kernel.h"
 
 namespace rc {
-RC_DEFINE_NULL_WIDE_RANGE(g, 48, 55)
+RC_DEFINE_NULL_RANGE(g, 48, 55)
 }  // namespace rc

@@ -2,5 +2,5 @@
 #include "rc_null_kernel.h"
 
 namespace rc {
-RC_DEFINE_NULL_WIDE_RANGE(h, 56, 63)
+RC_DEFINE_NULL_RANGE(h, 56, 63)
 }  // namespace rc

@@ -225,7 +225,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
   using Regs = KRegs<std::make_integer_sequence<int, NK>>;
   // DUAL: two rows of S per pass (see "rows a and a + 1 together" below): for instantiations whose codes are staged in LDS and whose
   // register budget has room for a second row's states and a 32-entry row buffer at four wavefronts per SIMD.  The host picks it per
-  // launch (NullArgs::dual): up to 127 VGPRs instead of 74, i.e. no other kernel shares a SIMD with four such wavefronts.
+  // launch (NullKind::StagedTwoRow, L2TwoRow): up to 127 VGPRs instead of 74, i.e. no other kernel shares a SIMD with four such wavefronts.
   static_assert(!DUAL || (!EXACT && NK <= kDualRowsMaxNK), "two rows per pass: fast division, few sequences");
   static_assert(!(LDSC && EXACT), "the EXACT instantiation uses no LDS");
   constexpr bool ROWS = MODE == 1, SIM = MODE == 2;
@@ -1426,138 +1426,72 @@ void k_null_occ(NullArgs A, const uint8_t *__restrict__ blob, const DevBlock *__
 }
 
 
-// launch / occupancy of one N-1 value, used by the range units
-// dynamic LDS of the instantiations that do not stage codes: at least phase A's threshold table (64 B per node) + pair table; the
-// host may give more (NullArgs::plainLds), which phase B uses as its suffix cache
-template <int NK> constexpr size_t phase_a_lds() { return NK < kFastRows ? static_cast<size_t>(kPhaseALds) : static_cast<size_t>(2 * (NK + 1)) * 64 + 64 * 64; }
-
+// launch / occupancy of one N-1 value, used by the range units.  The dynamic LDS of the instantiations that do not stage codes is at least
+// phase A's threshold table (64 B per node) and pair table, kPhaseALds; the host may give more, which phase B uses as its suffix cache.
+// Wide blocks (N-1 in [32, 63]) have the EXACT instantiation without code staging only -- the 4 N-1 per-sequence registers no longer fit the
+// register file (the compiler parks part of them in AGPRs), so this is the slow but complete path for the rare wide block; the reference
+// accepts up to 500 rows (rnaz_utils.h:7).  The other kinds exist where their comment in rc_launch.h says.
 template <int NK>
-inline int null_occupancy_one(size_t ldsBytes) {
+inline int null_occupancy_one(NullKind kind, size_t lds) {
   int nb = 0;
-  hipError_t e = ldsBytes ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_null<NK, true, false>, 64, ldsBytes)
-                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_null<NK, false, false>, 64, phase_a_lds<NK>());
-  if (e != hipSuccess) return 0;
-  return nb;
-}
-// codes from L2 with `dynLds` bytes of dynamic LDS; hiOcc: the k_null_occ build (0 if this N-1 has none)
-template <int NK>
-inline int null_occupancy_plain_one(size_t dynLds, int hiOcc) {
-  int nb = 0;
-  hipError_t e;
-  if (hiOcc == 2) {   // the two-row kernel with its codes from L2
-    if constexpr (NK >= 3 && NK <= kDualRowsMaxNK) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_null<NK, false, false, true>, 64, dynLds);
-    else return 0;
-  } else if (hiOcc) {
-    if constexpr (hi_occ_waves(NK) != 0) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_null_occ<NK>, 64, dynLds);
-    else return 0;
-  } else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_null<NK, false, false>, 64, dynLds);
-  if (e != hipSuccess) return 0;
-  return nb;
-}
-
-// exact: the class contains blocks flagged exact_div (never staged in LDS: a rare parameter choice)
-template <int NK>
-inline void launch_null_one(const NullArgs &a, int grid, size_t ldsBytes, bool exact, hipStream_t stream) {
-  if (exact) {
-    hipLaunchKernelGGL((k_null<NK, false, true>), dim3(grid), dim3(64), 0, stream, a, a.blob, a.dblocks,
-                       a.classBlocks, a.flags, a.U, a.pair, a.scratch, a.maxima);
-  } else if (ldsBytes) {
-    if constexpr (NK <= kDualRowsMaxNK) {
-      if (a.dual && ldsBytes <= 48 * 1024) {
-        hipLaunchKernelGGL((k_null<NK, true, false, true>), dim3(grid), dim3(64), ldsBytes, stream, a, a.blob, a.dblocks,
-                           a.classBlocks, a.flags, a.U, a.pair, a.scratch, a.maxima);
-        return;
-      }
-    }
-    if (ldsBytes > 48 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_null<NK, true, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ldsBytes));
-    hipLaunchKernelGGL((k_null<NK, true, false>), dim3(grid), dim3(64), ldsBytes, stream, a, a.blob, a.dblocks,
-                       a.classBlocks, a.flags, a.U, a.pair, a.scratch, a.maxima);
-  } else {
-    const size_t dyn = a.plainLds ? static_cast<size_t>(a.plainLds) : phase_a_lds<NK>();
-    if constexpr (NK < kFastRows) {
-      if (a.rowParts > 1) {   // an item's simulation split by sites (a.simGrid workgroups), then its scoring split by rows; k_null_rowscan (rc_kernels.hip) follows on the same stream
-        hipLaunchKernelGGL((k_null<NK, false, false, false, 2>), dim3(a.simGrid), dim3(64), phase_a_lds<NK>(), stream, a, a.blob, a.dblocks,
-                           a.classBlocks, a.flags, a.U, a.pair, a.scratch, a.maxima);
-        hipLaunchKernelGGL((k_null<NK, false, false, false, 1>), dim3(grid), dim3(64), dyn, stream, a, a.blob, a.dblocks,
-                           a.classBlocks, a.flags, a.U, a.pair, a.scratch, a.maxima);
-        return;
-      }
-    }
-    if constexpr (NK >= 3 && NK <= kDualRowsMaxNK) {
-      if (a.hiOcc == 2) {
-        hipLaunchKernelGGL((k_null<NK, false, false, true>), dim3(grid), dim3(64), dyn, stream, a, a.blob, a.dblocks,
-                           a.classBlocks, a.flags, a.U, a.pair, a.scratch, a.maxima);
-        return;
-      }
-    }
-    if constexpr (hi_occ_waves(NK) != 0) {
-      if (a.hiOcc) {
-        hipLaunchKernelGGL((k_null_occ<NK>), dim3(grid), dim3(64), dyn, stream, a, a.blob, a.dblocks,
-                           a.classBlocks, a.flags, a.U, a.pair, a.scratch, a.maxima);
-        return;
-      }
-    }
-    hipLaunchKernelGGL((k_null<NK, false, false>), dim3(grid), dim3(64), dyn, stream, a, a.blob, a.dblocks,
-                       a.classBlocks, a.flags, a.U, a.pair, a.scratch, a.maxima);
+  hipError_t e = hipErrorInvalidValue;
+  switch (kind) {
+    case NullKind::Exact: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_null<NK, false, true>, 64, lds); break;
+    case NullKind::Staged: if constexpr (NK < kFastRows) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_null<NK, true, false>, 64, lds); break;
+    case NullKind::StagedTwoRow: if constexpr (NK <= kDualRowsMaxNK) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_null<NK, true, false, true>, 64, lds); break;
+    case NullKind::L2: if constexpr (NK < kFastRows) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_null<NK, false, false>, 64, lds); break;
+    case NullKind::L2Occ: if constexpr (hi_occ_waves(NK) != 0) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_null_occ<NK>, 64, lds); break;
+    case NullKind::L2TwoRow: if constexpr (NK >= 3 && NK <= kDualRowsMaxNK) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_null<NK, false, false, true>, 64, lds); break;
+    case NullKind::RowSplit: if constexpr (NK < kFastRows) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_null<NK, false, false, false, 1>, 64, lds); break;
+    default: break;
   }
+  return e == hipSuccess ? nb : 0;
 }
 
-// one translation unit per range [LO, HI]
-#define RC_DEFINE_NULL_RANGE(SUFFIX, LO, HI)                                                        \
-  template <int NK> static int occ_rec_##SUFFIX(int nk, size_t lds) {                                \
-    if constexpr (NK > HI) return 0;                                                                 \
-    else return nk == NK ? null_occupancy_one<NK>(lds) : occ_rec_##SUFFIX<NK + 1>(nk, lds);           \
-  }                                                                                                  \
-  template <int NK> static bool launch_rec_##SUFFIX(int nk, const NullArgs &a, int grid, size_t lds, bool exact, hipStream_t st) { \
-    if constexpr (NK > HI) return false;                                                             \
-    else {                                                                                           \
-      if (nk == NK) { launch_null_one<NK>(a, grid, lds, exact, st); return true; }                   \
-      return launch_rec_##SUFFIX<NK + 1>(nk, a, grid, lds, exact, st);                               \
-    }                                                                                                \
-  }                                                                                                  \
-  template <int NK> static int occp_rec_##SUFFIX(int nk, size_t lds, int hiOcc) {                    \
-    if constexpr (NK > HI) return 0;                                                                 \
-    else return nk == NK ? null_occupancy_plain_one<NK>(lds, hiOcc) : occp_rec_##SUFFIX<NK + 1>(nk, lds, hiOcc); \
-  }                                                                                                  \
-  int null_occupancy_##SUFFIX(int nk, size_t lds) { return occ_rec_##SUFFIX<LO>(nk, lds); }          \
-  int null_occupancy_plain_##SUFFIX(int nk, size_t lds, int hiOcc) { return occp_rec_##SUFFIX<LO>(nk, lds, hiOcc); } \
-  bool launch_null_##SUFFIX(int nk, const NullArgs &a, int grid, size_t lds, bool exact, hipStream_t st) { \
-    return launch_rec_##SUFFIX<LO>(nk, a, grid, lds, exact, st);                                     \
+#define RC_NULL_GO(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(grid), dim3(64), lds, stream, a, a.blob, a.dblocks, a.classBlocks, a.flags, a.U, a.pair, a.scratch, a.maxima)
+template <int NK>
+inline bool launch_null_one(NullKind kind, const NullArgs &a, int grid, size_t lds, hipStream_t stream) {
+  switch (kind) {
+    case NullKind::Exact: RC_NULL_GO(k_null<NK, false, true>); return true;
+    case NullKind::Staged:
+      if constexpr (NK < kFastRows) {
+        if (lds > 48 * 1024)
+          (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_null<NK, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+        RC_NULL_GO(k_null<NK, true, false>);
+        return true;
+      }
+      break;
+    case NullKind::StagedTwoRow: if constexpr (NK <= kDualRowsMaxNK) { RC_NULL_GO(k_null<NK, true, false, true>); return true; } break;
+    case NullKind::L2: if constexpr (NK < kFastRows) { RC_NULL_GO(k_null<NK, false, false>); return true; } break;
+    case NullKind::L2Occ: if constexpr (hi_occ_waves(NK) != 0) { RC_NULL_GO(k_null_occ<NK>); return true; } break;
+    case NullKind::L2TwoRow: if constexpr (NK >= 3 && NK <= kDualRowsMaxNK) { RC_NULL_GO(k_null<NK, false, false, true>); return true; } break;
+    case NullKind::RowSplit:   // an item's simulation split by sites (a.simGrid workgroups), then its scoring split by rows
+      if constexpr (NK < kFastRows) {
+        hipLaunchKernelGGL((k_null<NK, false, false, false, 2>), dim3(a.simGrid), dim3(64), kPhaseALds, stream, a, a.blob, a.dblocks,
+                           a.classBlocks, a.flags, a.U, a.pair, a.scratch, a.maxima);
+        RC_NULL_GO(k_null<NK, false, false, false, 1>);
+        return true;
+      }
+      break;
+    default: break;
   }
+  return false;
+}
+#undef RC_NULL_GO
 
-
-// Blocks with more than 32 rows (N-1 in [32, 63]): one instantiation per N-1, the EXACT one without code staging -- the 4 N-1
-// per-sequence registers no longer fit the register file (the compiler parks part of them in AGPRs), so this is the slow but
-// complete path for the rare wide block; the reference accepts up to 500 rows (rnaz_utils.h:7).
-#define RC_DEFINE_NULL_WIDE_RANGE(SUFFIX, LO, HI)                                                   \
-  template <int NK> static int occ_rec_##SUFFIX(int nk) {                                            \
-    if constexpr (NK > HI) return 0;                                                                 \
-    else {                                                                                           \
-      if (nk == NK) {                                                                                \
-        int nb = 0;                                                                                  \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_null<NK, false, true>, 64, 0) != hipSuccess) return 0; \
-        return nb;                                                                                   \
-      }                                                                                              \
-      return occ_rec_##SUFFIX<NK + 1>(nk);                                                           \
-    }                                                                                                \
-  }                                                                                                  \
-  template <int NK> static bool launch_rec_##SUFFIX(int nk, const NullArgs &a, int grid, hipStream_t st) { \
-    if constexpr (NK > HI) return false;                                                             \
-    else {                                                                                           \
-      if (nk == NK) {                                                                                \
-        hipLaunchKernelGGL((k_null<NK, false, true>), dim3(grid), dim3(64), 0, st, a, a.blob, a.dblocks, a.classBlocks, \
-                           a.flags, a.U, a.pair, a.scratch, a.maxima);                                \
-        return true;                                                                                 \
-      }                                                                                              \
-      return launch_rec_##SUFFIX<NK + 1>(nk, a, grid, st);                                           \
-    }                                                                                                \
-  }                                                                                                  \
-  int null_occupancy_##SUFFIX(int nk, size_t) { return occ_rec_##SUFFIX<LO>(nk); }                   \
-  int null_occupancy_plain_##SUFFIX(int, size_t, int) { return 0; }                                  \
-  bool launch_null_##SUFFIX(int nk, const NullArgs &a, int grid, size_t, bool, hipStream_t st) {     \
-    return launch_rec_##SUFFIX<LO>(nk, a, grid, st);                                                 \
+// one translation unit per range [LO, HI] of N-1 (rc_null_a..h.hip)
+#define RC_DEFINE_NULL_RANGE(SUFFIX, LO, HI)                                                                                    \
+  template <int NK> static int occ_rec_##SUFFIX(int nk, NullKind k, size_t lds) {                                                \
+    if constexpr (NK > HI) return 0;                                                                                             \
+    else return nk == NK ? null_occupancy_one<NK>(k, lds) : occ_rec_##SUFFIX<NK + 1>(nk, k, lds);                                 \
+  }                                                                                                                              \
+  template <int NK> static bool launch_rec_##SUFFIX(int nk, NullKind k, const NullArgs &a, int grid, size_t lds, hipStream_t st) { \
+    if constexpr (NK > HI) return false;                                                                                         \
+    else return nk == NK ? launch_null_one<NK>(k, a, grid, lds, st) : launch_rec_##SUFFIX<NK + 1>(nk, k, a, grid, lds, st);       \
+  }                                                                                                                              \
+  int null_occupancy_##SUFFIX(int nk, NullKind k, size_t lds) { return occ_rec_##SUFFIX<LO>(nk, k, lds); }                       \
+  bool launch_null_##SUFFIX(int nk, NullKind k, const NullArgs &a, int grid, size_t lds, hipStream_t st) {                        \
+    return launch_rec_##SUFFIX<LO>(nk, k, a, grid, lds, st);                                                                     \
   }
 
 }  // namespace rc

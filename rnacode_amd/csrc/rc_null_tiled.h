@@ -1,4 +1,4 @@
-// rc_null_tiled.h -- the null-distribution DP for blocks of 28..64 rows: the sequences in TILES of KT, the cell's running sum carried from tile to tile.
+// rc_null_tiled.h -- the null-distribution DP for blocks of 32 rows and more (rc_device.h, block_class): the sequences in TILES of KT, the cell's running sum carried from tile to tile.
 //
 // Why: a wavefront issues one vector instruction per ~8 cycles whatever its instruction-level parallelism (tools/microbench.hip: v_add_f32 at
 // 1 / 2 / 4 wavefronts per SIMD = 9.0 / 4.6 / 2.8 cycles per instruction), so a SIMD needs FOUR wavefronts to issue at its rate, and k_null<N-1>,

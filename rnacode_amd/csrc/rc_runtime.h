@@ -334,9 +334,7 @@ struct rc_ctx {
   bool U_valid = false;
   Event U_ready;
   float tieThr = 0.0f;
-  std::map<std::pair<int, size_t>, int> occ;   // (N-1, LDS bytes) -> resident workgroups per CU of k_null
-  struct PlainPlan { int occ; size_t lds; int hiOcc; };
-  std::map<std::tuple<int, int, int>, PlainPlan> plainPlans;   // (N-1, tree nodes, high-occupancy wanted) -> launch shape of a k_null that reads its codes from L2
+  std::map<std::tuple<NullKind, int, size_t>, int> occ;   // (kind, N-1 or tile size, dynamic LDS bytes) -> resident workgroups per CU (rc_schedule.cpp, occupancy)
   size_t ldsPerCU = 160 * 1024;
   int rowSplit = 1;             // RC_ROW_SPLIT=0: never split a strand x frame part's rows over workgroups (tiny batches; A/B)
   int highOccupancy = 1;        // RC_HIGH_OCCUPANCY: 1 k_null_occ (one more wavefront per SIMD) for batches of one row-count class, 0 never, 2 always (A/B)
@@ -431,7 +429,7 @@ struct rc_batch {
   int nModels = 0;
   // device
   DevBuf dblob, dmaxima, dhss, dhssCount, dhssPacked, dhssOffsets, dfit, dflags, dexact, dcounters, dscratch, dnativeScratch, dnativeTile, dnativeAll, dsteal, dsbuf;
-  size_t sbufNeed = 0;      // floats of row buffer the rounds of the current run need (launch_null_groups, sizing pass)
+  size_t sbufNeed = 0;      // floats of row buffer the rounds of the current run need (null_round_need)
   float *maxPtr = nullptr;
   bool maximaExternal = false;
   PinBuf hstage, hpacked;
@@ -494,6 +492,8 @@ struct RunEnv {
   bool nativeFirst;   // the native-block kernels run on this run's compute stream in front of k_null, with the chip to themselves
   int nativeMode;     // native_grid's mode
   bool fat;           // every class of the batch takes the two-row k_null (fat_class) and nothing runs beside it
+  // a class of N-1 other sequences takes the two-row k_null (its codes staged in LDS where they fit, else from L2 when that is faster)
+  bool two_rows(int NK) const { return NK <= kDualRowsMaxNK && (NK == 2 || fat); }
 };
 
 // functions that cross unit boundaries
@@ -511,4 +511,7 @@ bool fat_class(const rc_batch *b, const rc_ctx *c, int NK, int maxL);
 int launch_native_block(const RunEnv &R);
 size_t steal_slots(const rc_ctx *c);
 size_t steal_words(const rc_ctx *c);
-int launch_null_groups(const RunEnv &R, int gLo, int gHi, int phase, uint32_t extraSkip, size_t *sizeOnly = nullptr);
+// null sampling of the sample groups [gLo, gHi) of every class: what the round's plan takes -- uint32 of staging scratch, the return value,
+// and floats of row buffer -- (the sizing pass of batch_run_async), and its launches; phase 0 or 1 selects the work counters
+size_t null_round_need(const RunEnv &R, int gLo, int gHi, size_t *sbufFloats);
+int launch_null_groups(const RunEnv &R, int gLo, int gHi, int phase, uint32_t extraSkip);
