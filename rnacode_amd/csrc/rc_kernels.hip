@@ -91,6 +91,41 @@ template <int B, typename F> __device__ __forceinline__ void for_codon_b(F &&f) 
   if constexpr (B < 64) { f(std::integral_constant<int, B>{}); for_codon_b<B + 1>(static_cast<F &&>(f)); }
 }
 
+// the model t of a preparation launch: the block whose [prefix, next prefix) holds t
+// (hi declared in front of lo and the step written as two selects, hi's first: the four kernels then keep, instruction for instruction, the
+// code they had with the search written out in each -- as `if (..) lo = mid; else hi = mid;` the two selects and the add's operands trade places.
+// Harmless for speed: write it the plain way once a change here no longer has to leave the machine code byte for byte as it was.)
+__device__ __forceinline__ ModelRec *prep_model_of(const PrepArgs &A, int t) {
+  int hi = A.nBlocks, lo = 0;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    const bool below = A.modelPrefix[mid] <= t;
+    hi = below ? hi : mid;
+    lo = below ? mid : lo;
+  }
+  const DevBlock *db = A.dblocks + A.blocks[lo];
+  return reinterpret_cast<ModelRec *>(A.blob + db->off_models) + (t - A.modelPrefix[lo]);
+}
+
+// a model's four nucleotide frequencies, by a (wave-uniform or per-lane) base
+struct PrepFreq {
+  float f0, f1, f2, f3;
+  __device__ __forceinline__ float operator()(int x) const { return x == 0 ? f0 : x == 1 ? f1 : x == 2 ? f2 : f3; }
+};
+// P(a -> b) x f(a) for ab = a << 6 | b, the products in calculateBG's order
+__device__ __forceinline__ float prep_term(const float *__restrict__ P, const PrepFreq &freq, int ab) {
+  const int a = ab >> 6, b = ab & 63;
+  const int a1 = a >> 4, a2 = (a >> 2) & 3, a3 = a & 3;
+  const float fa = freq(a1) * freq(a2) * freq(a3);
+  float pAB = P[a1 * 4 + (b >> 4)] * P[a2 * 4 + ((b >> 2) & 3)] * P[a3 * 4 + (b & 3)];
+  pAB = pAB * fa;
+  return pAB;
+}
+// acc += v of lane 0, 1, ..., cnt - 1
+__device__ __forceinline__ void add_in_order(float &acc, float v, int cnt) {
+  for (int l = 0; l < cnt; l++) acc = acc + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+
 __global__ __launch_bounds__(64) void k_prep_models(PrepArgs A) {
   __builtin_amdgcn_s_setprio(3);   // a short latency-bound kernel beside k_null: the SIMD issues its instructions first
   // Four wavefronts per 64 models, one per Hamming class: a wavefront is a serial instruction stream (one VALU instruction per ~9 cycles
@@ -102,17 +137,10 @@ __global__ __launch_bounds__(64) void k_prep_models(PrepArgs A) {
   int t = (blockIdx.x >> 2) * kWave + lane;
   const bool active = t < A.nModels;
   if (!active) t = A.nModels - 1;
-  int lo = 0, hi = A.nBlocks;                       // block whose [prefix, next prefix) holds t
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (A.modelPrefix[mid] <= t) lo = mid; else hi = mid;
-  }
-  const DevBlock *db = A.dblocks + A.blocks[lo];
-  ModelRec *m = reinterpret_cast<ModelRec *>(A.blob + db->off_models) + (t - A.modelPrefix[lo]);
+  ModelRec *m = prep_model_of(A, t);
   const float *__restrict__ P = m->P;
-  const float f0 = m->freqs[0], f1 = m->freqs[1], f2 = m->freqs[2], f3 = m->freqs[3];
+  const PrepFreq freq{m->freqs[0], m->freqs[1], m->freqs[2], m->freqs[3]};
   const int *__restrict__ blosum = A.blosum;
-  auto freq = [&](int x) { return x == 0 ? f0 : x == 1 ? f1 : x == 2 ? f2 : f3; };   // x is wave-uniform
   float probStop = 0.0f;
   for (int a = 0; a < 64; a++) {
     const int a1 = a >> 4, a2 = (a >> 2) & 3, a3 = a & 3;
@@ -192,31 +220,13 @@ __global__ __launch_bounds__(64) void k_prep_models_few(PrepArgs A) {
   __builtin_amdgcn_s_setprio(3);
   const int lane = threadIdx.x;
   const int hq = blockIdx.x & 3, t = blockIdx.x >> 2;   // the grid is 4 x nModels
-  int lo = 0, hi = A.nBlocks;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (A.modelPrefix[mid] <= t) lo = mid; else hi = mid;
-  }
-  const DevBlock *db = A.dblocks + A.blocks[lo];
-  ModelRec *m = reinterpret_cast<ModelRec *>(A.blob + db->off_models) + (t - A.modelPrefix[lo]);
+  ModelRec *m = prep_model_of(A, t);
   const float *__restrict__ P = m->P;
-  const float f0 = m->freqs[0], f1 = m->freqs[1], f2 = m->freqs[2], f3 = m->freqs[3];
-  auto freq = [&](int x) { return x == 0 ? f0 : x == 1 ? f1 : x == 2 ? f2 : f3; };
-  auto term = [&](int ab) {   // P(a -> b) x f(a), the products in calculateBG's order
-    const int a = ab >> 6, b = ab & 63;
-    const int a1 = a >> 4, a2 = (a >> 2) & 3, a3 = a & 3;
-    const float fa = freq(a1) * freq(a2) * freq(a3);
-    float pAB = P[a1 * 4 + (b >> 4)] * P[a2 * 4 + ((b >> 2) & 3)] * P[a3 * 4 + (b & 3)];
-    pAB = pAB * fa;
-    return pAB;
-  };
-  auto add_in_order = [&](float &acc, float v, int cnt) {   // acc += v of lane 0, 1, ..., cnt - 1
-    for (int l = 0; l < cnt; l++) acc = acc + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-  };
+  const PrepFreq freq{m->freqs[0], m->freqs[1], m->freqs[2], m->freqs[3]};
   float probStop = 0.0f;
   for (int base = kPrepLists.off[0]; base < kPrepLists.off[1]; base += kWave) {
     const int cnt = kPrepLists.off[1] - base < kWave ? kPrepLists.off[1] - base : kWave;
-    const float v = lane < cnt ? term(kPrepLists.ab[base + lane]) : 0.0f;
+    const float v = lane < cnt ? prep_term(P, freq, kPrepLists.ab[base + lane]) : 0.0f;
     add_in_order(probStop, v, cnt);
   }
   const float keep = 1.0f - probStop;
@@ -226,7 +236,7 @@ __global__ __launch_bounds__(64) void k_prep_models_few(PrepArgs A) {
     float pAB = 0.0f, sp = 0.0f;
     if (lane < cnt) {
       const int ab = kPrepLists.ab[base + lane];
-      pAB = term(ab);
+      pAB = prep_term(P, freq, ab);
       pAB = pAB / keep;
       const float sc = static_cast<float>(A.blosum[A.pep[ab >> 6] * 20 + A.pep[ab & 63]]);
       sp = sc * pAB;
@@ -256,17 +266,10 @@ __global__ __launch_bounds__(64) void k_prep_models_rt(PrepArgs A) {
   int t = (blockIdx.x >> 2) * kWave + lane;
   const bool active = t < A.nModels;
   if (!active) t = A.nModels - 1;
-  int lo = 0, hi = A.nBlocks;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (A.modelPrefix[mid] <= t) lo = mid; else hi = mid;
-  }
-  const DevBlock *db = A.dblocks + A.blocks[lo];
-  ModelRec *m = reinterpret_cast<ModelRec *>(A.blob + db->off_models) + (t - A.modelPrefix[lo]);
+  ModelRec *m = prep_model_of(A, t);
   const float *__restrict__ P = m->P;
-  const float f0 = m->freqs[0], f1 = m->freqs[1], f2 = m->freqs[2], f3 = m->freqs[3];
+  const PrepFreq freq{m->freqs[0], m->freqs[1], m->freqs[2], m->freqs[3]};
   const int *__restrict__ blosum = A.blosum;
-  auto freq = [&](int x) { return x == 0 ? f0 : x == 1 ? f1 : x == 2 ? f2 : f3; };   // x is wave-uniform
   float probStop = 0.0f;
   for (int a = 0; a < 64; a++) {
     const int a1 = a >> 4, a2 = (a >> 2) & 3, a3 = a & 3;
@@ -321,34 +324,16 @@ __global__ __launch_bounds__(64) void k_prep_models_few_rt(PrepArgs A) {
   __builtin_amdgcn_s_setprio(3);
   const int lane = threadIdx.x;
   const int hq = blockIdx.x & 3, t = blockIdx.x >> 2;   // the grid is 4 x nModels
-  int lo = 0, hi = A.nBlocks;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (A.modelPrefix[mid] <= t) lo = mid; else hi = mid;
-  }
-  const DevBlock *db = A.dblocks + A.blocks[lo];
-  ModelRec *m = reinterpret_cast<ModelRec *>(A.blob + db->off_models) + (t - A.modelPrefix[lo]);
+  ModelRec *m = prep_model_of(A, t);
   const float *__restrict__ P = m->P;
-  const float f0 = m->freqs[0], f1 = m->freqs[1], f2 = m->freqs[2], f3 = m->freqs[3];
+  const PrepFreq freq{m->freqs[0], m->freqs[1], m->freqs[2], m->freqs[3]};
   const int *__restrict__ off = A.prepOff;
   const uint16_t *__restrict__ abList = A.prepAb;
-  auto freq = [&](int x) { return x == 0 ? f0 : x == 1 ? f1 : x == 2 ? f2 : f3; };
-  auto term = [&](int ab) {   // P(a -> b) x f(a), the products in calculateBG's order
-    const int a = ab >> 6, b = ab & 63;
-    const int a1 = a >> 4, a2 = (a >> 2) & 3, a3 = a & 3;
-    const float fa = freq(a1) * freq(a2) * freq(a3);
-    float pAB = P[a1 * 4 + (b >> 4)] * P[a2 * 4 + ((b >> 2) & 3)] * P[a3 * 4 + (b & 3)];
-    pAB = pAB * fa;
-    return pAB;
-  };
-  auto add_in_order = [&](float &acc, float v, int cnt) {   // acc += v of lane 0, 1, ..., cnt - 1
-    for (int l = 0; l < cnt; l++) acc = acc + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-  };
   const int s0 = off[0], s1 = off[1], c0 = off[1 + hq], c1 = off[2 + hq];
   float probStop = 0.0f;
   for (int base = s0; base < s1; base += kWave) {
     const int cnt = s1 - base < kWave ? s1 - base : kWave;
-    const float v = lane < cnt ? term(abList[base + lane]) : 0.0f;
+    const float v = lane < cnt ? prep_term(P, freq, abList[base + lane]) : 0.0f;
     add_in_order(probStop, v, cnt);
   }
   const float keep = 1.0f - probStop;
@@ -358,7 +343,7 @@ __global__ __launch_bounds__(64) void k_prep_models_few_rt(PrepArgs A) {
     float pAB = 0.0f, sp = 0.0f;
     if (lane < cnt) {
       const int ab = abList[base + lane];
-      pAB = term(ab);
+      pAB = prep_term(P, freq, ab);
       pAB = pAB / keep;
       const float sc = static_cast<float>(A.blosum[A.pep[ab >> 6] * 20 + A.pep[ab & 63]]);
       sp = sc * pAB;

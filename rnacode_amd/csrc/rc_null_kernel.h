@@ -1,6 +1,16 @@
 // rc_null_kernel.h -- device pieces shared by the kernels and the k_null<N-1, LDSC, EXACT> template.
 // Included by rc_kernels.hip (native path) and by the rc_null_*.hip units, each of which
 // instantiates k_null for a range of N-1 so that the ranges compile in parallel.
+//
+// In the order of the file:
+//   shared device pieces     ref_max / pair_step (the recurrence), scan_step and native_scan_rows (getHSS for the native block), KRegs and
+//                            static_for (per-sequence registers), div_by_nk, SampleScan (getHSS per null sample)
+//   null_body                the work queues and the sharing of a launch's last items; phase A (simulation -> sigma codes in the staging
+//                            scratch); phase B per strand x frame: staging of the codes, the fetch_* lambdas and load_words, lookup, finish,
+//                            the cell kinds (fast, pristine, tail, event -- with the reference's maximum for NaN tables), next_event,
+//                            then the rows: two per pass (DUAL: the ...2 cells, a pair's walk with dspan, the row left over) or one per
+//                            pass (take / one / span), and the result
+//   null_min_waves, k_null, k_null_occ, null_occupancy_one, launch_null_one, RC_DEFINE_NULL_RANGE
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -691,7 +701,8 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
         // latency.  (As plain C++ loads into a second register set the compiler's own wait-count placement waited for them twenty
         // instructions after they had been issued: its analysis merges the loop-entry state, where the first words are still on
         // their way, into the loop.)
-        auto lookup = [&](uint32_t (&w)[NCW], float (&sig)[NK], auto jn, auto scalarLoadsNearby, auto kind) {   // (kind: unused)
+        // kind: DeepFetch for a cell of the span loops that fetch two cells ahead (it selects kYounger below), anything else otherwise.
+        auto lookup = [&](uint32_t (&w)[NCW], float (&sig)[NK], auto jn, auto scalarLoadsNearby, auto kind) {
           if constexpr (LDSC) {
 #pragma unroll
             for (int x = 0; x < NCW; x++) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(w[x]));
@@ -845,7 +856,9 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
           return finish(sum);
         };
         // codon where some sequence has z != 0 (score.c:512-533), wave-uniform branch per sequence
-        auto event_cell = [&](uint32_t (&w)[NCW], int j, int jn, auto kind) -> float {
+        // sem = true: every codon of a block with NaN score tables: the recurrence as the reference writes it, its MAX macro and operand order (ref_max)
+        auto event_cell = [&](uint32_t (&w)[NCW], int j, int jn, auto kind, auto sem) -> float {
+          constexpr bool SEM = decltype(sem)::value;
           float sig[NK];
           lookup(w, sig, jn, std::true_type{}, kind);
           unsigned long long z[ZW];
@@ -855,25 +868,8 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
           static_for<NK>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
             auto &r = R.template at<k>();
-            pair_step(static_cast<int>((z[k >> 5] >> (2 * (k & 31))) & 3ull), sig[k], Delta, Omega, omega, r.s0, r.s1, r.s2);
-            const float m = fmaxf(fmaxf(r.s0, r.s1), r.s2);
-            sum = (k == 0) ? m : sum + m;
-          });
-          return finish(sum);
-        };
-        // every codon of a block with NaN score tables: the recurrence as the reference writes it, its MAX macro and operand order (ref_max)
-        auto nan_cell = [&](uint32_t (&w)[NCW], int j, int jn, auto kind) -> float {
-          float sig[NK];
-          lookup(w, sig, jn, std::true_type{}, kind);
-          unsigned long long z[ZW];
-#pragma unroll
-          for (int x = 0; x < ZW; x++) z[x] = zbase[static_cast<size_t>(3 * j) * ZW + x];
-          float sum = 0.0f;
-          static_for<NK>([&](auto kc) {
-            constexpr int k = decltype(kc)::value;
-            auto &r = R.template at<k>();
-            pair_step<true>(static_cast<int>((z[k >> 5] >> (2 * (k & 31))) & 3ull), sig[k], Delta, Omega, omega, r.s0, r.s1, r.s2);
-            const float m = ref_max3<true>(r.s0, r.s1, r.s2);
+            pair_step<SEM>(static_cast<int>((z[k >> 5] >> (2 * (k & 31))) & 3ull), sig[k], Delta, Omega, omega, r.s0, r.s1, r.s2);
+            const float m = ref_max3<SEM>(r.s0, r.s1, r.s2);
             sum = (k == 0) ? m : sum + m;
           });
           return finish(sum);
@@ -891,6 +887,25 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
         float two_v;
         asm volatile("v_mov_b32 %0, 2.0" : "=v"(two_v));
         const float negTie = -A.tieThr;
+        // The part of a span j .. e - 1 that lies in front of the suffix cache, in pairs of cells on two register sets (see "Two cells of distance"
+        // at the one-row loops below): act(w, jj, jn) is the cell of site jj on the set w, which fetches site jn behind its look-ups.
+        auto deep_pairs = [&](int &j, uint32_t (&wcur)[NCW], int e, auto &&act) {
+          const int lim = e < jc - 2 ? e : jc - 2;   // a deep cell j fetches site j + 2, its partner j + 3: both in front of the suffix cache
+          if (lim - j >= 4) {
+            uint32_t wB[NCW];
+            {
+              const uint32_t *p = sbase + static_cast<size_t>(j + 1) * kSiteWords;
+              asm volatile("s_nop 4" : "+s"(p));   // a VMEM instruction must not read an SGPR within five wait states of the scalar write
+              fetch_global(wB, p);
+            }
+            for (; j + 2 <= lim; j += 2) {
+              act(wcur, j, j + 2);
+              act(wB, j + 1, j + 3);
+            }
+#pragma unroll
+            for (int x = 0; x < NCW; x++) asm volatile("s_waitcnt vmcnt(0)" : "+v"(wB[x]));   // (pending registers are not given away)
+          }
+        };
         if constexpr (DUAL) {
           // ---- Two rows per pass.  sigma of (site j, sequence k) is the same for every row a <= j, and the look-up -- a shift and a
           // ds_bpermute per sequence -- is what the cell loop waits for most (tools/ab_lookup.sh: four of the five look-ups left out,
@@ -1034,23 +1049,8 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
               // the cells j .. e - 1 of one kind; codes from L2: in front of the suffix cache with two cells of fetch distance on two register sets
               // (see "Two cells of distance" at the one-row loops below)
               auto dspan = [&](int e, auto &&fn) {
-                if constexpr (!LDSC && !EXACT && MODE == 0) {
-                  const int lim = e < jc - 2 ? e : jc - 2;
-                  if (lim - j >= 4) {
-                    uint32_t wB[NCW];
-                    {
-                      const uint32_t *p = sbase + static_cast<size_t>(j + 1) * kSiteWords;
-                      asm volatile("s_nop 4" : "+s"(p));   // a VMEM instruction must not read an SGPR within five wait states of the scalar write
-                      fetch_global(wB, p);
-                    }
-                    for (; j + 2 <= lim; j += 2) {
-                      pair_cell(wcur, j, j + 2, DeepFetch{}, fn);
-                      pair_cell(wB, j + 1, j + 3, DeepFetch{}, fn);
-                    }
-#pragma unroll
-                    for (int x = 0; x < NCW; x++) asm volatile("s_waitcnt vmcnt(0)" : "+v"(wB[x]));   // (pending registers are not given away)
-                  }
-                }
+                if constexpr (!LDSC && !EXACT && MODE == 0)
+                  deep_pairs(j, wcur, e, [&](uint32_t (&w)[NCW], int jj, int jn) { pair_cell(w, jj, jn, DeepFetch{}, fn); });
                 if constexpr (LDSC) {
                   // Codes staged in LDS: the cells go in GROUPS of kGroup, one loop test, one buffer index and one s_set_gpr_idx window per
                   // group; the next sites' words come from one base address plus a constant offset per cell.  The cells whose row a + 1 values
@@ -1127,99 +1127,72 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
               pendRow = a + 1; pendExtra = extra; pendN = sites - b0;
               a += 2;
             } else {
-              // ---- one row: row `a`, or the row left over from a pair (its first pendExtra cells, then its buffered values)
+              // ---- one row: row `a`, or the row left over from a pair (its first pendExtra cells, then its buffered values).  The walk of
+              // the one-row kernels below, without their deep fetches.  (Its span loops stand here and not in a lambda like `span` there,
+              // and j2f in front of the row's begin: either changed, the compiler names every two-row kernel's registers differently --
+              // instruction counts within a few lines, one kernel's register figures moved, speed not measured.  That only matters while a change must leave the machine
+              // code byte for byte as it was; profiles/r07/refactor_isa_identity.txt.)
               const bool pend = pendRow >= 0;
               const int row = pend ? pendRow : a;
               const int jend = pend ? row + pendExtra : ((row == sites - 1) ? sites - 1 : sites);
               float j2f = static_cast<float>(2 * row + 1);
-                sample_scan_row_begin(st, best, static_cast<uint32_t>(row));
+              sample_scan_row_begin(st, best, static_cast<uint32_t>(row));
+              static_for<NK>([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                auto &r = R.template at<k>();
+                r.s0 = r.s1 = r.s2 = 0.0f;
+              });
+              uint32_t wcur[NCW];
+              load_words(row, wcur);
+              int j = row;
+              auto take = [&](float v) {
+                sample_scan_step(st, v, j2f, negTie);
+                asm volatile("v_add_f32 %0, %1, %0" : "+v"(j2f) : "v"(two_v));
+              };
+              auto one = [&](auto &&cell) {   // cell(w, jn, kind) -> S
+                const int jn = j + 1 < sites ? j + 1 : j;
+                take(cell(wcur, jn, std::true_type{}));
+              };
+              {   // pristine segment: up to the row's first event
+                const int e = next_event(j, jend);
+                float wv = 0.0f;
+                asm volatile("v_mov_b32 %0, 0" : "=v"(wv));   // keep w a per-lane register (full-rate v_add/v_max operands)
+                for (; j < e; j++) one([&](uint32_t (&w)[NCW], int jn, auto kd) {
+                  if constexpr (kProfiling) statPristine++;
+                  return pristine_cell(w, wv, jn, kd);
+                });
                 static_for<NK>([&](auto kc) {
                   constexpr int k = decltype(kc)::value;
                   auto &r = R.template at<k>();
-                  r.s0 = r.s1 = r.s2 = 0.0f;
+                  r.s1 = r.s2 = wv;
                 });
-                uint32_t wcur[NCW];
-                load_words(row, wcur);
-                int j = row;
-                {   // pristine segment: up to the row's first event
-                  const int e = next_event(j, jend);
-                  float wv = 0.0f;
-                  asm volatile("v_mov_b32 %0, 0" : "=v"(wv));   // keep w a per-lane register (full-rate v_add/v_max operands)
-                  for (; j < e; j++) {
-                    const int jn = j + 1 < sites ? j + 1 : j;
-                    uint32_t wnext[NCW];
-                    if constexpr (EXACT) load_words(jn, wnext);
-                    if constexpr (kProfiling) statPristine++;
-                    const float v = pristine_cell(wcur, wv, jn, std::true_type{});
-                    sample_scan_step(st, v, j2f, negTie);
-                    asm volatile("v_add_f32 %0, %1, %0" : "+v"(j2f) : "v"(two_v));
-                    if constexpr (EXACT) {
-      #pragma unroll
-                      for (int x = 0; x < NCW; x++) wcur[x] = wnext[x];
-                    }
-                  }
+              }
+              while (j < jend) {
+                if ((zany[j >> 6] >> (j & 63)) & 1ull) {               // event codon
+                  if constexpr (kProfiling) statEvent++;
+                  const int jj = j;
+                  one([&](uint32_t (&w)[NCW], int jn, auto kd) { return event_cell(w, jj, jn, kd, std::false_type{}); });
+                  j++;
+                }
+                const int e = next_event(j, jend);
+                if (e == jend) {                                       // no further event in this row: the tail
                   static_for<NK>([&](auto kc) {
                     constexpr int k = decltype(kc)::value;
                     auto &r = R.template at<k>();
-                    r.s1 = r.s2 = wv;
+                    r.s1 = fmaxf(r.s1, r.s2);
+                  });
+                  for (; j < e; j++) one([&](uint32_t (&w)[NCW], int jn, auto kd) {
+                    if constexpr (kProfiling) statTail++;
+                    return tail_cell(w, jn, kd);
                   });
                 }
-                while (j < jend) {
-                  if ((zany[j >> 6] >> (j & 63)) & 1ull) {               // event codon
-                    const int jn = j + 1 < sites ? j + 1 : j;
-                    uint32_t wnext[NCW];
-                    if constexpr (EXACT) load_words(jn, wnext);
-                    if constexpr (kProfiling) statEvent++;
-                    const float v = event_cell(wcur, j, jn, std::true_type{});
-                    sample_scan_step(st, v, j2f, negTie);
-                    asm volatile("v_add_f32 %0, %1, %0" : "+v"(j2f) : "v"(two_v));
-                    if constexpr (EXACT) {
-      #pragma unroll
-                      for (int x = 0; x < NCW; x++) wcur[x] = wnext[x];
-                    }
-                    j++;
-                  }
-                  const int e = next_event(j, jend);
-                  if (e == jend) {                                       // no further event in this row: the tail
-                    static_for<NK>([&](auto kc) {
-                      constexpr int k = decltype(kc)::value;
-                      auto &r = R.template at<k>();
-                      r.s1 = fmaxf(r.s1, r.s2);
-                    });
-                    for (; j < e; j++) {
-                      const int jn = j + 1 < sites ? j + 1 : j;
-                      uint32_t wnext[NCW];
-                      if constexpr (EXACT) load_words(jn, wnext);
-                      if constexpr (kProfiling) statTail++;
-                      const float v = tail_cell(wcur, jn, std::true_type{});
-                      sample_scan_step(st, v, j2f, negTie);
-                      asm volatile("v_add_f32 %0, %1, %0" : "+v"(j2f) : "v"(two_v));
-                      if constexpr (EXACT) {
-      #pragma unroll
-                        for (int x = 0; x < NCW; x++) wcur[x] = wnext[x];
-                      }
-                    }
-                  }
-                  for (; j < e; j++) {                                   // tight loop: no events
-                    const int jn = j + 1 < sites ? j + 1 : j;
-                    uint32_t wnext[NCW];
-                    if constexpr (EXACT) load_words(jn, wnext);
-                    const float v = fast_cell(wcur, jn, std::true_type{});
-                    sample_scan_step(st, v, j2f, negTie);
-                    asm volatile("v_add_f32 %0, %1, %0" : "+v"(j2f) : "v"(two_v));
-                    if constexpr (EXACT) {
-      #pragma unroll
-                      for (int x = 0; x < NCW; x++) wcur[x] = wnext[x];
-                    }
-                  }
-                }
-                if constexpr (!EXACT) {   // the last cell's fetch-ahead must have landed before its registers are given away
-      #pragma unroll
-                  for (int x = 0; x < NCW; x++) {
-                    if constexpr (LDSC) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wcur[x]));
-                    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(wcur[x]));
-                  }
-                }
+                for (; j < e; j++) one([&](uint32_t (&w)[NCW], int jn, auto kd) { return fast_cell(w, jn, kd); });   // tight loop: no events
+              }
+#pragma unroll
+              for (int x = 0; x < NCW; x++) {   // the last cell's fetch-ahead must have landed before its registers are given away
+                if constexpr (LDSC) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wcur[x]));
+                else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(wcur[x]));
+              }
               if (pend) {
                 // the buffered values, entry 0 first: unrolled, so that every entry is a register operand of its scan step (an
                 // indexed read costs three instructions and 9 cycles of the SIMD, tools/microbench_gpr_idx.hip)
@@ -1297,30 +1270,14 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
             // copied.  The pair loop is entered with one extra fetch (cell j + 1 into wB) and left with wB drained and dropped -- wcur then holds
             // cell j as the single-set loop expects it, which fetches cell j + 1 once more: two fetches per span for nothing, from four cells on.
             auto span = [&](int e, auto &&cell) {
-              if constexpr (kDeep) {
-                const int lim = e < jc - 2 ? e : jc - 2;   // a deep cell j fetches site j + 2, its partner j + 3: both in front of the suffix cache
-                if (lim - j >= 4) {
-                  uint32_t wB[NCW];
-                  {
-                    const uint32_t *p = sbase + static_cast<size_t>(j + 1) * kSiteWords;
-                    asm volatile("s_nop 4" : "+s"(p));   // a VMEM instruction must not read an SGPR within five wait states of the scalar write
-                    fetch_global(wB, p);
-                  }
-                  for (; j + 2 <= lim; j += 2) {
-                    take(cell(wcur, j + 2, DeepFetch{}));
-                    take(cell(wB, j + 3, DeepFetch{}));
-                  }
-#pragma unroll
-                  for (int x = 0; x < NCW; x++) asm volatile("s_waitcnt vmcnt(0)" : "+v"(wB[x]));   // (pending registers are not given away)
-                }
-              }
+              if constexpr (kDeep) deep_pairs(j, wcur, e, [&](uint32_t (&w)[NCW], int, int jn) { take(cell(w, jn, DeepFetch{})); });
               for (; j < e; j++) one(cell);
             };
             if constexpr (EXACT) {
               if (nanSem)   // (the whole row: none of the shortcuts below holds with NaN states)
                 for (; j < jend; j++) {
                   const int jj = j;
-                  one([&](uint32_t (&w)[NCW], int jn, auto kd) { return nan_cell(w, jj, jn, kd); });
+                  one([&](uint32_t (&w)[NCW], int jn, auto kd) { return event_cell(w, jj, jn, kd, std::true_type{}); });
                 }
             }
             {   // pristine segment: up to the row's first event
@@ -1341,7 +1298,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
               if ((zany[j >> 6] >> (j & 63)) & 1ull) {               // event codon
                 if constexpr (kProfiling) statEvent++;
                 const int jj = j;
-                one([&](uint32_t (&w)[NCW], int jn, auto kd) { return event_cell(w, jj, jn, kd); });
+                one([&](uint32_t (&w)[NCW], int jn, auto kd) { return event_cell(w, jj, jn, kd, std::false_type{}); });
                 j++;
               }
               const int e = next_event(j, jend);
