@@ -23,12 +23,14 @@ extern "C" {
 #define RC_ERR_UNSUPPORTED (-3) /* shape outside the built kernels (N > RC_MAX_ROWS, more than RC_MAX_COLS columns) */
 #define RC_ERR_SKIP (-4)        /* block the reference driver skips (RNAcode.c:142-150) */
 
-#define RC_MAX_ROWS 500         /* rows per block, the reference's own limit (MAX_NUM_NAMES, rnaz_utils.h:7).  By default up to 31 rows
-                                   run the register-resident kernels; from 32 rows on, blocks short enough (200 reference residues, 250
-                                   at 37..64 rows, any length from 112 rows) a kernel that scores the sequences in tiles, the others a
-                                   slower instantiation of the register-resident code up to 36 rows and generic kernels (sequence by
-                                   sequence, codes in a global scratch) from 37 (RC_GENERIC_MIN_ROWS, RC_TILED_*); the built-in tree
-                                   estimator runs on the GPU for up to 64 rows and on host threads for wider blocks */
+#define RC_MAX_ROWS 500         /* rows per block, the reference's own limit (MAX_NUM_NAMES, rnaz_utils.h:7).  Which kernels score a block
+                                   is decided per block (block_class in rc_device.h): up to 31 rows the kernels instantiated per row count,
+                                   their states in registers; from 32 rows on a kernel that scores the sequences in tiles of 12..15, for
+                                   blocks with omega <= 0 that are short enough (32..36 rows: 200 reference residues, 37..64: 250,
+                                   65..111: 200, from 112 rows on any length); every other block the per-row-count kernels up to 36 rows
+                                   and the generic kernels (sequence by sequence, states and codes in a global scratch) from 37
+                                   (RC_GENERIC_MIN_ROWS, RC_TILED_* move the thresholds); the built-in tree estimator runs on the GPU for
+                                   up to 64 rows and on host threads for wider blocks */
 #define RC_MAX_COLS 65535       /* alignment columns per block (16-bit column indices); longer blocks get the status RC_ERR_UNSUPPORTED --
                                    the reference's breakMAF.pl (python -m rnacode_amd.breakmaf) splits them first, as its README asks */
 /* Two further bounds on a block's size.  (1) Device memory: the MT19937 streams of a block take 4 bytes x (2 rows - 1) x columns x
@@ -258,6 +260,23 @@ int rc_batch_native_S(const rc_batch *b, int32_t blk, int32_t strand /*0:'+',1:'
  * i = opt_i, opt_i-3, ... >= opt_b+2.  Arrays are [n_rows][n_cols+1]; untouched entries -9. */
 int rc_batch_backtrack(const rc_batch *b, int32_t blk, int32_t strand, int32_t opt_b, int32_t opt_i,
                        int32_t *states, int32_t *z, int32_t *transitions);
+
+/* The same paths for many ranges of a batch with ONE kernel launch, one synchronisation and one copy: the trace-back runs on the
+ * device and one packed byte per row and codon step comes back.  Range r has steps_r = (opt_i - (opt_b + 2)) / 3 + 1 codon steps
+ * (0 if opt_i < opt_b + 2, the reference's empty loop); its cells are out[offsets[r] + (k - 1) * steps_r + t] for the rows
+ * k = 1..n_rows-1, t the step at position i = opt_b + 2 + 3 t.  offsets (n_ranges + 1 entries) is filled on the host; offsets[n_ranges]
+ * may exceed cap, in which case nothing is computed -- call with cap = 0 first to size the buffer.  A malformed range (the tests of
+ * rc_batch_backtrack) returns RC_ERR_ARG and rc_last_error names its index; a range on a block that was not scored returns that
+ * block's status; nothing is launched then, out is left alone and the contents of offsets are undefined.  A call whose ranges
+ * need more device memory than a fixed budget (256 MB; RC_BT_MAX_BYTES overrides) walks them in several launches, with the same
+ * result. */
+typedef struct rc_bt_range { int32_t blk, strand /*0:'+',1:'-'*/, opt_b, opt_i; } rc_bt_range;
+/* packed cell: bits 0-1 state+1 (0 = the reference's -1), bits 2-3 transition (0,1,2; 3 = the reference's -9), bits 4-5 z+1 */
+#define RC_BT_STATE(c) (((c) & 3) - 1)
+#define RC_BT_TRANSITION(c) ((((c) >> 2) & 3) == 3 ? -9 : (((c) >> 2) & 3))
+#define RC_BT_Z(c) ((((c) >> 4) & 3) - 1)
+int rc_batch_backtrack_many(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges,
+                            uint8_t *out, int64_t cap, int64_t *offsets /* n_ranges + 1 */);
 
 /* The substitution matrix and genetic code the scorer uses, for callers that render results
  * (getScoringMatrix() score.c:50-76 and transcode[4][4][4] code.c:28-39, which src/postscript.c:362,412

@@ -72,6 +72,33 @@ class RcModel(C.Structure):
                     scores=list(self.scores), probs=list(self.probs))
 
 
+def pack_bt_cell(state: int, z: int, transition: int) -> int:
+    """One cell of rc_batch_backtrack_many: bits 0-1 state + 1, bits 2-3 the transition (3 = the reference's -9), bits 4-5 z + 1."""
+    return (state + 1) | ((3 if transition == -9 else transition) << 2) | ((z + 1) << 4)
+
+
+def unpack_bt_cells(cells: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(states, z, transitions) as int8 arrays of the packed cells' shape (RC_BT_STATE, RC_BT_Z, RC_BT_TRANSITION of the header)."""
+    c = np.asarray(cells, dtype=np.uint8)
+    states = (c & 3).astype(np.int8) - 1
+    tr = ((c >> 2) & 3).astype(np.int8)
+    tr[tr == 3] = -9
+    z = ((c >> 4) & 3).astype(np.int8) - 1
+    return states, z, tr
+
+
+def expand_backtrack(path, n_rows: int, n_cols: int, opt_b: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """One (states, z, transitions) triple of Batch.backtrack_many as the [n_rows][n_cols + 1] int32 arrays Batch.backtrack returns:
+    row k = 1..n_rows-1, step t at position opt_b + 2 + 3 t, everything else -9."""
+    out = tuple(np.full((n_rows, n_cols + 1), -9, dtype=np.int32) for _ in range(3))
+    steps = path[0].shape[1] if path[0].ndim == 2 else 0
+    if steps:
+        at = opt_b + 2 + 3 * np.arange(steps)
+        for dst, src in zip(out, path):
+            dst[1:, at] = src
+    return out
+
+
 class RnacodeError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"librnacode_hip error {code}: {msg}")
@@ -141,6 +168,7 @@ def lib():
         l.rc_batch_native_S.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32]
         l.rc_batch_backtrack.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        l.rc_batch_backtrack_many.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         l.rc_evd_fit.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         l.rc_mt_stream.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_int32]
         l.rc_pvalue.argtypes = [C.c_float, C.c_float, C.c_float]
@@ -174,7 +202,7 @@ EXPORTED_SYMBOLS = [
     "rc_batch_prep_timing", "rc_host_cpus", "rc_ctx_set_host_threads", "rc_ctx_host_threads", "rc_ctx_fit_exp_mode", "rc_stream_create_v2", "rc_stream_submit", "rc_stream_submit_bound",
     "rc_stream_next", "rc_stream_recycle", "rc_stream_pending", "rc_stream_plan", "rc_stream_destroy", "rc_set_stream_cache", "rc_batch_work", "rc_batch_timing", "rc_batch_null_kernel", "rc_batch_status",
     "rc_batch_models", "rc_batch_maxima", "rc_batch_maxima_all", "rc_batch_fit", "rc_batch_fit_all", "rc_batch_hss", "rc_batch_hss_all", "rc_batch_clamped",
-    "rc_batch_native_S", "rc_batch_backtrack", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
+    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
     "rc_code_tables_for", "rc_genetic_code", "rc_species_tree_create", "rc_species_tree_destroy", "rc_species_tree_tips", "rc_species_tree_prune",
     "rc_fit_species_trees", "rc_fit_species_trees_device",
 ]
@@ -623,6 +651,29 @@ class Batch:
         ip = C.POINTER(C.c_int32)
         _check(lib().rc_batch_backtrack(self._h, blk, strand, b, i, st.ctypes.data_as(ip), z.ctypes.data_as(ip), tr.ctypes.data_as(ip)))
         return st, z, tr
+
+    def backtrack_many(self, ranges) -> List[Tuple[np.ndarray, np.ndarray, np.ndarray]]:
+        """rc_batch_backtrack_many: the paths of all `ranges` -- (blk, strand 0 | 1, opt_b, opt_i) tuples -- with one launch.  Per range a
+        (states, z, transitions) triple of int8 arrays [n_rows - 1][steps], step t at position opt_b + 2 + 3 t (expand_backtrack gives
+        the arrays of backtrack())."""
+        arr = np.ascontiguousarray(np.asarray(list(ranges), dtype=np.int32).reshape(-1, 4))
+        n = arr.shape[0]
+        offs = np.zeros(n + 1, dtype=np.int64)
+        op = offs.ctypes.data_as(C.POINTER(C.c_int64))
+        _check(lib().rc_batch_backtrack_many(self._h, arr.ctypes.data, n, None, 0, op))
+        total = int(offs[n])
+        cells = np.zeros(max(total, 1), dtype=np.uint8)
+        if total:
+            _check(lib().rc_batch_backtrack_many(self._h, arr.ctypes.data, n, cells.ctypes.data, total, op))
+        st, z, tr = unpack_bt_cells(cells)
+        out = []
+        o = offs.tolist()
+        for r in range(n):
+            nk = self.blocks[int(arr[r, 0])].n - 1
+            lo, hi = o[r], o[r + 1]
+            shape = (nk, (hi - lo) // nk if nk > 0 else 0)
+            out.append((st[lo:hi].reshape(shape), z[lo:hi].reshape(shape), tr[lo:hi].reshape(shape)))
+        return out
 
     def results(self, blk: int, with_maxima: bool = False) -> BlockScores:
         st = self.status(blk)

@@ -4,7 +4,7 @@ Mirrors the reference's command line (src/cmdline.ggo:6-20, src/RNAcode.c:236-37
 options that concern the scoring path and the listings:
 
     python -m rnacode_amd.cli [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S]
-                              [-e [-i CUTOFF] [-d DIR]] [-o OUT] [--trees SIDECAR | --species-tree NEWICK
+                              [-e [-i CUTOFF] [-d DIR]] [--details FILE] [-o OUT] [--trees SIDECAR | --species-tree NEWICK
                               [--species-tree-fit fixed|scale|branches]] [--write-trees SIDECAR] [FILE]
 
 Tree + kappa per block (PhyML in the reference, RNAcode.c:153) come either from a sidecar
@@ -14,7 +14,8 @@ block), or from one species tree for the whole run (`--species-tree`: pruned to 
 the mode --species-tree-fit names, rc_fit_species_trees_device; a block whose rows the tree does not cover is skipped with a line
 on stderr).  `--write-trees` writes the trees a run scored with as a sidecar (one line per block read, kappa as %.9g so that the
 float round-trips).  The blocks are scored on the GPU as a stream of sub-batches (--sub-blocks, rc_stream_*).  -e writes the reference's colored
-alignment plots (src/postscript.c) as <DIR>/hss-<n>.eps.
+alignment plots (src/postscript.c) as <DIR>/hss-<n>.eps.  --details FILE (not in the reference) writes what those plots show as a table: one
+line per listed HSS and aligned sequence (details.py); plots and table of a sub-batch come from one rc_batch_backtrack_many call.
 Quirk kept from the reference: the 4th value of --pars goes to stopPenalty_0 (RNAcode.c:318)."""
 from __future__ import annotations
 
@@ -24,7 +25,9 @@ import sys
 import time
 from typing import List, Optional
 
-from . import api, eps, report
+import numpy as np
+
+from . import api, details, eps, report
 from .alnio import AlnBlock, read_alignment_file
 
 
@@ -75,7 +78,7 @@ def fit_trees(blocks, threads: int = 0, ctx: "Optional[api.Context]" = None) -> 
     return api.fit_trees(blocks, threads, ctx=ctx)
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="rnacode-hip", description="RNAcode scoring path on MI355X")
     ap.add_argument("file", nargs="?", help="alignment file (MAF or ClustalW); default stdin")
     ap.add_argument("-o", "--outfile")
@@ -106,7 +109,15 @@ def main(argv=None) -> int:
     ap.add_argument("--genetic-code", metavar="ID|LETTERS",
                     help="genetic code: an NCBI translation table id (e.g. 2, vertebrate mitochondrial) or its 64 letters in NCBI's TCAG order "
                          "(FFLLSSSS...); default: the standard code")
-    a = ap.parse_args(argv)
+    ap.add_argument("--details", metavar="FILE",
+                    help="write a tab-separated table with one line per listed HSS and aligned sequence: how many codons of the "
+                         "backtracked path are in frame (identical, synonymous, conservative, radical, stop, gap), Omega or Delta moves, "
+                         "out of frame")
+    return ap
+
+
+def main(argv=None) -> int:
+    a = build_parser().parse_args(argv)
 
     if a.blosum not in (62, 90):
         print("ERROR: Currently only BLOSUM62 and BLOSUM90 are supported.", file=sys.stderr)
@@ -188,33 +199,64 @@ def main(argv=None) -> int:
     # sub-batch sizes: --sub-blocks, or the library's schedule (rc_stream_plan: a small first sub-batch, then doubling, whole rounds of
     # the chip; every row count is a launch of its own, so more classes mean larger sub-batches)
     sub_blocks = a.sub_blocks if a.sub_blocks > 0 else 0
-    for batch in api.score_stream(ctx, marshalled, params, sub_blocks, depth=3):
-        all_hss = batch.scoreAln_all()
-        for i in range(batch.n):
-            b = prepared[base + i]
-            code = batch.status(i)
-            if base + i in refused:   # the species tree does not cover the block's rows
-                print(f"Skipping alignment {read_index[base + i] + 1} ({b.rows[0].name}). {refused[base + i]}", file=sys.stderr)
-                continue
-            if code == api.RC_ERR_SKIP:   # RNAcode.c:142-150
-                msg = "There must be at least three sequences in the alignment." if b.n <= 2 else "Too short."
-                print(f"Skipping alignment. {msg}", file=sys.stderr)
-                continue
-            if code != api.RC_OK:         # RNAcode.c:153-156: the reference has no tree for this block either
-                print(f"Skipping alignment. Failed to build ML tree. ({batch.block_error(i) or 'not scored'})", file=sys.stderr)
-                continue
-            hook = None
-            if a.eps:   # misc.c:461-474: hss-<counter>.eps for every listed HSS with p below the plot cutoff
-                def hook(counter, h, i=i, b=b, batch=batch):
-                    os.makedirs(a.eps_dir, exist_ok=True)
-                    text = eps.color_aln(b, h, lambda strand, lo, hi: batch.backtrack(i, 0 if strand == "+" else 1, lo, hi), a.blosum,
-                                          params.genetic_code.decode())
-                    with open(os.path.join(a.eps_dir, f"hss-{counter}.eps"), "w") as fh:
-                        fh.write(text)
-            report.print_results(out, fmt, all_hss[i], b.rows[0].name, st, cutoff=a.cutoff, best_only=a.best_only,
-                                 best_region=a.best_region, eps=hook, eps_cutoff=a.eps_cutoff)
-        base += batch.n
-        batch.close()
+    code = params.genetic_code.decode()
+    details_out = None
+    if a.details:
+        details_out = open(a.details, "w")
+        details_out.write(details.header())
+        pep, matrix = api.code_tables(a.blosum, code)
+    eps_cutoff32 = float(np.float32(a.eps_cutoff))
+    try:
+        for batch in api.score_stream(ctx, marshalled, params, sub_blocks, depth=3):
+            all_hss = batch.scoreAln_all()
+            status = [batch.status(i) for i in range(batch.n)]
+            # --eps / --details: the backtracked paths of every listed HSS of the sub-batch with ONE call (rc_batch_backtrack_many) --
+            # the segments themselves for the table; for the plots (p below the plot cutoff) the segment and its two extensions
+            index, ranges = {}, []
+            if a.eps or a.details:
+                for i in range(batch.n):
+                    if status[i] != api.RC_OK or base + i in refused:
+                        continue
+                    for h in report.listed_hss(all_hss[i], a.cutoff, a.best_only, a.best_region):
+                        want = [(h["start"], h["end"])] if a.details else []
+                        if a.eps and float(np.float32(h["pvalue"])) < eps_cutoff32:
+                            want += eps.backtrack_ranges(prepared[base + i], h, a.blosum, code)
+                        for lo, hi in want:
+                            if (i, h["strand"], lo, hi) not in index:
+                                index[(i, h["strand"], lo, hi)] = len(ranges)
+                                ranges.append((i, 0 if h["strand"] == "+" else 1, lo, hi))
+            paths = batch.backtrack_many(ranges) if ranges else []
+            for i in range(batch.n):
+                b = prepared[base + i]
+                code_i = status[i]
+                if base + i in refused:   # the species tree does not cover the block's rows
+                    print(f"Skipping alignment {read_index[base + i] + 1} ({b.rows[0].name}). {refused[base + i]}", file=sys.stderr)
+                    continue
+                if code_i == api.RC_ERR_SKIP:   # RNAcode.c:142-150
+                    msg = "There must be at least three sequences in the alignment." if b.n <= 2 else "Too short."
+                    print(f"Skipping alignment. {msg}", file=sys.stderr)
+                    continue
+                if code_i != api.RC_OK:         # RNAcode.c:153-156: the reference has no tree for this block either
+                    print(f"Skipping alignment. Failed to build ML tree. ({batch.block_error(i) or 'not scored'})", file=sys.stderr)
+                    continue
+                hook = on_listed = None
+                if a.eps:   # misc.c:461-474: hss-<counter>.eps for every listed HSS with p below the plot cutoff
+                    def hook(counter, h, i=i, b=b):
+                        os.makedirs(a.eps_dir, exist_ok=True)
+                        text = eps.color_aln(b, h, lambda strand, lo, hi: api.expand_backtrack(paths[index[(i, strand, lo, hi)]], b.n, b.cols, lo),
+                                             a.blosum, code)
+                        with open(os.path.join(a.eps_dir, f"hss-{counter}.eps"), "w") as fh:
+                            fh.write(text)
+                if a.details:
+                    def on_listed(counter, h, i=i, b=b):
+                        details_out.writelines(details.details_lines(counter, b, h, paths[index[(i, h["strand"], h["start"], h["end"])]], pep, matrix))
+                report.print_results(out, fmt, all_hss[i], b.rows[0].name, st, cutoff=a.cutoff, best_only=a.best_only,
+                                     best_region=a.best_region, eps=hook, eps_cutoff=a.eps_cutoff, listed=on_listed)
+            base += batch.n
+            batch.close()
+    finally:
+        if details_out is not None:   # what has been listed so far is in the file, whatever a batch raised
+            details_out.close()
     if fmt == 0:
         report.print_footer(out, n_read, time.perf_counter() - t0, params.sampleN, params.Delta, params.Omega,
                             params.omega, params.stopPenalty_k)

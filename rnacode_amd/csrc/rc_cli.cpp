@@ -8,7 +8,7 @@
 // (which additionally draws the EPS plots):
 //
 //   rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]
-//               [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]
+//               [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]
 //               [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]
 //               [--write-trees SIDECAR] [FILE]
 //
@@ -26,6 +26,9 @@
 // blocks, misc.c:392-552).  Few blocks (fewer than two per GPU): every GPU simulates a slice of every block's SAMPLE range
 // (rc_params.seed_base + first sample, so the union is the single-GPU sample set bit for bit), the slices meet on the host and
 // are fitted there (rc_evd_fit), as getExtremeValuePars does after its loop (score.c:1004-1052).
+//
+// --details FILE (not in the reference): what the --eps plots show, as a table -- one line per listed HSS and aligned sequence (rc_eps.h,
+// details_tail; the same bytes as python -m rnacode_amd.cli --details).  With --gpus N the one writer emits it in listing order.
 //
 // Quirk kept from the reference: the 4th value of --pars goes to stopPenalty_0 (RNAcode.c:318).
 #include <algorithm>
@@ -287,6 +290,7 @@ struct Listing {
   bool eps = false;
   float epsCutoff = 0.05f;
   std::string epsDir = "eps";
+  FILE *details = nullptr;   // --details: the table's file, header written
   int hitCounter = 0;
 
   // The HSS of a block in the order printResults walks them, the hidden ones marked (misc.c:400-433).  `res` is filtered and, with
@@ -322,8 +326,9 @@ struct Listing {
   }
 
   // epsText: for the k-th listed HSS the EPS file's text, or empty (drawn while the block's batch was alive; misc.c:461-474 writes
-  // hss-<counter>.eps in front of the line)
-  void block(std::vector<rc_hss> res, const std::string &refName, const std::vector<std::string> *epsText = nullptr) {
+  // hss-<counter>.eps in front of the line); detailText: for the k-th listed HSS its --details lines without the counter in front
+  void block(std::vector<rc_hss> res, const std::string &refName, const std::vector<std::string> *epsText = nullptr,
+             const std::vector<std::vector<std::string>> *detailText = nullptr) {
     std::vector<char> hide;
     std::vector<size_t> order;
     arrange(res, hide, order);
@@ -347,6 +352,8 @@ struct Listing {
         if (FILE *f = std::fopen(fn.c_str(), "w")) { std::fwrite((*epsText)[k].data(), 1, (*epsText)[k].size(), f); std::fclose(f); }
         else std::fprintf(stderr, "ERROR: Can't open output file %s\n", fn.c_str());
       }
+      if (details && detailText && k < detailText->size())
+        for (const std::string &tail : (*detailText)[k]) std::fprintf(details, "%i\t%s", hitCounter, tail.c_str());
       k++;
       const int length = h.endSite - h.startSite + 1;
       const char strand[2] = {static_cast<char>(h.strand), 0};
@@ -374,7 +381,7 @@ struct Listing {
 
 void usage() {
   std::fprintf(stderr, "usage: rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]\n"
-                       "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]\n"
+                       "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]\n"
                        "                   [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]\n"
                        "                   [--write-trees SIDECAR] [--dump-blocks] [FILE]\n"
                        "  --genetic-code ID|LETTERS  an NCBI translation table id (e.g. 2, vertebrate mitochondrial) or its 64 letters in\n"
@@ -383,7 +390,10 @@ void usage() {
                        "                             matches the tip named like it, or like its name before the first '.') and fitted:\n"
                        "  --species-tree-fit MODE    fixed: kappa only; scale (default): kappa and one factor on all lengths; branches:\n"
                        "                             kappa and every length\n"
-                       "  --write-trees FILE         write the trees the run scored with, in the form --trees reads\n");
+                       "  --write-trees FILE         write the trees the run scored with, in the form --trees reads\n"
+                       "  --details FILE             a tab-separated table, one line per listed HSS and aligned sequence: how many codons of the\n"
+                       "                             backtracked path are in frame (identical, synonymous, conservative, radical, stop, gap),\n"
+                       "                             Omega or Delta moves, out of frame\n");
 }
 
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -397,6 +407,7 @@ struct Job {
   std::vector<int> status;
   std::vector<std::string> why;
   std::vector<std::vector<std::string>> eps;   // per block: the EPS texts of its listed HSS (--eps)
+  std::vector<std::vector<std::vector<std::string>>> details;   // per block and listed HSS: its --details lines, one per row, without the counter
 };
 
 // everything the threads share
@@ -457,7 +468,7 @@ void writer_thread(Run &R) {
         continue;
       }
       R.list.block(std::vector<rc_hss>(j->hss.begin() + j->offs[i], j->hss.begin() + j->offs[i + 1]), std::string(blk.rows[0].name),
-                   j->eps.empty() ? nullptr : &j->eps[i]);
+                   j->eps.empty() ? nullptr : &j->eps[i], j->details.empty() ? nullptr : &j->details[i]);
     }
     R.tList += now() - t;
   }
@@ -468,32 +479,90 @@ void post(Run &R, std::unique_ptr<Job> j) {
   R.jcv.notify_all();
 }
 
-// --eps: the EPS texts of a block's listed HSS, drawn while its batch is alive (the backtracked paths come from the device)
-std::vector<std::string> draw_block(const Run &R, rc_batch *b, int i, const Block &blk, const std::vector<rc_hss> &hss, std::string &err) {
-  std::vector<rc_hss> res = hss;
-  std::vector<char> hide;
-  std::vector<size_t> order;
-  R.list.arrange(res, hide, order);
-  std::vector<std::string> texts;
-  std::vector<rceps::Row> rows;
-  for (const Row &r : blk.rows) rows.push_back(rceps::Row{std::string(r.name), std::string(r.seq), r.start});
-  const int cols = static_cast<int>(blk.rows[0].seq.size()), N = static_cast<int>(blk.rows.size());
-  for (size_t idx : R.list.listed(res, hide, order)) {
-    const rc_hss &h = res[idx];
-    if (!(h.pvalue < R.list.epsCutoff)) { texts.emplace_back(); continue; }   // misc.c:462
-    auto bt = [&](char strand, int lo, int hi) {
-      rceps::Path p;
-      p.pitch = cols + 1;
-      p.states.assign(static_cast<size_t>(N) * p.pitch, 0);
-      p.transitions.assign(static_cast<size_t>(N) * p.pitch, 0);
-      std::vector<int32_t> z(static_cast<size_t>(N) * p.pitch, 0);
-      if (rc_batch_backtrack(b, i, strand == '+' ? 0 : 1, lo, hi, p.states.data(), z.data(), p.transitions.data()) != RC_OK) err = rc_last_error();
-      else p.valid = true;
-      return p;
-    };
-    texts.push_back(rceps::color_aln(rows, rceps::Hss{static_cast<char>(h.strand), h.frame, h.start, h.end, h.pvalue}, bt, R.tables));
+// --eps / --details for every block of a finished batch, while the batch is alive: the backtracked paths of all listed HSS come from the
+// device with ONE call (rc_batch_backtrack_many) -- the segments themselves for the table; for the plots (p below the plot cutoff, misc.c:462)
+// the segment and its two extensions -- then the plots are drawn and the table's lines made from the packed cells.
+bool annotate(const Run &R, rc_batch *b, Job &j, std::string &err) {
+  const int m = static_cast<int>(j.blockIdx.size());
+  struct Item { int blk; rc_hss h; bool plot; int segment = -1; std::vector<std::pair<std::pair<int, int>, int>> ext; };   // ext: (b, e) -> range index
+  std::vector<Item> items;
+  std::vector<rc_bt_range> ranges;
+  std::vector<std::vector<rceps::Row>> rowsOf(m);
+  if (R.list.eps) j.eps.resize(m);
+  if (R.list.details) j.details.resize(m);
+  auto rows_of = [&](int i) -> const std::vector<rceps::Row> & {
+    if (rowsOf[i].empty()) for (const Row &r : R.blocks[j.blockIdx[i]].rows) rowsOf[i].push_back(rceps::Row{std::string(r.name), std::string(r.seq), r.start});
+    return rowsOf[i];
+  };
+  // a block's rows on either strand, made once per block and strand
+  std::vector<std::vector<std::string>> strandsOf(static_cast<size_t>(2) * m);
+  auto strand_rows = [&](int i, char strand) -> const std::vector<std::string> & {
+    std::vector<std::string> &fwd = strandsOf[2 * static_cast<size_t>(i)], &rev = strandsOf[2 * static_cast<size_t>(i) + 1];
+    if (fwd.empty()) for (const rceps::Row &r : rows_of(i)) fwd.push_back(r.seq);
+    if (strand != '+' && rev.empty()) rev = rceps::rev_rows(fwd);
+    return strand == '+' ? fwd : rev;
+  };
+  for (int i = 0; i < m; i++) {
+    if (j.status[i] != RC_OK) continue;
+    std::vector<rc_hss> res(j.hss.begin() + j.offs[i], j.hss.begin() + j.offs[i + 1]);
+    std::vector<char> hide;
+    std::vector<size_t> order;
+    R.list.arrange(res, hide, order);
+    for (size_t idx : R.list.listed(res, hide, order)) {
+      Item it{i, res[idx], R.list.eps && res[idx].pvalue < R.list.epsCutoff};
+      const rc_hss &h = it.h;
+      const int strand = h.strand == '+' ? 0 : 1;
+      if (R.list.details) { it.segment = static_cast<int>(ranges.size()); ranges.push_back(rc_bt_range{i, strand, h.start, h.end}); }
+      if (it.plot)
+        for (const rceps::Range &r : rceps::hss_ranges(strand_rows(i, static_cast<char>(h.strand)), rceps::Hss{static_cast<char>(h.strand), h.frame, h.start, h.end, h.pvalue}, R.tables))
+          if (rceps::needs_backtrack(r.b, r.e)) {
+            if (it.segment >= 0 && r.b == h.start && r.e == h.end) { it.ext.push_back({{r.b, r.e}, it.segment}); continue; }   // the table's range
+            it.ext.push_back({{r.b, r.e}, static_cast<int>(ranges.size())});
+            ranges.push_back(rc_bt_range{i, strand, r.b, r.e});
+          }
+      items.push_back(std::move(it));
+    }
   }
-  return texts;
+  const int nr = static_cast<int>(ranges.size());
+  std::vector<int64_t> offs(static_cast<size_t>(nr) + 1, 0);
+  std::vector<uint8_t> cells;
+  if (nr) {
+    if (rc_batch_backtrack_many(b, ranges.data(), nr, nullptr, 0, offs.data()) != RC_OK) { err = rc_last_error(); return false; }
+    cells.resize(static_cast<size_t>(std::max<int64_t>(offs[nr], 1)));
+    if (rc_batch_backtrack_many(b, ranges.data(), nr, cells.data(), offs[nr], offs.data()) != RC_OK) { err = rc_last_error(); return false; }
+  }
+  for (const Item &it : items) {
+    const int i = it.blk;
+    const rc_hss &h = it.h;
+    const std::vector<rceps::Row> &rows = rows_of(i);
+    const int N = static_cast<int>(rows.size()), cols = static_cast<int>(rows[0].seq.size());
+    if (R.list.eps) {
+      if (!it.plot) j.eps[i].emplace_back();
+      else {
+        auto bt = [&](char, int lo, int hi) {
+          for (const auto &e : it.ext)
+            if (e.first.first == lo && e.first.second == hi) {
+              const int64_t at = offs[e.second], n = offs[e.second + 1] - at;
+              return rceps::expand_path(cells.data() + at, N, cols, lo, static_cast<int>(n / (N - 1)));
+            }
+          return rceps::Path();
+        };
+        j.eps[i].push_back(rceps::color_aln(rows, rceps::Hss{static_cast<char>(h.strand), h.frame, h.start, h.end, h.pvalue}, bt, R.tables));
+      }
+    }
+    if (R.list.details) {
+      const std::vector<std::string> &curr = strand_rows(i, static_cast<char>(h.strand));
+      const std::vector<int> map0 = rceps::pos2col(curr[0]);
+      const int64_t at = offs[it.segment];
+      const int steps = static_cast<int>((offs[it.segment + 1] - at) / (N - 1));
+      std::vector<std::string> lines;
+      for (int k = 1; k < N; k++)
+        lines.push_back(rceps::details_tail(curr, map0, rows[0].name, rows[k].name, k, static_cast<char>(h.strand), h.frame, h.startGenomic, h.endGenomic,
+                                            h.score, h.pvalue, h.start, h.end, cells.data() + at + static_cast<int64_t>(k - 1) * steps, R.tables));
+      j.details[i].push_back(std::move(lines));
+    }
+  }
+  return true;
 }
 
 // what the writer needs from a finished batch
@@ -512,13 +581,7 @@ std::unique_ptr<Job> collect(const Run &R, rc_batch *b, int seq, const std::vect
     j->status[i] = rc_batch_status(b, i);
     if (j->status[i] != RC_OK && j->status[i] != RC_ERR_SKIP) { const char *why = rc_batch_block_error(b, i); j->why[i] = why ? why : ""; }
   }
-  if (R.list.eps) {
-    j->eps.resize(m);
-    for (int i = 0; i < m && err.empty(); i++)
-      if (j->status[i] == RC_OK)
-        j->eps[i] = draw_block(R, b, i, R.blocks[blockIdx[i]], std::vector<rc_hss>(j->hss.begin() + j->offs[i], j->hss.begin() + j->offs[i + 1]), err);
-    if (!err.empty()) return nullptr;
-  }
+  if ((R.list.eps || R.list.details) && !annotate(R, b, *j, err)) return nullptr;
   return j;
 }
 
@@ -724,12 +787,7 @@ bool run_sample_split(Run &R, std::vector<Worker> &W, std::string &err) {
     const float mu32 = static_cast<float>(mu), lam32 = static_cast<float>(lambda);   // *parMu = mu, score.c:1051-1052
     for (int64_t k = j->offs[i]; k < j->offs[i + 1]; k++) j->hss[k].pvalue = rc == 1 ? rc_pvalue(j->hss[k].score, mu32, lam32) : 99.0f;   // RNAcode.c:180-188
   }
-  if (R.list.eps) {
-    j->eps.resize(n);
-    for (int i = 0; i < n && err.empty(); i++)
-      if (j->status[i] == RC_OK)
-        j->eps[i] = draw_block(R, batch[0], i, R.blocks[i], std::vector<rc_hss>(j->hss.begin() + j->offs[i], j->hss.begin() + j->offs[i + 1]), err);
-  }
+  if (R.list.eps || R.list.details) annotate(R, batch[0], *j, err);
   for (rc_batch *b : batch) if (b) rc_batch_destroy(b);
   if (!err.empty()) return false;
   post(R, std::move(j));
@@ -743,7 +801,7 @@ int main(int argc, char **argv) {
   rc_default_params(&R.par);
   rc_params &par = R.par;
   Listing &list = R.list;
-  std::string file, outfile, trees, limit, devicesArg, speciesFile, writeTrees;
+  std::string file, outfile, trees, limit, devicesArg, speciesFile, writeTrees, detailsFile;
   int device = 0, subBlocks = 0, gpus = 1;   // subBlocks 0: the library's schedule
   bool dumpBlocks = false;
   for (int a = 1; a < argc; a++) {
@@ -791,6 +849,7 @@ int main(int argc, char **argv) {
     else if (o == "-e" || o == "--eps") list.eps = true;
     else if (o == "-i" || o == "--eps-cutoff") list.epsCutoff = static_cast<float>(std::atof(val()));
     else if (o == "-d" || o == "--eps-dir") list.epsDir = val();
+    else if (o == "--details") detailsFile = val();
     else if (!o.empty() && o[0] == '-' && o != "-") { usage(); return 2; }
     else file = o;
   }
@@ -853,7 +912,7 @@ int main(int argc, char **argv) {
   const int nRead = static_cast<int>(blocks.size());
   for (int i = 0; i < nRead; i++) blocks[i].index = i;
   if (std::getenv("RC_CLI_TIMES")) std::fprintf(stderr, "[rnacode_hip] %d blocks read and parsed in %.3f s\n", nRead, now() - tRead);
-  if (list.eps)   // the plots show the rows as main() leaves them: upper-cased (RNAcode.c:121-128; the library upper-cases its own copy)
+  if (list.eps || !detailsFile.empty())   // the plots (and the table) show the rows as main() leaves them: upper-cased (RNAcode.c:121-128; the library upper-cases its own copy)
     for (Block &b : blocks) for (Row &r : b.rows) for (size_t x = 0; x < r.seq.size(); x++) { char &c = const_cast<char &>(r.seq[x]); c = static_cast<char>(std::toupper(static_cast<unsigned char>(c))); }
   if (!limit.empty()) {   // pruneAln (rnaz_utils.c:724-752, RNAcode.c:130-132): rows whose name starts with a listed string stay
     std::vector<std::string> keep;
@@ -903,7 +962,12 @@ int main(int argc, char **argv) {
   }
 
   if (!outfile.empty()) { list.out = std::fopen(outfile.c_str(), "w"); if (!list.out) die("Could not open " + outfile); }
-  if (list.eps && rc_code_tables_for(&par, R.tables.pep, R.tables.matrix) != RC_OK) die(rc_last_error());
+  if (!detailsFile.empty()) {
+    list.details = std::fopen(detailsFile.c_str(), "w");
+    if (!list.details) die("Could not open " + detailsFile);
+    std::fputs(rceps::details_header(), list.details);
+  }
+  if ((list.eps || list.details) && rc_code_tables_for(&par, R.tables.pep, R.tables.matrix) != RC_OK) die(rc_last_error());
   tRead = now() - tRead;
   if (ctxThread.joinable()) ctxThread.join();
   for (int g = 0; g < gpus; g++) if (ctxRc[g] != RC_OK) die(ctxErr[g]);
@@ -1009,6 +1073,7 @@ int main(int argc, char **argv) {
   // context) takes longer than the operating system needs to reclaim the process, so a driver that is done leaves at once
   // (RC_CLI_TEARDOWN=1: the orderly way, for leak checkers).
   if (list.out != stdout) std::fclose(list.out);
+  if (list.details && std::fclose(list.details) != 0) die("Could not write " + detailsFile);
   std::fflush(stdout);
   std::fflush(stderr);
   if (!std::getenv("RC_CLI_TEARDOWN")) {

@@ -2,8 +2,8 @@
 //
 // colorAln / colorHSS of the reference (src/postscript.c:38-680), byte for byte: the alignment in blocks of 60 columns with names,
 // coordinates, ruler and conservation bars, then the segment -- extended left and right to the next stop codon of the reference
-// sequence (extendRegion, src/misc.c:555-626) -- colored codon by codon from the backtracked state path (rc_batch_backtrack,
-// score.c:558-797).  Same layout code as rnacode_amd/eps.py (which tests/test_eps_cpu.py pins to EPS files the reference wrote);
+// sequence (extendRegion, src/misc.c:555-626) -- colored codon by codon from the backtracked state path (rc_batch_backtrack_many: the
+// driver asks for the ranges of every listed HSS of a sub-batch, hss_ranges, in one call; score.c:558-797).  The same path as a table: details_tail.  Same layout code as rnacode_amd/eps.py (which tests/test_eps_cpu.py pins to EPS files the reference wrote);
 // tests/test_gpu_dropin.py compares the two drivers' files byte for byte.  Plain C++ on the public C-ABI only: the genetic code and
 // the BLOSUM matrix come from rc_code_tables_for (the run's rc_params: its genetic code decides the translated letters and where
 // extend_region's walk to the next stop ends).
@@ -19,6 +19,8 @@
 #include <string>
 #include <tuple>
 #include <vector>
+
+#include "../../include/rnacode_hip.h"
 
 namespace rceps {
 
@@ -216,6 +218,82 @@ inline void color_hss(std::string &out, const std::vector<std::string> &rows, co
   }
 }
 
+// The ranges colorAln colors for one segment, in its order (postscript.c:262-300): the extension to the left, the segment itself with
+// its "Frame ... p =" label, the extension to the right unless it is empty.  curr: the rows of the segment's strand.
+struct Range { int b, e; std::string label; };
+inline std::vector<Range> hss_ranges(const std::vector<std::string> &curr, const Hss &hss, const Tables &t) {
+  std::vector<Range> out;
+  out.push_back(Range{extend_region(curr, hss.start, 0, t), hss.start - 1, ""});
+  const double p = static_cast<double>(hss.pvalue);
+  char ps[64];
+  if (p < 0.001) { if (p < 10e-16) std::snprintf(ps, sizeof ps, "<1e-16\n"); else std::snprintf(ps, sizeof ps, "%9.1e\n", p); }
+  else std::snprintf(ps, sizeof ps, "%9.3f\n", p);
+  char lb[128];
+  std::snprintf(lb, sizeof lb, "Frame %c%i p =%s", hss.strand, hss.frame + 1, ps);
+  out.push_back(Range{hss.start, hss.end, lb});
+  const int b = hss.end + 1, e = extend_region(curr, hss.end, 1, t);
+  if (b < e) out.push_back(Range{b, e, ""});
+  return out;
+}
+// colorHSS walks x = b + 2, b + 5, ... < e + 3: a range without such an x is drawn without a path
+inline bool needs_backtrack(int b, int e) { return b + 2 < e + 3; }
+
+// One range's packed cells of rc_batch_backtrack_many ([N-1][steps]) as the [row][position] arrays color_hss reads
+inline Path expand_path(const uint8_t *cells, int N, int cols, int opt_b, int steps) {
+  Path p;
+  p.pitch = cols + 1;
+  p.states.assign(static_cast<size_t>(N) * p.pitch, -9);
+  p.transitions.assign(static_cast<size_t>(N) * p.pitch, -9);
+  for (int k = 1; k < N; k++)
+    for (int s = 0; s < steps; s++) {
+      const uint8_t c = cells[static_cast<size_t>(k - 1) * steps + s];
+      p.states[static_cast<size_t>(k) * p.pitch + opt_b + 2 + 3 * s] = RC_BT_STATE(c);
+      p.transitions[static_cast<size_t>(k) * p.pitch + opt_b + 2 + 3 * s] = RC_BT_TRANSITION(c);
+    }
+  p.valid = true;
+  return p;
+}
+
+// --details: the columns of one line behind the HSS counter (the writer knows the counter), for row k of the segment [b, e] on the strand
+// whose rows are curr; cells: that row's packed cells, one per codon step.  Same rules and bytes as rnacode_amd/details.py: a step is in
+// frame (state 0, transition 0), an Omega (1) or Delta (2) move, out of frame (transition 0 in another state) or unset; an in-frame
+// codon is a gap, a stop, identical, synonymous, conservative (matrix entry >= 0) or radical -- the first that applies.
+inline std::string details_tail(const std::vector<std::string> &curr, const std::vector<int> &map0, const std::string &refName, const std::string &rowName,
+                                int k, char strand, int frame, int startGenomic, int endGenomic, float score, float pvalue, int b, int e,
+                                const uint8_t *cells, const Tables &t) {
+  int codonsN = 0, inFrame = 0, identical = 0, synonymous = 0, conservative = 0, radical = 0, stop = 0, gap = 0, omega = 0, delta = 0, outOfFrame = 0, unset = 0;
+  std::string b0, bk, ca, cb;
+  int s = 0;
+  for (int x = b + 2; x < e + 3; x += 3, s++) {
+    codonsN++;
+    const int st = RC_BT_STATE(cells[s]), tr = RC_BT_TRANSITION(cells[s]);
+    if (tr == 1) { omega++; continue; }
+    if (tr == 2) { delta++; continue; }
+    if (tr != 0) { unset++; continue; }
+    if (st != 0) { outOfFrame++; continue; }
+    inFrame++;
+    get_block(x, curr[0], curr[k], map0, b0, bk);
+    codons(b0, bk, ca, cb);
+    if (cb.find('-') != std::string::npos) { gap++; continue; }
+    const int pa = pep_of(t, ca), pb = pep_of(t, cb);
+    if (pa == -1 || pb == -1) stop++;
+    else if (ca == cb) identical++;
+    else if (pa == pb) synonymous++;
+    else if (t.matrix[20 * pa + pb] >= 0) conservative++;
+    else radical++;
+  }
+  std::string out;
+  put(out, "%s\t%c\t%i\t%i\t%i\t%.2f\t%.3e\t%i\t%s", refName.c_str(), strand, frame + 1, startGenomic, endGenomic, static_cast<double>(score),
+      static_cast<double>(pvalue), k, rowName.c_str());
+  put(out, "\t%i\t%i\t%i\t%i\t%i\t%i\t%i\t%i\t%i\t%i\t%i\t%i\n", codonsN, inFrame, identical, synonymous, conservative, radical, stop, gap, omega, delta,
+      outOfFrame, unset);
+  return out;
+}
+inline const char *details_header() {
+  return "hss\tname\tstrand\tframe\tstart\tend\tscore\tp\trow\trow_name\tcodons\tin_frame\tidentical\tsynonymous\tconservative\tradical\tstop\tgap\t"
+         "omega\tdelta\tout_of_frame\tunset\n";
+}
+
 // colorAln, postscript.c:38-332: the EPS text for one high-scoring segment of a block (rows upper-cased, as RNAcode.c:121-128 leaves them)
 inline std::string color_aln(const std::vector<Row> &block, const Hss &hss, const Backtrack &backtrack, const Tables &t) {
   std::vector<std::string> rows;
@@ -299,26 +377,10 @@ inline std::string color_aln(const std::vector<Row> &block, const Hss &hss, cons
 
   out += "0.0 setgray\n";
   const std::vector<std::string> curr = hss.strand == '+' ? rows : rev_rows(rows);
-  for (int part = 0; part < 3; part++) {
-    int b, e;
-    std::string label;
-    if (part == 0) { b = extend_region(curr, hss.start, 0, t); e = hss.start - 1; }
-    else if (part == 1) {
-      b = hss.start; e = hss.end;
-      const double p = static_cast<double>(hss.pvalue);
-      char ps[64];
-      if (p < 0.001) { if (p < 10e-16) std::snprintf(ps, sizeof ps, "<1e-16\n"); else std::snprintf(ps, sizeof ps, "%9.1e\n", p); }
-      else std::snprintf(ps, sizeof ps, "%9.3f\n", p);
-      char lb[128];
-      std::snprintf(lb, sizeof lb, "Frame %c%i p =%s", hss.strand, hss.frame + 1, ps);
-      label = lb;
-    } else {
-      b = hss.end + 1; e = extend_region(curr, hss.end, 1, t);
-      if (b >= e) break;
-    }
+  for (const Range &r : hss_ranges(curr, hss, t)) {
     Path bt;
-    if (b + 2 < e + 3) bt = backtrack(hss.strand, b, e);
-    color_hss(out, curr, bt, label, b, e, column_width, seqs_x, t);
+    if (needs_backtrack(r.b, r.e)) bt = backtrack(hss.strand, r.b, r.e);
+    color_hss(out, curr, bt, r.label, r.b, r.e, column_width, seqs_x, t);
   }
   out += "showpage\n";
   return out;

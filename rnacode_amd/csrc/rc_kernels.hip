@@ -13,6 +13,7 @@
 //                                                                             (score.c:441-556, 811-848)
 //                     (getHSS, score.c:864-974, runs inside k_native_dp: native_scan_rows in rc_null_kernel.h)
 //   k_sk_row          one row b of Sk for backtracking                        (score.c:496-535)
+//   k_backtrack_many  the backtracked paths of many ranges, one lane per (range, sequence)   (score.c:558-797)
 //   k_evd_fit         Gumbel maximum-likelihood fit per block                 (extreme_fit.c:157-251)
 //
 // Numerics: every add/max of the DP is a single IEEE binary32 operation in the reference's
@@ -729,6 +730,89 @@ __global__ __launch_bounds__(64) void k_sk_row(const uint8_t *blob, const DevBlo
   }
 }
 
+// backtrack (score.c:558-797) for many ranges of a batch in one launch: one lane per (range, sequence k) item, whatever the blocks' row
+// counts (the lanes of a wavefront may sit in different ranges and blocks and run different numbers of steps: they diverge, which
+// this latency-bound helper accepts).  A lane keeps ONE byte per codon step, at cells[item.off + t]:
+//   forward   the recurrence of k_sk_row over i = opt_b+2, +3, ...; no Sk value is stored -- only what the walk back will ask: the z
+//             code (bits 0-1) and, for each state the path may be in at this step (bits 2-3, 4-5, 6-7: state 0, 1, 2), which of the
+//             reference's two CMP tests held (score.c:647-718): 0 neither, 1 the first only, 2 the second (it overrides the first);
+//   backward  from the best final state (strict > over MINUS_INF = -99: none, state -1, if nothing beats it) the decisions are
+//             replayed and each byte is overwritten with the packed cell of include/rnacode_hip.h (RC_BT_STATE / _TRANSITION / _Z).
+//             Where neither test held, prev and the transition stay what the step before left them, as in the reference.
+// (tr, prev) of the first / second test, by z and current state: 4 bits each (tr | prev << 2), entry ((z == +1 ? 0 : 3) + state) * 2 + test
+constexpr unsigned long long kBtMoves = 0x2u | (0x9ull << 4)          // z = +1, state 0: Delta from 0 (tr 2) | Omega from 2
+                                        | (0x1ull << 8) | (0x5ull << 12)    //          state 1: Omega from 0 | Delta from 1, recorded as tr 1 (score.c's own)
+                                        | (0x5ull << 16) | (0xaull << 20)   //          state 2: Omega from 1 | Delta from 2
+                                        | (0x2ull << 24) | (0x5ull << 28)   // z = -1, state 0: Delta from 0 | Omega from 1
+                                        | (0x6ull << 32) | (0x9ull << 36)   //          state 1: Delta from 1 | Omega from 2
+                                        | (0xaull << 40) | (0x1ull << 44);  //          state 2: Delta from 2 | Omega from 0
+
+// CMP (score.h:30): the float difference against the DOUBLE constant 0.00001
+__device__ __forceinline__ bool bt_near(float x, float y) {
+  const float d = (x > y) ? (x - y) : (y - x);
+  return static_cast<double>(d) < 0.00001;
+}
+__device__ __forceinline__ unsigned bt_tests(float s, float first, float second) { return bt_near(s, second) ? 2u : (bt_near(s, first) ? 1u : 0u); }
+
+// the forward pass of one item; returns the state the walk back starts in
+template <bool SEM>
+__device__ __forceinline__ int bt_forward(const unsigned long long *__restrict__ zw, const float *__restrict__ sig, int zww, int k, int i0, int steps,
+                                          float Delta, float Omega, float omega, uint8_t *__restrict__ cell) {
+  float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+  for (int t = 0, i = i0; t < steps; t++, i += 3) {
+    const int zc = static_cast<int>((zw[static_cast<size_t>(i) * zww + (k >> 5)] >> (2 * (k & 31))) & 3ull);
+    const float p0 = s0, p1 = s1, p2 = s2;
+    pair_step<SEM>(zc, sig[i], Delta, Omega, omega, s0, s1, s2);
+    unsigned d = static_cast<unsigned>(zc);
+    if (zc == 1) {          // score.c:647-682
+      d |= bt_tests(s0, p0 + Delta, p2 + Omega) << 2;
+      d |= bt_tests(s1, p0 + Omega, p1 + Delta) << 4;
+      d |= bt_tests(s2, p1 + Omega, p2 + Delta) << 6;
+    } else if (zc != 0) {   // score.c:685-718
+      d |= bt_tests(s0, p0 + Delta, p1 + Omega) << 2;
+      d |= bt_tests(s1, p1 + Delta, p2 + Omega) << 4;
+      d |= bt_tests(s2, p2 + Delta, p0 + Omega) << 6;
+    }
+    cell[t] = static_cast<uint8_t>(d);
+  }
+  float opt = -99.0f;   // MINUS_INF, score.h:27
+  int curr = -1;
+  if (s0 > opt) { opt = s0; curr = 0; }
+  if (s1 > opt) { opt = s1; curr = 1; }
+  if (s2 > opt) { opt = s2; curr = 2; }
+  return curr;
+}
+
+__global__ __launch_bounds__(64) void k_backtrack_many(const uint8_t *__restrict__ blob, const DevBlock *__restrict__ dblocks, const uint32_t *__restrict__ flags,
+                                                       const BtItem *__restrict__ items, int nItems, uint8_t *__restrict__ cells) {
+  const int at = blockIdx.x * kWave + threadIdx.x;
+  if (at >= nItems) return;
+  const BtItem it = items[at];
+  const DevBlock *db = dblocks + it.blk;
+  const int L1 = db->L + 1, zww = db->zw_words, k = it.k;
+  const unsigned long long *zw = reinterpret_cast<const unsigned long long *>(blob + db->off_zw) + static_cast<size_t>(it.strand) * L1 * zww;
+  const float *sig = reinterpret_cast<const float *>(blob + db->off_sigma) + (static_cast<size_t>(it.strand) * db->NK + k) * L1;
+  uint8_t *cell = cells + it.off;
+  int curr = (flags[it.blk] & kFlagNan) ? bt_forward<true>(zw, sig, zww, k, it.opt_b + 2, it.steps, db->Delta, db->Omega, db->omega, cell)
+                                        : bt_forward<false>(zw, sig, zww, k, it.opt_b + 2, it.steps, db->Delta, db->Omega, db->omega, cell);
+  int prev = -1;
+  unsigned tr = 3u;   // the reference's -9: nothing recorded yet
+  for (int t = it.steps - 1; t >= 0; t--) {
+    const unsigned d = cell[t], zc = d & 3u;
+    if (zc == 0u) { prev = curr; tr = 0u; }
+    else if (curr >= 0) {
+      const unsigned test = (d >> (2 + 2 * curr)) & 3u;
+      if (test) {
+        const unsigned e = static_cast<unsigned>(kBtMoves >> (4 * (((zc == 1u ? 0 : 3) + curr) * 2 + static_cast<int>(test) - 1))) & 15u;
+        tr = e & 3u; prev = static_cast<int>(e >> 2);
+      }
+    }
+    const unsigned zenc = zc == 0u ? 1u : (zc == 1u ? 2u : 0u);   // z + 1
+    cell[t] = static_cast<uint8_t>(static_cast<unsigned>(curr + 1) | (tr << 2) | (zenc << 4));
+    curr = prev;
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // EVD fit (extreme_fit.c:157-251), one workgroup per block, sums reduced across 256 threads
 // ------------------------------------------------------------------------------------------
@@ -1111,6 +1195,12 @@ void launch_results_out(const ResultsOutArgs &a, hipStream_t stream) {
 void launch_sk_row(const uint8_t *blob, const DevBlock *dblocks, const uint32_t *flags, int bi, int s, int b, int iMax, float *out, int stride,
                    hipStream_t stream) {
   hipLaunchKernelGGL(k_sk_row, dim3(1), dim3(64), 0, stream, blob, dblocks, flags, bi, s, b, iMax, out, stride);
+}
+
+void launch_backtrack_many(const uint8_t *blob, const DevBlock *dblocks, const uint32_t *flags, const BtItem *items, int nItems, uint8_t *cells,
+                           hipStream_t stream) {
+  if (nItems <= 0) return;
+  hipLaunchKernelGGL(k_backtrack_many, dim3((nItems + kWave - 1) / kWave), dim3(kWave), 0, stream, blob, dblocks, flags, items, nItems, cells);
 }
 
 size_t null_generic_lds_bytes(int N, int nnodes) { return generic_lds_bytes(N, nnodes); }

@@ -242,6 +242,13 @@ struct ResultsOutArgs {
 void launch_results_out(const ResultsOutArgs &a, hipStream_t stream);
 void launch_sk_row(const uint8_t *blob, const DevBlock *dblocks, const uint32_t *flags, int bi, int s, int b, int iMax, float *out, int stride,
                    hipStream_t stream);
+// k_backtrack_many: one lane per item = one sequence k (0-based) of one range; the lane's bytes are cells[off .. off + steps)
+struct BtItem {
+  int32_t blk, strand, opt_b, steps, k, pad;
+  int64_t off;
+};
+void launch_backtrack_many(const uint8_t *blob, const DevBlock *dblocks, const uint32_t *flags, const BtItem *items, int nItems, uint8_t *cells,
+                           hipStream_t stream);
 // wider blocks (N > 64): generic kernels with their states in a global scratch (rc_null_generic.h)
 size_t null_generic_lds_bytes(int N, int nnodes);   // packed node states + codon windows of the widest block of the launch
 // the same in two launches (simulation with many light wavefronts, then the DP): bytes of an item's codes / of a DP workgroup's states

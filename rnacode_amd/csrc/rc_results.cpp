@@ -299,6 +299,83 @@ int rc_batch_backtrack(const rc_batch *b, int32_t blk, int32_t strand, int32_t o
   return RC_OK;
 }
 
+// The paths of many ranges with one launch (k_backtrack_many): the trace-back runs on the device, one packed byte per sequence and
+// codon step comes back, and neither Sk values nor the z table leave the device.
+int rc_batch_backtrack_many(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, uint8_t *out, int64_t cap, int64_t *offsets) {
+  if (!b || !offsets || n_ranges < 0 || (n_ranges > 0 && !ranges) || (!out && cap > 0)) return fail(RC_ERR_ARG, "bad argument");
+  if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
+  // every range is checked, and the layout made, before anything touches the device
+  std::vector<int32_t> stepsOf(static_cast<size_t>(n_ranges));
+  int64_t total = 0;
+  size_t nItems = 0;
+  for (int r = 0; r < n_ranges; r++) {
+    const rc_bt_range &g = ranges[r];
+    offsets[r] = total;
+    if (g.blk < 0 || g.blk >= b->n) return fail(RC_ERR_ARG, "backtrack range " + std::to_string(r) + ": block index out of range");
+    const BlockMeta &h = b->meta[g.blk];
+    if (h.status != RC_OK) { g_err = "backtrack range " + std::to_string(r) + ": the block was not scored"; return h.status; }
+    if (g.strand < 0 || g.strand > 1 || g.opt_b < 1 || g.opt_i > h.L) return fail(RC_ERR_ARG, "backtrack range " + std::to_string(r) + ": bad backtrack range");
+    int steps = 0;
+    if (g.opt_i >= g.opt_b + 2) {   // (else the reference's loop, score.c:629, does not run)
+      if ((g.opt_i - g.opt_b - 2) % 3 != 0) return fail(RC_ERR_ARG, "backtrack range " + std::to_string(r) + ": bad backtrack range");
+      steps = (g.opt_i - (g.opt_b + 2)) / 3 + 1;
+    }
+    stepsOf[r] = steps;
+    total += static_cast<int64_t>(h.NK) * steps;
+    if (steps) nItems += static_cast<size_t>(h.NK);
+  }
+  offsets[n_ranges] = total;
+  if (total > cap || total == 0) return RC_OK;
+  rc_ctx *c = b->ctx;
+  HIP_TRY(hipSetDevice(c->device));
+  size_t budget = kBtMaxBytes;
+  if (const char *e = std::getenv("RC_BT_MAX_BYTES")) budget = static_cast<size_t>(std::max(1ll, std::atoll(e)));
+  RC_STREAM_TRY(st, stream_aux(c));
+  HIP_TRY(hipEventSynchronize(b->evPrep));   // the z and sigma tables are made on the device (k_prep_gaps, k_native_sigma)
+  DevBuf d_items, d_cells;
+  for (DevBuf *d : {&d_items, &d_cells}) { d->retired = c->retired.get(); d->pool = c->bufPool.get(); }
+  const uint8_t *blob = b->dblob.as<uint8_t>();
+  std::vector<BtItem> items;
+  items.reserve(nItems);
+  bool launched = false;
+  // (a lambda: whatever fails in it, nothing returns to the caller -- who owns `out`, while `items` and the two buffers die with this
+  // frame -- before the work already queued on the stream has drained)
+  const int rc = [&]() -> int {
+    for (int r0 = 0; r0 < n_ranges;) {
+      // ranges [r0, r1): as many as the budget holds, at least one
+      if (launched) HIP_TRY(hipStreamSynchronize(st));   // the launch before this one still reads `items` and both buffers
+      items.clear();
+      int r1 = r0;
+      for (; r1 < n_ranges; r1++) {
+        const int NK = b->meta[ranges[r1].blk].NK;
+        const size_t cells = static_cast<size_t>(offsets[r1 + 1] - offsets[r0]);
+        const size_t more = stepsOf[r1] ? static_cast<size_t>(NK) : 0;
+        if (r1 > r0 && cells + (items.size() + more) * sizeof(BtItem) > budget) break;
+        if (!stepsOf[r1]) continue;
+        for (int k = 0; k < NK; k++)
+          items.push_back(BtItem{ranges[r1].blk, ranges[r1].strand, ranges[r1].opt_b, stepsOf[r1], k, 0,
+                                 (offsets[r1] - offsets[r0]) + static_cast<int64_t>(k) * stepsOf[r1]});
+      }
+      const size_t cells = static_cast<size_t>(offsets[r1] - offsets[r0]);
+      if (!items.empty()) {
+        HIP_TRY(d_items.ensure(items.size() * sizeof(BtItem)));
+        HIP_TRY(d_cells.ensure(cells));
+        launched = true;   // from here on something may be in flight
+        HIP_TRY(hipMemcpyAsync(d_items.p, items.data(), items.size() * sizeof(BtItem), hipMemcpyHostToDevice, st));
+        launch_backtrack_many(blob, reinterpret_cast<const DevBlock *>(blob + b->oDblocks), b->dflags.as<uint32_t>(), d_items.as<BtItem>(),
+                              static_cast<int>(items.size()), d_cells.as<uint8_t>(), st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out + offsets[r0], d_cells.p, cells, hipMemcpyDeviceToHost, st));
+      }
+      r0 = r1;
+    }
+    if (launched) HIP_TRY(hipStreamSynchronize(st));   // (the streams are non-blocking: nothing else would wait for the copy)
+    return RC_OK;
+  }();
+  if (rc != RC_OK && launched) (void)hipStreamSynchronize(st);
+  return rc;
+}
+
 int rc_code_tables(int32_t blosum, int32_t pep_out[64], int32_t matrix_out[400]) {
   if ((blosum != 62 && blosum != 90) || !pep_out || !matrix_out) return fail(RC_ERR_ARG, "bad argument");
   const CodeTables ct(blosum);

@@ -291,6 +291,10 @@ class Pool {
 
 inline size_t al256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
+// rc_batch_backtrack_many: device bytes (item descriptors + one byte per sequence and codon step) one launch may take; a call with more
+// walks its ranges in several launches (RC_BT_MAX_BYTES overrides: tests reach the split with it).  A range is never cut.
+constexpr size_t kBtMaxBytes = static_cast<size_t>(256) << 20;
+
 
 struct TableSet;
 

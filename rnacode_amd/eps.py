@@ -3,7 +3,7 @@
 Mirrors colorAln / colorHSS of src/postscript.c:38-680 byte for byte: the alignment in blocks of 60
 columns with names, coordinates, ruler and conservation bars, then the segment -- extended left and
 right to the next stop codon of the reference sequence (extendRegion, misc.c:555-626) -- colored codon
-by codon from the backtracked state path (rc_batch_backtrack, score.c:558-797): synonymous /
+by codon from the backtracked state path (rc_batch_backtrack / rc_batch_backtrack_many, score.c:558-797): synonymous /
 conservative / radical substitutions, stops, gaps and out-of-frame stretches.
 
 The layout arithmetic of the reference is in C float; the only place where that matters for the printed
@@ -283,6 +283,38 @@ def _color_hss(out: List[str], rows: Sequence[str], bt, label: str, b: int, i: i
                 out.append("0 setgray\n")
 
 
+def hss_ranges(curr: Sequence[str], hss: dict, pep: np.ndarray) -> List[Tuple[int, int, str]]:
+    """The ranges (b, e, label) colorAln colors for one segment, in its order (postscript.c:262-300): the extension to the left, the
+    segment itself with its "Frame ... p =" label, the extension to the right unless it is empty.  curr: the rows of the segment's
+    strand (reverse-complemented for '-')."""
+    strand = hss["strand"]
+    start, end = int(hss["start"]), int(hss["end"])
+    out = [(extend_region(curr, start, 0, pep), start - 1, "")]
+    p = float(hss["pvalue"])
+    if p < 0.001:
+        ps = "<1e-16\n" if p < 10e-16 else "%9.1e\n" % p
+    else:
+        ps = "%9.3f\n" % p
+    out.append((start, end, "Frame %s%i p =%s" % (strand, int(hss["frame"]) + 1, ps)))
+    b, e = end + 1, extend_region(curr, end, 1, pep)
+    if b < e:
+        out.append((b, e, ""))
+    return out
+
+
+def needs_backtrack(b: int, e: int) -> bool:
+    """colorHSS walks x = b + 2, b + 5, ... < e + 3: a range without such an x is drawn without a path."""
+    return b + 2 < e + 3
+
+
+def backtrack_ranges(block: AlnBlock, hss: dict, blosum: int = 62, genetic_code: str = "") -> List[Tuple[int, int]]:
+    """The (b, e) ranges whose backtracked paths color_aln asks its callback for, for this segment (on the segment's strand)."""
+    pep, _ = _Tables.get(blosum, genetic_code)
+    rows = [r.seq for r in block.rows]
+    curr = rows if hss["strand"] == "+" else _rev_rows(rows)
+    return [(b, e) for b, e, _ in hss_ranges(curr, hss, pep) if needs_backtrack(b, e)]
+
+
 def color_aln(block: AlnBlock, hss: dict, backtrack: Backtrack, blosum: int = 62, genetic_code: str = "") -> str:
     """EPS text for one high-scoring segment of `block` (colorAln, postscript.c:38-332).
 
@@ -361,25 +393,8 @@ def color_aln(block: AlnBlock, hss: dict, backtrack: Backtrack, blosum: int = 62
 
     out.append("0.0 setgray\n")
     curr = rows if strand == "+" else _rev_rows(rows)
-    start, end = int(hss["start"]), int(hss["end"])
-    for part in range(3):
-        if part == 0:
-            b, e = extend_region(curr, start, 0, pep), start - 1
-            label = ""
-        elif part == 1:
-            b, e = start, end
-            p = float(hss["pvalue"])
-            if p < 0.001:
-                ps = "<1e-16\n" if p < 10e-16 else "%9.1e\n" % p
-            else:
-                ps = "%9.3f\n" % p
-            label = "Frame %s%i p =%s" % (strand, int(hss["frame"]) + 1, ps)
-        else:
-            b, e = end + 1, extend_region(curr, end, 1, pep)
-            if b >= e:
-                break
-            label = ""
-        bt = backtrack(strand, b, e) if b + 2 < e + 3 else None
+    for b, e, label in hss_ranges(curr, hss, pep):
+        bt = backtrack(strand, b, e) if needs_backtrack(b, e) else None
         _color_hss(out, curr, bt, label, b, e, column_width, seqs_x, pep, matrix)
     out.append("showpage\n")
     return "".join(out)

@@ -31,11 +31,8 @@ def _c_f(value: float, prec: int, width: int, space_flag: bool) -> str:
     return s.rjust(width)
 
 
-def print_results(out: IO[str], fmt: int, hss: List[dict], ref_name: str, state: ReportState, cutoff: float = 1.0,
-                  best_only: bool = False, best_region: bool = False, eps=None, eps_cutoff: float = 0.05) -> None:
-    """hss: the block's HSS (dicts as returned by Batch.scoreAln, any order), p-values filled.
-    eps: optional callback eps(hit_counter, hss_record), called for every listed HSS with p < eps_cutoff
-    before its line is written -- where the reference draws hss-<counter>.eps (misc.c:461-474)."""
+def _arranged(hss: List[dict], best_region: bool) -> List[dict]:
+    """The block's HSS in the order printResults walks them, the hidden ones marked (misc.c:400-433)."""
     res = [dict(h, hide=False) for h in hss if h["score"] > 0.0]
     if best_region:   # misc.c:408-433: sort by start codon, hide the weaker of two overlapping HSS
         res.sort(key=lambda h: h["startSite"])
@@ -51,6 +48,34 @@ def print_results(out: IO[str], fmt: int, hss: List[dict], ref_name: str, state:
                 curr = nxt
             nxt += 1
     res.sort(key=lambda h: -h["score"])
+    return res
+
+
+def listed_hss(hss: List[dict], cutoff: float = 1.0, best_only: bool = False, best_region: bool = False) -> List[dict]:
+    """The HSS print_results writes a line for, in its order (the loop of misc.c:444-547 without its output)."""
+    res = _arranged(hss, best_region)
+    cutoff32 = float(np.float32(cutoff))
+    out: List[dict] = []
+    if not res or float(np.float32(res[0]["pvalue"])) > cutoff32:
+        return out
+    for h in res:
+        if not (float(np.float32(h["pvalue"])) < cutoff32):
+            break
+        if h["hide"]:
+            continue
+        out.append(h)
+        if best_only:
+            break
+    return out
+
+
+def print_results(out: IO[str], fmt: int, hss: List[dict], ref_name: str, state: ReportState, cutoff: float = 1.0,
+                  best_only: bool = False, best_region: bool = False, eps=None, eps_cutoff: float = 0.05, listed=None) -> None:
+    """hss: the block's HSS (dicts as returned by Batch.scoreAln, any order), p-values filled.
+    eps: optional callback eps(hit_counter, hss_record), called for every listed HSS with p < eps_cutoff
+    before its line is written -- where the reference draws hss-<counter>.eps (misc.c:461-474).
+    listed: optional callback listed(hit_counter, hss_record), called for every HSS that gets a line (--details)."""
+    res = _arranged(hss, best_region)
     cutoff32 = float(np.float32(cutoff))
     if not res or float(np.float32(res[0]["pvalue"])) > cutoff32:
         if fmt == 0:
@@ -68,6 +93,8 @@ def print_results(out: IO[str], fmt: int, hss: List[dict], ref_name: str, state:
             continue
         if eps is not None and p < float(np.float32(eps_cutoff)):
             eps(state.hit_counter, h)
+        if listed is not None:
+            listed(state.hit_counter, h)
         length = h["endSite"] - h["startSite"] + 1
         if fmt == 0:
             out.write("%6i %4s%i%7i%6i%6i%12s%12i%12i%9.2f" % (state.hit_counter, h["strand"], h["frame"] + 1, length,
