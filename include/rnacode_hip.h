@@ -29,8 +29,10 @@ extern "C" {
                                    blocks with omega <= 0 that are short enough (32..36 rows: 200 reference residues, 37..64: 250,
                                    65..111: 200, from 112 rows on any length); every other block the per-row-count kernels up to 36 rows
                                    and the generic kernels (sequence by sequence, states and codes in a global scratch) from 37
-                                   (RC_GENERIC_MIN_ROWS, RC_TILED_* move the thresholds); the built-in tree estimator runs on the GPU for
-                                   up to 64 rows and on host threads for wider blocks */
+                                   (RC_GENERIC_MIN_ROWS, RC_TILED_* move the thresholds).  That is the sampling pass; the native block
+                                   (and rc_batch_track) takes a DP kernel instantiated per row count up to 64 rows, tiled classes
+                                   included, and the generic one for wider blocks and the generic class.  The built-in tree estimator
+                                   runs on the GPU for up to 64 rows and on host threads for wider blocks */
 #define RC_MAX_COLS 65535       /* alignment columns per block (16-bit column indices); longer blocks get the status RC_ERR_UNSUPPORTED --
                                    the reference's breakMAF.pl (python -m rnacode_amd.breakmaf) splits them first, as its README asks */
 /* Two further bounds on a block's size.  (1) Device memory: the MT19937 streams of a block take 4 bytes x (2 rows - 1) x columns x
@@ -277,6 +279,23 @@ typedef struct rc_bt_range { int32_t blk, strand /*0:'+',1:'-'*/, opt_b, opt_i; 
 #define RC_BT_Z(c) ((((c) >> 4) & 3) - 1)
 int rc_batch_backtrack_many(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges,
                             uint8_t *out, int64_t cap, int64_t *offsets /* n_ranges + 1 */);
+
+/* Per-codon coding-potential track (not in the reference, which only lists what getHSS keeps): for a scored block, strand s (0 '+',
+ * 1 '-'), frame f (0..2) and codon c in [0, sites), sites = (L - f) / 3 with L the reference row's ungapped length,
+ *     T[s][f][c] = max over a <= c <= j of S[a][j],
+ * S the matrix rc_batch_native_S documents: the score of the best segment of that strand and frame that contains codon c, whether or not
+ * the listing shows it.  The maximum is fmaxf's (a NaN operand loses; NaN only where every operand is NaN) and nothing is computed on S,
+ * so T is bit-equal to a maximum taken over rc_batch_native_S's output.  '-' is indexed like that strand's HSS: codons of the reversed
+ * alignment.  An HSS with startSite = c, endSite = c' has the coordinates of a run c..c' of the track (start = 3 c + f + 1, ...).
+ * Array (k, s, f) of the k-th listed block is out[offsets[6 k + 3 s + f] .. offsets[6 k + 3 s + f + 1]) and holds sites floats;
+ * blks == NULL means the blocks 0 .. n_blks - 1; a block may be listed more than once.  offsets (6 n_blks + 1 entries) is filled on the
+ * host; if offsets[6 n_blks] exceeds cap nothing is launched and out is left alone -- call with cap = 0 first to size the buffer.  A
+ * block that was not scored (status != RC_OK) contributes six empty arrays and is not an error: a driver asks for all blocks.  A block
+ * index out of range returns RC_ERR_ARG and rc_last_error names its position in blks; so does a batch that has not completed a run.
+ * The call repeats the native block's DP on the device, one launch per row count as the run itself, with one synchronisation and one
+ * copy back; no sites x sites matrix is held.  p-values are the caller's: rc_pvalue(T, mu, lambda) with rc_batch_fit, 99 where the
+ * fit failed, as for an HSS. */
+int rc_batch_track(const rc_batch *b, const int32_t *blks, int32_t n_blks, float *out, int64_t cap, int64_t *offsets /* 6 n_blks + 1 */);
 
 /* The substitution matrix and genetic code the scorer uses, for callers that render results
  * (getScoringMatrix() score.c:50-76 and transcode[4][4][4] code.c:28-39, which src/postscript.c:362,412

@@ -169,6 +169,7 @@ def lib():
         l.rc_batch_backtrack.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.rc_batch_backtrack_many.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        l.rc_batch_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         l.rc_evd_fit.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         l.rc_mt_stream.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_int32]
         l.rc_pvalue.argtypes = [C.c_float, C.c_float, C.c_float]
@@ -202,7 +203,7 @@ EXPORTED_SYMBOLS = [
     "rc_batch_prep_timing", "rc_host_cpus", "rc_ctx_set_host_threads", "rc_ctx_host_threads", "rc_ctx_fit_exp_mode", "rc_stream_create_v2", "rc_stream_submit", "rc_stream_submit_bound",
     "rc_stream_next", "rc_stream_recycle", "rc_stream_pending", "rc_stream_plan", "rc_stream_destroy", "rc_set_stream_cache", "rc_batch_work", "rc_batch_timing", "rc_batch_null_kernel", "rc_batch_status",
     "rc_batch_models", "rc_batch_maxima", "rc_batch_maxima_all", "rc_batch_fit", "rc_batch_fit_all", "rc_batch_hss", "rc_batch_hss_all", "rc_batch_clamped",
-    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
+    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
     "rc_code_tables_for", "rc_genetic_code", "rc_species_tree_create", "rc_species_tree_destroy", "rc_species_tree_tips", "rc_species_tree_prune",
     "rc_fit_species_trees", "rc_fit_species_trees_device",
 ]
@@ -674,6 +675,25 @@ class Batch:
             shape = (nk, (hi - lo) // nk if nk > 0 else 0)
             out.append((st[lo:hi].reshape(shape), z[lo:hi].reshape(shape), tr[lo:hi].reshape(shape)))
         return out
+
+    def track(self, blks=None) -> List[List[List[np.ndarray]]]:
+        """rc_batch_track: the per-codon coding-potential track of the blocks `blks` (default: all, in order) with one call per sizing
+        and one for the values.  Per block [strand 0 | 1][frame 0..2] float32 arrays of (L - frame) // 3 codons,
+        T[c] = max over a <= c <= j of S[a][j] (native_S's matrix); a block that was not scored has six empty arrays."""
+        if blks is None:
+            arr, n, ptr = None, self.n, None
+        else:
+            arr = np.ascontiguousarray(np.asarray(list(blks), dtype=np.int32).reshape(-1))
+            n, ptr = arr.shape[0], arr.ctypes.data
+        offs = np.zeros(6 * n + 1, dtype=np.int64)
+        op = offs.ctypes.data_as(C.POINTER(C.c_int64))
+        _check(lib().rc_batch_track(self._h, ptr, n, None, 0, op))
+        total = int(offs[6 * n])
+        vals = np.zeros(max(total, 1), dtype=np.float32)
+        if total:
+            _check(lib().rc_batch_track(self._h, ptr, n, vals.ctypes.data, total, op))
+        o = offs.tolist()
+        return [[[vals[o[6 * k + 3 * s + f]:o[6 * k + 3 * s + f + 1]] for f in range(3)] for s in range(2)] for k in range(n)]
 
     def results(self, blk: int, with_maxima: bool = False) -> BlockScores:
         st = self.status(blk)

@@ -4,7 +4,7 @@ Mirrors the reference's command line (src/cmdline.ggo:6-20, src/RNAcode.c:236-37
 options that concern the scoring path and the listings:
 
     python -m rnacode_amd.cli [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S]
-                              [-e [-i CUTOFF] [-d DIR]] [--details FILE] [-o OUT] [--trees SIDECAR | --species-tree NEWICK
+                              [-e [-i CUTOFF] [-d DIR]] [--details FILE] [--track FILE] [-o OUT] [--trees SIDECAR | --species-tree NEWICK
                               [--species-tree-fit fixed|scale|branches]] [--write-trees SIDECAR] [FILE]
 
 Tree + kappa per block (PhyML in the reference, RNAcode.c:153) come either from a sidecar
@@ -16,6 +16,8 @@ on stderr).  `--write-trees` writes the trees a run scored with as a sidecar (on
 float round-trips).  The blocks are scored on the GPU as a stream of sub-batches (--sub-blocks, rc_stream_*).  -e writes the reference's colored
 alignment plots (src/postscript.c) as <DIR>/hss-<n>.eps.  --details FILE (not in the reference) writes what those plots show as a table: one
 line per listed HSS and aligned sequence (details.py); plots and table of a sub-batch come from one rc_batch_backtrack_many call.
+--track FILE (not in the reference) writes the per-codon coding-potential track of every scored block, strand and frame as runs of equal score
+(track.py; one rc_batch_track call per sub-batch).  -b and -r filter the listing only: the track covers every scored block.
 Quirk kept from the reference: the 4th value of --pars goes to stopPenalty_0 (RNAcode.c:318)."""
 from __future__ import annotations
 
@@ -27,7 +29,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import api, details, eps, report
+from . import api, details, eps, report, track
 from .alnio import AlnBlock, read_alignment_file
 
 
@@ -113,6 +115,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="write a tab-separated table with one line per listed HSS and aligned sequence: how many codons of the "
                          "backtracked path are in frame (identical, synonymous, conservative, radical, stop, gap), Omega or Delta moves, "
                          "out of frame")
+    ap.add_argument("--track", metavar="FILE",
+                    help="write a tab-separated per-codon track: for every scored block, strand and frame the runs of codons that share "
+                         "their best segment's score, where that score is positive and its p below --cutoff")
     return ap
 
 
@@ -205,6 +210,10 @@ def main(argv=None) -> int:
         details_out = open(a.details, "w")
         details_out.write(details.header())
         pep, matrix = api.code_tables(a.blosum, code)
+    track_out = None
+    if a.track:
+        track_out = open(a.track, "w")
+        track_out.write(track.header())
     eps_cutoff32 = float(np.float32(a.eps_cutoff))
     try:
         for batch in api.score_stream(ctx, marshalled, params, sub_blocks, depth=3):
@@ -226,6 +235,11 @@ def main(argv=None) -> int:
                                 index[(i, h["strand"], lo, hi)] = len(ranges)
                                 ranges.append((i, 0 if h["strand"] == "+" else 1, lo, hi))
             paths = batch.backtrack_many(ranges) if ranges else []
+            # --track: the tracks of the sub-batch's scored blocks (those the listing covers) with ONE call (rc_batch_track)
+            tracked = {}
+            if track_out is not None:
+                want = [i for i in range(batch.n) if status[i] == api.RC_OK and base + i not in refused]
+                tracked = dict(zip(want, batch.track(want))) if want else {}
             for i in range(batch.n):
                 b = prepared[base + i]
                 code_i = status[i]
@@ -252,11 +266,16 @@ def main(argv=None) -> int:
                         details_out.writelines(details.details_lines(counter, b, h, paths[index[(i, h["strand"], h["start"], h["end"])]], pep, matrix))
                 report.print_results(out, fmt, all_hss[i], b.rows[0].name, st, cutoff=a.cutoff, best_only=a.best_only,
                                      best_region=a.best_region, eps=hook, eps_cutoff=a.eps_cutoff, listed=on_listed)
+                if i in tracked:
+                    rc, mu, lam = batch.getExtremeValuePars(i)
+                    track_out.writelines(track.block_lines(b.rows[0].name, b.rows[0].start, b.rows[0].length, tracked[i], rc, mu, lam, a.cutoff))
             base += batch.n
             batch.close()
     finally:
         if details_out is not None:   # what has been listed so far is in the file, whatever a batch raised
             details_out.close()
+        if track_out is not None:
+            track_out.close()
     if fmt == 0:
         report.print_footer(out, n_read, time.perf_counter() - t0, params.sampleN, params.Delta, params.Omega,
                             params.omega, params.stopPenalty_k)

@@ -8,7 +8,7 @@
 // (which additionally draws the EPS plots):
 //
 //   rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]
-//               [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]
+//               [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]
 //               [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]
 //               [--write-trees SIDECAR] [FILE]
 //
@@ -29,6 +29,10 @@
 //
 // --details FILE (not in the reference): what the --eps plots show, as a table -- one line per listed HSS and aligned sequence (rc_eps.h,
 // details_tail; the same bytes as python -m rnacode_amd.cli --details).  With --gpus N the one writer emits it in listing order.
+//
+// --track FILE (not in the reference): the per-codon coding-potential track of every scored block, strand and frame as runs of equal score
+// (rc_batch_track, one call per sub-batch; rc_eps.h, track_block; the same bytes as python -m rnacode_amd.cli --track).  -b and -r filter the
+// listing only: the track covers every scored block.  With --gpus N the one writer emits it in input order.
 //
 // Quirk kept from the reference: the 4th value of --pars goes to stopPenalty_0 (RNAcode.c:318).
 #include <algorithm>
@@ -291,6 +295,7 @@ struct Listing {
   float epsCutoff = 0.05f;
   std::string epsDir = "eps";
   FILE *details = nullptr;   // --details: the table's file, header written
+  FILE *track = nullptr;     // --track: the track's file, header written
   int hitCounter = 0;
 
   // The HSS of a block in the order printResults walks them, the hidden ones marked (misc.c:400-433).  `res` is filtered and, with
@@ -381,7 +386,7 @@ struct Listing {
 
 void usage() {
   std::fprintf(stderr, "usage: rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]\n"
-                       "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]\n"
+                       "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]\n"
                        "                   [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]\n"
                        "                   [--write-trees SIDECAR] [--dump-blocks] [FILE]\n"
                        "  --genetic-code ID|LETTERS  an NCBI translation table id (e.g. 2, vertebrate mitochondrial) or its 64 letters in\n"
@@ -393,7 +398,9 @@ void usage() {
                        "  --write-trees FILE         write the trees the run scored with, in the form --trees reads\n"
                        "  --details FILE             a tab-separated table, one line per listed HSS and aligned sequence: how many codons of the\n"
                        "                             backtracked path are in frame (identical, synonymous, conservative, radical, stop, gap),\n"
-                       "                             Omega or Delta moves, out of frame\n");
+                       "                             Omega or Delta moves, out of frame\n"
+                       "  --track FILE               a tab-separated per-codon track: for every scored block, strand and frame the runs of codons\n"
+                       "                             that share their best segment's score, where that score is positive and its p below -p\n");
 }
 
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -408,6 +415,7 @@ struct Job {
   std::vector<std::string> why;
   std::vector<std::vector<std::string>> eps;   // per block: the EPS texts of its listed HSS (--eps)
   std::vector<std::vector<std::vector<std::string>>> details;   // per block and listed HSS: its --details lines, one per row, without the counter
+  std::vector<std::string> track;    // per block: its --track lines
 };
 
 // everything the threads share
@@ -469,6 +477,7 @@ void writer_thread(Run &R) {
       }
       R.list.block(std::vector<rc_hss>(j->hss.begin() + j->offs[i], j->hss.begin() + j->offs[i + 1]), std::string(blk.rows[0].name),
                    j->eps.empty() ? nullptr : &j->eps[i], j->details.empty() ? nullptr : &j->details[i]);
+      if (R.list.track && !j->track.empty()) std::fwrite(j->track[i].data(), 1, j->track[i].size(), R.list.track);
     }
     R.tList += now() - t;
   }
@@ -565,6 +574,33 @@ bool annotate(const Run &R, rc_batch *b, Job &j, std::string &err) {
   return true;
 }
 
+// --track for every scored block of a finished batch, while the batch is alive: ONE rc_batch_track call (after the sizing call) for the blocks
+// the listing covers -- scored, and not refused by the species tree --, then their lines (rc_eps.h, track_block).  fits: per block {evd_rc, mu,
+// lambda} where the caller made the fits itself (the sample split); else the batch's own.
+struct TrackFit { int rc; float mu, lambda; };
+bool add_track(const Run &R, rc_batch *b, Job &j, std::string &err, const std::vector<TrackFit> *fits = nullptr) {
+  const int m = static_cast<int>(j.blockIdx.size());
+  j.track.assign(m, std::string());
+  std::vector<int32_t> blks;
+  for (int i = 0; i < m; i++) if (j.status[i] == RC_OK && R.blocks[j.blockIdx[i]].refused.empty()) blks.push_back(i);
+  const int nb = static_cast<int>(blks.size());
+  if (!nb) return true;
+  std::vector<int64_t> offs(static_cast<size_t>(6) * nb + 1, 0);
+  if (rc_batch_track(b, blks.data(), nb, nullptr, 0, offs.data()) != RC_OK) { err = rc_last_error(); return false; }
+  std::vector<float> vals(static_cast<size_t>(std::max<int64_t>(offs[6 * static_cast<size_t>(nb)], 1)));
+  if (rc_batch_track(b, blks.data(), nb, vals.data(), offs[6 * static_cast<size_t>(nb)], offs.data()) != RC_OK) { err = rc_last_error(); return false; }
+  for (int k = 0; k < nb; k++) {
+    const int i = blks[k];
+    const Block &blk = R.blocks[j.blockIdx[i]];
+    TrackFit fit{-1, 0.0f, 0.0f};
+    if (fits) fit = (*fits)[i];
+    else if (rc_batch_fit(b, i, &fit.rc, &fit.mu, &fit.lambda) != RC_OK) { err = rc_last_error(); return false; }
+    rceps::track_block(j.track[i], std::string(blk.rows[0].name), blk.rows[0].start, blk.rows[0].length, vals.data(), offs.data() + 6 * static_cast<size_t>(k),
+                       fit.rc, fit.mu, fit.lambda, R.list.cutoff);
+  }
+  return true;
+}
+
 // what the writer needs from a finished batch
 std::unique_ptr<Job> collect(const Run &R, rc_batch *b, int seq, const std::vector<int> &blockIdx, std::string &err) {
   std::unique_ptr<Job> j(new Job());
@@ -582,6 +618,7 @@ std::unique_ptr<Job> collect(const Run &R, rc_batch *b, int seq, const std::vect
     if (j->status[i] != RC_OK && j->status[i] != RC_ERR_SKIP) { const char *why = rc_batch_block_error(b, i); j->why[i] = why ? why : ""; }
   }
   if ((R.list.eps || R.list.details) && !annotate(R, b, *j, err)) return nullptr;
+  if (R.list.track && !add_track(R, b, *j, err)) return nullptr;
   return j;
 }
 
@@ -765,6 +802,7 @@ bool run_sample_split(Run &R, std::vector<Worker> &W, std::string &err) {
   if (rc_batch_hss_all(batch[0], j->hss.data(), j->offs[n], j->offs.data()) != RC_OK) { err = rc_last_error(); return false; }
   j->status.resize(n); j->why.resize(n);
   std::vector<double> row(sampleN);
+  std::vector<TrackFit> fits(n, TrackFit{-1, 0.0f, 0.0f});
   for (int i = 0; i < n; i++) {
     j->status[i] = rc_batch_status(batch[0], i);
     if (j->status[i] != RC_OK) { if (j->status[i] != RC_ERR_SKIP) { const char *why = rc_batch_block_error(batch[0], i); j->why[i] = why ? why : ""; } continue; }
@@ -785,9 +823,11 @@ bool run_sample_split(Run &R, std::vector<Worker> &W, std::string &err) {
     }
     if (!stopped) rc = rc_evd_fit(W[0].ctx, row.data(), sampleN, &mu, &lambda) == 1 ? 1 : -1;
     const float mu32 = static_cast<float>(mu), lam32 = static_cast<float>(lambda);   // *parMu = mu, score.c:1051-1052
+    fits[i] = TrackFit{rc, mu32, lam32};
     for (int64_t k = j->offs[i]; k < j->offs[i + 1]; k++) j->hss[k].pvalue = rc == 1 ? rc_pvalue(j->hss[k].score, mu32, lam32) : 99.0f;   // RNAcode.c:180-188
   }
   if (R.list.eps || R.list.details) annotate(R, batch[0], *j, err);
+  if (R.list.track && err.empty()) add_track(R, batch[0], *j, err, &fits);
   for (rc_batch *b : batch) if (b) rc_batch_destroy(b);
   if (!err.empty()) return false;
   post(R, std::move(j));
@@ -801,7 +841,7 @@ int main(int argc, char **argv) {
   rc_default_params(&R.par);
   rc_params &par = R.par;
   Listing &list = R.list;
-  std::string file, outfile, trees, limit, devicesArg, speciesFile, writeTrees, detailsFile;
+  std::string file, outfile, trees, limit, devicesArg, speciesFile, writeTrees, detailsFile, trackFile;
   int device = 0, subBlocks = 0, gpus = 1;   // subBlocks 0: the library's schedule
   bool dumpBlocks = false;
   for (int a = 1; a < argc; a++) {
@@ -850,6 +890,7 @@ int main(int argc, char **argv) {
     else if (o == "-i" || o == "--eps-cutoff") list.epsCutoff = static_cast<float>(std::atof(val()));
     else if (o == "-d" || o == "--eps-dir") list.epsDir = val();
     else if (o == "--details") detailsFile = val();
+    else if (o == "--track") trackFile = val();
     else if (!o.empty() && o[0] == '-' && o != "-") { usage(); return 2; }
     else file = o;
   }
@@ -967,6 +1008,11 @@ int main(int argc, char **argv) {
     if (!list.details) die("Could not open " + detailsFile);
     std::fputs(rceps::details_header(), list.details);
   }
+  if (!trackFile.empty()) {
+    list.track = std::fopen(trackFile.c_str(), "w");
+    if (!list.track) die("Could not open " + trackFile);
+    std::fputs(rceps::track_header(), list.track);
+  }
   if ((list.eps || list.details) && rc_code_tables_for(&par, R.tables.pep, R.tables.matrix) != RC_OK) die(rc_last_error());
   tRead = now() - tRead;
   if (ctxThread.joinable()) ctxThread.join();
@@ -1074,6 +1120,7 @@ int main(int argc, char **argv) {
   // (RC_CLI_TEARDOWN=1: the orderly way, for leak checkers).
   if (list.out != stdout) std::fclose(list.out);
   if (list.details && std::fclose(list.details) != 0) die("Could not write " + detailsFile);
+  if (list.track && std::fclose(list.track) != 0) die("Could not write " + trackFile);
   std::fflush(stdout);
   std::fflush(stderr);
   if (!std::getenv("RC_CLI_TEARDOWN")) {

@@ -294,6 +294,41 @@ inline const char *details_header() {
          "omega\tdelta\tout_of_frame\tunset\n";
 }
 
+// --track: the per-codon track of a scored block (rc_batch_track) as runs of equal score.  Same rules and bytes as rnacode_amd/track.py: a run is
+// a maximal stretch of BIT-equal floats (two NaNs count as equal; -0.0 and +0.0 are different bits and do not merge); it has the coordinates of
+// an HSS with startSite = c1, endSite = c2 (rc_results.cpp, score.c:921-936); it is written if its score is positive and its p-value -- rc_pvalue
+// under the block's fit, 99 where the fit failed -- is below the cutoff, the listing's own float comparison.
+struct TrackRun { int c1, c2; float v; };
+inline std::vector<TrackRun> track_runs(const float *t, int n) {
+  std::vector<TrackRun> out;
+  auto bits = [](float x) { uint32_t u; std::memcpy(&u, &x, sizeof u); return u; };
+  for (int c = 0; c < n; c++) {
+    if (!out.empty() && (bits(t[c]) == bits(out.back().v) || (t[c] != t[c] && out.back().v != out.back().v))) out.back().c2 = c;
+    else out.push_back(TrackRun{c, c, t[c]});
+  }
+  return out;
+}
+inline const char *track_header() { return "name\tstrand\tframe\tfrom\tto\tstart\tend\tscore\tp\n"; }
+inline void track_line(std::string &out, const std::string &refName, int strand, int frame, const TrackRun &r, int refStart, int refLength, float p) {
+  int sg = r.c1 * 3 + frame + 1, eg = r.c2 * 3 + frame + 3;   // start, end: what ClustalW input (no coordinates) lists
+  if (!(refStart == 0 && refLength == 0)) {
+    if (!strand) { sg = refStart + r.c1 * 3 + frame; eg = refStart + r.c2 * 3 + frame + 2; }
+    else { eg = (refStart + refLength - 1) - r.c1 * 3 - frame; sg = (refStart + refLength - 1) - r.c2 * 3 - frame - 2; }
+  }
+  put(out, "%s\t%c\t%i\t%i\t%i\t%i\t%i\t%.3f\t%.3e\n", refName.c_str(), strand ? '-' : '+', frame + 1, r.c1 + 1, r.c2 + 1, sg, eg, static_cast<double>(r.v),
+      static_cast<double>(p));
+}
+// the lines of one scored block: vals / offs are rc_batch_track's, offs[0..6] the block's seven offsets; '+' before '-', frames 1..3, runs ascending
+inline void track_block(std::string &out, const std::string &refName, int refStart, int refLength, const float *vals, const int64_t *offs, int evdRc, float mu,
+                        float lambda, float cutoff) {
+  for (int combo = 0; combo < 6; combo++)
+    for (const TrackRun &r : track_runs(vals + offs[combo], static_cast<int>(offs[combo + 1] - offs[combo]))) {
+      if (!(r.v > 0.0f)) continue;
+      const float p = evdRc == 1 ? rc_pvalue(r.v, mu, lambda) : 99.0f;
+      if (p < cutoff) track_line(out, refName, combo / 3, combo % 3, r, refStart, refLength, p);
+    }
+}
+
 // colorAln, postscript.c:38-332: the EPS text for one high-scoring segment of a block (rows upper-cased, as RNAcode.c:121-128 leaves them)
 inline std::string color_aln(const std::vector<Row> &block, const Hss &hss, const Backtrack &backtrack, const Tables &t) {
   std::vector<std::string> rows;

@@ -264,6 +264,11 @@ size_t null_tiled_state_bytes(int L);
 int tiled_dp_occupancy(int KT, NullKind kind, size_t ldsBytes);
 bool launch_tiled_dp(int KT, NullKind kind, const NullArgs &a, int grid, size_t ldsBytes, uint8_t *scratchBytes, hipStream_t stream);
 void launch_native_dp_generic(const NativeArgs &a, int nblocks, float *scratch, size_t scratchStride, hipStream_t stream);
+// the per-codon track instead of getHSS (rc_track.hip; rc_batch_track): the same DP, each 64 rows of S reduced to the item's track -- position p of
+// a.blocks has its six arrays ('+' frames 0..2, then '-') one behind the other from track[trackOff[p]]; one launcher per kernel above
+bool launch_native_track(int NK, const NativeArgs &a, int grid, float *track, const long long *trackOff, hipStream_t stream);
+void launch_native_track_generic(const NativeArgs &a, int nblocks, float *scratch, size_t scratchStride, float *track, const long long *trackOff,
+                                 hipStream_t stream);
 void launch_stop_mark(const FitArgs &a, int nblocks, hipStream_t stream);
 void launch_evd_fit(const FitArgs &a, int nblocks, bool latency, hipStream_t stream);   // latency: no other batch is in flight
 void launch_evd_fit_f64(const double *x, int n, FitOut *out, int expMode, hipStream_t stream);

@@ -631,54 +631,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RC_GENERIC_W
   generic_body<false>(A, blob, dblocks, classBlocks, flags, Ustream, pairTab, scratch, maxima, ldsGeneric);
 }
 
-// native block, any number of rows: one wavefront per (block, strand x frame), lane = start codon, the states of the lane's row
-// in a scratch [3][NK][64] per workgroup (score.c:441-556, 811-848); like k_native_dp, 64 rows of S at a time go through a buffer
-// [64][sites] behind the states and are scanned (getHSS) before the next 64
-__global__ __launch_bounds__(64) void k_native_dp_generic(NativeArgs A, float *__restrict__ scratch, size_t scratchStride) {
-  const int lane = threadIdx.x;
-  const int bi = A.blocks[blockIdx.x / 6];
-  const int combo = blockIdx.x % 6, s = combo / 3, f = combo % 3;
-  const DevBlock *__restrict__ db = A.dblocks + bi;
-  const int L = db->L, L1 = L + 1, NK = db->NK, ZW = db->zw_words;
-  const float Delta = db->Delta, Omega = db->Omega, omega = db->omega, nkf = db->nkf;
-  const unsigned long long *zw = reinterpret_cast<const unsigned long long *>(A.blob + db->off_zw);
-  const float *sigma = reinterpret_cast<const float *>(A.blob + db->off_sigma);
-  const int sites = (L - f) / 3, smax = L / 3;
-  float *dp = scratch + static_cast<size_t>(blockIdx.x) * scratchStride;
-  float *tile = dp + static_cast<size_t>(3) * NK * kWave;
-  float *full = A.fullS ? A.fullS + static_cast<size_t>(combo) * smax * smax : nullptr;
-  DevHss *out = A.fullS ? nullptr : A.hss + (static_cast<size_t>(bi) * 6 + combo) * A.hssCap;
-  int n = 0;
-  ScanState st{0.0f, -1, -1};
-  const bool nanSem = A.flags && (A.flags[bi] & kFlagNan);   // NaN score tables: the reference's MAX macro (rc_null_kernel.h, ref_max)
-  for (int a0 = 0; a0 < sites; a0 += kWave) {
-    const int a = a0 + lane;
-    for (int k = 0; k < 3 * NK; k++) dp[static_cast<size_t>(k) * kWave + lane] = 0.0f;
-    for (int j = a0; j < sites; j++) {
-      const int i = 3 * j + 3 + f;
-      const unsigned long long *z = zw + static_cast<size_t>(s * L1 + i) * ZW;
-      if (a <= j && a < sites) {
-        float sum = 0.0f;
-        for (int k = 0; k < NK; k++) {
-          float s0 = dp[(0 * static_cast<size_t>(NK) + k) * kWave + lane], s1 = dp[(1 * static_cast<size_t>(NK) + k) * kWave + lane],
-                s2 = dp[(2 * static_cast<size_t>(NK) + k) * kWave + lane];
-          if (nanSem) pair_step<true>(static_cast<int>((z[k >> 5] >> (2 * (k & 31))) & 3ull), sigma[(static_cast<size_t>(s) * NK + k) * L1 + i], Delta, Omega, omega, s0, s1, s2);
-          else pair_step(static_cast<int>((z[k >> 5] >> (2 * (k & 31))) & 3ull), sigma[(static_cast<size_t>(s) * NK + k) * L1 + i], Delta, Omega, omega, s0, s1, s2);
-          dp[(0 * static_cast<size_t>(NK) + k) * kWave + lane] = s0;
-          dp[(1 * static_cast<size_t>(NK) + k) * kWave + lane] = s1;
-          dp[(2 * static_cast<size_t>(NK) + k) * kWave + lane] = s2;
-          sum = sum + (nanSem ? ref_max3<true>(s0, s1, s2) : fmaxf(fmaxf(s0, s1), s2));
-        }
-        const float v = fmaxf(sum, Delta) / nkf;
-        tile[static_cast<size_t>(lane) * sites + j] = v;
-        if (full) full[static_cast<size_t>(a) * sites + j] = v;
-      }
-    }
-    __syncthreads();   // the rows written by the other lanes
-    native_scan_rows(tile, a0, (a0 + kWave < sites) ? a0 + kWave : sites, sites, s, f, A.tieThr, st, n, out, A.hssCap, lane);
-    __syncthreads();
-  }
-  if (out && lane == 0) A.hssCount[static_cast<size_t>(bi) * 6 + combo] = n;
-}
+// (k_native_dp_generic, the native block of these blocks: rc_native_dp.h)
 
 }  // namespace rc

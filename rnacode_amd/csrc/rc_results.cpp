@@ -1,4 +1,4 @@
-// rc_results.cpp -- what a finished batch holds: statuses, models, maxima, fits, HSS tables, native S matrices, backtrack paths.
+// rc_results.cpp -- what a finished batch holds: statuses, models, maxima, fits, HSS tables, native S matrices, backtrack paths, per-codon tracks.
 #include "rc_runtime.h"
 
 extern "C" {
@@ -370,6 +370,106 @@ int rc_batch_backtrack_many(const rc_batch *b, const rc_bt_range *ranges, int32_
       r0 = r1;
     }
     if (launched) HIP_TRY(hipStreamSynchronize(st));   // (the streams are non-blocking: nothing else would wait for the copy)
+    return RC_OK;
+  }();
+  if (rc != RC_OK && launched) (void)hipStreamSynchronize(st);
+  return rc;
+}
+
+// The per-codon track of the listed blocks: the native block's DP again (rc_track.hip: the scoring kernels with the track's reduction where
+// they have getHSS), one launch per row-count class as in launch_native_block, every array written by the wavefront that owns it into one device
+// buffer that comes back with one copy.  Nothing sites x sites exists: a workgroup holds 64 rows of S, an item's track is its output.
+int rc_batch_track(const rc_batch *b, const int32_t *blks, int32_t n_blks, float *out, int64_t cap, int64_t *offsets) {
+  if (!b || !offsets || n_blks < 0 || (!out && cap > 0)) return fail(RC_ERR_ARG, "bad argument");
+  if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
+  // every index is checked, and the layout made, before anything touches the device
+  struct Pos { int blk; long long off; };
+  std::map<int, std::vector<Pos>> byNK;   // N-1 -> positions whose block takes k_native_track<N-1>
+  std::vector<Pos> wide;                  // ... k_native_track_generic
+  rc_ctx *c = b->ctx;
+  int64_t total = 0;
+  for (int k = 0; k < n_blks; k++) {
+    const int blk = blks ? blks[k] : k;
+    if (blk < 0 || blk >= b->n) return fail(RC_ERR_ARG, "track block " + std::to_string(k) + ": block index out of range");
+    const BlockMeta &h = b->meta[blk];
+    const bool scored = h.status == RC_OK;
+    if (scored) {   // (the kernels of rc_batch_native_S: the tiled classes' native block takes k_native_dp<N-1> up to 64 rows)
+      const bool generic = h.N > kTemplRows || block_class(h.N, h.L, b->db[blk].omega, c->rule) == kGenericClass;
+      (generic ? wide : byNK[h.NK]).push_back(Pos{blk, static_cast<long long>(total)});
+    }
+    for (int combo = 0; combo < 6; combo++) {
+      offsets[6 * static_cast<size_t>(k) + combo] = total;
+      if (scored) total += (h.L - combo % 3) / 3;
+    }
+  }
+  offsets[6 * static_cast<size_t>(n_blks)] = total;
+  if (total > cap || total == 0) return RC_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  RC_STREAM_TRY(st, stream_aux(c));
+  HIP_TRY(hipEventSynchronize(b->evPrep));   // the z and sigma tables are made on the device (k_prep_gaps, k_native_sigma)
+  // the launches' block lists and track offsets, class by class, in one upload: ints, then (8-aligned) the offsets
+  size_t nPos = wide.size();
+  for (const auto &kv : byNK) nPos += kv.second.size();
+  const size_t offAt = (nPos * sizeof(int) + 7) & ~static_cast<size_t>(7);
+  std::vector<uint8_t> lists(offAt + nPos * sizeof(long long));
+  int *hBlocks = reinterpret_cast<int *>(lists.data());
+  long long *hOff = reinterpret_cast<long long *>(lists.data() + offAt);
+  struct Launch { int NK; size_t at, count; int smax, maxNK; };   // NK 0: the generic kernel
+  std::vector<Launch> launches;
+  size_t at = 0;
+  auto add = [&](int NK, const std::vector<Pos> &v) {
+    Launch l{NK, at, v.size(), 1, 0};
+    for (const Pos &p : v) {
+      hBlocks[at] = p.blk; hOff[at] = p.off; at++;
+      l.smax = std::max(l.smax, b->meta[p.blk].L / 3); l.maxNK = std::max(l.maxNK, b->meta[p.blk].NK);
+    }
+    launches.push_back(l);
+  };
+  for (const auto &kv : byNK) add(kv.first, kv.second);
+  if (!wide.empty()) add(0, wide);
+  // beside other batches of the context that are being scored: the grid the run's native stage takes beside k_null; else every wavefront slot
+  const int mode = c->inflight.load() > 0 ? 0 : 1;
+  const int chunk = 256;   // blocks per launch of the generic kernel, which share its scratch (launch_native_block)
+  auto wide_stride = [](const Launch &l) { return static_cast<size_t>(3) * l.maxNK * kWave + static_cast<size_t>(kWave) * l.smax; };   // states, then 64 rows of S
+  size_t tileFloats = 4;
+  for (const Launch &l : launches)
+    tileFloats = std::max(tileFloats, l.NK ? native_grid(c, l.count * 6, l.smax, mode) * kWave * l.smax : wide_stride(l) * 6 * std::min<size_t>(chunk, l.count));
+  DevBuf d_lists, d_tile, d_out;
+  for (DevBuf *d : {&d_lists, &d_tile, &d_out}) { d->retired = c->retired.get(); d->pool = c->bufPool.get(); }
+  const uint8_t *blob = b->dblob.as<uint8_t>();
+  bool launched = false;
+  // (a lambda: whatever fails in it, nothing returns to the caller -- who owns `out`, while `lists` and the buffers die with this frame --
+  // before the work already queued on the stream has drained)
+  const int rc = [&]() -> int {
+    HIP_TRY(d_lists.ensure(lists.size()));
+    HIP_TRY(d_tile.ensure(tileFloats * sizeof(float)));
+    HIP_TRY(d_out.ensure(static_cast<size_t>(total) * sizeof(float)));
+    launched = true;   // from here on something may be in flight
+    HIP_TRY(hipMemcpyAsync(d_lists.p, lists.data(), lists.size(), hipMemcpyHostToDevice, st));
+    NativeArgs na{};
+    na.blob = b->dblob.as<uint8_t>(); na.dblocks = reinterpret_cast<const DevBlock *>(blob + b->oDblocks);
+    na.flags = b->dflags.as<uint32_t>();
+    for (const Launch &l : launches) {
+      NativeArgs nc = na;
+      nc.blocks = d_lists.as<int>() + l.at;
+      const long long *trackOff = reinterpret_cast<const long long *>(d_lists.as<uint8_t>() + offAt) + l.at;
+      if (l.NK) {
+        nc.nItems = static_cast<int>(l.count) * 6;
+        nc.tile = d_tile.as<float>(); nc.tileStride = static_cast<size_t>(kWave) * l.smax;
+        if (!launch_native_track(l.NK, nc, static_cast<int>(native_grid(c, static_cast<size_t>(nc.nItems), l.smax, mode)), d_out.as<float>(), trackOff, st))
+          return fail(RC_ERR_UNSUPPORTED, "no native DP kernel for this number of rows");
+      } else {
+        for (size_t lo = 0; lo < l.count; lo += chunk) {
+          NativeArgs ng = nc;
+          ng.blocks = nc.blocks + lo;
+          launch_native_track_generic(ng, static_cast<int>(std::min<size_t>(chunk, l.count - lo)), d_tile.as<float>(), wide_stride(l), d_out.as<float>(),
+                                      trackOff + lo, st);
+        }
+      }
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(out, d_out.p, static_cast<size_t>(total) * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // (the streams are non-blocking: nothing else would wait for the copy)
     return RC_OK;
   }();
   if (rc != RC_OK && launched) (void)hipStreamSynchronize(st);
