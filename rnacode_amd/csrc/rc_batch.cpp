@@ -83,7 +83,8 @@ int batch_prepare(rc_batch *b, const rc_block *blocks, int32_t n_blocks, const r
     // The MT19937 streams of a batch are U[nodes x cols][samples padded to 64] (4 bytes each), one array for the batch's largest
     // block: a block whose array would not fit a quarter of the device memory (288 GB: nodes x cols x samples > 1.8e10, e.g.
     // 500 rows x 18 000 columns at n = 1000) gets a status of its own instead of failing the whole batch's allocation.
-    if (static_cast<double>(b->db[i].nnodes) * m.cols * static_cast<double>(SpadBytes) > static_cast<double>(ctx->totalMem) / 4.0) {
+    // (the sampling kernels address a lane's draw by a 32-bit byte offset into the row of its column: a row stays below 4 GB)
+    if (static_cast<double>(b->db[i].nnodes) * m.cols * static_cast<double>(SpadBytes) > static_cast<double>(ctx->totalMem) / 4.0 || SpadBytes >= (1ull << 32)) {
       m.status = RC_ERR_UNSUPPORTED; b->db[i].status = RC_ERR_UNSUPPORTED;
       b->errs[i] = "rows x columns x samples too large for the device: the block's random-number streams (4 bytes x tree nodes x columns x samples) exceed a quarter of its memory; split the block (breakmaf) or lower --num-samples";
       continue;

@@ -81,7 +81,8 @@ struct alignas(16) U4 { uint32_t x, y, z, w; };
 struct alignas(16) NodeRec {
   U4 thr[4];        // thr[p] = {t0, t1, t2, t3} for parent state p
   uint32_t basepack;   // base[p] in bits 2p..2p+1 (non-zero only for degenerate cumulative rows)
-  uint16_t parent;     // index of the parent node in this order (root: 0); the instantiated kernels (< 256 nodes) read its low byte
+  uint16_t parent;     // index of the parent node in this order (root: 0); the instantiated kernels (< 256 nodes) read its low byte;
+                       // bit 15 (kNodeMayClamp, rc_sim_core.h): some thr[p].w is below 2^32 - 1, a draw of this node can be clamped
   int16_t tiprow;      // alignment row of this tip, -1 for internal nodes
   uint32_t gctrl;      // k_generic_sim: where the parent's state is -- node_ctrl(parent) | bit 31 if the parent is one of this node's group of eight
   uint8_t pad[4];

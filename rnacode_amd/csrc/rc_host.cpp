@@ -12,6 +12,7 @@
 // Float/double promotions follow the reference's C expressions exactly;
 // f32()/f64() below make every rounding step explicit.
 #include "rc_host.h"
+#include "rc_sim_core.h"
 #include "rc_refexp.h"
 
 #include <algorithm>
@@ -535,6 +536,7 @@ int prepare_block(const rc_block &in, const rc_params &par, const PairTable &pt,
       uint32_t b = 0;
       pack_thresholds(q == 0 ? hky.addFreq : M[p], &nr.thr[p], &b);
       nr.basepack |= b << (2 * p);
+      if (sim_may_clamp(nr.thr[p].w)) nr.parent |= kNodeMayClamp;   // k_null compares with t3 only at such nodes
     }
   }
   uint8_t *qtip = base + d.off_qtip;

@@ -281,8 +281,8 @@ __device__ __forceinline__ void generic_body(const NullArgs &A, const uint8_t *_
           const uint32_t thx = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(at, tv)), thy = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(at + 4, tv)),
                          thz = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(at + 8, tv)), thw = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(at + 12, tv));
           const uint32_t u = uu[t];
-          const uint32_t st = (u > thx) + (u > thy) + (u > thz) + ((bp >> (2 * ps)) & 3u);
-          clamped += (u > thw);
+          const uint32_t st = sim_draw(u, thx, thy, thz) + sim_base(bp, ps);
+          clamped += sim_clamps(u, thw);
           cur |= (st & 3u) << (2 * t);
         };
         if (full) {
@@ -307,11 +307,10 @@ __device__ __forceinline__ void generic_body(const NullArgs &A, const uint8_t *_
       {
         const uint32_t c = node_ctrl(qtip[0]);
         const uint32_t wv = *reinterpret_cast<const uint16_t *>(ldsBytes + ((c & 0x7f80u) | laneSt));
-        aF = ((static_cast<uint32_t>(win[0]) << 2) | ((wv >> (c & 31u)) & 3u)) & 63u;
+        aF = sim_window6(win[0], (wv >> (c & 31u)) & 3u);
         win[0] = static_cast<uint8_t>(aF);
-        aR = codon_flip(aF) ^ 63u;
+        aR = sim_ref_rev(aF);
       }
-      const uint32_t aF64 = aF * 64u, aR64 = aR * 64u;
       uint8_t *__restrict__ kp = codes;   // sequence k's words of strand x frame 0, word 0
       const size_t kstep = static_cast<size_t>(lay.nW) * (kWave * 4);
       // (TILED: a chunk of sequences is a whole number of tiles, so that no word of the tiled layout straddles two chunks)
@@ -340,7 +339,7 @@ __device__ __forceinline__ void generic_body(const NullArgs &A, const uint8_t *_
               bb[t] = wrow[t * kWave];
             }
 #pragma unroll
-            for (int t = 0; t < CNT; t++) bb[t] = ((bb[t] << 2) | ((wv[t] >> (cc[t] & 31u)) & 3u)) & 63u;
+            for (int t = 0; t < CNT; t++) bb[t] = sim_window6(bb[t], (wv[t] >> (cc[t] & 31u)) & 3u);
 #pragma unroll
             for (int t = 0; t < CNT; t++) wrow[t * kWave] = static_cast<uint8_t>(bb[t]);
             if (emit) {
@@ -349,8 +348,8 @@ __device__ __forceinline__ void generic_body(const NullArgs &A, const uint8_t *_
               for (int t = 0; t < CNT; t++) {
                 const uint32_t mF = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(mFv), kk - k0 + t));
                 const uint32_t mR = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(mRv), kk - k0 + t));
-                wf |= static_cast<uint32_t>(pairTab[aF64 + (bb[t] & mF)]) << (6 * t + 2);
-                wr |= static_cast<uint32_t>(pairTab[aR64 + ((codon_flip(bb[t]) ^ 63u) & mR)]) << (6 * t + 2);
+                wf |= sim_pack(pairTab[sim_index_fwd(aF, bb[t], mF)], t);
+                wr |= sim_pack(pairTab[sim_index_rev(aR, bb[t], mR)], t);
               }
               cwp[posF + static_cast<size_t>(widx) * kWave] = wf;
               cwp[posR + static_cast<size_t>(widx) * kWave] = wr;
@@ -384,7 +383,7 @@ __device__ __forceinline__ void generic_body(const NullArgs &A, const uint8_t *_
             bb[t] = wrow[t * kWave];
           }
 #pragma unroll
-          for (int t = 0; t < CNT; t++) bb[t] = ((bb[t] << 2) | ((wv[t] >> (cc[t] & 31u)) & 3u)) & 63u;
+          for (int t = 0; t < CNT; t++) bb[t] = sim_window6(bb[t], (wv[t] >> (cc[t] & 31u)) & 3u);
 #pragma unroll
           for (int t = 0; t < CNT; t++) wrow[t * kWave] = static_cast<uint8_t>(bb[t]);
           if (emit) {
@@ -392,13 +391,13 @@ __device__ __forceinline__ void generic_body(const NullArgs &A, const uint8_t *_
             for (int t = 0; t < CNT; t++) {
               const uint32_t mF = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(mFv), kk + t));
               const uint32_t mR = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(mRv), kk + t));
-              pf[t] = pairTab[aF64 + (bb[t] & mF)];
-              pr[t] = pairTab[aR64 + ((codon_flip(bb[t]) ^ 63u) & mR)];
+              pf[t] = pairTab[sim_index_fwd(aF, bb[t], mF)];
+              pr[t] = pairTab[sim_index_rev(aR, bb[t], mR)];
             }
 #pragma unroll
             for (int t = 0; t < CNT; t++) {
-              kp[offF] = static_cast<uint8_t>(pf[t] << 2);
-              kp[offR] = static_cast<uint8_t>(pr[t] << 2);
+              kp[offF] = static_cast<uint8_t>(sim_pack(pf[t], 0));
+              kp[offR] = static_cast<uint8_t>(sim_pack(pr[t], 0));
               kp += kstep;
             }
           }

@@ -19,6 +19,7 @@
 
 #include "rc_device.h"
 #include "rc_launch.h"
+#include "rc_sim_core.h"
 
 namespace rc {
 
@@ -78,7 +79,6 @@ __device__ __forceinline__ void scan_step(ScanState &st, float v, int a, int j, 
   }
 }
 
-// reverse the three 2-bit fields of a codon index
 // getHSS (score.c:864-974) over the rows [aLo, aHi) of one strand x frame, the rows' entries at row[(a - aLo) * sites + j]:
 // the state machine only looks at positive entries and at the frame's final one (score.c:898); the wavefront finds them with a
 // ballot and walks the set bits in order (every lane the same walk, the entry's value comes from its lane by a shuffle; lane 0
@@ -104,8 +104,6 @@ __device__ __forceinline__ void native_scan_rows(const float *rows, int aLo, int
     }
   }
 }
-
-__device__ __forceinline__ uint32_t codon_flip(uint32_t c) { return ((c & 3u) << 4) | (c & 12u) | ((c >> 4) & 3u); }
 
 // ------------------------------------------------------------------------------------------
 // k_null<NK, LDSC>: the null-distribution loop body, lane = sample
@@ -404,10 +402,57 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
         for (int x = 0; x < 64 * 64 / 4 / kWave; x++) lds_codes[nnodes * 16 + x * kWave + lane] = psrc[x * kWave + lane];
       }
       const uint32_t *__restrict__ nodew = reinterpret_cast<const uint32_t *>(nodes);
-      uint32_t win[N];
+      // a row's last three columns twice: win for the forward strand (the newest column lowest), winR in the reverse strand's order
+      // (the newest column highest; the complement is taken where it is used) -- kept up column by column, instead of reversing
+      // the forward window's three fields for every row at every site.  Up to sixteen rows: beyond, the second set of windows costs the
+      // kernels that are held to a register budget more spills than the flips cost instructions, and those reverse the forward window
+      constexpr bool kRevWindow = N <= 16;
+      // The same bound for the tree walk below: the lean walk (kLean) holds four scalar base pairs and four scalar masks more than the
+      // plain one, and in the kernels of seventeen rows and more, which are compiled for fewer registers than they would take, scalar
+      // registers spilled to lanes of vector registers cost the cells of phase B their own (20..22 rows: 112 to 128 bytes of scratch more)
+      constexpr bool kLean = N <= 16;
+      uint32_t win[N], winR[kRevWindow ? N : 1];
 #pragma unroll
       for (int r = 0; r < N; r++) win[r] = 0;
-      unsigned int clamped = 0;
+#pragma unroll
+      for (int r = 0; r < (kRevWindow ? N : 1); r++) winR[r] = 0;
+      unsigned int clamped = 0;   // the item's draws past the end of a cumulative row; kLean: wave-uniform, padding lanes left out
+      const uint32_t laneDraw = static_cast<uint32_t>(sidx) * 4u;   // (a row of draws is below 4 GB: rc_batch.cpp)
+      const uint32_t laneWord = static_cast<uint32_t>(lane) * 4u, laneTailB = static_cast<uint32_t>(lane) * LB;
+      // The draws of one node at the pass's four sites.  asm loads: the compiler does not know them as memory operations and places no
+      // wait -- wait_draws does, before the first use; `younger`: asm loads issued behind these that may stay in flight (loads return
+      // in order).  s_nop 4: a VMEM instruction must not read an SGPR within five wait states of the scalar instruction that wrote
+      // it, and the compiler's hazard recognizer does not look inside inline asm.  (RC_PLAIN_FETCH: plain loads, as in phase B.)
+      auto fetch_draws = [&](uint32_t (&u)[4], const uint8_t *b0, const uint8_t *b1, const uint8_t *b2, const uint8_t *b3) {
+#ifdef RC_PLAIN_FETCH
+        u[0] = *reinterpret_cast<const uint32_t *>(b0 + laneDraw); u[1] = *reinterpret_cast<const uint32_t *>(b1 + laneDraw);
+        u[2] = *reinterpret_cast<const uint32_t *>(b2 + laneDraw); u[3] = *reinterpret_cast<const uint32_t *>(b3 + laneDraw);
+#else
+        asm volatile("s_nop 4\n\tglobal_load_dword %0, %4, %5\n\tglobal_load_dword %1, %4, %6\n\tglobal_load_dword %2, %4, %7\n\tglobal_load_dword %3, %4, %8"
+                     : "=&v"(u[0]), "=&v"(u[1]), "=&v"(u[2]), "=&v"(u[3]) : "v"(laneDraw), "s"(b0), "s"(b1), "s"(b2), "s"(b3));
+#endif
+      };
+      auto wait_draws = [&](uint32_t (&u)[4], auto younger) {
+#ifndef RC_PLAIN_FETCH
+        asm volatile("s_waitcnt vmcnt(%4)" : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3]) : "n"(decltype(younger)::value));
+#endif
+      };
+      // a site's code word of either strand: wave-uniform bases, the lane's byte offset added by the store itself (s_nop 4: as above)
+      auto store_words = [&](auto tail, uint32_t off, uint32_t wf, uint32_t wr, uint8_t *bF, uint8_t *bR) {
+        constexpr int W = decltype(tail)::value;   // bytes per lane: 4, or the narrow tail word's
+#ifdef RC_PLAIN_FETCH
+        constexpr bool kPlain = true;
+#else
+        constexpr bool kPlain = !kLean;
+#endif
+        if constexpr (kPlain) {
+          using T = std::conditional_t<W == 1, uint8_t, std::conditional_t<W == 2, uint16_t, uint32_t>>;
+          *reinterpret_cast<T *>(bF + off) = static_cast<T>(wf);
+          *reinterpret_cast<T *>(bR + off) = static_cast<T>(wr);
+        } else if constexpr (W == 1) asm volatile("s_nop 4\n\tglobal_store_byte %0, %1, %3\n\tglobal_store_byte %0, %2, %4" : : "v"(off), "v"(wf), "v"(wr), "s"(bF), "s"(bR) : "memory");
+        else if constexpr (W == 2) asm volatile("s_nop 4\n\tglobal_store_short %0, %1, %3\n\tglobal_store_short %0, %2, %4" : : "v"(off), "v"(wf), "v"(wr), "s"(bF), "s"(bR) : "memory");
+        else asm volatile("s_nop 4\n\tglobal_store_dword %0, %1, %3\n\tglobal_store_dword %0, %2, %4" : : "v"(off), "v"(wf), "v"(wr), "s"(bF), "s"(bR) : "memory");
+      };
       auto get_state = [&](const uint32_t (&ns)[NODEW], int q) -> uint32_t {   // q is wave-uniform
         uint32_t word = ns[0];
 #pragma unroll
@@ -419,18 +464,26 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
       int iLo = 1, iHi = L;
       if constexpr (SIM) { iLo = 1 + static_cast<int>(static_cast<long long>(L) * rowPart / parts); iHi = static_cast<int>(static_cast<long long>(L) * (rowPart + 1) / parts); }
       for (int i0 = (SIM && iLo > 3) ? iLo - 2 : 1; i0 <= iHi; i0 += SPI) {
-        size_t ubase[SPI];
+        // a site's draws: node q's lie qstrideB bytes behind node q - 1's, a lane's at laneDraw bytes into the row of its column -- a
+        // wave-uniform base per site (scalar registers, advanced per node) and ONE lane offset: the loads take both as they are and
+        // the node loop has no vector address arithmetic.  (Left to the compiler, the lane offset is widened to 64 bits outside the
+        // loop and every load gets a v_lshl_add_u64 of its own.)
+        static_assert(SPI == 4, "fetch_draws / wait_draws: four sites per pass");
+        const uint8_t *ub[SPI];
+        size_t ubase[SPI];   // (the plain walk: a lane's draw as an index)
         uint32_t ns[SPI][NODEW];
 #pragma unroll
         for (int t = 0; t < SPI; t++) {
           const int i = (i0 + t <= L) ? i0 + t : L;     // tail: repeat the last site, results unused
           const uint32_t col = (refcolw[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
+          ub[t] = reinterpret_cast<const uint8_t *>(Ustream + static_cast<size_t>(col) * A.Spad);
           ubase[t] = static_cast<size_t>(col) * A.Spad + sidx;
 #pragma unroll
           for (int x = 0; x < NODEW; x++) ns[t][x] = 0;
         }
-        const size_t qstride = static_cast<size_t>(cols) * A.Spad;
-        auto node_step = [&](int q, const uint32_t (&u)[SPI]) {
+        const size_t qstride = static_cast<size_t>(cols) * A.Spad, qstrideB = qstride * sizeof(uint32_t);
+        // the plain walk (more than sixteen rows): a site at a time, its draw loaded by the compiler, the clamp count kept per lane
+        auto node_step_plain = [&](int q, const uint32_t (&u)[SPI]) {
           const uint32_t bp = nodew[q * 20 + 16];                                // NodeRec as 20 words: scalar loads
           const int pq = static_cast<int>(nodew[q * 20 + 17] & 255u);
           auto evolve = [&](auto withBase) {   // seqgen/evolve.c:416-433 for node q at the pass's sites
@@ -438,9 +491,9 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
             for (int t = 0; t < SPI; t++) {
               const uint32_t ps = (q == 0) ? 0u : get_state(ns[t], pq);
               const U4 th = thrTab[q * thrStride + ps];
-              uint32_t st = (u[t] > th.x) + (u[t] > th.y) + (u[t] > th.z);
-              if constexpr (decltype(withBase)::value) st += (bp >> (2 * ps)) & 3u;
-              if constexpr (SIM) clamped += (u[t] > th.w) & (i0 + t >= iLo) & (i0 + t <= iHi); else clamped += (u[t] > th.w);
+              uint32_t st = sim_draw(u[t], th.x, th.y, th.z);
+              if constexpr (decltype(withBase)::value) st += sim_base(bp, ps);
+              if constexpr (SIM) clamped += sim_clamps(u[t], th.w) & (i0 + t >= iLo) & (i0 + t <= iHi); else clamped += sim_clamps(u[t], th.w);
               const uint32_t bits = st << (2 * (q & 15));
 #pragma unroll
               for (int x = 0; x < NODEW; x++) if (NODEW == 1 || (q >> 4) == x) ns[t][x] |= bits;
@@ -449,28 +502,113 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
           // base offsets exist only for degenerate cumulative rows: a real (scalar) branch, not a select
           if (__builtin_expect(bp != 0u, 0)) evolve(std::true_type{}); else evolve(std::false_type{});
         };
+        // arrived(): the wait for the draws u, placed behind the threshold reads so that those overlap the draws' round trip
+        auto node_step = [&](int q, uint32_t (&u)[SPI], auto &&arrived) {
+          const uint32_t bp = nodew[q * 20 + 16];                                // NodeRec as 20 words: scalar loads
+          const uint32_t w17 = nodew[q * 20 + 17];
+          const int pq = static_cast<int>(w17 & 255u);
+          {   // seqgen/evolve.c:416-433 for node q at the pass's sites
+            uint32_t ps[SPI], st[SPI];
+            U4 th[SPI];
+#pragma unroll
+            for (int t = 0; t < SPI; t++) {
+              ps[t] = (q == 0) ? 0u : get_state(ns[t], pq);
+              th[t] = thrTab[q * thrStride + ps[t]];
+            }
+            arrived();
+#ifndef RC_PLAIN_FETCH
+            {
+              // sim_draw at the four sites, the sites interleaved: a compare leaves its lane mask in a scalar pair of its own and the
+              // instruction that adds the mask in as a carry comes three instructions later -- a VALU instruction that reads as
+              // carry or mask an SGPR pair (or VCC) a VALU compare has just written needs two wait states in between (what the
+              // compiler pads with s_nop 1 behind every compare into VCC when it writes the sites one after the other)
+              unsigned long long m0, m1, m2, m3;
+              asm("v_cmp_gt_u32_e64 %4, %8, %12\n\tv_cmp_gt_u32_e64 %5, %9, %15\n\tv_cmp_gt_u32_e64 %6, %10, %18\n\tv_cmp_gt_u32_e64 %7, %11, %21\n\t"
+                  "v_cndmask_b32_e64 %0, 0, 1, %4\n\tv_cndmask_b32_e64 %1, 0, 1, %5\n\tv_cndmask_b32_e64 %2, 0, 1, %6\n\tv_cndmask_b32_e64 %3, 0, 1, %7\n\t"
+                  "v_cmp_gt_u32_e64 %4, %8, %13\n\tv_cmp_gt_u32_e64 %5, %9, %16\n\tv_cmp_gt_u32_e64 %6, %10, %19\n\tv_cmp_gt_u32_e64 %7, %11, %22\n\t"
+                  "v_addc_co_u32_e64 %0, %4, 0, %0, %4\n\tv_addc_co_u32_e64 %1, %5, 0, %1, %5\n\tv_addc_co_u32_e64 %2, %6, 0, %2, %6\n\tv_addc_co_u32_e64 %3, %7, 0, %3, %7\n\t"
+                  "v_cmp_gt_u32_e64 %4, %8, %14\n\tv_cmp_gt_u32_e64 %5, %9, %17\n\tv_cmp_gt_u32_e64 %6, %10, %20\n\tv_cmp_gt_u32_e64 %7, %11, %23\n\t"
+                  "v_addc_co_u32_e64 %0, %4, 0, %0, %4\n\tv_addc_co_u32_e64 %1, %5, 0, %1, %5\n\tv_addc_co_u32_e64 %2, %6, 0, %2, %6\n\tv_addc_co_u32_e64 %3, %7, 0, %3, %7"
+                  : "=&v"(st[0]), "=&v"(st[1]), "=&v"(st[2]), "=&v"(st[3]), "=&s"(m0), "=&s"(m1), "=&s"(m2), "=&s"(m3)
+                  : "v"(u[0]), "v"(u[1]), "v"(u[2]), "v"(u[3]), "v"(th[0].x), "v"(th[0].y), "v"(th[0].z), "v"(th[1].x), "v"(th[1].y), "v"(th[1].z),
+                    "v"(th[2].x), "v"(th[2].y), "v"(th[2].z), "v"(th[3].x), "v"(th[3].y), "v"(th[3].z));
+            }
+#else
+#pragma unroll
+            for (int t = 0; t < SPI; t++) st[t] = sim_draw(u[t], th[t].x, th[t].y, th[t].z);
+#endif
+            // A draw can only lie past the end of a cumulative row whose last threshold is below 2^32 - 1: the host marks the nodes that
+            // have one (kNodeMayClamp; 45 % of the bench workload's), the others never compare with it.  The compares leave lane masks
+            // in scalar registers; a mask with a bit set (about one draw in 10^7) is counted in the arm nobody takes.
+            if (w17 & kNodeMayClamp) {
+              auto clamp_mask = [&](int t) -> unsigned long long {
+                const unsigned long long m = __ballot(sim_clamps(u[t], th[t].w) != 0u);
+                if constexpr (SIM) return (i0 + t >= iLo && i0 + t <= iHi) ? m : 0ull; else return m;
+              };
+              unsigned long long any = 0;
+#pragma unroll
+              for (int t = 0; t < SPI; t++) any |= clamp_mask(t);
+              if (__builtin_expect(any != 0ull, 0)) {
+                const unsigned long long live = __ballot(sidx < A.sampleN);   // padding lanes do not count
+#pragma unroll
+                for (int t = 0; t < SPI; t++) clamped += static_cast<unsigned int>(__builtin_popcountll(clamp_mask(t) & live));
+              }
+            }
+            // base offsets exist only for degenerate cumulative rows: a real (scalar) branch, not a select
+            if (__builtin_expect(bp != 0u, 0)) {
+#pragma unroll
+              for (int t = 0; t < SPI; t++) st[t] += sim_base(bp, ps[t]);
+            }
+#pragma unroll
+            for (int t = 0; t < SPI; t++) {
+              const uint32_t bits = st[t] << (2 * (q & 15));
+#pragma unroll
+              for (int x = 0; x < NODEW; x++) if (NODEW == 1 || (q >> 4) == x) ns[t][x] |= bits;
+            }
+          }
+        };
         if constexpr (SIM) {
           // Rows split over workgroups is the path of a chip that is nearly empty (one wavefront per SIMD at most): nothing hides the
           // round trip of a node's draws, and 2N - 2 of them per pass in a chain were 0.55 of the 0.67 ms a one-block launch took.  The draws
           // of eight nodes are fetched together here (32 loads in flight) -- the form that was slower where sixteen wavefronts share a CU.
           constexpr int QB = 8;
           for (int q0 = 0; q0 < nnodes; q0 += QB) {
-            uint32_t ub[QB][SPI];
+            uint32_t ubq[QB][SPI];
+            if constexpr (!kLean) {
 #pragma unroll
-            for (int x = 0; x < QB; x++) {
-              const int q = q0 + x < nnodes ? q0 + x : nnodes - 1;
+              for (int x = 0; x < QB; x++) {
+                const int q = q0 + x < nnodes ? q0 + x : nnodes - 1;
 #pragma unroll
-              for (int t = 0; t < SPI; t++) ub[x][t] = Ustream[ubase[t] + q * qstride];
+                for (int t = 0; t < SPI; t++) ubq[x][t] = Ustream[ubase[t] + q * qstride];
+              }
+#pragma unroll
+              for (int x = 0; x < QB; x++) if (q0 + x < nnodes) node_step_plain(q0 + x, ubq[x]);
+              continue;
             }
 #pragma unroll
-            for (int x = 0; x < QB; x++) if (q0 + x < nnodes) node_step(q0 + x, ub[x]);
+            for (int x = 0; x < QB; x++) {
+              const size_t at = static_cast<size_t>(q0 + x < nnodes ? q0 + x : nnodes - 1) * qstrideB;
+              fetch_draws(ubq[x], ub[0] + at, ub[1] + at, ub[2] + at, ub[3] + at);
+            }
+            static_for<QB>([&](auto xc) {
+              constexpr int x = decltype(xc)::value;
+              wait_draws(ubq[x], std::integral_constant<int, SPI * (QB - 1 - x)>{});
+              if (q0 + x < nnodes) node_step(q0 + x, ubq[x], [] {});
+            });
           }
         } else {
           for (int q = 0; q < nnodes; q++) {
             uint32_t u[SPI];
+            if constexpr (!kLean) {
 #pragma unroll
-            for (int t = 0; t < SPI; t++) u[t] = Ustream[ubase[t] + q * qstride];
-            node_step(q, u);
+              for (int t = 0; t < SPI; t++) u[t] = Ustream[ubase[t] + q * qstride];
+              node_step_plain(q, u);
+              continue;
+            }
+            fetch_draws(u, ub[0], ub[1], ub[2], ub[3]);
+#pragma unroll
+            for (int t = 0; t < SPI; t++) ub[t] += qstrideB;
+            node_step(q, u, [&] { wait_draws(u, std::integral_constant<int, 0>{}); });
           }
         }
 #pragma unroll
@@ -478,11 +616,19 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
           const int i = i0 + t;
           if (i <= L) {
 #pragma unroll
-            for (int r = 0; r < N; r++) win[r] = (win[r] << 2) | get_state(ns[t], static_cast<int>((qtipw[r >> 2] >> (8 * (r & 3))) & 255u));   // low 6 bits = the codon; older sites drift out at the top
+            for (int r = 0; r < N; r++) {
+              const uint32_t tip = get_state(ns[t], static_cast<int>((qtipw[r >> 2] >> (8 * (r & 3))) & 255u));
+              win[r] = sim_window(win[r], tip);   // low 6 bits = the codon; older sites drift out at the top
+              if constexpr (kRevWindow) winR[r] = sim_window_rev(winR[r], tip);
+            }
             if (i >= 3 && (!SIM || (i >= iLo && i <= iHi))) {
               const int ip = L + 3 - i;  // reverse-strand position whose codon is these three columns
               const uint32_t aF = win[0] & 63u;
-              const uint32_t aR = codon_flip(aF) ^ 63u;
+              uint32_t aR = kRevWindow ? sim_rev_codon(winR[0]) : sim_ref_rev(aF);
+              asm("" : "+v"(aR));   // (opaque: its table row is addressed once per site, not folded into every row's index)
+              // the two strands' words of this site: a wave-uniform base each, the lane's offset added by the store itself
+              uint8_t *siteF = reinterpret_cast<uint8_t *>(cod + static_cast<size_t>(0 * L1 + i) * PSW);
+              uint8_t *siteR = reinterpret_cast<uint8_t *>(cod + static_cast<size_t>(1 * L1 + ip) * PSW);
 #pragma unroll
               for (int w = 0; w < NCW; w++) {
                 uint32_t wf = 0, wr = 0;
@@ -491,27 +637,24 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                 for (int c = 0; c < CPW; c++) {
                   const int k = w * CPW + c;  // 0-based index of sequence k+1
                   if (k < NK) {
-                    const uint32_t bF = win[k + 1] & ((mF >> (6 * c)) & 63u);
-                    const uint32_t bR = (codon_flip(win[k + 1]) ^ 63u) & ((mR >> (6 * c)) & 63u);
                     // field c sits at bits [6c+7 : 6c+2]: shifted down by 6c it is a ds_bpermute address
-                    wf |= static_cast<uint32_t>(pairLut[aF * 64 + bF]) << (6 * c + 2);
-                    wr |= static_cast<uint32_t>(pairLut[aR * 64 + bR]) << (6 * c + 2);
+                    wf |= sim_pack(pairLut[sim_index_fwd(aF, win[k + 1], sim_mask_field(mF, c))], c);
+                    if constexpr (kRevWindow) wr |= sim_pack(pairLut[sim_index_rev_window(aR, winR[k + 1], sim_mask_field(mR, c))], c);
+                    else wr |= sim_pack(pairLut[sim_index_rev(aR, win[k + 1], sim_mask_field(mR, c))], c);
                   }
                 }
                 if (w < NCW - 1) {
-                  cod[static_cast<size_t>(0 * L1 + i) * PSW + w * kWave + lane] = wf;
-                  cod[static_cast<size_t>(1 * L1 + ip) * PSW + w * kWave + lane] = wr;
+                  store_words(std::integral_constant<int, 4>{}, laneWord, wf, wr, siteF + w * kWave * 4, siteR + w * kWave * 4);
                 } else {
-                  reinterpret_cast<TailT *>(cod + static_cast<size_t>(0 * L1 + i) * PSW + (NCW - 1) * kWave)[lane] = static_cast<TailT>(wf);
-                  reinterpret_cast<TailT *>(cod + static_cast<size_t>(1 * L1 + ip) * PSW + (NCW - 1) * kWave)[lane] = static_cast<TailT>(wr);
+                  store_words(std::integral_constant<int, LB>{}, laneTailB, wf, wr, siteF + (NCW - 1) * kWave * 4, siteR + (NCW - 1) * kWave * 4);
                 }
               }
             }
           }
         }
       }
-      // padding lanes do not count; with comboSplit the six parts of an item redo the same simulation: the first one reports
-      if (clamped && sidx < A.sampleN && (SIM || onlyCombo <= 0)) atomicAdd(A.clampCount, static_cast<unsigned long long>(clamped));
+      // with comboSplit the six parts of an item redo the same simulation: the first one reports
+      if (clamped && (kLean ? lane == 0 : sidx < A.sampleN) && (SIM || onlyCombo <= 0)) atomicAdd(A.clampCount, static_cast<unsigned long long>(clamped));
     }
     if constexpr (SIM) continue;   // the scoring is another launch's (MODE 1)
     if (!helping && shared) {   // a late item: its codes are in the scratch, open it to the workgroups that have run out of work
