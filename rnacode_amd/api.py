@@ -279,9 +279,7 @@ def code_tables(blosum: int = 62, genetic_code: Union[int, str, None] = None) ->
 
 def fit_tree(block: AlnBlock) -> Tuple[str, float]:
     """Tree + kappa of one block (what treeML hands to the scorer, src/treeML.c:35-152); host code."""
-    rows = (C.c_char_p * block.n)(*[r.seq.encode() for r in block.rows])
-    names = (C.c_char_p * block.n)(*[r.name.encode() for r in block.rows])
-    blk = RcBlock(block.n, block.cols, rows, names, block.rows[0].start, block.rows[0].length, None, 0.0)
+    blk, _keep = _one_block(block)
     buf = C.create_string_buffer(1 << 16)
     kappa = C.c_float()
     _check(lib().rc_fit_tree(C.byref(blk), buf, len(buf), C.byref(kappa)))
@@ -298,10 +296,8 @@ class Marshalled:
         self.arr = (RcBlock * max(n, 1))()
         self.keep = []
         for i, b in enumerate(self.blocks):
-            rows = (C.c_char_p * b.n)(*[r.seq.encode() for r in b.rows])
-            names = (C.c_char_p * b.n)(*[r.name.encode() for r in b.rows])
-            self.keep.append((rows, names))
-            self.arr[i] = RcBlock(b.n, b.cols, rows, names, b.rows[0].start, b.rows[0].length, None, 0.0)
+            self.arr[i], keep = _one_block(b)
+            self.keep.append(keep)
 
     def set_trees(self, strict: bool = True):
         """Copy tree and kappa of the AlnBlocks into the array (after they were fitted or read from a sidecar).
@@ -322,31 +318,35 @@ class Marshalled:
             self.arr[i].kappa = b.kappa
 
 
+def _tree_outputs(m: Marshalled, cap: int):
+    """(n, cap, text buffer, kappa array) of an rc_fit_*trees* call over m's blocks: `cap` bytes of Newick text per block."""
+    n = len(m.blocks)
+    if cap <= 0:   # room for the widest block's Newick text (name + ":0.123456" + brackets per node)
+        cap = max(1 << 14, 96 * max((b.n for b in m.blocks), default=0))
+    return n, cap, C.create_string_buffer(max(n, 1) * cap), (C.c_float * max(n, 1))()
+
+
+def _decode_trees(n, cap, buf, kap) -> List[Optional[Tuple[str, float]]]:
+    raw = buf.raw   # one copy (buf.raw copies the whole buffer on every access)
+    texts = [raw[i * cap:(i + 1) * cap].split(b"\0", 1)[0].decode() for i in range(n)]
+    return [(s, float(k)) if s else None for s, k in zip(texts, kap)]
+
+
 def fit_trees(blocks, threads: int = 0, cap: int = 0, ctx: "Optional[Context]" = None,
               lnl: Optional[list] = None) -> List[Optional[Tuple[str, float]]]:
     """Trees + kappas of many blocks (a sequence of AlnBlocks or a Marshalled); None for blocks the driver skips.
     With ctx: rc_fit_trees_device (one wavefront per block on that context's GPU; `lnl`, if a list, receives the
     log-likelihoods); without: rc_fit_trees on host threads."""
     m = blocks if isinstance(blocks, Marshalled) else Marshalled(blocks)
-    n = len(m.blocks)
-    arr = m.arr
-    if cap <= 0:   # room for the widest block's Newick text (name + ":0.123456" + brackets per node)
-        cap = max(1 << 14, 96 * max((b.n for b in m.blocks), default=0))
-    buf = C.create_string_buffer(max(n, 1) * cap)
-    kap = (C.c_float * max(n, 1))()
+    n, cap, buf, kap = _tree_outputs(m, cap)
     if ctx is not None:
         ll = (C.c_double * max(n, 1))()
-        _check(lib().rc_fit_trees_device(ctx._h, arr, n, buf, cap, kap, ll))
+        _check(lib().rc_fit_trees_device(ctx._h, m.arr, n, buf, cap, kap, ll))
         if lnl is not None:
             lnl[:] = [float(x) for x in ll[:n]]
     else:
-        _check(lib().rc_fit_trees(arr, n, buf, cap, kap, threads))
-    out = []
-    raw = buf.raw   # one copy (buf.raw copies the whole buffer on every access)
-    for i in range(n):
-        s = raw[i * cap:(i + 1) * cap].split(b"\0", 1)[0].decode()
-        out.append((s, float(kap[i])) if s else None)
-    return out
+        _check(lib().rc_fit_trees(m.arr, n, buf, cap, kap, threads))
+    return _decode_trees(n, cap, buf, kap)
 
 
 SPECIES_MODES = {"fixed": 0, "scale": 1, "branches": 2}   # RC_SPECIES_FIXED / _SCALE / _BRANCHES
@@ -401,11 +401,7 @@ def fit_species_trees(blocks, tree: SpeciesTree, mode: str = "scale", ctx: "Opti
     if mode not in SPECIES_MODES:
         raise ValueError(f"species tree fit mode must be one of {', '.join(SPECIES_MODES)}")
     m = blocks if isinstance(blocks, Marshalled) else Marshalled(blocks)
-    n = len(m.blocks)
-    if cap <= 0:
-        cap = max(1 << 14, 96 * max((b.n for b in m.blocks), default=0))
-    buf = C.create_string_buffer(max(n, 1) * cap)
-    kap = (C.c_float * max(n, 1))()
+    n, cap, buf, kap = _tree_outputs(m, cap)
     sc = (C.c_double * max(n, 1))()
     if ctx is not None:
         ll = (C.c_double * max(n, 1))()
@@ -419,19 +415,12 @@ def fit_species_trees(blocks, tree: SpeciesTree, mode: str = "scale", ctx: "Opti
         _check(lib().rc_fit_species_trees(tree._h, SPECIES_MODES[mode], m.arr, n, buf, cap, kap, sc, threads))
     if scale is not None:
         scale[:] = [float(x) for x in sc[:n]]
-    out = []
-    raw = buf.raw
-    for i in range(n):
-        s = raw[i * cap:(i + 1) * cap].split(b"\0", 1)[0].decode()
-        out.append((s, float(kap[i])) if s else None)
-    return out
+    return _decode_trees(n, cap, buf, kap)
 
 
 def tree_lnl(block: AlnBlock, newick: str, kappa: float) -> float:
     """HKY85 log-likelihood of a given tree + kappa on the block (same model/data handling as fit_tree)."""
-    rows = (C.c_char_p * block.n)(*[r.seq.encode() for r in block.rows])
-    names = (C.c_char_p * block.n)(*[r.name.encode() for r in block.rows])
-    blk = RcBlock(block.n, block.cols, rows, names, block.rows[0].start, block.rows[0].length, newick.encode(), kappa)
+    blk, _keep = _one_block(block, newick, kappa)
     out = C.c_double()
     _check(lib().rc_tree_lnl(C.byref(blk), C.byref(out)))
     return out.value

@@ -289,6 +289,19 @@ class Pool {
   }
 };
 
+// fn(i) for every i in [0, n) on `threads` threads (never more than n): the caller and threads - 1 helpers that live for the call, items
+// handed out one by one.  The tree fits' loops (rc_trees_api.cpp).  Not Pool::run, on purpose: a Pool serves one caller at a time, and the
+// drivers fit trees on a thread of their own while rc_stream_submit prepares blocks on the context's pool.  `threads` is the caller's rule,
+// from the context's hostThreads or effective_cpus().
+template <typename F> void parallel_for(int n, unsigned threads, F &&fn) {
+  std::atomic<int> next{0};
+  const auto work = [&] { for (int i; (i = next.fetch_add(1)) < n;) fn(i); };
+  std::vector<std::thread> th;
+  for (unsigned t = 1; t < threads && t < static_cast<unsigned>(std::max(n, 0)); t++) th.emplace_back(work);
+  work();
+  for (auto &x : th) x.join();
+}
+
 inline size_t al256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
 // rc_batch_backtrack_many: device bytes (item descriptors + one byte per sequence and codon step) one launch may take; a call with more

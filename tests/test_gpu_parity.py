@@ -1134,6 +1134,35 @@ def test_device_tree_fit_in_several_launches(ctx, monkeypatch):
     assert parts == whole and all(t is not None for t in whole)
 
 
+def test_device_tree_fit_of_a_batch_that_takes_every_route_at_once(ctx):
+    """One rc_fit_trees_device call whose blocks go every way a block can go -- enough small ones for the second stream, a class of fewer
+    workgroups per CU, columns in global memory, the host estimator (more than 64 tips), skipped -- gives each block the tree it gets in
+    a call of its own shape alone, and the host fit's tree to test_device_tree_fit_matches_the_host_fit's tolerances."""
+    import dataclasses
+    from rnacode_amd import api
+    from rnacode_amd.synth import synth_blocks
+    short_ref = synth_blocks(1, 4, 30, seed=16)[0]
+    short_ref.rows[0] = dataclasses.replace(short_ref.rows[0], seq="AC" + "-" * 28)
+    shapes = [synth_blocks(4096, 3, 30, seed=11), synth_blocks(40, 9, 150, seed=12), synth_blocks(4, 12, 600, seed=13),
+              synth_blocks(1, 65, 30, seed=14), [dataclasses.replace(b, rows=b.rows[:2]) for b in synth_blocks(2, 3, 30, seed=15)], [short_ref]]
+    blocks = [b for s in shapes for b in s]
+    lnl = []
+    whole = api.fit_trees(blocks, ctx=ctx, lnl=lnl)
+    parts = [t for s in shapes for t in api.fit_trees(s, ctx=ctx)]
+    assert parts == whole
+    assert whole[-3:] == [None, None, None] and all(t is not None for t in whole[:-3])
+    at = 0
+    for s in shapes[:4]:
+        some = s[:20]
+        for b, d, h, l in zip(some, whole[at:at + len(some)], api.fit_trees(some), lnl[at:at + len(some)]):
+            (td, ld), (th, lh) = _newick_parts(d[0]), _newick_parts(h[0])
+            assert td == th, b.block_id
+            assert max(abs(x - y) for x, y in zip(ld, lh)) < 2e-4
+            assert abs(d[1] - h[1]) <= 1e-3 * h[1]
+            assert abs(l - api.tree_lnl(b, d[0], d[1])) < 1e-2
+        at += len(s)
+
+
 def test_bulk_hss_fetch_equals_per_block_fetch(ctx):
     """rc_batch_hss_all against rc_batch_hss block by block (scored, skipped and empty blocks mixed)."""
     doc = load_golden("genomic_preprocessed_n100")
