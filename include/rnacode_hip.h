@@ -297,6 +297,32 @@ int rc_batch_backtrack_many(const rc_batch *b, const rc_bt_range *ranges, int32_
  * fit failed, as for an HSS. */
 int rc_batch_track(const rc_batch *b, const int32_t *blks, int32_t n_blks, float *out, int64_t cap, int64_t *offsets /* 6 n_blks + 1 */);
 
+/* The score of given segments, with the per-row scores it is made of (not in the reference, which only lists what getHSS keeps).  A range
+ * (blk, strand, opt_b, opt_i) is the segment an HSS with start = opt_b, end = opt_i describes: start codon a = (opt_b - 1) / 3 of frame
+ * (opt_b - 1) % 3, end codon j = (opt_i - 3 - frame) / 3; the ranges and their validity rules are those of rc_batch_backtrack_many.  For
+ * every range r the call returns
+ *     score_out[r] = S[a][j] = max(sum over k of P_k, Delta) / (N - 1),
+ * S the matrix rc_batch_native_S documents, and -- if pair_out is not NULL -- the pair scores P_k of the rows k = 1 .. n_rows - 1 against
+ * the reference row at pair_out[offsets[r] + k - 1]: P_k is the maximum of the three states of the recurrence (score.c:506-533) started
+ * at codon a with every state 0 and stepped to codon j.  The sum is taken in binary32 from 0.0f in row order, as the scoring kernels take
+ * it, so score_out[r] has the bits of rc_batch_native_S(blk, strand, frame)[a][j] -- and of the score of an HSS with these coordinates --
+ * and folding the returned P_k that way (max with Delta, division by (float)(N - 1)) gives score_out[r] again; leaving row k out of the
+ * sum gives the score without that row.  A range without a step (opt_i < opt_b + 2) has P_k = 0 for every k.
+ * offsets (n_ranges + 1 entries; may be NULL iff pair_out is NULL) is filled on the host: offsets[r] is the sum of n_rows - 1 over the
+ * ranges before r, so the caller knows offsets[n_ranges] beforehand; with pair_out, cap < offsets[n_ranges] is RC_ERR_ARG.  The pair scores
+ * are made on the device whether or not they are asked for (the sum needs them); without pair_out only the scores come back.
+ * A malformed range or a block index out of range returns RC_ERR_ARG and rc_last_error names the range's index; a range on a block that
+ * was not scored returns that block's status; a batch that has not completed a run, or more than 2^31 - 1 (range, row) items in one call,
+ * RC_ERR_ARG.  Every range is checked before the device is touched: on any of these errors nothing is launched and score_out and
+ * pair_out are left alone.  n_ranges = 0 is RC_OK; a range may be listed more than once.  One launch per kernel (pair scores, then one
+ * lane per range for the sums), one synchronisation, one copy back per output array; device memory is 20 bytes per range and 4 per
+ * (range, row).  Works on a batch rc_stream_next handed out until it is recycled.
+ * p-values are the caller's: rc_pvalue(score, mu, lambda) with rc_batch_fit, 99 where the fit failed.  The fit describes the block's
+ * MAXIMUM over all segments, so this is the probability that the block-wide maximum of a null alignment reaches the score: for a segment
+ * chosen beforehand it is conservative. */
+int rc_batch_segment_scores(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, float *score_out /* n_ranges */,
+                            float *pair_out /* may be NULL */, int64_t cap, int64_t *offsets /* n_ranges + 1, may be NULL iff pair_out is NULL */);
+
 /* The substitution matrix and genetic code the scorer uses, for callers that render results
  * (getScoringMatrix() score.c:50-76 and transcode[4][4][4] code.c:28-39, which src/postscript.c:362,412
  * read): pep_out[16a+4b+c] = amino-acid index 0..19 of codon (a,b,c) in A,C,G,T order or -1 for a stop;

@@ -170,6 +170,7 @@ def lib():
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.rc_batch_backtrack_many.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         l.rc_batch_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        l.rc_batch_segment_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.rc_evd_fit.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         l.rc_mt_stream.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_int32]
         l.rc_pvalue.argtypes = [C.c_float, C.c_float, C.c_float]
@@ -203,7 +204,7 @@ EXPORTED_SYMBOLS = [
     "rc_batch_prep_timing", "rc_host_cpus", "rc_ctx_set_host_threads", "rc_ctx_host_threads", "rc_ctx_fit_exp_mode", "rc_stream_create_v2", "rc_stream_submit", "rc_stream_submit_bound",
     "rc_stream_next", "rc_stream_recycle", "rc_stream_pending", "rc_stream_plan", "rc_stream_destroy", "rc_set_stream_cache", "rc_batch_work", "rc_batch_timing", "rc_batch_null_kernel", "rc_batch_status",
     "rc_batch_models", "rc_batch_maxima", "rc_batch_maxima_all", "rc_batch_fit", "rc_batch_fit_all", "rc_batch_hss", "rc_batch_hss_all", "rc_batch_clamped",
-    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
+    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_batch_segment_scores", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
     "rc_code_tables_for", "rc_genetic_code", "rc_species_tree_create", "rc_species_tree_destroy", "rc_species_tree_tips", "rc_species_tree_prune",
     "rc_fit_species_trees", "rc_fit_species_trees_device",
 ]
@@ -683,6 +684,25 @@ class Batch:
             _check(lib().rc_batch_track(self._h, ptr, n, vals.ctypes.data, total, op))
         o = offs.tolist()
         return [[[vals[o[6 * k + 3 * s + f]:o[6 * k + 3 * s + f + 1]] for f in range(3)] for s in range(2)] for k in range(n)]
+
+    def segment_scores(self, ranges, pairs: bool = True) -> Tuple[np.ndarray, Optional[List[np.ndarray]]]:
+        """rc_batch_segment_scores: the scores of all `ranges` -- (blk, strand 0 | 1, opt_b, opt_i) tuples, as backtrack_many takes -- with one
+        call: a float32 array, scores[r] bit-equal to native_S(blk, strand, frame)[a][j] of the range's codons, and (pairs) per range the
+        float32 pair scores of its rows 1 .. n_rows - 1 against the reference row, whose float32 sum in row order, max with Delta, divided
+        by float32(n_rows - 1), is that score (segments.leave_one_out drops a row from it); else None."""
+        arr = np.ascontiguousarray(np.asarray(list(ranges), dtype=np.int32).reshape(-1, 4))
+        n = arr.shape[0]
+        scores = np.zeros(n, dtype=np.float32)
+        if not pairs:
+            _check(lib().rc_batch_segment_scores(self._h, arr.ctypes.data, n, scores.ctypes.data, None, 0, None))
+            return scores, None
+        # the layout is known beforehand: n_rows - 1 pair scores per range (a bad block index is the library's to report)
+        total = sum(self.blocks[b].n - 1 for b in arr[:, 0].tolist() if 0 <= b < self.n)
+        vals = np.zeros(max(total, 1), dtype=np.float32)
+        offs = np.zeros(n + 1, dtype=np.int64)
+        _check(lib().rc_batch_segment_scores(self._h, arr.ctypes.data, n, scores.ctypes.data, vals.ctypes.data, total, offs.ctypes.data))
+        o = offs.tolist()
+        return scores, [vals[o[r]:o[r + 1]] for r in range(n)]
 
     def results(self, blk: int, with_maxima: bool = False) -> BlockScores:
         st = self.status(blk)

@@ -4,7 +4,8 @@ Mirrors the reference's command line (src/cmdline.ggo:6-20, src/RNAcode.c:236-37
 options that concern the scoring path and the listings:
 
     python -m rnacode_amd.cli [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S]
-                              [-e [-i CUTOFF] [-d DIR]] [--details FILE] [--track FILE] [-o OUT] [--trees SIDECAR | --species-tree NEWICK
+                              [-e [-i CUTOFF] [-d DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE]
+                              [-o OUT] [--trees SIDECAR | --species-tree NEWICK
                               [--species-tree-fit fixed|scale|branches]] [--write-trees SIDECAR] [FILE]
 
 Tree + kappa per block (PhyML in the reference, RNAcode.c:153) come either from a sidecar
@@ -18,6 +19,10 @@ alignment plots (src/postscript.c) as <DIR>/hss-<n>.eps.  --details FILE (not in
 line per listed HSS and aligned sequence (details.py); plots and table of a sub-batch come from one rc_batch_backtrack_many call.
 --track FILE (not in the reference) writes the per-codon coding-potential track of every scored block, strand and frame as runs of equal score
 (track.py; one rc_batch_track call per sub-batch).  -b and -r filter the listing only: the track covers every scored block.
+--support FILE (not in the reference) writes, per listed HSS and aligned sequence, the sequence's pair score against the reference row, its
+share of the segment's score and the score without it; --regions FILE with --regions-out FILE scores the segments the file lists (name,
+strand and the listing's Start / End) in every scored block that contains them, whether or not the listing shows them (segments.py; the
+ranges of a sub-batch go in one rc_batch_segment_scores call).
 Quirk kept from the reference: the 4th value of --pars goes to stopPenalty_0 (RNAcode.c:318)."""
 from __future__ import annotations
 
@@ -29,7 +34,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import api, details, eps, report, track
+from . import api, details, eps, report, segments, track
 from .alnio import AlnBlock, read_alignment_file
 
 
@@ -118,6 +123,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--track", metavar="FILE",
                     help="write a tab-separated per-codon track: for every scored block, strand and frame the runs of codons that share "
                          "their best segment's score, where that score is positive and its p below --cutoff")
+    ap.add_argument("--support", metavar="FILE",
+                    help="write a tab-separated table with one line per listed HSS and aligned sequence: the sequence's pair score against "
+                         "the reference, its share of the segment's score, and the segment's score without that sequence")
+    ap.add_argument("--regions", metavar="FILE",
+                    help="score given segments (with --regions-out): tab-separated lines 'name strand start end [id]', name a block's "
+                         "reference sequence and start / end as the -t listing prints them")
+    ap.add_argument("--regions-out", metavar="FILE",
+                    help="where the scores of the --regions segments go: one line per region and scored block that contains it")
     return ap
 
 
@@ -139,6 +152,18 @@ def main(argv=None) -> int:
     except api.RnacodeError as e:   # a bad --genetic-code: before any context exists
         print(f"ERROR: --genetic-code: {str(e).split(': ', 1)[-1]}", file=sys.stderr)
         return 1
+    regions = None
+    if bool(a.regions) != bool(a.regions_out):   # before any context exists
+        print("ERROR: --regions and --regions-out go together", file=sys.stderr)
+        return 1
+    if a.regions:
+        try:
+            with open(a.regions) as fh:
+                regions = segments.read_regions(fh.readlines())
+        except OSError as e:
+            print(f"ERROR: --regions: {e}", file=sys.stderr)
+            return 1
+        regions_of = segments.by_name(regions)
     species = None
     if a.species_tree:   # parsed before any context exists
         if a.trees:
@@ -214,6 +239,13 @@ def main(argv=None) -> int:
     if a.track:
         track_out = open(a.track, "w")
         track_out.write(track.header())
+    support_out = regions_out = None
+    if a.support:
+        support_out = open(a.support, "w")
+        support_out.write(segments.support_header())
+    if regions is not None:
+        regions_out = open(a.regions_out, "w")
+        regions_out.write(segments.regions_header())
     eps_cutoff32 = float(np.float32(a.eps_cutoff))
     try:
         for batch in api.score_stream(ctx, marshalled, params, sub_blocks, depth=3):
@@ -240,6 +272,28 @@ def main(argv=None) -> int:
             if track_out is not None:
                 want = [i for i in range(batch.n) if status[i] == api.RC_OK and base + i not in refused]
                 tracked = dict(zip(want, batch.track(want))) if want else {}
+            # --support / --regions: the scores and pair scores of every listed HSS, and of every region a scored block of the sub-batch
+            # contains, with ONE call (rc_batch_segment_scores)
+            seg_index, seg_ranges, found = {}, [], {}
+            if support_out is not None or regions_out is not None:
+                for i in range(batch.n):
+                    if status[i] != api.RC_OK or base + i in refused:
+                        continue
+                    b = prepared[base + i]
+                    if support_out is not None:
+                        for h in report.listed_hss(all_hss[i], a.cutoff, a.best_only, a.best_region):
+                            key = (i, h["strand"], h["start"], h["end"])
+                            if key not in seg_index:
+                                seg_index[key] = len(seg_ranges)
+                                seg_ranges.append((i, 0 if h["strand"] == "+" else 1, h["start"], h["end"]))
+                    if regions_out is not None:
+                        for reg in regions_of.get(b.rows[0].name, ()):
+                            at = segments.locate(reg.strand, reg.start, reg.end, b.rows[0].start, b.rows[0].length, b.ref_len)
+                            if isinstance(at, tuple):
+                                lo, hi = segments.range_of(*at)
+                                found.setdefault(i, []).append((reg, at, len(seg_ranges)))
+                                seg_ranges.append((i, 0 if reg.strand == "+" else 1, lo, hi))
+            seg_scores, seg_pairs = batch.segment_scores(seg_ranges) if seg_ranges else (None, None)
             for i in range(batch.n):
                 b = prepared[base + i]
                 code_i = status[i]
@@ -261,14 +315,24 @@ def main(argv=None) -> int:
                                              a.blosum, code)
                         with open(os.path.join(a.eps_dir, f"hss-{counter}.eps"), "w") as fh:
                             fh.write(text)
-                if a.details:
+                if a.details or support_out is not None:
                     def on_listed(counter, h, i=i, b=b):
-                        details_out.writelines(details.details_lines(counter, b, h, paths[index[(i, h["strand"], h["start"], h["end"])]], pep, matrix))
+                        if a.details:
+                            details_out.writelines(details.details_lines(counter, b, h, paths[index[(i, h["strand"], h["start"], h["end"])]], pep, matrix))
+                        if support_out is not None:
+                            support_out.writelines(segments.support_lines(counter, b.rows[0].name, h, [r.name for r in b.rows],
+                                                                          seg_pairs[seg_index[(i, h["strand"], h["start"], h["end"])]], params.Delta))
                 report.print_results(out, fmt, all_hss[i], b.rows[0].name, st, cutoff=a.cutoff, best_only=a.best_only,
                                      best_region=a.best_region, eps=hook, eps_cutoff=a.eps_cutoff, listed=on_listed)
                 if i in tracked:
                     rc, mu, lam = batch.getExtremeValuePars(i)
                     track_out.writelines(track.block_lines(b.rows[0].name, b.rows[0].start, b.rows[0].length, tracked[i], rc, mu, lam, a.cutoff))
+                if i in found:
+                    rc, mu, lam = batch.getExtremeValuePars(i)
+                    for reg, (frame, c1, c2), r in found[i]:
+                        p = api.pvalue(float(seg_scores[r]), mu, lam) if rc == 1 else 99.0
+                        regions_out.write(segments.region_line(reg, frame, c1, c2, seg_scores[r], p, seg_pairs[r]))
+                        reg.matched = True
             base += batch.n
             batch.close()
     finally:
@@ -276,6 +340,12 @@ def main(argv=None) -> int:
             details_out.close()
         if track_out is not None:
             track_out.close()
+        if support_out is not None:
+            support_out.close()
+        if regions_out is not None:
+            regions_out.close()
+    if regions is not None:   # what matched nothing: one line each, the exit status stays 0
+        sys.stderr.write("".join(segments.skipped_lines(regions)))
     if fmt == 0:
         report.print_footer(out, n_read, time.perf_counter() - t0, params.sampleN, params.Delta, params.Omega,
                             params.omega, params.stopPenalty_k)

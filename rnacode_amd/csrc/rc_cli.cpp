@@ -8,7 +8,7 @@
 // (which additionally draws the EPS plots):
 //
 //   rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]
-//               [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]
+//               [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]
 //               [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]
 //               [--write-trees SIDECAR] [FILE]
 //
@@ -33,6 +33,12 @@
 // --track FILE (not in the reference): the per-codon coding-potential track of every scored block, strand and frame as runs of equal score
 // (rc_batch_track, one call per sub-batch; rc_eps.h, track_block; the same bytes as python -m rnacode_amd.cli --track).  -b and -r filter the
 // listing only: the track covers every scored block.  With --gpus N the one writer emits it in input order.
+//
+// --support FILE (not in the reference): per listed HSS and aligned sequence the sequence's pair score against the reference row, its share of
+// the segment's score and the score without it.  --regions FILE with --regions-out FILE: the score, p and supporting rows of the segments the
+// file lists (name, strand, the listing's Start / End) in every scored block that contains them; a region that matches nothing gets a line on
+// stderr at the end of the run.  The ranges of a sub-batch go in ONE rc_batch_segment_scores call (rc_eps.h, support_tail / region_line; the
+// same bytes as python -m rnacode_amd.cli, whose segments.py documents the rules).  With --gpus N the one writer emits both in input order.
 //
 // Quirk kept from the reference: the 4th value of --pars goes to stopPenalty_0 (RNAcode.c:318).
 #include <algorithm>
@@ -296,6 +302,8 @@ struct Listing {
   std::string epsDir = "eps";
   FILE *details = nullptr;   // --details: the table's file, header written
   FILE *track = nullptr;     // --track: the track's file, header written
+  FILE *support = nullptr;   // --support: the table's file, header written
+  FILE *regions = nullptr;   // --regions-out: the file, header written
   int hitCounter = 0;
 
   // The HSS of a block in the order printResults walks them, the hidden ones marked (misc.c:400-433).  `res` is filtered and, with
@@ -331,9 +339,10 @@ struct Listing {
   }
 
   // epsText: for the k-th listed HSS the EPS file's text, or empty (drawn while the block's batch was alive; misc.c:461-474 writes
-  // hss-<counter>.eps in front of the line); detailText: for the k-th listed HSS its --details lines without the counter in front
+  // hss-<counter>.eps in front of the line); detailText / supportText: for the k-th listed HSS its --details / --support lines without the
+  // counter in front
   void block(std::vector<rc_hss> res, const std::string &refName, const std::vector<std::string> *epsText = nullptr,
-             const std::vector<std::vector<std::string>> *detailText = nullptr) {
+             const std::vector<std::vector<std::string>> *detailText = nullptr, const std::vector<std::vector<std::string>> *supportText = nullptr) {
     std::vector<char> hide;
     std::vector<size_t> order;
     arrange(res, hide, order);
@@ -359,6 +368,8 @@ struct Listing {
       }
       if (details && detailText && k < detailText->size())
         for (const std::string &tail : (*detailText)[k]) std::fprintf(details, "%i\t%s", hitCounter, tail.c_str());
+      if (support && supportText && k < supportText->size())
+        for (const std::string &tail : (*supportText)[k]) std::fprintf(support, "%i\t%s", hitCounter, tail.c_str());
       k++;
       const int length = h.endSite - h.startSite + 1;
       const char strand[2] = {static_cast<char>(h.strand), 0};
@@ -386,7 +397,8 @@ struct Listing {
 
 void usage() {
   std::fprintf(stderr, "usage: rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]\n"
-                       "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]\n"
+                       "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE]\n"
+                       "                   [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]\n"
                        "                   [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]\n"
                        "                   [--write-trees SIDECAR] [--dump-blocks] [FILE]\n"
                        "  --genetic-code ID|LETTERS  an NCBI translation table id (e.g. 2, vertebrate mitochondrial) or its 64 letters in\n"
@@ -400,7 +412,12 @@ void usage() {
                        "                             backtracked path are in frame (identical, synonymous, conservative, radical, stop, gap),\n"
                        "                             Omega or Delta moves, out of frame\n"
                        "  --track FILE               a tab-separated per-codon track: for every scored block, strand and frame the runs of codons\n"
-                       "                             that share their best segment's score, where that score is positive and its p below -p\n");
+                       "                             that share their best segment's score, where that score is positive and its p below -p\n"
+                       "  --support FILE             a tab-separated table, one line per listed HSS and aligned sequence: the sequence's pair score\n"
+                       "                             against the reference, its share of the segment's score, the score without that sequence\n"
+                       "  --regions FILE             score given segments: tab-separated lines 'name strand start end [id]', name a block's reference\n"
+                       "                             sequence, start / end as the -t listing prints them; needs\n"
+                       "  --regions-out FILE         one line per region and scored block that contains it: score, p, supporting sequences\n");
 }
 
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -416,6 +433,9 @@ struct Job {
   std::vector<std::vector<std::string>> eps;   // per block: the EPS texts of its listed HSS (--eps)
   std::vector<std::vector<std::vector<std::string>>> details;   // per block and listed HSS: its --details lines, one per row, without the counter
   std::vector<std::string> track;    // per block: its --track lines
+  std::vector<std::vector<std::vector<std::string>>> support;   // per block and listed HSS: its --support lines, one per row, without the counter
+  std::vector<std::string> regions;  // per block: its --regions-out lines
+  std::vector<int> matched;          // the regions (positions in Run::regions) those lines belong to
 };
 
 // everything the threads share
@@ -430,6 +450,9 @@ struct Run {
   int speciesMode = RC_SPECIES_SCALE;
   bool keepTrees = false;            // --write-trees: the fitted trees go back into `blocks`
   rceps::Tables tables;
+  std::vector<rceps::Region> regions;                     // --regions, in file order
+  std::map<std::string, std::vector<int>> regionsOf;      // reference row name -> the regions that can match a block, in file order
+  std::vector<char> regionMatched;                        // set by the writer
   // the writer: one thread, jobs in input order
   std::mutex jm;
   std::condition_variable jcv;
@@ -476,9 +499,11 @@ void writer_thread(Run &R) {
         continue;
       }
       R.list.block(std::vector<rc_hss>(j->hss.begin() + j->offs[i], j->hss.begin() + j->offs[i + 1]), std::string(blk.rows[0].name),
-                   j->eps.empty() ? nullptr : &j->eps[i], j->details.empty() ? nullptr : &j->details[i]);
+                   j->eps.empty() ? nullptr : &j->eps[i], j->details.empty() ? nullptr : &j->details[i], j->support.empty() ? nullptr : &j->support[i]);
       if (R.list.track && !j->track.empty()) std::fwrite(j->track[i].data(), 1, j->track[i].size(), R.list.track);
+      if (R.list.regions && !j->regions.empty()) std::fwrite(j->regions[i].data(), 1, j->regions[i].size(), R.list.regions);
     }
+    for (int r : j->matched) R.regionMatched[r] = 1;
     R.tList += now() - t;
   }
 }
@@ -601,6 +626,78 @@ bool add_track(const Run &R, rc_batch *b, Job &j, std::string &err, const std::v
   return true;
 }
 
+// --support / --regions for every scored block of a finished batch, while the batch is alive: the scores and pair scores of all listed HSS,
+// and of every region a block contains, with ONE call (rc_batch_segment_scores), then their lines (rc_eps.h, support_tail / region_line).
+// fits: as for add_track.
+bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std::vector<TrackFit> *fits = nullptr) {
+  const int m = static_cast<int>(j.blockIdx.size());
+  struct Listed { int blk; rc_hss h; int range; };
+  struct Found { int blk, region; rceps::SegLoc at; int range; };
+  std::vector<Listed> listed;
+  std::vector<Found> found;
+  std::vector<rc_bt_range> ranges;
+  std::vector<int> rowsOf;   // per range: N - 1
+  if (R.list.support) j.support.resize(m);
+  if (R.list.regions) j.regions.assign(m, std::string());
+  for (int i = 0; i < m; i++) {
+    const Block &blk = R.blocks[j.blockIdx[i]];
+    if (j.status[i] != RC_OK || !blk.refused.empty()) continue;
+    const int nk = static_cast<int>(blk.rows.size()) - 1;
+    if (R.list.support) {
+      std::vector<rc_hss> res(j.hss.begin() + j.offs[i], j.hss.begin() + j.offs[i + 1]);
+      std::vector<char> hide;
+      std::vector<size_t> order;
+      R.list.arrange(res, hide, order);
+      for (size_t idx : R.list.listed(res, hide, order)) {
+        listed.push_back(Listed{i, res[idx], static_cast<int>(ranges.size())});
+        ranges.push_back(rc_bt_range{i, res[idx].strand == '+' ? 0 : 1, res[idx].start, res[idx].end});
+        rowsOf.push_back(nk);
+      }
+    }
+    if (R.list.regions) {
+      const auto it = R.regionsOf.find(std::string(blk.rows[0].name));
+      if (it == R.regionsOf.end()) continue;
+      long long L = 0;
+      for (char c : blk.rows[0].seq) L += c != '-';
+      for (int r : it->second) {
+        const rceps::Region &g = R.regions[r];
+        rceps::SegLoc at;
+        if (rceps::seg_locate(g.strand, g.start, g.end, blk.rows[0].start, blk.rows[0].length, L, at) != rceps::kSegOk) continue;
+        found.push_back(Found{i, r, at, static_cast<int>(ranges.size())});
+        ranges.push_back(rc_bt_range{i, g.strand == '+' ? 0 : 1, 3 * at.c1 + at.frame + 1, 3 * at.c2 + at.frame + 3});
+        rowsOf.push_back(nk);
+      }
+    }
+  }
+  const int nr = static_cast<int>(ranges.size());
+  if (!nr) return true;
+  int64_t total = 0;
+  for (int k : rowsOf) total += k;
+  std::vector<float> scores(nr), pairs(static_cast<size_t>(total));
+  std::vector<int64_t> offs(static_cast<size_t>(nr) + 1, 0);
+  if (rc_batch_segment_scores(b, ranges.data(), nr, scores.data(), pairs.data(), total, offs.data()) != RC_OK) { err = rc_last_error(); return false; }
+  for (const Listed &l : listed) {
+    const Block &blk = R.blocks[j.blockIdx[l.blk]];
+    const int nk = static_cast<int>(blk.rows.size()) - 1;
+    const float *p = pairs.data() + offs[l.range];
+    const std::vector<float> loo = rceps::leave_one_out(p, nk, R.par.Delta);
+    std::vector<std::string> lines;
+    for (int k = 1; k <= nk; k++)
+      lines.push_back(rceps::support_tail(std::string(blk.rows[0].name), std::string(blk.rows[k].name), k, static_cast<char>(l.h.strand), l.h.frame, l.h.startGenomic,
+                                          l.h.endGenomic, l.h.score, l.h.pvalue, p[k - 1], static_cast<float>(nk), loo[k - 1]));
+    j.support[l.blk].push_back(std::move(lines));
+  }
+  for (const Found &f : found) {
+    TrackFit fit{-1, 0.0f, 0.0f};
+    if (fits) fit = (*fits)[f.blk];
+    else if (rc_batch_fit(b, f.blk, &fit.rc, &fit.mu, &fit.lambda) != RC_OK) { err = rc_last_error(); return false; }
+    const float p = fit.rc == 1 ? rc_pvalue(scores[f.range], fit.mu, fit.lambda) : 99.0f;
+    j.regions[f.blk] += rceps::region_line(R.regions[f.region], f.at, scores[f.range], p, pairs.data() + offs[f.range], static_cast<int>(offs[f.range + 1] - offs[f.range]));
+    j.matched.push_back(f.region);
+  }
+  return true;
+}
+
 // what the writer needs from a finished batch
 std::unique_ptr<Job> collect(const Run &R, rc_batch *b, int seq, const std::vector<int> &blockIdx, std::string &err) {
   std::unique_ptr<Job> j(new Job());
@@ -619,6 +716,7 @@ std::unique_ptr<Job> collect(const Run &R, rc_batch *b, int seq, const std::vect
   }
   if ((R.list.eps || R.list.details) && !annotate(R, b, *j, err)) return nullptr;
   if (R.list.track && !add_track(R, b, *j, err)) return nullptr;
+  if ((R.list.support || R.list.regions) && !add_segments(R, b, *j, err)) return nullptr;
   return j;
 }
 
@@ -828,6 +926,7 @@ bool run_sample_split(Run &R, std::vector<Worker> &W, std::string &err) {
   }
   if (R.list.eps || R.list.details) annotate(R, batch[0], *j, err);
   if (R.list.track && err.empty()) add_track(R, batch[0], *j, err, &fits);
+  if ((R.list.support || R.list.regions) && err.empty()) add_segments(R, batch[0], *j, err, &fits);
   for (rc_batch *b : batch) if (b) rc_batch_destroy(b);
   if (!err.empty()) return false;
   post(R, std::move(j));
@@ -841,7 +940,7 @@ int main(int argc, char **argv) {
   rc_default_params(&R.par);
   rc_params &par = R.par;
   Listing &list = R.list;
-  std::string file, outfile, trees, limit, devicesArg, speciesFile, writeTrees, detailsFile, trackFile;
+  std::string file, outfile, trees, limit, devicesArg, speciesFile, writeTrees, detailsFile, trackFile, supportFile, regionsFile, regionsOutFile;
   int device = 0, subBlocks = 0, gpus = 1;   // subBlocks 0: the library's schedule
   bool dumpBlocks = false;
   for (int a = 1; a < argc; a++) {
@@ -891,6 +990,9 @@ int main(int argc, char **argv) {
     else if (o == "-d" || o == "--eps-dir") list.epsDir = val();
     else if (o == "--details") detailsFile = val();
     else if (o == "--track") trackFile = val();
+    else if (o == "--support") supportFile = val();
+    else if (o == "--regions") regionsFile = val();
+    else if (o == "--regions-out") regionsOutFile = val();
     else if (!o.empty() && o[0] == '-' && o != "-") { usage(); return 2; }
     else file = o;
   }
@@ -898,6 +1000,16 @@ int main(int argc, char **argv) {
   {   // the genetic code is checked (host only) before any context exists
     int32_t pep[64], matrix[400];
     if (rc_code_tables_for(&par, pep, matrix) != RC_OK) die("--genetic-code: " + std::string(rc_last_error()));
+  }
+  if (regionsFile.empty() != regionsOutFile.empty()) die("--regions and --regions-out go together");   // before any context exists
+  if (!regionsFile.empty()) {
+    std::ifstream in(regionsFile, std::ios::binary);
+    if (!in) die("--regions: could not open " + regionsFile);
+    std::stringstream ss;
+    ss << in.rdbuf();
+    R.regions = rceps::regions_read(ss.str());
+    R.regionMatched.assign(R.regions.size(), 0);
+    for (size_t r = 0; r < R.regions.size(); r++) if (R.regions[r].reason == rceps::kSegOk) R.regionsOf[R.regions[r].name].push_back(static_cast<int>(r));
   }
   if (!speciesFile.empty()) {   // parsed (host only) before any context exists
     if (!trees.empty()) die("--species-tree and --trees cannot be used together");
@@ -1013,6 +1125,16 @@ int main(int argc, char **argv) {
     if (!list.track) die("Could not open " + trackFile);
     std::fputs(rceps::track_header(), list.track);
   }
+  if (!supportFile.empty()) {
+    list.support = std::fopen(supportFile.c_str(), "w");
+    if (!list.support) die("Could not open " + supportFile);
+    std::fputs(rceps::support_header(), list.support);
+  }
+  if (!regionsOutFile.empty()) {
+    list.regions = std::fopen(regionsOutFile.c_str(), "w");
+    if (!list.regions) die("Could not open " + regionsOutFile);
+    std::fputs(rceps::regions_header(), list.regions);
+  }
   if ((list.eps || list.details) && rc_code_tables_for(&par, R.tables.pep, R.tables.matrix) != RC_OK) die(rc_last_error());
   tRead = now() - tRead;
   if (ctxThread.joinable()) ctxThread.join();
@@ -1121,6 +1243,10 @@ int main(int argc, char **argv) {
   if (list.out != stdout) std::fclose(list.out);
   if (list.details && std::fclose(list.details) != 0) die("Could not write " + detailsFile);
   if (list.track && std::fclose(list.track) != 0) die("Could not write " + trackFile);
+  if (list.support && std::fclose(list.support) != 0) die("Could not write " + supportFile);
+  if (list.regions && std::fclose(list.regions) != 0) die("Could not write " + regionsOutFile);
+  for (size_t r = 0; r < R.regions.size(); r++)   // what matched nothing: one line each, the exit status stays 0
+    if (!R.regionMatched[r]) std::fputs(rceps::region_skipped(R.regions[r]).c_str(), stderr);
   std::fflush(stdout);
   std::fflush(stderr);
   if (!std::getenv("RC_CLI_TEARDOWN")) {

@@ -329,6 +329,113 @@ inline void track_block(std::string &out, const std::string &refName, int refSta
     }
 }
 
+// --support / --regions: scores of given segments with their per-row pair scores (rc_batch_segment_scores).  Same rules and bytes as
+// rnacode_amd/segments.py, which documents them.
+enum SegReason { kSegOk = 0, kSegMalformed, kSegBadLength, kSegOutside, kSegPastLastCodon };
+struct SegLoc { int frame, c1, c2; };
+// the inverse of an HSS's coordinates (rc_results.cpp, score.c:921-936): the frame and codons whose segment the listing prints as start..end
+inline SegReason seg_locate(char strand, long long start, long long end, long long refStart, long long refLength, long long L, SegLoc &out) {
+  if (end < start || (end - start + 1) % 3 != 0) return kSegBadLength;
+  long long first, last, size;
+  if (refStart == 0 && refLength == 0) { first = start - 1; last = end - 1; size = L; }
+  else if (strand == '+') { first = start - refStart; last = end - refStart; size = refLength; }
+  else { const long long top = refStart + refLength - 1; first = top - end; last = top - start; size = refLength; }
+  if (first < 0 || last >= size) return kSegOutside;
+  const long long frame = first % 3, c1 = first / 3, c2 = (last - frame - 2) / 3;
+  if (c2 > (L - frame) / 3 - 1) return kSegPastLastCodon;
+  out = SegLoc{static_cast<int>(frame), static_cast<int>(c1), static_cast<int>(c2)};
+  return kSegOk;
+}
+struct Region { int line = 0; std::string id, name; char strand = '+'; long long start = 0, end = 0; SegReason reason = kSegOk; };
+// an optional sign and one to ten digits, nothing else
+inline bool seg_int(const std::string &s, long long &v) {
+  const size_t at = (!s.empty() && (s[0] == '+' || s[0] == '-')) ? 1 : 0;
+  if (s.size() - at < 1 || s.size() - at > 10) return false;
+  for (size_t i = at; i < s.size(); i++) if (s[i] < '0' || s[i] > '9') return false;
+  v = std::atoll(s.c_str());
+  return true;
+}
+// the regions of a --regions file's text, in file order; a malformed line and a length that is no multiple of three keep their reason
+inline std::vector<Region> regions_read(const std::string &text) {
+  std::vector<Region> out;
+  int n = 0;
+  for (size_t at = 0; at < text.size();) {
+    size_t eol = text.find('\n', at);
+    if (eol == std::string::npos) eol = text.size();
+    std::string line = text.substr(at, eol - at);
+    at = eol + 1;
+    n++;
+    while (!line.empty() && (line.back() == '\r' || line.back() == '\n')) line.pop_back();
+    if (line.find_first_not_of(" \t\r\n\v\f") == std::string::npos || line[0] == '#') continue;
+    std::vector<std::string> f;
+    for (size_t p = 0;;) {
+      const size_t tab = line.find('\t', p);
+      f.push_back(line.substr(p, tab == std::string::npos ? std::string::npos : tab - p));
+      if (tab == std::string::npos) break;
+      p = tab + 1;
+    }
+    if (n == 1 && f[0] == "name") continue;
+    Region r;
+    r.line = n;
+    r.id = (f.size() > 4 && !f[4].empty()) ? f[4] : "region" + std::to_string(n);
+    if (f.size() < 4 || f[0].empty() || (f[1] != "+" && f[1] != "-") || !seg_int(f[2], r.start) || !seg_int(f[3], r.end) || r.end < r.start) {
+      r.reason = kSegMalformed;
+      out.push_back(r);
+      continue;
+    }
+    r.name = f[0]; r.strand = f[1][0];
+    if ((r.end - r.start + 1) % 3 != 0) r.reason = kSegBadLength;
+    out.push_back(r);
+  }
+  return out;
+}
+inline std::string region_skipped(const Region &r) {
+  std::string out;
+  put(out, "Skipping region %s (line %i): %s\n", r.id.c_str(), r.line,
+      r.reason == kSegMalformed ? "malformed line" : r.reason == kSegBadLength ? "length not a multiple of three" : "no scored alignment block contains it");
+  return out;
+}
+// %.3f; a NaN is `nan` whatever its sign (printf may write -nan)
+inline std::string fmt3(float x) {
+  if (x != x) return "nan";
+  char b[64];
+  std::snprintf(b, sizeof b, "%.3f", static_cast<double>(x));
+  return b;
+}
+// per row the segment's score without it: the other rows' pair scores summed in row order from 0, fmaxf(sum, Delta) / (float)(N - 2)
+inline std::vector<float> leave_one_out(const float *pairs, int nk, float Delta) {
+  std::vector<float> out(static_cast<size_t>(nk));
+  const float d = static_cast<float>(nk - 1);
+  for (int k = 0; k < nk; k++) {
+    float sum = 0.0f;
+    for (int j = 0; j < nk; j++) if (j != k) sum = sum + pairs[j];
+    out[k] = std::fmax(sum, Delta) / d;
+  }
+  return out;
+}
+inline const char *support_header() { return "hss\tname\tstrand\tframe\tstart\tend\tscore\tp\trow\trow_name\tpair_score\tshare\tloo_score\n"; }
+inline const char *regions_header() { return "id\tname\tstrand\tframe\tfrom\tto\tstart\tend\tscore\tp\tsupport\trows\n"; }
+// --support: the columns of row k's line behind the HSS counter (details_tail's head, then the row's pair score, its share and the score without it)
+inline std::string support_tail(const std::string &refName, const std::string &rowName, int k, char strand, int frame, int startGenomic, int endGenomic,
+                                float score, float pvalue, float pair, float nkf, float loo) {
+  std::string out;
+  put(out, "%s\t%c\t%i\t%i\t%i\t%.2f\t%.3e\t%i\t%s", refName.c_str(), strand, frame + 1, startGenomic, endGenomic, static_cast<double>(score),
+      static_cast<double>(pvalue), k, rowName.c_str());
+  const float share = pair / nkf;
+  out += "\t" + fmt3(pair) + "\t" + fmt3(share) + "\t" + fmt3(loo) + "\n";
+  return out;
+}
+inline std::string region_line(const Region &r, const SegLoc &at, float score, float p, const float *pairs, int nk) {
+  int support = 0;
+  for (int k = 0; k < nk; k++) support += pairs[k] > 0.0f;
+  std::string out;
+  char pe[64];
+  if (p != p) std::snprintf(pe, sizeof pe, "nan"); else std::snprintf(pe, sizeof pe, "%.3e", static_cast<double>(p));
+  put(out, "%s\t%s\t%c\t%i\t%i\t%i\t%lld\t%lld\t%s\t%s\t%i\t%i\n", r.id.c_str(), r.name.c_str(), r.strand, at.frame + 1, at.c1 + 1, at.c2 + 1, r.start, r.end,
+      fmt3(score).c_str(), pe, support, nk);
+  return out;
+}
+
 // colorAln, postscript.c:38-332: the EPS text for one high-scoring segment of a block (rows upper-cased, as RNAcode.c:121-128 leaves them)
 inline std::string color_aln(const std::vector<Row> &block, const Hss &hss, const Backtrack &backtrack, const Tables &t) {
   std::vector<std::string> rows;

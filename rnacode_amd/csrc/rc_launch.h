@@ -249,6 +249,21 @@ struct BtItem {
 };
 void launch_backtrack_many(const uint8_t *blob, const DevBlock *dblocks, const uint32_t *flags, const BtItem *items, int nItems, uint8_t *cells,
                            hipStream_t stream);
+// rc_batch_segment_scores (rc_segments.hip): the ranges as the caller lists them (rc_bt_range's layout) and prefix[r] = the sum of N-1 over
+// the ranges before r ([nRanges + 1]; prefix[nRanges] = nItems): item t = row t - prefix[r] of the range r whose [prefix[r], prefix[r + 1])
+// holds t -- no descriptor per item.  k_segment_pairs writes pairs[t], k_segment_fold scores[r] from them in row order.
+struct SegRange { int32_t blk, strand, opt_b, opt_i; };
+struct SegArgs {
+  const uint8_t *blob;
+  const DevBlock *dblocks;
+  const uint32_t *flags;      // per batch index: kFlagNan picks the reference's MAX macro
+  const SegRange *ranges;     // [nRanges]
+  const int *prefix;          // [nRanges + 1]
+  int nRanges, nItems;
+  float *pairs;               // [nItems]
+  float *scores;              // [nRanges]
+};
+void launch_segment_scores(const SegArgs &a, hipStream_t stream);   // both kernels, in that order
 // wider blocks (N > 64): generic kernels with their states in a global scratch (rc_null_generic.h)
 size_t null_generic_lds_bytes(int N, int nnodes);   // packed node states + codon windows of the widest block of the launch
 // the same in two launches (simulation with many light wavefronts, then the DP): bytes of an item's codes / of a DP workgroup's states

@@ -1,4 +1,4 @@
-// rc_results.cpp -- what a finished batch holds: statuses, models, maxima, fits, HSS tables, native S matrices, backtrack paths, per-codon tracks.
+// rc_results.cpp -- what a finished batch holds: statuses, models, maxima, fits, HSS tables, native S matrices, backtrack paths, per-codon tracks, segment scores.
 #include "rc_runtime.h"
 
 extern "C" {
@@ -470,6 +470,71 @@ int rc_batch_track(const rc_batch *b, const int32_t *blks, int32_t n_blks, float
     }
     HIP_TRY(hipMemcpyAsync(out, d_out.p, static_cast<size_t>(total) * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));   // (the streams are non-blocking: nothing else would wait for the copy)
+    return RC_OK;
+  }();
+  if (rc != RC_OK && launched) (void)hipStreamSynchronize(st);
+  return rc;
+}
+
+// The scores of many ranges with their per-row pair scores (rc_segments.hip): one lane per (range, row) runs the recurrence of k_sk_row from
+// zeros and keeps the maximum of its three states, one lane per range folds them in row order -- the cell S[a][j] of rc_batch_native_S bit for
+// bit.  The device gets the ranges and the running sum of their row counts, nothing per item; both kernels go to one stream, and each
+// output array comes back with one copy behind one synchronisation.
+static_assert(sizeof(SegRange) == sizeof(rc_bt_range), "SegRange is rc_bt_range's layout");
+int rc_batch_segment_scores(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, float *score_out, float *pair_out, int64_t cap,
+                            int64_t *offsets) {
+  if (!b || n_ranges < 0 || (n_ranges > 0 && (!ranges || !score_out)) || (pair_out && !offsets)) return fail(RC_ERR_ARG, "bad argument");
+  if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
+  // every range is checked, and the layout made, before anything touches the device (or the caller's arrays)
+  std::vector<int32_t> up(static_cast<size_t>(n_ranges) * 4 + static_cast<size_t>(n_ranges) + 1);   // the ranges, then the prefix: one upload
+  int32_t *prefix = up.data() + static_cast<size_t>(n_ranges) * 4;
+  int64_t total = 0;
+  for (int r = 0; r < n_ranges; r++) {
+    const rc_bt_range &g = ranges[r];
+    if (g.blk < 0 || g.blk >= b->n) return fail(RC_ERR_ARG, "segment range " + std::to_string(r) + ": block index out of range");
+    const BlockMeta &h = b->meta[g.blk];
+    if (h.status != RC_OK) { g_err = "segment range " + std::to_string(r) + ": the block was not scored"; return h.status; }
+    if (g.strand < 0 || g.strand > 1 || g.opt_b < 1 || g.opt_i > h.L) return fail(RC_ERR_ARG, "segment range " + std::to_string(r) + ": bad range");
+    if (g.opt_i >= g.opt_b + 2 && (g.opt_i - g.opt_b - 2) % 3 != 0)   // (else the recurrence has no step: every pair score 0)
+      return fail(RC_ERR_ARG, "segment range " + std::to_string(r) + ": bad range");
+    prefix[r] = static_cast<int32_t>(total);
+    total += h.NK;
+    if (total > INT32_MAX) return fail(RC_ERR_ARG, "segment range " + std::to_string(r) + ": more than 2^31 - 1 (range, row) items in one call");
+  }
+  if (pair_out && cap < total) return fail(RC_ERR_ARG, "pair_out too small: " + std::to_string(total) + " pair scores");
+  if (offsets) {
+    for (int r = 0; r < n_ranges; r++) offsets[r] = prefix[r];
+    offsets[n_ranges] = total;
+  }
+  if (n_ranges == 0) return RC_OK;
+  prefix[n_ranges] = static_cast<int32_t>(total);
+  std::memcpy(up.data(), ranges, static_cast<size_t>(n_ranges) * sizeof(rc_bt_range));
+  rc_ctx *c = b->ctx;
+  HIP_TRY(hipSetDevice(c->device));
+  RC_STREAM_TRY(st, stream_aux(c));
+  HIP_TRY(hipEventSynchronize(b->evPrep));   // the z and sigma tables are made on the device (k_prep_gaps, k_native_sigma)
+  DevBuf d_up, d_pairs, d_scores;
+  for (DevBuf *d : {&d_up, &d_pairs, &d_scores}) { d->retired = c->retired.get(); d->pool = c->bufPool.get(); }
+  const uint8_t *blob = b->dblob.as<uint8_t>();
+  bool launched = false;
+  // (a lambda: whatever fails in it, nothing returns to the caller -- who owns the outputs, while `up` and the buffers die with this frame --
+  // before the work already queued on the stream has drained)
+  const int rc = [&]() -> int {
+    HIP_TRY(d_up.ensure(up.size() * sizeof(int32_t)));
+    HIP_TRY(d_pairs.ensure(static_cast<size_t>(total) * sizeof(float)));
+    HIP_TRY(d_scores.ensure(static_cast<size_t>(n_ranges) * sizeof(float)));
+    launched = true;   // from here on something may be in flight
+    HIP_TRY(hipMemcpyAsync(d_up.p, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    SegArgs sa{};
+    sa.blob = blob; sa.dblocks = reinterpret_cast<const DevBlock *>(blob + b->oDblocks); sa.flags = b->dflags.as<uint32_t>();
+    sa.ranges = d_up.as<SegRange>(); sa.prefix = d_up.as<int>() + static_cast<size_t>(n_ranges) * 4;
+    sa.nRanges = n_ranges; sa.nItems = static_cast<int>(total);
+    sa.pairs = d_pairs.as<float>(); sa.scores = d_scores.as<float>();
+    launch_segment_scores(sa, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(score_out, d_scores.p, static_cast<size_t>(n_ranges) * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (pair_out) HIP_TRY(hipMemcpyAsync(pair_out, d_pairs.p, static_cast<size_t>(total) * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // (the streams are non-blocking: nothing else would wait for the copies)
     return RC_OK;
   }();
   if (rc != RC_OK && launched) (void)hipStreamSynchronize(st);

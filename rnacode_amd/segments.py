@@ -1,0 +1,156 @@
+"""Scores of given segments: the host rules behind --regions / --regions-out and --support.
+
+Batch.segment_scores (rc_batch_segment_scores) gives, for a range (blk, strand, opt_b, opt_i), the cell S[a][j] of the block's score matrix
+and the pair scores P_k of its rows against the reference row: S[a][j] = max(sum of P_k, Delta) / (N - 1), float32 throughout, the sum in
+row order.  This module holds what both drivers do around that call -- nothing here needs a GPU; the native driver (rc_eps.h, seg_locate /
+regions_read / support_tail / region_line) follows the same rules and writes the same bytes.
+
+  --regions FILE   tab-separated `name strand start end [id]`: name a block's reference row as the listing prints it, start / end the
+                   numbers -t prints in its Start and End columns (a listing line can be fed back), id `region<line number>` by default.
+                   Blank lines, lines starting with '#' and a first line whose first field is `name` are skipped.
+  --regions-out    one line per region and scored block that contains it (locate), COLUMNS_REGIONS; blocks in input order, within a
+                   block the regions in file order.  p is rc_pvalue under the block's fit (99 where it failed): the probability that the
+                   block-wide MAXIMUM reaches the score, conservative for a segment chosen beforehand.
+  --support FILE   one line per listed HSS and non-reference row, COLUMNS_SUPPORT: the first ten columns are the --details table's, then
+                   the row's pair score, its share float32(pair / float32(N - 1)) of the sum behind the score, and the leave-one-out
+                   score -- the segment's score without that row.
+  NaN prints as `nan` whatever its sign.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+COLUMNS_SUPPORT = ("hss", "name", "strand", "frame", "start", "end", "score", "p", "row", "row_name", "pair_score", "share", "loo_score")
+COLUMNS_REGIONS = ("id", "name", "strand", "frame", "from", "to", "start", "end", "score", "p", "support", "rows")
+
+BAD_LENGTH = "length not a multiple of three"
+OUTSIDE = "outside the block"
+PAST_LAST_CODON = "end past the last whole codon of the frame"
+MALFORMED = "malformed line"
+NO_BLOCK = "no scored alignment block contains it"
+
+
+def support_header() -> str:
+    return "\t".join(COLUMNS_SUPPORT) + "\n"
+
+
+def regions_header() -> str:
+    return "\t".join(COLUMNS_REGIONS) + "\n"
+
+
+def locate(strand: str, start: int, end: int, ref_start: int, ref_length: int, L: int) -> Union[Tuple[int, int, int], str]:
+    """The inverse of track.run_coords: (frame, c1, c2) with run_coords(strand, frame, c1, c2, ref_start, ref_length)[2:] == (start, end),
+    or the reason (a string) there is none.  start / end: what the listing prints -- positions in the strand's own row, 1-based, for
+    ClustalW input (ref_start == ref_length == 0); else MAF coordinates, 0-based on '+', mirrored on '-'.  L: the reference row's
+    ungapped length; the frame's last whole codon is (L - frame) // 3 - 1."""
+    if end < start or (end - start + 1) % 3 != 0:
+        return BAD_LENGTH
+    if ref_start == 0 and ref_length == 0:
+        first, last, size = start - 1, end - 1, L                # 0-based offsets into the strand's row
+    elif strand == "+":
+        first, last, size = start - ref_start, end - ref_start, ref_length
+    else:
+        top = ref_start + ref_length - 1
+        first, last, size = top - end, top - start, ref_length
+    if first < 0 or last >= size:
+        return OUTSIDE
+    frame, c1 = first % 3, first // 3
+    c2 = (last - frame - 2) // 3
+    if c2 > (L - frame) // 3 - 1:
+        return PAST_LAST_CODON
+    return frame, c1, c2
+
+
+def range_of(frame: int, c1: int, c2: int) -> Tuple[int, int]:
+    """(opt_b, opt_i) of the segment of codons c1..c2 in `frame`: an HSS's start and end."""
+    return 3 * c1 + frame + 1, 3 * c2 + frame + 3
+
+
+class Region:
+    __slots__ = ("line", "id", "name", "strand", "start", "end", "reason", "matched")
+
+    def __init__(self, line: int, id: str, name: str = "", strand: str = "+", start: int = 0, end: int = 0, reason: Optional[str] = None):
+        self.line, self.id, self.name, self.strand, self.start, self.end = line, id, name, strand, start, end
+        self.reason = reason      # set: the region can match nothing (malformed line, bad length)
+        self.matched = False
+
+
+def _int(text: str) -> Optional[int]:
+    """An optional sign and one to ten ASCII digits, nothing else."""
+    body = text[1:] if text[:1] in ("+", "-") else text
+    return int(text) if 1 <= len(body) <= 10 and body.isascii() and body.isdigit() else None
+
+
+def read_regions(lines: Sequence[str]) -> List[Region]:
+    """The regions of a --regions file, in file order; a malformed line (fewer than four fields, a strand other than + or -, a start or
+    end that is no integer, an end before the start) and a length that is no multiple of three stay in the list with their reason."""
+    out: List[Region] = []
+    for n, raw in enumerate(lines, 1):
+        line = raw.rstrip("\r\n")
+        if not line.strip() or line.startswith("#"):
+            continue
+        f = line.split("\t")
+        if n == 1 and f[0] == "name":
+            continue
+        rid = f[4] if len(f) > 4 and f[4] else f"region{n}"
+        start, end = (_int(f[2]), _int(f[3])) if len(f) >= 4 else (None, None)
+        if len(f) < 4 or not f[0] or f[1] not in ("+", "-") or start is None or end is None or end < start:
+            out.append(Region(n, rid, reason=MALFORMED))
+            continue
+        out.append(Region(n, rid, f[0], f[1], start, end, BAD_LENGTH if (end - start + 1) % 3 else None))
+    return out
+
+
+def by_name(regions: Sequence[Region]) -> Dict[str, List[Region]]:
+    """The regions that can match a block, by reference row name, each list in file order."""
+    out: Dict[str, List[Region]] = {}
+    for r in regions:
+        if r.reason is None:
+            out.setdefault(r.name, []).append(r)
+    return out
+
+
+def skipped_lines(regions: Sequence[Region]) -> List[str]:
+    """The stderr lines of the regions that matched nothing, in file order."""
+    return ["Skipping region %s (line %i): %s\n" % (r.id, r.line, r.reason or NO_BLOCK) for r in regions if not r.matched]
+
+
+def leave_one_out(pairs, Delta) -> np.ndarray:
+    """Per row k the segment's score without it, float32 throughout: the sum of the other rows' pair scores in row order from 0, then
+    fmax(sum, Delta) / float32(N - 2) (N - 1 = len(pairs) rows besides the reference)."""
+    p = np.ascontiguousarray(pairs, dtype=np.float32)
+    nk = p.shape[0]
+    acc = np.zeros(nk, dtype=np.float32)
+    idx = np.arange(nk)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for j in range(nk):
+            acc = np.where(idx != j, acc + p[j], acc)    # (row k's own term is skipped, not added as zero)
+        return (np.fmax(acc, np.float32(Delta)) / np.float32(nk - 1)).astype(np.float32)
+
+
+def fmt3(x) -> str:
+    """%.3f of a float32; a NaN is `nan` whatever its sign."""
+    v = float(np.float32(x))
+    return "nan" if v != v else "%.3f" % v
+
+
+def support_lines(counter: int, ref_name: str, h: dict, row_names: Sequence[str], pairs, Delta) -> List[str]:
+    """The lines of one listed HSS: one per non-reference row (row_names: the block's row names, the reference's first)."""
+    p = np.ascontiguousarray(pairs, dtype=np.float32)
+    nkf = np.float32(p.shape[0])
+    loo = leave_one_out(p, Delta)
+    out = []
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(1, p.shape[0] + 1):
+            head = "%i\t%s\t%s\t%i\t%i\t%i\t%.2f\t%.3e\t%i\t%s" % (counter, ref_name, h["strand"], h["frame"] + 1, h["startGenomic"], h["endGenomic"],
+                                                                 h["score"], float(np.float32(h["pvalue"])), k, row_names[k])   # details.format_line's head
+            out.append("%s\t%s\t%s\t%s\n" % (head, fmt3(p[k - 1]), fmt3(np.float32(p[k - 1] / nkf)), fmt3(loo[k - 1])))
+    return out
+
+
+def region_line(region: Region, frame: int, c1: int, c2: int, score, p, pairs) -> str:
+    pr = np.asarray(pairs, dtype=np.float32)
+    return "%s\t%s\t%s\t%i\t%i\t%i\t%i\t%i\t%s\t%.3e\t%i\t%i\n" % (region.id, region.name, region.strand, frame + 1, c1 + 1, c2 + 1, region.start,
+                                                              region.end, fmt3(score), float(np.float32(p)), int((pr > 0).sum()), pr.shape[0])
