@@ -28,6 +28,7 @@ struct SerialExec {
   int nlanes() const { return 1; }
   double sum(double x) const { return x; }
   void sum2(double &, double &) const {}
+  bool any(bool x) const { return x; }
   void exp3(double x0, double x1, double x2, double &e0, double &e1, double &e2) const { e0 = std::exp(x0); e1 = std::exp(x1); e2 = std::exp(x2); }
   void sync() const {}
   void mark(int) const {}

@@ -8,7 +8,7 @@
 // branch lengths and kappa on that topology; ambiguity codes as partial information, gaps as missing.
 //
 // Exec supplies: lane(), nlanes() (site patterns p = lane, lane + nlanes, ... belong to a lane for the
-// whole fit, so per-pattern arrays need no synchronisation), sum(x) / sum2(a, b) (the same totals on every lane),
+// whole fit, so per-pattern arrays need no synchronisation), sum(x) / sum2(a, b) (the same totals on every lane), any(flag),
 // exp3 (three exponentials at once), sync() (makes lane 0's serial work visible), mark(phase) / count(counter)
 // (profiling builds of the kernel: cycles per phase, see tools/tree_phases.sh; nothing otherwise).
 #pragma once
@@ -70,6 +70,8 @@ struct Coef { double a, bR, bY, eR, eY; };
 RC_HD inline Coef coef_of(const Hky &m, double e1, double eR, double eY) {
   Coef c;
   c.a = 1.0 - e1; c.bR = (e1 - eR) / m.G[0]; c.bY = (e1 - eY) / m.G[1]; c.eR = eR; c.eY = eY;
+  if (!(m.G[0] > 0)) c.bR = 0.0;   // a class nothing belongs to (an alignment of C and T only) carries no mass: S_g is 0, b_g not 0/0
+  if (!(m.G[1] > 0)) c.bY = 0.0;
   return c;
 }
 RC_HD inline void transfer(const Hky &m, const Coef &c, const double d[4], double out[4]) {
@@ -487,6 +489,7 @@ RC_HD void branch_constants(Work &k, Exec &ex, int v) {
   const double *upPar = above ? k.upI + static_cast<size_t>(par - k.N) * 4 * k.P : nullptr;
   double *upV = v >= k.N ? k.upI + static_cast<size_t>(v - k.N) * 4 * k.P : nullptr;
   const Hky &m = k.mod;
+  const double gR = m.G[0] > 0 ? m.G[0] : 1.0, gY = m.G[1] > 0 ? m.G[1] : 1.0;   // an empty class: q_g = S_g U_g / G_g is 0, not 0/0
   for (int p = ex.lane(); p < k.P; p += ex.nlanes()) {
     double u[4];
     sib.product(k, p, u);
@@ -503,7 +506,7 @@ RC_HD void branch_constants(Work &k, Exec &ex, int v) {
     const double UR = u0 + u2, UY = u1 + u3;
     const double SR = m.pi[0] * d[0] + m.pi[2] * d[2], SY = m.pi[1] * d[1] + m.pi[3] * d[3];
     const double TR = u0 * d[0] + u2 * d[2], TY = u1 * d[1] + u3 * d[3];
-    const double k0 = (SR + SY) * (UR + UY), qR = SR * UR / m.G[0], qY = SY * UY / m.G[1];
+    const double k0 = (SR + SY) * (UR + UY), qR = SR * UR / gR, qY = SY * UY / gY;
     k.kc[p] = k0;
     k.kc[static_cast<size_t>(k.P) + p] = qR + qY - k0;
     k.kc[2 * static_cast<size_t>(k.P) + p] = TR - qR;
@@ -549,26 +552,45 @@ RC_HD double edge_newton(const Work &k, Exec &ex, double t) {
   return t;
 }
 
+// A tip whose row holds no data (gaps, N) has the column (1, 1, 1, 1) at every pattern: its image across its branch is 1 whatever the
+// length, d lnL / dt is rounding noise, and Newton's steps would go where the order of the sums sends them.
+template <typename Exec>
+RC_HD bool tip_has_data(const Work &k, Exec &ex, int v) {
+  bool some = false;
+  for (int p = ex.lane(); p < k.P; p += ex.nlanes()) some |= k.mask[static_cast<size_t>(v) * k.P + p] != 15;
+  return ex.any(some);
+}
+// is any branch longer than the floor
+template <typename Exec>
+RC_HD bool any_length(const Work &k, Exec &ex) {
+  bool some = false;
+  for (int v = ex.lane(); v < k.nn; v += ex.nlanes()) some |= k.len[v] > kBlMin;
+  return ex.any(some);
+}
+
 // One pass over the branches in the tree's pre-order (parents before children; what PhyML's own branch optimiser walks too): at
 // node v everything above it has its new lengths already and everything below is untouched, so up(v) is one product of the
 // siblings' images and the parent's up column, and dn(v) is still the column the last bottom-up pass left.  When a subtree is
 // finished (the next node of the order hangs off one of v's ancestors) the dn columns on the way up to that ancestor are rebuilt
 // from their children: three images per branch and round, where recomputing "whatever is stale" cost two per level of the tree.
+// The branch of a tip without data keeps its starting length.
 // Needs coef_all + full_down first; leaves every dn column current again.
 template <typename Exec>
 RC_HD void branch_pass(Work &k, Exec &ex) {
   for (int o = 1; o < k.nn; o++) {
     const int v = k.preorder[o];
     ex.mark(7);
-    branch_constants(k, ex, v);
-    ex.mark(5);
-    const double t = edge_newton(k, ex, k.len[v]);
-    ex.mark(6);
-    double e1, eR, eY;
-    ex.exp3(-k.mod.beta * t, -k.mod.beta * k.mod.c[0] * t, -k.mod.beta * k.mod.c[1] * t, e1, eR, eY);
-    k.len[v] = t;                          // (every lane stores the same values)
-    k.coef[v] = coef_of(k.mod, e1, eR, eY);
-    ex.sync();
+    if (v >= k.N || tip_has_data(k, ex, v)) {
+      branch_constants(k, ex, v);
+      ex.mark(5);
+      const double t = edge_newton(k, ex, k.len[v]);
+      ex.mark(6);
+      double e1, eR, eY;
+      ex.exp3(-k.mod.beta * t, -k.mod.beta * k.mod.c[0] * t, -k.mod.beta * k.mod.c[1] * t, e1, eR, eY);
+      k.len[v] = t;                          // (every lane stores the same values)
+      k.coef[v] = coef_of(k.mod, e1, eR, eY);
+      ex.sync();
+    }
     const int stop = o + 1 < k.nn ? k.parent[k.preorder[o + 1]] : k.root;
     for (int a = v; a != stop; a = k.parent[a]) if (a >= k.N) refresh_down_node(k, ex, a);
   }
@@ -604,6 +626,13 @@ RC_HD double optimise(Work &k, Exec &ex) {
   st.what = kClose; st.round = -1; st.probe = 0;
   st.prev = 0; st.kap = k.mod.kappa; st.h = 0; st.f0 = 0; st.f1 = 0;
   st.scale = 1.0; st.param = 0;
+  // kappa is the rate of transitions (A<->G, C<->T) against transversions.  An alignment without purines or without pyrimidines has
+  // no transversions, one without both letters of either pair no transitions; the mean rate is scaled to 1, so the likelihood is then
+  // flat in kappa and a search would walk on rounding noise.  kappa stays where it started (as the reference's PhyML leaves it).
+  // The same while every branch is at the floor (identical rows): to first order in the lengths lnL is minus the sum over the sites
+  // of their states' rates out, and the frequencies being the data's that is the mean rate, 1 at every kappa.
+  const bool kappaMeans = k.mod.G[0] > 0 && k.mod.G[1] > 0 && k.pi[0] * k.pi[2] + k.pi[1] * k.pi[3] > 0;
+  bool kappaFree = kappaMeans;
   for (;;) {
     ex.sync();
     ex.mark(8);
@@ -620,6 +649,8 @@ RC_HD double optimise(Work &k, Exec &ex) {
         branch_pass(k, ex);
       }
       st.param = k.mode == kFitScale ? 1 : 0;
+      kappaFree = kappaMeans && any_length(k, ex);
+      if (!st.param && !kappaFree) continue;   // nothing to search: the next value closes the round
       st.kap = st.param ? st.scale : k.mod.kappa; st.h = 0.01 * st.kap;
       st.what = kProbe; st.probe = 0;
       set_param(k, ex, st.param, st.kap - st.h);
@@ -641,12 +672,12 @@ RC_HD double optimise(Work &k, Exec &ex) {
     }
     if (close) {
       set_param(k, ex, st.param, st.kap);
-      if (st.param) {   // the scale is done: kappa's probes next, on the scaled lengths
+      if (st.param && kappaFree) {   // the scale is done: kappa's probes next, on the scaled lengths
         st.scale = st.kap; st.param = 0;
         st.kap = k.mod.kappa; st.h = 0.01 * st.kap;
         st.what = kProbe; st.probe = 0;
         set_param(k, ex, 0, st.kap - st.h);
-      } else st.what = kClose;
+      } else { if (st.param) st.scale = st.kap; st.param = 0; st.what = kClose; }
     }
   }
 }

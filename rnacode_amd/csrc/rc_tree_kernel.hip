@@ -68,6 +68,7 @@ struct WaveExec {
   __device__ int nlanes() const { return kWave; }
   __device__ double sum(double x) const { return wave_sum(x); }
   __device__ void sum2(double &a, double &b) const { a = wave_sum(a); b = wave_sum(b); }
+  __device__ bool any(bool x) const { return __builtin_amdgcn_ballot_w64(x) != 0; }
   // three exponentials for the price of one: lane 1 and lane 2 take the second and third argument
   __device__ void exp3(double x0, double x1, double x2, double &e0, double &e1, double &e2) const {
     const int l = static_cast<int>(threadIdx.x);

@@ -49,6 +49,7 @@ def kernel_resources(build_dir: str = os.path.join(ROOT, "rnacode_amd", "csrc", 
     res = {}
     for n, d in zip(names, dem):
         d = re.sub(r"^void ", "", d)
+        d = d.replace("(anonymous namespace)::", "")   # (k_tree_fit: or the argument list's rule below would take the name with it)
         d = d.replace("(bool)1", "true").replace("(bool)0", "false")
         d = re.sub(r"\(int\)(\d+)", r"\1", d)
         d = re.sub(r"\(rc::.*$|\(unsigned.*$|\(double.*$|\(float.*$|\(int.*$|\(.*\)$", "", d)
