@@ -27,10 +27,12 @@ Quirk kept from the reference: the 4th value of --pars goes to stopPenalty_0 (RN
 from __future__ import annotations
 
 import argparse
+import contextlib
 import os
 import sys
 import time
-from typing import List, Optional
+from dataclasses import dataclass, field
+from typing import IO, List, Optional
 
 import numpy as np
 
@@ -134,12 +136,15 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
-def main(argv=None) -> int:
-    a = build_parser().parse_args(argv)
+class _Refused(Exception):
+    """An option or input the driver turns down: main() prints 'ERROR: <message>' and returns 1."""
 
+
+def _intake(a):
+    """What the options name, checked and read before any context exists: the parameters, the --regions (or None) and the --species-tree
+    (or None)."""
     if a.blosum not in (62, 90):
-        print("ERROR: Currently only BLOSUM62 and BLOSUM90 are supported.", file=sys.stderr)
-        return 1
+        raise _Refused("Currently only BLOSUM62 and BLOSUM90 are supported.")
     kw = dict(sampleN=a.num_samples, cutoff=a.cutoff, stopEarly=int(a.stop_early), blosum=a.blosum, seed_base=a.seed_base)
     if a.pars:
         vals = [float(x) for x in a.pars.split(",")]
@@ -149,32 +154,171 @@ def main(argv=None) -> int:
         kw["genetic_code"] = a.genetic_code
     try:
         params = api.default_params(**kw)
-    except api.RnacodeError as e:   # a bad --genetic-code: before any context exists
-        print(f"ERROR: --genetic-code: {str(e).split(': ', 1)[-1]}", file=sys.stderr)
-        return 1
-    regions = None
-    if bool(a.regions) != bool(a.regions_out):   # before any context exists
-        print("ERROR: --regions and --regions-out go together", file=sys.stderr)
-        return 1
+    except api.RnacodeError as e:
+        raise _Refused(f"--genetic-code: {str(e).split(': ', 1)[-1]}")
+    regions = species = None
+    if bool(a.regions) != bool(a.regions_out):
+        raise _Refused("--regions and --regions-out go together")
     if a.regions:
         try:
             with open(a.regions) as fh:
                 regions = segments.read_regions(fh.readlines())
         except OSError as e:
-            print(f"ERROR: --regions: {e}", file=sys.stderr)
-            return 1
-        regions_of = segments.by_name(regions)
-    species = None
-    if a.species_tree:   # parsed before any context exists
+            raise _Refused(f"--regions: {e}")
+    if a.species_tree:
         if a.trees:
-            print("ERROR: --species-tree and --trees cannot be used together", file=sys.stderr)
-            return 1
+            raise _Refused("--species-tree and --trees cannot be used together")
         try:
             with open(a.species_tree) as fh:
                 species = api.SpeciesTree(fh.read())
         except (OSError, api.RnacodeError) as e:
-            print(f"ERROR: --species-tree: {str(e).split(': ', 1)[-1]}", file=sys.stderr)
-            return 1
+            raise _Refused(f"--species-tree: {str(e).split(': ', 1)[-1]}")
+    return params, regions, species
+
+
+def _trees(a, ctx, blocks, marshalled, species, n_read: int, read_index: List[int]):
+    """Tree + kappa (or None) per block, from the sidecar, the species tree or the built-in estimator, and -- with --species-tree -- why the
+    tree does not cover a block's rows (block -> reason)."""
+    refused = {}
+    if a.trees:
+        side = read_sidecar(a.trees)
+        if len(side) == n_read and len(blocks) != n_read:   # one entry per block read (--write-trees): the kept blocks' entries
+            side = [side[at] for at in read_index]
+        if len(side) != len(blocks):
+            raise _Refused(f"{len(blocks)} alignment blocks but {len(side)} sidecar entries")
+    elif species is not None:
+        side = api.fit_species_trees(marshalled, species, a.species_tree_fit, ctx=ctx)
+        for i, (b, s) in enumerate(zip(blocks, side)):
+            if s is None and b.n >= 3:
+                try:
+                    species.prune(b)
+                except api.RnacodeError as e:
+                    refused[i] = str(e).split(": ", 1)[-1]
+    else:
+        side = fit_trees(marshalled, ctx=ctx)
+    return side, refused
+
+
+SIDE_FILES = (("details", details.header), ("track", track.header), ("support", segments.support_header),
+              ("regions_out", segments.regions_header))   # the option's name in the parsed arguments, its header line
+
+
+class _Ranges:
+    """The ranges (block, strand, lo, hi) of one device call, each once; add() returns a range's position in the call's results."""
+    def __init__(self):
+        self.at, self.ranges = {}, []
+
+    def add(self, i: int, strand: str, lo: int, hi: int) -> int:
+        key = (i, strand, lo, hi)
+        if key not in self.at:
+            self.at[key] = len(self.ranges)
+            self.ranges.append((i, 0 if strand == "+" else 1, lo, hi))
+        return self.at[key]
+
+
+@dataclass
+class _Run:
+    """What every sub-batch of a run is listed with."""
+    a: argparse.Namespace
+    params: object
+    code: str                  # the genetic code's letters
+    tables: Optional[tuple]    # --details: api.code_tables of the run
+    blocks: List[AlnBlock]     # as scored, trees filled in
+    read_index: List[int]      # their positions in the input
+    refused: dict              # --species-tree: block -> why its rows do not match the tree
+    regions_of: dict           # --regions: reference row name -> its regions
+    out: IO[str]
+    fmt: int
+    side: dict                 # the side files that are on: option name -> open file, header written
+    state: report.ReportState = field(default_factory=report.ReportState)
+
+
+def _list_block(run: _Run, i: int, b: AlnBlock, hss: List[dict], bt: _Ranges, paths, seg: _Ranges, seg_pairs) -> None:
+    """One scored block's part of the listing, and of --eps, --details and --support beside each of its lines."""
+    a, side = run.a, run.side
+
+    def plot(counter, h):   # misc.c:461-474: hss-<counter>.eps for every listed HSS with p below the plot cutoff
+        os.makedirs(a.eps_dir, exist_ok=True)
+        text = eps.color_aln(b, h, lambda strand, lo, hi: api.expand_backtrack(paths[bt.at[(i, strand, lo, hi)]], b.n, b.cols, lo), a.blosum,
+                             run.code)
+        with open(os.path.join(a.eps_dir, f"hss-{counter}.eps"), "w") as fh:
+            fh.write(text)
+
+    def tables(counter, h):
+        key = (i, h["strand"], h["start"], h["end"])
+        if "details" in side:
+            side["details"].writelines(details.details_lines(counter, b, h, paths[bt.at[key]], *run.tables))
+        if "support" in side:
+            side["support"].writelines(segments.support_lines(counter, b.rows[0].name, h, [r.name for r in b.rows], seg_pairs[seg.at[key]],
+                                                              run.params.Delta))
+
+    report.print_results(run.out, run.fmt, hss, b.rows[0].name, run.state, cutoff=a.cutoff, best_only=a.best_only, best_region=a.best_region,
+                         eps=plot if a.eps else None, eps_cutoff=a.eps_cutoff, listed=tables if "details" in side or "support" in side else None)
+
+
+def _list_batch(run: _Run, batch, base: int) -> None:
+    """A finished sub-batch (its first block is block `base` of the run): what the side outputs need from the device with one call each
+    while the batch is alive, then every block's part of the listing and the side files, in input order."""
+    a, side = run.a, run.side
+    all_hss = batch.scoreAln_all()
+    status = [batch.status(i) for i in range(batch.n)]
+    scored = [i for i in range(batch.n) if status[i] == api.RC_OK and base + i not in run.refused]   # the blocks the listing covers
+    # the HSS that get a line, once per block: what --eps, --details and --support ask the device about
+    per_line = a.eps or "details" in side or "support" in side
+    listed = {i: report.listed_hss(all_hss[i], a.cutoff, a.best_only, a.best_region) if per_line else [] for i in scored}
+    # --eps / --details: the backtracked paths with ONE call (rc_batch_backtrack_many) -- the segments themselves for the table; for the
+    # plots (p below the plot cutoff) the segment and its two extensions.  --support / --regions: the scores and pair scores of every listed
+    # HSS, and of every region a block contains, with ONE call (rc_batch_segment_scores)
+    bt, seg, found = _Ranges(), _Ranges(), {}
+    for i in scored:
+        b = run.blocks[base + i]
+        for h in listed[i]:
+            if "details" in side:
+                bt.add(i, h["strand"], h["start"], h["end"])
+            if a.eps and float(np.float32(h["pvalue"])) < float(np.float32(a.eps_cutoff)):
+                for lo, hi in eps.backtrack_ranges(b, h, a.blosum, run.code):
+                    bt.add(i, h["strand"], lo, hi)
+            if "support" in side:
+                seg.add(i, h["strand"], h["start"], h["end"])
+        if "regions_out" in side:
+            for reg in run.regions_of.get(b.rows[0].name, ()):
+                at = segments.locate(reg.strand, reg.start, reg.end, b.rows[0].start, b.rows[0].length, b.ref_len)
+                if isinstance(at, tuple):
+                    found.setdefault(i, []).append((reg, at, seg.add(i, reg.strand, *segments.range_of(*at))))
+    paths = batch.backtrack_many(bt.ranges) if bt.ranges else []
+    # --track: the tracks of the blocks the listing covers with ONE call (rc_batch_track)
+    tracked = dict(zip(scored, batch.track(scored))) if "track" in side and scored else {}
+    seg_scores, seg_pairs = batch.segment_scores(seg.ranges) if seg.ranges else (None, None)
+    for i in range(batch.n):
+        b = run.blocks[base + i]
+        if base + i in run.refused:   # the species tree does not cover the block's rows
+            print(f"Skipping alignment {run.read_index[base + i] + 1} ({b.rows[0].name}). {run.refused[base + i]}", file=sys.stderr)
+            continue
+        if status[i] == api.RC_ERR_SKIP:   # RNAcode.c:142-150
+            msg = "There must be at least three sequences in the alignment." if b.n <= 2 else "Too short."
+            print(f"Skipping alignment. {msg}", file=sys.stderr)
+            continue
+        if status[i] != api.RC_OK:         # RNAcode.c:153-156: the reference has no tree for this block either
+            print(f"Skipping alignment. Failed to build ML tree. ({batch.block_error(i) or 'not scored'})", file=sys.stderr)
+            continue
+        _list_block(run, i, b, all_hss[i], bt, paths, seg, seg_pairs)
+        if i in tracked or i in found:
+            rc, mu, lam = batch.getExtremeValuePars(i)
+            if i in tracked:
+                side["track"].writelines(track.block_lines(b.rows[0].name, b.rows[0].start, b.rows[0].length, tracked[i], rc, mu, lam, a.cutoff))
+            for reg, (frame, c1, c2), r in found.get(i, ()):
+                p = api.pvalue(float(seg_scores[r]), mu, lam) if rc == 1 else 99.0
+                side["regions_out"].write(segments.region_line(reg, frame, c1, c2, seg_scores[r], p, seg_pairs[r]))
+                reg.matched = True
+
+
+def main(argv=None) -> int:
+    a = build_parser().parse_args(argv)
+    try:
+        params, regions, species = _intake(a)
+    except _Refused as e:
+        print(f"ERROR: {e}", file=sys.stderr)
+        return 1
 
     if a.file:
         blocks = read_alignment_file(a.file)
@@ -190,160 +334,41 @@ def main(argv=None) -> int:
         blocks, read_index = apply_limit(blocks, a.limit)
     ctx = api.Context(a.device)
     marshalled = api.Marshalled(blocks)   # one rc_block array for the tree fit and the batch
-    refused = {}   # --species-tree: block -> why its rows do not match the tree
-    if a.trees:
-        side = read_sidecar(a.trees)
-        if len(side) == n_read and len(blocks) != n_read:   # one entry per block read (--write-trees): the kept blocks' entries
-            side = [side[at] for at in read_index]
-        if len(side) != len(blocks):
-            print(f"ERROR: {len(blocks)} alignment blocks but {len(side)} sidecar entries", file=sys.stderr)
-            ctx.close()
-            return 1
-    elif species is not None:
-        side = api.fit_species_trees(marshalled, species, a.species_tree_fit, ctx=ctx)
-        for i, (b, s) in enumerate(zip(blocks, side)):
-            if s is None and b.n >= 3:
-                try:
-                    species.prune(b)
-                except api.RnacodeError as e:
-                    refused[i] = str(e).split(": ", 1)[-1]
-    else:
-        side = fit_trees(marshalled, ctx=ctx)
+    try:
+        trees, refused = _trees(a, ctx, blocks, marshalled, species, n_read, read_index)
+    except _Refused as e:
+        print(f"ERROR: {e}", file=sys.stderr)
+        ctx.close()
+        return 1
     if a.write_trees:
-        write_sidecar(a.write_trees, n_read, read_index, side)
-    prepared: List[AlnBlock] = []
-    for b, s in zip(blocks, side):
+        write_sidecar(a.write_trees, n_read, read_index, trees)
+    for b, s in zip(blocks, trees):
         # no tree: either a block the driver skips anyway (N <= 2, too short) or one whose tree could not be built;
         # the library leaves the latter out with a per-block status, the other blocks are scored (RNAcode.c:153-156)
         b.tree, b.kappa = s if s is not None else (None, None)
-        prepared.append(b)
+    marshalled.set_trees(strict=False)
 
     out = open(a.outfile, "w") if a.outfile else sys.stdout
     fmt = 2 if a.tabular else (1 if a.gtf else 0)
     t0 = time.perf_counter()
-    # the blocks go through the GPU as a stream of sub-batches (rc_stream_*): while one is being scored the next is prepared
-    # on the host threads, and the listing of a finished one is written meanwhile (the reference's loop, RNAcode.c:115-221)
-    marshalled.set_trees(strict=False)
-    st = report.ReportState()
-    base = 0
-    # sub-batch sizes: --sub-blocks, or the library's schedule (rc_stream_plan: a small first sub-batch, then doubling, whole rounds of
-    # the chip; every row count is a launch of its own, so more classes mean larger sub-batches)
-    sub_blocks = a.sub_blocks if a.sub_blocks > 0 else 0
-    code = params.genetic_code.decode()
-    details_out = None
-    if a.details:
-        details_out = open(a.details, "w")
-        details_out.write(details.header())
-        pep, matrix = api.code_tables(a.blosum, code)
-    track_out = None
-    if a.track:
-        track_out = open(a.track, "w")
-        track_out.write(track.header())
-    support_out = regions_out = None
-    if a.support:
-        support_out = open(a.support, "w")
-        support_out.write(segments.support_header())
-    if regions is not None:
-        regions_out = open(a.regions_out, "w")
-        regions_out.write(segments.regions_header())
-    eps_cutoff32 = float(np.float32(a.eps_cutoff))
-    try:
-        for batch in api.score_stream(ctx, marshalled, params, sub_blocks, depth=3):
-            all_hss = batch.scoreAln_all()
-            status = [batch.status(i) for i in range(batch.n)]
-            # --eps / --details: the backtracked paths of every listed HSS of the sub-batch with ONE call (rc_batch_backtrack_many) --
-            # the segments themselves for the table; for the plots (p below the plot cutoff) the segment and its two extensions
-            index, ranges = {}, []
-            if a.eps or a.details:
-                for i in range(batch.n):
-                    if status[i] != api.RC_OK or base + i in refused:
-                        continue
-                    for h in report.listed_hss(all_hss[i], a.cutoff, a.best_only, a.best_region):
-                        want = [(h["start"], h["end"])] if a.details else []
-                        if a.eps and float(np.float32(h["pvalue"])) < eps_cutoff32:
-                            want += eps.backtrack_ranges(prepared[base + i], h, a.blosum, code)
-                        for lo, hi in want:
-                            if (i, h["strand"], lo, hi) not in index:
-                                index[(i, h["strand"], lo, hi)] = len(ranges)
-                                ranges.append((i, 0 if h["strand"] == "+" else 1, lo, hi))
-            paths = batch.backtrack_many(ranges) if ranges else []
-            # --track: the tracks of the sub-batch's scored blocks (those the listing covers) with ONE call (rc_batch_track)
-            tracked = {}
-            if track_out is not None:
-                want = [i for i in range(batch.n) if status[i] == api.RC_OK and base + i not in refused]
-                tracked = dict(zip(want, batch.track(want))) if want else {}
-            # --support / --regions: the scores and pair scores of every listed HSS, and of every region a scored block of the sub-batch
-            # contains, with ONE call (rc_batch_segment_scores)
-            seg_index, seg_ranges, found = {}, [], {}
-            if support_out is not None or regions_out is not None:
-                for i in range(batch.n):
-                    if status[i] != api.RC_OK or base + i in refused:
-                        continue
-                    b = prepared[base + i]
-                    if support_out is not None:
-                        for h in report.listed_hss(all_hss[i], a.cutoff, a.best_only, a.best_region):
-                            key = (i, h["strand"], h["start"], h["end"])
-                            if key not in seg_index:
-                                seg_index[key] = len(seg_ranges)
-                                seg_ranges.append((i, 0 if h["strand"] == "+" else 1, h["start"], h["end"]))
-                    if regions_out is not None:
-                        for reg in regions_of.get(b.rows[0].name, ()):
-                            at = segments.locate(reg.strand, reg.start, reg.end, b.rows[0].start, b.rows[0].length, b.ref_len)
-                            if isinstance(at, tuple):
-                                lo, hi = segments.range_of(*at)
-                                found.setdefault(i, []).append((reg, at, len(seg_ranges)))
-                                seg_ranges.append((i, 0 if reg.strand == "+" else 1, lo, hi))
-            seg_scores, seg_pairs = batch.segment_scores(seg_ranges) if seg_ranges else (None, None)
-            for i in range(batch.n):
-                b = prepared[base + i]
-                code_i = status[i]
-                if base + i in refused:   # the species tree does not cover the block's rows
-                    print(f"Skipping alignment {read_index[base + i] + 1} ({b.rows[0].name}). {refused[base + i]}", file=sys.stderr)
-                    continue
-                if code_i == api.RC_ERR_SKIP:   # RNAcode.c:142-150
-                    msg = "There must be at least three sequences in the alignment." if b.n <= 2 else "Too short."
-                    print(f"Skipping alignment. {msg}", file=sys.stderr)
-                    continue
-                if code_i != api.RC_OK:         # RNAcode.c:153-156: the reference has no tree for this block either
-                    print(f"Skipping alignment. Failed to build ML tree. ({batch.block_error(i) or 'not scored'})", file=sys.stderr)
-                    continue
-                hook = on_listed = None
-                if a.eps:   # misc.c:461-474: hss-<counter>.eps for every listed HSS with p below the plot cutoff
-                    def hook(counter, h, i=i, b=b):
-                        os.makedirs(a.eps_dir, exist_ok=True)
-                        text = eps.color_aln(b, h, lambda strand, lo, hi: api.expand_backtrack(paths[index[(i, strand, lo, hi)]], b.n, b.cols, lo),
-                                             a.blosum, code)
-                        with open(os.path.join(a.eps_dir, f"hss-{counter}.eps"), "w") as fh:
-                            fh.write(text)
-                if a.details or support_out is not None:
-                    def on_listed(counter, h, i=i, b=b):
-                        if a.details:
-                            details_out.writelines(details.details_lines(counter, b, h, paths[index[(i, h["strand"], h["start"], h["end"])]], pep, matrix))
-                        if support_out is not None:
-                            support_out.writelines(segments.support_lines(counter, b.rows[0].name, h, [r.name for r in b.rows],
-                                                                          seg_pairs[seg_index[(i, h["strand"], h["start"], h["end"])]], params.Delta))
-                report.print_results(out, fmt, all_hss[i], b.rows[0].name, st, cutoff=a.cutoff, best_only=a.best_only,
-                                     best_region=a.best_region, eps=hook, eps_cutoff=a.eps_cutoff, listed=on_listed)
-                if i in tracked:
-                    rc, mu, lam = batch.getExtremeValuePars(i)
-                    track_out.writelines(track.block_lines(b.rows[0].name, b.rows[0].start, b.rows[0].length, tracked[i], rc, mu, lam, a.cutoff))
-                if i in found:
-                    rc, mu, lam = batch.getExtremeValuePars(i)
-                    for reg, (frame, c1, c2), r in found[i]:
-                        p = api.pvalue(float(seg_scores[r]), mu, lam) if rc == 1 else 99.0
-                        regions_out.write(segments.region_line(reg, frame, c1, c2, seg_scores[r], p, seg_pairs[r]))
-                        reg.matched = True
+    with contextlib.ExitStack() as files:   # what has been listed so far is in the side files, whatever a batch raises
+        side = {}
+        for name, header in SIDE_FILES:
+            if getattr(a, name):
+                side[name] = files.enter_context(open(getattr(a, name), "w"))
+                side[name].write(header())
+        code = params.genetic_code.decode()
+        run = _Run(a, params, code, api.code_tables(a.blosum, code) if a.details else None, blocks, read_index, refused,
+                   segments.by_name(regions) if regions is not None else {}, out, fmt, side)
+        # the blocks go through the GPU as a stream of sub-batches (rc_stream_*): while one is being scored the next is prepared
+        # on the host threads, and the listing of a finished one is written meanwhile (the reference's loop, RNAcode.c:115-221).
+        # Sub-batch sizes: --sub-blocks, or the library's schedule (rc_stream_plan: a small first sub-batch, then doubling, whole rounds
+        # of the chip; every row count is a launch of its own, so more classes mean larger sub-batches)
+        base = 0
+        for batch in api.score_stream(ctx, marshalled, params, max(a.sub_blocks, 0), depth=3):
+            _list_batch(run, batch, base)
             base += batch.n
             batch.close()
-    finally:
-        if details_out is not None:   # what has been listed so far is in the file, whatever a batch raised
-            details_out.close()
-        if track_out is not None:
-            track_out.close()
-        if support_out is not None:
-            support_out.close()
-        if regions_out is not None:
-            regions_out.close()
     if regions is not None:   # what matched nothing: one line each, the exit status stays 0
         sys.stderr.write("".join(segments.skipped_lines(regions)))
     if fmt == 0:

@@ -5,12 +5,7 @@
 // (include/rnacode_hip.h): MAF / ClustalW readers (src/rnaz_utils.c:44-234), trees from a sidecar or fitted on the GPU
 // (rc_fit_trees_device), scoring as a stream of sub-batches (rc_stream_*), listings in the reference's three formats
 // (src/misc.c:392-552 printResults, footer RNAcode.c:223-228) byte for byte.  Same options as `python -m rnacode_amd.cli`
-// (which additionally draws the EPS plots):
-//
-//   rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]
-//               [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE] [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]
-//               [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]
-//               [--write-trees SIDECAR] [FILE]
+// (which additionally draws the EPS plots); usage() below has the synopsis.
 //
 // --species-tree (not in the reference, which fits a tree per block): one species tree for the run, parsed before any context
 // exists, pruned to each block's rows and fitted on the GPU (rc_fit_species_trees_device) where rc_fit_trees_device would run; a
@@ -291,7 +286,23 @@ std::vector<Block> read_alignment(FILE *in) {
   return read_maf(text, size);
 }
 
-// printResults (misc.c:392-552); the HSS counter runs across blocks and is not advanced after a --best-only break
+// A side file (--details, --track, --support, --regions-out): opened and given its header before the first batch, closed and checked
+// when everything has been listed.  An empty path: the option is off.
+struct SideFile {
+  const char *(*header)();
+  std::string path;
+  FILE *f;
+};
+enum { kDetails, kTrack, kSupport, kRegions, kSides };
+
+// an HSS that gets a line of the listing, and what goes out beside that line
+struct Line {
+  rc_hss h;
+  std::string eps;                             // --eps: the plot's text, or empty (drawn while the block's batch was alive)
+  std::vector<std::string> details, support;   // its --details / --support lines, one per row, without the counter in front
+};
+
+// printResults (misc.c:392-552); the HSS counter runs across blocks and is not advanced after a --best-only line
 struct Listing {
   FILE *out = stdout;
   int fmt = 0;          // 0 default table, 1 GTF, 2 tabular
@@ -300,17 +311,18 @@ struct Listing {
   bool eps = false;
   float epsCutoff = 0.05f;
   std::string epsDir = "eps";
-  FILE *details = nullptr;   // --details: the table's file, header written
-  FILE *track = nullptr;     // --track: the track's file, header written
-  FILE *support = nullptr;   // --support: the table's file, header written
-  FILE *regions = nullptr;   // --regions-out: the file, header written
+  SideFile side[kSides] = {{rceps::details_header, "", nullptr}, {rceps::track_header, "", nullptr}, {rceps::support_header, "", nullptr},
+                           {rceps::regions_header, "", nullptr}};
+  bool on(int s) const { return !side[s].path.empty(); }
   int hitCounter = 0;
 
-  // The HSS of a block in the order printResults walks them, the hidden ones marked (misc.c:400-433).  `res` is filtered and, with
-  // --best-region, re-ordered in place; `order` indexes it by descending score.
-  void arrange(std::vector<rc_hss> &res, std::vector<char> &hide, std::vector<size_t> &order) const {
+  // The HSS of a block (p-values filled) that get a line, in line order: those with a positive score, with --best-region the weaker of two
+  // overlapping ones hidden (misc.c:400-433), by descending score up to the first p at or above the cutoff, one only with --best-only (the loop
+  // of misc.c:444-547 without its output).  none: the block gets "No significant coding regions found." instead of the table's header -- no
+  // HSS, or the best p ABOVE the cutoff (a best p equal to the cutoff gets the header and no line).
+  std::vector<Line> arrange(std::vector<rc_hss> res, bool &none) const {
     res.erase(std::remove_if(res.begin(), res.end(), [](const rc_hss &h) { return !(h.score > 0.0f); }), res.end());
-    hide.assign(res.size(), 0);
+    std::vector<char> hide(res.size(), 0);
     if (bestRegion) {   // misc.c:408-433: sort by start codon, hide the weaker of two overlapping HSS
       std::stable_sort(res.begin(), res.end(), [](const rc_hss &a, const rc_hss &b) { return a.startSite < b.startSite; });
       size_t curr = 0;
@@ -321,32 +333,27 @@ struct Listing {
         } else curr = nxt;
       }
     }
-    order.resize(res.size());
+    std::vector<size_t> order(res.size());
     for (size_t i = 0; i < order.size(); i++) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return res[a].score > res[b].score; });
-  }
-  // positions in `order` of the HSS that get a line (the loop of misc.c:444-547 without its output)
-  std::vector<size_t> listed(const std::vector<rc_hss> &res, const std::vector<char> &hide, const std::vector<size_t> &order) const {
-    std::vector<size_t> out;
-    if (res.empty() || res[order[0]].pvalue > cutoff) return out;
+    std::vector<Line> lines;
+    none = res.empty() || res[order[0]].pvalue > cutoff;
+    if (none) return lines;
+    lines.reserve(bestOnly ? 1 : res.size());
     for (size_t idx : order) {
       if (!(res[idx].pvalue < cutoff)) break;
       if (hide[idx]) continue;
-      out.push_back(idx);
+      lines.emplace_back();
+      lines.back().h = res[idx];
       if (bestOnly) break;
     }
-    return out;
+    return lines;
   }
 
-  // epsText: for the k-th listed HSS the EPS file's text, or empty (drawn while the block's batch was alive; misc.c:461-474 writes
-  // hss-<counter>.eps in front of the line); detailText / supportText: for the k-th listed HSS its --details / --support lines without the
-  // counter in front
-  void block(std::vector<rc_hss> res, const std::string &refName, const std::vector<std::string> *epsText = nullptr,
-             const std::vector<std::vector<std::string>> *detailText = nullptr, const std::vector<std::vector<std::string>> *supportText = nullptr) {
-    std::vector<char> hide;
-    std::vector<size_t> order;
-    arrange(res, hide, order);
-    if (res.empty() || res[order[0]].pvalue > cutoff) {
+  // a block's part of the listing: its lines as arrange() chose them, each with its plot (misc.c:461-474 writes hss-<counter>.eps in front
+  // of the line) and its lines of the side tables
+  void block(const std::vector<Line> &lines, bool none, const std::string &refName) {
+    if (none) {
       if (fmt == 0) std::fprintf(out, "\nNo significant coding regions found.\n");
       return;
     }
@@ -354,23 +361,19 @@ struct Listing {
       std::fprintf(out, "\n%6s%5s%7s%6s%6s%12s%12s%12s%9s%9s\n", " HSS # ", "Frame", "Length", "From", "To", "Name", "Start", "End", "Score", "P");
       std::fprintf(out, "======================================================================================\n");
     }
-    size_t k = 0;
-    for (size_t idx : listed(res, hide, order)) {
-      const rc_hss &h = res[idx];
+    for (const Line &l : lines) {
+      const rc_hss &h = l.h;
       const double p = static_cast<double>(h.pvalue);
-      if (epsText && k < epsText->size() && !(*epsText)[k].empty()) {
+      if (!l.eps.empty()) {
         struct stat sp;
         if (stat(epsDir.c_str(), &sp) != 0 && mkdir(epsDir.c_str(), S_IRWXU | S_IROTH | S_IRGRP) != 0)
           std::fprintf(stderr, "WARNING: Could not create directory: %s", epsDir.c_str());
         const std::string fn = epsDir + "/hss-" + std::to_string(hitCounter) + ".eps";
-        if (FILE *f = std::fopen(fn.c_str(), "w")) { std::fwrite((*epsText)[k].data(), 1, (*epsText)[k].size(), f); std::fclose(f); }
+        if (FILE *f = std::fopen(fn.c_str(), "w")) { std::fwrite(l.eps.data(), 1, l.eps.size(), f); std::fclose(f); }
         else std::fprintf(stderr, "ERROR: Can't open output file %s\n", fn.c_str());
       }
-      if (details && detailText && k < detailText->size())
-        for (const std::string &tail : (*detailText)[k]) std::fprintf(details, "%i\t%s", hitCounter, tail.c_str());
-      if (support && supportText && k < supportText->size())
-        for (const std::string &tail : (*supportText)[k]) std::fprintf(support, "%i\t%s", hitCounter, tail.c_str());
-      k++;
+      for (const std::string &tail : l.details) std::fprintf(side[kDetails].f, "%i\t%s", hitCounter, tail.c_str());
+      for (const std::string &tail : l.support) std::fprintf(side[kSupport].f, "%i\t%s", hitCounter, tail.c_str());
       const int length = h.endSite - h.startSite + 1;
       const char strand[2] = {static_cast<char>(h.strand), 0};
       if (fmt == 0) {
@@ -389,8 +392,7 @@ struct Listing {
                      refName.c_str(), h.startGenomic, h.endGenomic, static_cast<double>(h.score));
         if (p < 0.001) std::fprintf(out, "% 9.3e\n", p); else std::fprintf(out, "% 9.3f\n", p);
       }
-      if (bestOnly) break;
-      hitCounter++;
+      if (!bestOnly) hitCounter++;
     }
   }
 };
@@ -422,20 +424,23 @@ void usage() {
 
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
+// what the writer needs of one block
+struct BlockOut {
+  int index = 0;               // the input block
+  int status = RC_OK;
+  std::string why;             // why it was not scored
+  bool none = true;            // Listing::arrange: nothing significant
+  std::vector<Line> lines;     // the HSS that get a line, what goes out beside each attached
+  std::string track, regions;  // its --track / --regions-out lines
+};
+
 // results of one sub-batch on their way to the writer
 struct Job {
   int seq = 0;                       // position of the sub-batch in the input: the writer takes them in this order
-  std::vector<int> blockIdx;         // input block of each of its blocks
-  std::vector<rc_hss> hss;
+  std::vector<BlockOut> blocks;
+  std::vector<rc_hss> hss;           // as fetched: block i's are [offs[i], offs[i + 1]); the writer reads the blocks' lines, not these
   std::vector<int64_t> offs;
-  std::vector<int> status;
-  std::vector<std::string> why;
-  std::vector<std::vector<std::string>> eps;   // per block: the EPS texts of its listed HSS (--eps)
-  std::vector<std::vector<std::vector<std::string>>> details;   // per block and listed HSS: its --details lines, one per row, without the counter
-  std::vector<std::string> track;    // per block: its --track lines
-  std::vector<std::vector<std::vector<std::string>>> support;   // per block and listed HSS: its --support lines, one per row, without the counter
-  std::vector<std::string> regions;  // per block: its --regions-out lines
-  std::vector<int> matched;          // the regions (positions in Run::regions) those lines belong to
+  std::vector<int> matched;          // the regions (positions in Run::regions) its --regions-out lines belong to
 };
 
 // everything the threads share
@@ -483,10 +488,9 @@ void writer_thread(Run &R) {
       R.nextSeq++;
     }
     const double t = now();
-    for (size_t i = 0; i < j->blockIdx.size(); i++) {
-      const int st = j->status[i];
-      const Block &blk = R.blocks[j->blockIdx[i]];
-      if (st == RC_ERR_SKIP) {   // RNAcode.c:142-150
+    for (const BlockOut &o : j->blocks) {
+      const Block &blk = R.blocks[o.index];
+      if (o.status == RC_ERR_SKIP) {   // RNAcode.c:142-150
         std::fprintf(stderr, "Skipping alignment. %s\n", blk.rows.size() <= 2 ? "There must be at least three sequences in the alignment." : "Too short.");
         continue;
       }
@@ -494,14 +498,13 @@ void writer_thread(Run &R) {
         std::fprintf(stderr, "Skipping alignment %d (%s). %s\n", blk.index + 1, std::string(blk.rows[0].name).c_str(), blk.refused.c_str());
         continue;
       }
-      if (st != RC_OK) {         // RNAcode.c:153-156
-        std::fprintf(stderr, "Skipping alignment. Failed to build ML tree. (%s)\n", j->why[i].empty() ? "not scored" : j->why[i].c_str());
+      if (o.status != RC_OK) {         // RNAcode.c:153-156
+        std::fprintf(stderr, "Skipping alignment. Failed to build ML tree. (%s)\n", o.why.empty() ? "not scored" : o.why.c_str());
         continue;
       }
-      R.list.block(std::vector<rc_hss>(j->hss.begin() + j->offs[i], j->hss.begin() + j->offs[i + 1]), std::string(blk.rows[0].name),
-                   j->eps.empty() ? nullptr : &j->eps[i], j->details.empty() ? nullptr : &j->details[i], j->support.empty() ? nullptr : &j->support[i]);
-      if (R.list.track && !j->track.empty()) std::fwrite(j->track[i].data(), 1, j->track[i].size(), R.list.track);
-      if (R.list.regions && !j->regions.empty()) std::fwrite(j->regions[i].data(), 1, j->regions[i].size(), R.list.regions);
+      R.list.block(o.lines, o.none, std::string(blk.rows[0].name));
+      if (!o.track.empty()) std::fwrite(o.track.data(), 1, o.track.size(), R.list.side[kTrack].f);
+      if (!o.regions.empty()) std::fwrite(o.regions.data(), 1, o.regions.size(), R.list.side[kRegions].f);
     }
     for (int r : j->matched) R.regionMatched[r] = 1;
     R.tList += now() - t;
@@ -513,19 +516,21 @@ void post(Run &R, std::unique_ptr<Job> j) {
   R.jcv.notify_all();
 }
 
-// --eps / --details for every block of a finished batch, while the batch is alive: the backtracked paths of all listed HSS come from the
-// device with ONE call (rc_batch_backtrack_many) -- the segments themselves for the table; for the plots (p below the plot cutoff, misc.c:462)
-// the segment and its two extensions -- then the plots are drawn and the table's lines made from the packed cells.
+// the blocks the listing covers: scored, and not refused by the species tree
+bool scored(const Run &R, const BlockOut &o) { return o.status == RC_OK && R.blocks[o.index].refused.empty(); }
+
+// --eps / --details for every listed HSS of a finished batch, while the batch is alive: the backtracked paths come from the device with ONE
+// call (rc_batch_backtrack_many) -- the segments themselves for the table; for the plots (p below the plot cutoff, misc.c:462) the segment
+// and its two extensions -- then the plots are drawn and the table's lines made from the packed cells.
 bool annotate(const Run &R, rc_batch *b, Job &j, std::string &err) {
-  const int m = static_cast<int>(j.blockIdx.size());
-  struct Item { int blk; rc_hss h; bool plot; int segment = -1; std::vector<std::pair<std::pair<int, int>, int>> ext; };   // ext: (b, e) -> range index
+  const int m = static_cast<int>(j.blocks.size());
+  const bool details = R.list.on(kDetails);
+  struct Item { int blk; Line *line; bool plot; int segment = -1; std::vector<std::pair<std::pair<int, int>, int>> ext; };   // ext: (b, e) -> range index
   std::vector<Item> items;
   std::vector<rc_bt_range> ranges;
   std::vector<std::vector<rceps::Row>> rowsOf(m);
-  if (R.list.eps) j.eps.resize(m);
-  if (R.list.details) j.details.resize(m);
   auto rows_of = [&](int i) -> const std::vector<rceps::Row> & {
-    if (rowsOf[i].empty()) for (const Row &r : R.blocks[j.blockIdx[i]].rows) rowsOf[i].push_back(rceps::Row{std::string(r.name), std::string(r.seq), r.start});
+    if (rowsOf[i].empty()) for (const Row &r : R.blocks[j.blocks[i].index].rows) rowsOf[i].push_back(rceps::Row{std::string(r.name), std::string(r.seq), r.start});
     return rowsOf[i];
   };
   // a block's rows on either strand, made once per block and strand
@@ -536,17 +541,12 @@ bool annotate(const Run &R, rc_batch *b, Job &j, std::string &err) {
     if (strand != '+' && rev.empty()) rev = rceps::rev_rows(fwd);
     return strand == '+' ? fwd : rev;
   };
-  for (int i = 0; i < m; i++) {
-    if (j.status[i] != RC_OK) continue;
-    std::vector<rc_hss> res(j.hss.begin() + j.offs[i], j.hss.begin() + j.offs[i + 1]);
-    std::vector<char> hide;
-    std::vector<size_t> order;
-    R.list.arrange(res, hide, order);
-    for (size_t idx : R.list.listed(res, hide, order)) {
-      Item it{i, res[idx], R.list.eps && res[idx].pvalue < R.list.epsCutoff};
-      const rc_hss &h = it.h;
+  for (int i = 0; i < m; i++)
+    for (Line &l : j.blocks[i].lines) {
+      Item it{i, &l, R.list.eps && l.h.pvalue < R.list.epsCutoff};
+      const rc_hss &h = l.h;
       const int strand = h.strand == '+' ? 0 : 1;
-      if (R.list.details) { it.segment = static_cast<int>(ranges.size()); ranges.push_back(rc_bt_range{i, strand, h.start, h.end}); }
+      if (details) { it.segment = static_cast<int>(ranges.size()); ranges.push_back(rc_bt_range{i, strand, h.start, h.end}); }
       if (it.plot)
         for (const rceps::Range &r : rceps::hss_ranges(strand_rows(i, static_cast<char>(h.strand)), rceps::Hss{static_cast<char>(h.strand), h.frame, h.start, h.end, h.pvalue}, R.tables))
           if (rceps::needs_backtrack(r.b, r.e)) {
@@ -556,7 +556,6 @@ bool annotate(const Run &R, rc_batch *b, Job &j, std::string &err) {
           }
       items.push_back(std::move(it));
     }
-  }
   const int nr = static_cast<int>(ranges.size());
   std::vector<int64_t> offs(static_cast<size_t>(nr) + 1, 0);
   std::vector<uint8_t> cells;
@@ -567,47 +566,48 @@ bool annotate(const Run &R, rc_batch *b, Job &j, std::string &err) {
   }
   for (const Item &it : items) {
     const int i = it.blk;
-    const rc_hss &h = it.h;
+    const rc_hss &h = it.line->h;
     const std::vector<rceps::Row> &rows = rows_of(i);
     const int N = static_cast<int>(rows.size()), cols = static_cast<int>(rows[0].seq.size());
-    if (R.list.eps) {
-      if (!it.plot) j.eps[i].emplace_back();
-      else {
-        auto bt = [&](char, int lo, int hi) {
-          for (const auto &e : it.ext)
-            if (e.first.first == lo && e.first.second == hi) {
-              const int64_t at = offs[e.second], n = offs[e.second + 1] - at;
-              return rceps::expand_path(cells.data() + at, N, cols, lo, static_cast<int>(n / (N - 1)));
-            }
-          return rceps::Path();
-        };
-        j.eps[i].push_back(rceps::color_aln(rows, rceps::Hss{static_cast<char>(h.strand), h.frame, h.start, h.end, h.pvalue}, bt, R.tables));
-      }
+    if (it.plot) {
+      auto bt = [&](char, int lo, int hi) {
+        for (const auto &e : it.ext)
+          if (e.first.first == lo && e.first.second == hi) {
+            const int64_t at = offs[e.second], n = offs[e.second + 1] - at;
+            return rceps::expand_path(cells.data() + at, N, cols, lo, static_cast<int>(n / (N - 1)));
+          }
+        return rceps::Path();
+      };
+      it.line->eps = rceps::color_aln(rows, rceps::Hss{static_cast<char>(h.strand), h.frame, h.start, h.end, h.pvalue}, bt, R.tables);
     }
-    if (R.list.details) {
+    if (details) {
       const std::vector<std::string> &curr = strand_rows(i, static_cast<char>(h.strand));
       const std::vector<int> map0 = rceps::pos2col(curr[0]);
       const int64_t at = offs[it.segment];
       const int steps = static_cast<int>((offs[it.segment + 1] - at) / (N - 1));
-      std::vector<std::string> lines;
       for (int k = 1; k < N; k++)
-        lines.push_back(rceps::details_tail(curr, map0, rows[0].name, rows[k].name, k, static_cast<char>(h.strand), h.frame, h.startGenomic, h.endGenomic,
-                                            h.score, h.pvalue, h.start, h.end, cells.data() + at + static_cast<int64_t>(k - 1) * steps, R.tables));
-      j.details[i].push_back(std::move(lines));
+        it.line->details.push_back(rceps::details_tail(curr, map0, rows[0].name, rows[k].name, k, static_cast<char>(h.strand), h.frame, h.startGenomic, h.endGenomic,
+                                                       h.score, h.pvalue, h.start, h.end, cells.data() + at + static_cast<int64_t>(k - 1) * steps, R.tables));
     }
   }
   return true;
 }
 
-// --track for every scored block of a finished batch, while the batch is alive: ONE rc_batch_track call (after the sizing call) for the blocks
-// the listing covers -- scored, and not refused by the species tree --, then their lines (rc_eps.h, track_block).  fits: per block {evd_rc, mu,
-// lambda} where the caller made the fits itself (the sample split); else the batch's own.
-struct TrackFit { int rc; float mu, lambda; };
-bool add_track(const Run &R, rc_batch *b, Job &j, std::string &err, const std::vector<TrackFit> *fits = nullptr) {
-  const int m = static_cast<int>(j.blockIdx.size());
-  j.track.assign(m, std::string());
+// A block's extreme-value fit {evd_rc, mu, lambda}: the caller's where it made the fits itself (the sample split: `fits`, one per block), else
+// the batch's own.
+struct EvdFit { int rc; float mu, lambda; };
+bool fit_of(rc_batch *b, const std::vector<EvdFit> *fits, int i, EvdFit &fit, std::string &err) {
+  fit = fits ? (*fits)[i] : EvdFit{-1, 0.0f, 0.0f};
+  if (fits || rc_batch_fit(b, i, &fit.rc, &fit.mu, &fit.lambda) == RC_OK) return true;
+  err = rc_last_error();
+  return false;
+}
+
+// --track for every block the listing covers, while the batch is alive: ONE rc_batch_track call (after the sizing call), then the blocks'
+// lines (rc_eps.h, track_block).
+bool add_track(const Run &R, rc_batch *b, Job &j, std::string &err, const std::vector<EvdFit> *fits) {
   std::vector<int32_t> blks;
-  for (int i = 0; i < m; i++) if (j.status[i] == RC_OK && R.blocks[j.blockIdx[i]].refused.empty()) blks.push_back(i);
+  for (size_t i = 0; i < j.blocks.size(); i++) if (scored(R, j.blocks[i])) blks.push_back(static_cast<int32_t>(i));
   const int nb = static_cast<int>(blks.size());
   if (!nb) return true;
   std::vector<int64_t> offs(static_cast<size_t>(6) * nb + 1, 0);
@@ -616,45 +616,36 @@ bool add_track(const Run &R, rc_batch *b, Job &j, std::string &err, const std::v
   if (rc_batch_track(b, blks.data(), nb, vals.data(), offs[6 * static_cast<size_t>(nb)], offs.data()) != RC_OK) { err = rc_last_error(); return false; }
   for (int k = 0; k < nb; k++) {
     const int i = blks[k];
-    const Block &blk = R.blocks[j.blockIdx[i]];
-    TrackFit fit{-1, 0.0f, 0.0f};
-    if (fits) fit = (*fits)[i];
-    else if (rc_batch_fit(b, i, &fit.rc, &fit.mu, &fit.lambda) != RC_OK) { err = rc_last_error(); return false; }
-    rceps::track_block(j.track[i], std::string(blk.rows[0].name), blk.rows[0].start, blk.rows[0].length, vals.data(), offs.data() + 6 * static_cast<size_t>(k),
+    const Block &blk = R.blocks[j.blocks[i].index];
+    EvdFit fit;
+    if (!fit_of(b, fits, i, fit, err)) return false;
+    rceps::track_block(j.blocks[i].track, std::string(blk.rows[0].name), blk.rows[0].start, blk.rows[0].length, vals.data(), offs.data() + 6 * static_cast<size_t>(k),
                        fit.rc, fit.mu, fit.lambda, R.list.cutoff);
   }
   return true;
 }
 
-// --support / --regions for every scored block of a finished batch, while the batch is alive: the scores and pair scores of all listed HSS,
-// and of every region a block contains, with ONE call (rc_batch_segment_scores), then their lines (rc_eps.h, support_tail / region_line).
-// fits: as for add_track.
-bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std::vector<TrackFit> *fits = nullptr) {
-  const int m = static_cast<int>(j.blockIdx.size());
-  struct Listed { int blk; rc_hss h; int range; };
+// --support / --regions for every block the listing covers, while the batch is alive: the scores and pair scores of all listed HSS, and of
+// every region a block contains, with ONE call (rc_batch_segment_scores), then their lines (rc_eps.h, support_tail / region_line).
+bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std::vector<EvdFit> *fits) {
+  const int m = static_cast<int>(j.blocks.size());
+  struct Listed { int blk; Line *line; int range; };
   struct Found { int blk, region; rceps::SegLoc at; int range; };
   std::vector<Listed> listed;
   std::vector<Found> found;
   std::vector<rc_bt_range> ranges;
   std::vector<int> rowsOf;   // per range: N - 1
-  if (R.list.support) j.support.resize(m);
-  if (R.list.regions) j.regions.assign(m, std::string());
   for (int i = 0; i < m; i++) {
-    const Block &blk = R.blocks[j.blockIdx[i]];
-    if (j.status[i] != RC_OK || !blk.refused.empty()) continue;
+    const Block &blk = R.blocks[j.blocks[i].index];
+    if (!scored(R, j.blocks[i])) continue;
     const int nk = static_cast<int>(blk.rows.size()) - 1;
-    if (R.list.support) {
-      std::vector<rc_hss> res(j.hss.begin() + j.offs[i], j.hss.begin() + j.offs[i + 1]);
-      std::vector<char> hide;
-      std::vector<size_t> order;
-      R.list.arrange(res, hide, order);
-      for (size_t idx : R.list.listed(res, hide, order)) {
-        listed.push_back(Listed{i, res[idx], static_cast<int>(ranges.size())});
-        ranges.push_back(rc_bt_range{i, res[idx].strand == '+' ? 0 : 1, res[idx].start, res[idx].end});
+    if (R.list.on(kSupport))
+      for (Line &l : j.blocks[i].lines) {
+        listed.push_back(Listed{i, &l, static_cast<int>(ranges.size())});
+        ranges.push_back(rc_bt_range{i, l.h.strand == '+' ? 0 : 1, l.h.start, l.h.end});
         rowsOf.push_back(nk);
       }
-    }
-    if (R.list.regions) {
+    if (R.list.on(kRegions)) {
       const auto it = R.regionsOf.find(std::string(blk.rows[0].name));
       if (it == R.regionsOf.end()) continue;
       long long L = 0;
@@ -677,47 +668,55 @@ bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std
   std::vector<int64_t> offs(static_cast<size_t>(nr) + 1, 0);
   if (rc_batch_segment_scores(b, ranges.data(), nr, scores.data(), pairs.data(), total, offs.data()) != RC_OK) { err = rc_last_error(); return false; }
   for (const Listed &l : listed) {
-    const Block &blk = R.blocks[j.blockIdx[l.blk]];
+    const Block &blk = R.blocks[j.blocks[l.blk].index];
+    const rc_hss &h = l.line->h;
     const int nk = static_cast<int>(blk.rows.size()) - 1;
     const float *p = pairs.data() + offs[l.range];
     const std::vector<float> loo = rceps::leave_one_out(p, nk, R.par.Delta);
-    std::vector<std::string> lines;
     for (int k = 1; k <= nk; k++)
-      lines.push_back(rceps::support_tail(std::string(blk.rows[0].name), std::string(blk.rows[k].name), k, static_cast<char>(l.h.strand), l.h.frame, l.h.startGenomic,
-                                          l.h.endGenomic, l.h.score, l.h.pvalue, p[k - 1], static_cast<float>(nk), loo[k - 1]));
-    j.support[l.blk].push_back(std::move(lines));
+      l.line->support.push_back(rceps::support_tail(std::string(blk.rows[0].name), std::string(blk.rows[k].name), k, static_cast<char>(h.strand), h.frame, h.startGenomic,
+                                                    h.endGenomic, h.score, h.pvalue, p[k - 1], static_cast<float>(nk), loo[k - 1]));
   }
   for (const Found &f : found) {
-    TrackFit fit{-1, 0.0f, 0.0f};
-    if (fits) fit = (*fits)[f.blk];
-    else if (rc_batch_fit(b, f.blk, &fit.rc, &fit.mu, &fit.lambda) != RC_OK) { err = rc_last_error(); return false; }
+    EvdFit fit;
+    if (!fit_of(b, fits, f.blk, fit, err)) return false;
     const float p = fit.rc == 1 ? rc_pvalue(scores[f.range], fit.mu, fit.lambda) : 99.0f;
-    j.regions[f.blk] += rceps::region_line(R.regions[f.region], f.at, scores[f.range], p, pairs.data() + offs[f.range], static_cast<int>(offs[f.range + 1] - offs[f.range]));
+    j.blocks[f.blk].regions += rceps::region_line(R.regions[f.region], f.at, scores[f.range], p, pairs.data() + offs[f.range], static_cast<int>(offs[f.range + 1] - offs[f.range]));
     j.matched.push_back(f.region);
   }
   return true;
 }
 
-// what the writer needs from a finished batch
-std::unique_ptr<Job> collect(const Run &R, rc_batch *b, int seq, const std::vector<int> &blockIdx, std::string &err) {
+// From a finished batch to the writer, step 1: the HSS, status and reason of each of its blocks (blockIdx: their input blocks).
+std::unique_ptr<Job> fetch(rc_batch *b, int seq, const int *blockIdx, std::string &err) {
   std::unique_ptr<Job> j(new Job());
   j->seq = seq;
-  j->blockIdx = blockIdx;
   const int m = rc_batch_size(b);
   j->offs.assign(static_cast<size_t>(m) + 1, 0);
   if (rc_batch_hss_all(b, nullptr, 0, j->offs.data()) != RC_OK) { err = rc_last_error(); return nullptr; }
   j->hss.resize(static_cast<size_t>(std::max<int64_t>(j->offs[m], 1)));
   if (rc_batch_hss_all(b, j->hss.data(), j->offs[m], j->offs.data()) != RC_OK) { err = rc_last_error(); return nullptr; }
-  j->status.resize(m);
-  j->why.resize(m);
+  j->blocks.resize(m);
   for (int i = 0; i < m; i++) {
-    j->status[i] = rc_batch_status(b, i);
-    if (j->status[i] != RC_OK && j->status[i] != RC_ERR_SKIP) { const char *why = rc_batch_block_error(b, i); j->why[i] = why ? why : ""; }
+    BlockOut &o = j->blocks[i];
+    o.index = blockIdx[i];
+    o.status = rc_batch_status(b, i);
+    if (o.status != RC_OK && o.status != RC_ERR_SKIP) { const char *why = rc_batch_block_error(b, i); o.why = why ? why : ""; }
   }
-  if ((R.list.eps || R.list.details) && !annotate(R, b, *j, err)) return nullptr;
-  if (R.list.track && !add_track(R, b, *j, err)) return nullptr;
-  if ((R.list.support || R.list.regions) && !add_segments(R, b, *j, err)) return nullptr;
   return j;
+}
+
+// Step 2, while the batch is alive: each block's listing arranged -- here and nowhere else --, what goes out beside it made, the job handed
+// to the writer.  fits: as for fit_of; the caller that passes them has filled in the p-values of j->hss as well.
+bool deliver(Run &R, rc_batch *b, std::unique_ptr<Job> j, std::string &err, const std::vector<EvdFit> *fits = nullptr) {
+  for (size_t i = 0; i < j->blocks.size(); i++)
+    if (scored(R, j->blocks[i]))
+      j->blocks[i].lines = R.list.arrange(std::vector<rc_hss>(j->hss.begin() + j->offs[i], j->hss.begin() + j->offs[i + 1]), j->blocks[i].none);
+  if ((R.list.eps || R.list.on(kDetails)) && !annotate(R, b, *j, err)) return false;
+  if (R.list.on(kTrack) && !add_track(R, b, *j, err, fits)) return false;
+  if ((R.list.on(kSupport) || R.list.on(kRegions)) && !add_segments(R, b, *j, err, fits)) return false;
+  post(R, std::move(j));
+  return true;
 }
 
 struct Times { double ctx = 0, trees = 0, treeWait = 0, submit = 0, wait = 0, fetch = 0; };
@@ -766,7 +765,10 @@ void run_worker(Run &R, Worker &W, int subBlocks) {
   std::condition_variable tcv;
   int fitted = R.haveSidecar ? n : 0;      // blocks [0, fitted) have their tree (or a sidecar entry, or none to be had)
   std::string treeErr;
+  // released on every way out, in this order: the tree thread is joined, then the stream destroyed
+  std::unique_ptr<rc_stream, void (*)(rc_stream *)> stream(nullptr, rc_stream_destroy);
   std::thread treeThread;
+  struct Joined { std::thread &t; ~Joined() { if (t.joinable()) t.join(); } } joined{treeThread};
   if (!R.haveSidecar) treeThread = std::thread([&] {
     std::vector<char> nwk;
     std::vector<float> kap;
@@ -795,34 +797,33 @@ void run_worker(Run &R, Worker &W, int subBlocks) {
     { std::lock_guard<std::mutex> lk(tm); fitted = n; }
     tcv.notify_all();
   });
-  auto finish = [&](const std::string &msg) {
-    if (!msg.empty()) R.fail(msg);
-    if (treeThread.joinable()) treeThread.join();
-  };
-  rc_stream *stream = nullptr;   // (created beside the first tree fits: it brings up the HIP streams of the scoring pipeline)
-  if (rc_stream_create(W.ctx, &R.par, 3, &stream) != RC_OK) { finish(rc_last_error()); return; }
+  {   // (created beside the first tree fits: it brings up the HIP streams of the scoring pipeline)
+    rc_stream *made = nullptr;
+    if (rc_stream_create(W.ctx, &R.par, 3, &made) != RC_OK) return R.fail(rc_last_error());
+    stream.reset(made);
+  }
   auto trees_ready = [&](int upto, bool wait) {   // are the trees of blocks [0, upto) there?
     std::unique_lock<std::mutex> lk(tm);
     if (wait) tcv.wait(lk, [&] { return fitted >= upto; });
     return fitted >= upto;
   };
-  size_t sent = 0, taken = 0;
+  size_t sent = 0;
   int next = 0;
   std::deque<std::pair<int, int>> inflight;   // (part index, first local block)
-  while ((sent < W.parts.size() || rc_stream_pending(stream) > 0) && !R.failed.load()) {
-    while (sent < W.parts.size() && rc_stream_pending(stream) < 3) {
+  while ((sent < W.parts.size() || rc_stream_pending(stream.get()) > 0) && !R.failed.load()) {
+    while (sent < W.parts.size() && rc_stream_pending(stream.get()) < 3) {
       const int m = W.parts[sent].second;
       // the fits have not got this far: take a finished batch first if there is one, else wait for them
       if (!trees_ready(next + m, false)) {
-        if (rc_stream_pending(stream) > 0) break;
+        if (rc_stream_pending(stream.get()) > 0) break;
         const double t0 = now();
         trees_ready(next + m, true);
         W.t.treeWait += now() - t0;
       }
-      { std::lock_guard<std::mutex> lk(tm); if (!treeErr.empty()) { finish(treeErr); rc_stream_destroy(stream); return; } }
+      { std::lock_guard<std::mutex> lk(tm); if (!treeErr.empty()) return R.fail(treeErr); }
       for (int i = next; i < next + m; i++) { rb[i].newick = tree[i].empty() ? nullptr : tree[i].c_str(); rb[i].kappa = kappa[i]; }
       const double t0 = now();
-      if (rc_stream_submit(stream, rb.data() + next, m) != RC_OK) { finish(rc_last_error()); rc_stream_destroy(stream); return; }
+      if (rc_stream_submit(stream.get(), rb.data() + next, m) != RC_OK) return R.fail(rc_last_error());
       W.t.submit += now() - t0;
       inflight.emplace_back(static_cast<int>(sent), next);
       next += m;
@@ -830,22 +831,18 @@ void run_worker(Run &R, Worker &W, int subBlocks) {
     }
     rc_batch *b = nullptr;
     double t0 = now();
-    if (rc_stream_next(stream, &b) != RC_OK) { finish(rc_last_error()); rc_stream_destroy(stream); return; }
+    if (rc_stream_next(stream.get(), &b) != RC_OK) return R.fail(rc_last_error());
     W.t.wait += now() - t0;
     t0 = now();
     const auto part = inflight.front();
     inflight.pop_front();
-    std::vector<int> blockIdx(idx.begin() + part.second, idx.begin() + part.second + W.parts[part.first].second);
     std::string err;
-    std::unique_ptr<Job> j = collect(R, b, W.seqs[part.first], blockIdx, err);
+    std::unique_ptr<Job> j = fetch(b, W.seqs[part.first], idx.data() + part.second, err);
+    const bool ok = j && deliver(R, b, std::move(j), err);
     W.t.fetch += now() - t0;
-    rc_stream_recycle(stream, b);
-    if (!j) { finish(err); rc_stream_destroy(stream); return; }
-    post(R, std::move(j));
-    taken++;
+    rc_stream_recycle(stream.get(), b);
+    if (!ok) return R.fail(err);
   }
-  finish("");
-  rc_stream_destroy(stream);
 }
 
 // Few blocks, several GPUs: every GPU simulates the samples [lo, hi) of EVERY block (seed_base + lo: sample s of a block is seeded
@@ -855,14 +852,14 @@ void run_worker(Run &R, Worker &W, int subBlocks) {
 bool run_sample_split(Run &R, std::vector<Worker> &W, std::string &err) {
   const int n = static_cast<int>(R.blocks.size()), G = static_cast<int>(W.size());
   const int sampleN = R.par.sampleN, groups = (sampleN + 63) / 64;
+  std::vector<int> all(n);   // the blocks of the one batch: the input's
+  for (int i = 0; i < n; i++) all[i] = i;
   // trees: once, on the first GPU
   std::vector<char> nwk;
   std::vector<float> kap(n, 0.0f);
   if (!R.haveSidecar) {
     nwk.assign(static_cast<size_t>(n) * R.cap, 0);
     const double t0 = now();
-    std::vector<int> all(n);
-    for (int i = 0; i < n; i++) all[i] = i;
     if (fit_chunk(R, W[0].ctx, R.rb.data(), n, nwk.data(), kap.data(), all.data()) < 0) { err = rc_last_error(); return false; }
     W[0].t.trees += now() - t0;
     for (int i = 0; i < n; i++) { R.blocks[i].tree = nwk.data() + static_cast<size_t>(i) * R.cap; R.blocks[i].kappa = kap[i]; }
@@ -890,20 +887,12 @@ bool run_sample_split(Run &R, std::vector<Worker> &W, std::string &err) {
   for (auto &t : th) t.join();
   for (int g = 0; g < G; g++) if (!werr[g].empty()) { err = werr[g]; return false; }
   // the native HSS lists are the same on every GPU: the first one's, with p-values from the fit of the gathered row
-  std::vector<int> blockIdx(n);
-  for (int i = 0; i < n; i++) blockIdx[i] = i;
-  std::unique_ptr<Job> j(new Job());
-  j->seq = 0; j->blockIdx = blockIdx;
-  j->offs.assign(static_cast<size_t>(n) + 1, 0);
-  if (rc_batch_hss_all(batch[0], nullptr, 0, j->offs.data()) != RC_OK) { err = rc_last_error(); return false; }
-  j->hss.resize(static_cast<size_t>(std::max<int64_t>(j->offs[n], 1)));
-  if (rc_batch_hss_all(batch[0], j->hss.data(), j->offs[n], j->offs.data()) != RC_OK) { err = rc_last_error(); return false; }
-  j->status.resize(n); j->why.resize(n);
+  std::unique_ptr<Job> j = fetch(batch[0], 0, all.data(), err);
+  if (!j) return false;
   std::vector<double> row(sampleN);
-  std::vector<TrackFit> fits(n, TrackFit{-1, 0.0f, 0.0f});
+  std::vector<EvdFit> fits(n, EvdFit{-1, 0.0f, 0.0f});
   for (int i = 0; i < n; i++) {
-    j->status[i] = rc_batch_status(batch[0], i);
-    if (j->status[i] != RC_OK) { if (j->status[i] != RC_ERR_SKIP) { const char *why = rc_batch_block_error(batch[0], i); j->why[i] = why ? why : ""; } continue; }
+    if (j->blocks[i].status != RC_OK) continue;
     for (int g = 0; g < G; g++) {
       if (!batch[g]) continue;
       const int w = std::max(1, hi[g] - lo[g]);
@@ -921,16 +910,19 @@ bool run_sample_split(Run &R, std::vector<Worker> &W, std::string &err) {
     }
     if (!stopped) rc = rc_evd_fit(W[0].ctx, row.data(), sampleN, &mu, &lambda) == 1 ? 1 : -1;
     const float mu32 = static_cast<float>(mu), lam32 = static_cast<float>(lambda);   // *parMu = mu, score.c:1051-1052
-    fits[i] = TrackFit{rc, mu32, lam32};
+    fits[i] = EvdFit{rc, mu32, lam32};
     for (int64_t k = j->offs[i]; k < j->offs[i + 1]; k++) j->hss[k].pvalue = rc == 1 ? rc_pvalue(j->hss[k].score, mu32, lam32) : 99.0f;   // RNAcode.c:180-188
   }
-  if (R.list.eps || R.list.details) annotate(R, batch[0], *j, err);
-  if (R.list.track && err.empty()) add_track(R, batch[0], *j, err, &fits);
-  if ((R.list.support || R.list.regions) && err.empty()) add_segments(R, batch[0], *j, err, &fits);
+  const bool ok = deliver(R, batch[0], std::move(j), err, &fits);
   for (rc_batch *b : batch) if (b) rc_batch_destroy(b);
-  if (!err.empty()) return false;
-  post(R, std::move(j));
-  return true;
+  return ok;
+}
+
+// input index -> kept block, -1 where --limit dropped it (the sidecar of --trees and --write-trees has one entry per block READ)
+std::vector<int> kept_at(const std::vector<Block> &blocks, int nRead) {
+  std::vector<int> at(nRead, -1);
+  for (size_t i = 0; i < blocks.size(); i++) at[blocks[i].index] = static_cast<int>(i);
+  return at;
 }
 
 }  // namespace
@@ -940,7 +932,7 @@ int main(int argc, char **argv) {
   rc_default_params(&R.par);
   rc_params &par = R.par;
   Listing &list = R.list;
-  std::string file, outfile, trees, limit, devicesArg, speciesFile, writeTrees, detailsFile, trackFile, supportFile, regionsFile, regionsOutFile;
+  std::string file, outfile, trees, limit, devicesArg, speciesFile, writeTrees, regionsFile;
   int device = 0, subBlocks = 0, gpus = 1;   // subBlocks 0: the library's schedule
   bool dumpBlocks = false;
   for (int a = 1; a < argc; a++) {
@@ -988,11 +980,11 @@ int main(int argc, char **argv) {
     else if (o == "-e" || o == "--eps") list.eps = true;
     else if (o == "-i" || o == "--eps-cutoff") list.epsCutoff = static_cast<float>(std::atof(val()));
     else if (o == "-d" || o == "--eps-dir") list.epsDir = val();
-    else if (o == "--details") detailsFile = val();
-    else if (o == "--track") trackFile = val();
-    else if (o == "--support") supportFile = val();
+    else if (o == "--details") list.side[kDetails].path = val();
+    else if (o == "--track") list.side[kTrack].path = val();
+    else if (o == "--support") list.side[kSupport].path = val();
     else if (o == "--regions") regionsFile = val();
-    else if (o == "--regions-out") regionsOutFile = val();
+    else if (o == "--regions-out") list.side[kRegions].path = val();
     else if (!o.empty() && o[0] == '-' && o != "-") { usage(); return 2; }
     else file = o;
   }
@@ -1001,7 +993,7 @@ int main(int argc, char **argv) {
     int32_t pep[64], matrix[400];
     if (rc_code_tables_for(&par, pep, matrix) != RC_OK) die("--genetic-code: " + std::string(rc_last_error()));
   }
-  if (regionsFile.empty() != regionsOutFile.empty()) die("--regions and --regions-out go together");   // before any context exists
+  if (!regionsFile.empty() != list.on(kRegions)) die("--regions and --regions-out go together");   // before any context exists
   if (!regionsFile.empty()) {
     std::ifstream in(regionsFile, std::ios::binary);
     if (!in) die("--regions: could not open " + regionsFile);
@@ -1065,7 +1057,7 @@ int main(int argc, char **argv) {
   const int nRead = static_cast<int>(blocks.size());
   for (int i = 0; i < nRead; i++) blocks[i].index = i;
   if (std::getenv("RC_CLI_TIMES")) std::fprintf(stderr, "[rnacode_hip] %d blocks read and parsed in %.3f s\n", nRead, now() - tRead);
-  if (list.eps || !detailsFile.empty())   // the plots (and the table) show the rows as main() leaves them: upper-cased (RNAcode.c:121-128; the library upper-cases its own copy)
+  if (list.eps || list.on(kDetails))   // the plots (and the table) show the rows as main() leaves them: upper-cased (RNAcode.c:121-128; the library upper-cases its own copy)
     for (Block &b : blocks) for (Row &r : b.rows) for (size_t x = 0; x < r.seq.size(); x++) { char &c = const_cast<char &>(r.seq[x]); c = static_cast<char>(std::toupper(static_cast<unsigned char>(c))); }
   if (!limit.empty()) {   // pruneAln (rnaz_utils.c:724-752, RNAcode.c:130-132): rows whose name starts with a listed string stay
     std::vector<std::string> keep;
@@ -1098,8 +1090,7 @@ int main(int argc, char **argv) {
   if (!trees.empty()) {   // one '<newick> TAB <kappa>' line per block of the input file, '-' for blocks without a tree
     std::ifstream in(trees);
     if (!in) die("Could not open " + trees);
-    std::vector<int> at(nRead, -1);   // input index -> kept block (--limit may have dropped some)
-    for (int i = 0; i < n; i++) at[blocks[i].index] = i;
+    const std::vector<int> at = kept_at(blocks, nRead);
     std::string line;
     int i = 0;
     while (std::getline(in, line)) {
@@ -1115,27 +1106,13 @@ int main(int argc, char **argv) {
   }
 
   if (!outfile.empty()) { list.out = std::fopen(outfile.c_str(), "w"); if (!list.out) die("Could not open " + outfile); }
-  if (!detailsFile.empty()) {
-    list.details = std::fopen(detailsFile.c_str(), "w");
-    if (!list.details) die("Could not open " + detailsFile);
-    std::fputs(rceps::details_header(), list.details);
+  for (SideFile &sf : list.side) {
+    if (sf.path.empty()) continue;
+    sf.f = std::fopen(sf.path.c_str(), "w");
+    if (!sf.f) die("Could not open " + sf.path);
+    std::fputs(sf.header(), sf.f);
   }
-  if (!trackFile.empty()) {
-    list.track = std::fopen(trackFile.c_str(), "w");
-    if (!list.track) die("Could not open " + trackFile);
-    std::fputs(rceps::track_header(), list.track);
-  }
-  if (!supportFile.empty()) {
-    list.support = std::fopen(supportFile.c_str(), "w");
-    if (!list.support) die("Could not open " + supportFile);
-    std::fputs(rceps::support_header(), list.support);
-  }
-  if (!regionsOutFile.empty()) {
-    list.regions = std::fopen(regionsOutFile.c_str(), "w");
-    if (!list.regions) die("Could not open " + regionsOutFile);
-    std::fputs(rceps::regions_header(), list.regions);
-  }
-  if ((list.eps || list.details) && rc_code_tables_for(&par, R.tables.pep, R.tables.matrix) != RC_OK) die(rc_last_error());
+  if ((list.eps || list.on(kDetails)) && rc_code_tables_for(&par, R.tables.pep, R.tables.matrix) != RC_OK) die(rc_last_error());
   tRead = now() - tRead;
   if (ctxThread.joinable()) ctxThread.join();
   for (int g = 0; g < gpus; g++) if (ctxRc[g] != RC_OK) die(ctxErr[g]);
@@ -1223,8 +1200,7 @@ int main(int argc, char **argv) {
   if (!writeTrees.empty()) {   // the sidecar --trees reads: one line per block READ, '-' for blocks without a tree
     FILE *f = std::fopen(writeTrees.c_str(), "w");
     if (!f) die("Could not open " + writeTrees);
-    std::vector<int> at(nRead, -1);
-    for (int i = 0; i < n; i++) at[blocks[i].index] = i;
+    const std::vector<int> at = kept_at(blocks, nRead);
     for (int i = 0; i < nRead; i++) {
       if (at[i] < 0 || blocks[at[i]].tree.empty()) std::fputs("-\n", f);
       else std::fprintf(f, "%s\t%.9g\n", blocks[at[i]].tree.c_str(), static_cast<double>(blocks[at[i]].kappa));   // %.9g: the float round-trips
@@ -1241,10 +1217,7 @@ int main(int argc, char **argv) {
   // context) takes longer than the operating system needs to reclaim the process, so a driver that is done leaves at once
   // (RC_CLI_TEARDOWN=1: the orderly way, for leak checkers).
   if (list.out != stdout) std::fclose(list.out);
-  if (list.details && std::fclose(list.details) != 0) die("Could not write " + detailsFile);
-  if (list.track && std::fclose(list.track) != 0) die("Could not write " + trackFile);
-  if (list.support && std::fclose(list.support) != 0) die("Could not write " + supportFile);
-  if (list.regions && std::fclose(list.regions) != 0) die("Could not write " + regionsOutFile);
+  for (SideFile &sf : list.side) if (sf.f && std::fclose(sf.f) != 0) die("Could not write " + sf.path);
   for (size_t r = 0; r < R.regions.size(); r++)   // what matched nothing: one line each, the exit status stays 0
     if (!R.regionMatched[r]) std::fputs(rceps::region_skipped(R.regions[r]).c_str(), stderr);
   std::fflush(stdout);

@@ -6,7 +6,7 @@ the reference's global `hitCounter` behaves."""
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import IO, List
+from typing import IO, List, Optional
 
 import numpy as np
 
@@ -51,13 +51,14 @@ def _arranged(hss: List[dict], best_region: bool) -> List[dict]:
     return res
 
 
-def listed_hss(hss: List[dict], cutoff: float = 1.0, best_only: bool = False, best_region: bool = False) -> List[dict]:
-    """The HSS print_results writes a line for, in its order (the loop of misc.c:444-547 without its output)."""
+def _selected(hss: List[dict], cutoff: float, best_only: bool, best_region: bool) -> Optional[List[dict]]:
+    """The HSS that get a line, in line order (the loop of misc.c:444-547 without its output).  None where the listing says "No significant
+    coding regions found." instead: no HSS, or the best p ABOVE the cutoff (a best p equal to the cutoff gets the header and no line)."""
     res = _arranged(hss, best_region)
     cutoff32 = float(np.float32(cutoff))
-    out: List[dict] = []
     if not res or float(np.float32(res[0]["pvalue"])) > cutoff32:
-        return out
+        return None
+    out: List[dict] = []
     for h in res:
         if not (float(np.float32(h["pvalue"])) < cutoff32):
             break
@@ -69,15 +70,19 @@ def listed_hss(hss: List[dict], cutoff: float = 1.0, best_only: bool = False, be
     return out
 
 
+def listed_hss(hss: List[dict], cutoff: float = 1.0, best_only: bool = False, best_region: bool = False) -> List[dict]:
+    """The HSS print_results writes a line for, in its order."""
+    return _selected(hss, cutoff, best_only, best_region) or []
+
+
 def print_results(out: IO[str], fmt: int, hss: List[dict], ref_name: str, state: ReportState, cutoff: float = 1.0,
                   best_only: bool = False, best_region: bool = False, eps=None, eps_cutoff: float = 0.05, listed=None) -> None:
     """hss: the block's HSS (dicts as returned by Batch.scoreAln, any order), p-values filled.
     eps: optional callback eps(hit_counter, hss_record), called for every listed HSS with p < eps_cutoff
     before its line is written -- where the reference draws hss-<counter>.eps (misc.c:461-474).
     listed: optional callback listed(hit_counter, hss_record), called for every HSS that gets a line (--details)."""
-    res = _arranged(hss, best_region)
-    cutoff32 = float(np.float32(cutoff))
-    if not res or float(np.float32(res[0]["pvalue"])) > cutoff32:
+    lines = _selected(hss, cutoff, best_only, best_region)
+    if lines is None:
         if fmt == 0:
             out.write("\nNo significant coding regions found.\n")
         return
@@ -85,12 +90,8 @@ def print_results(out: IO[str], fmt: int, hss: List[dict], ref_name: str, state:
         out.write("\n%6s%5s%7s%6s%6s%12s%12s%12s%9s%9s\n" % (" HSS # ", "Frame", "Length", "From", "To", "Name", "Start",
                                                            "End", "Score", "P"))
         out.write("======================================================================================\n")
-    for h in res:
+    for h in lines:
         p = float(np.float32(h["pvalue"]))
-        if not (p < cutoff32):
-            break
-        if h["hide"]:
-            continue
         if eps is not None and p < float(np.float32(eps_cutoff)):
             eps(state.hit_counter, h)
         if listed is not None:
@@ -115,9 +116,8 @@ def print_results(out: IO[str], fmt: int, hss: List[dict], ref_name: str, state:
                                                                      h["startSite"] + 1, h["endSite"] + 1, ref_name,
                                                                      h["startGenomic"], h["endGenomic"], h["score"]))
             out.write((_c_e(p, 3, 9, True) if p < 0.001 else _c_f(p, 3, 9, True)) + "\n")
-        if best_only:
-            break
-        state.hit_counter += 1
+        if not best_only:   # (one line at the most, and the counter stays)
+            state.hit_counter += 1
 
 
 def print_footer(out: IO[str], n_alignments: int, seconds: float, sampleN: int, Delta: float, Omega: float, omega: float,

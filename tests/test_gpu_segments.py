@@ -266,8 +266,8 @@ def write_inputs(tmp_path, name, samples):
     return [str(path), "--trees", str(side), "-n", str(samples), "--seed-base", str(doc["seed_base"])], doc
 
 
-def native(args):
-    r = subprocess.run([EXE, *args], capture_output=True, text=True, timeout=300)
+def native(args, **env):
+    r = subprocess.run([EXE, *args], capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
     assert r.returncode == 0, r.stderr
     return r
 
@@ -374,6 +374,62 @@ def test_sub_batches_and_contexts(tmp_path):
     assert {g[0] for g in got} == {"hss" + f[0] for f in listed}
     for f in listed:
         assert f[9] in {g[8] for g in got if g[0] == "hss" + f[0]}, f
+
+
+SIDE_OUTPUTS = ("eps", "details", "track", "support", "regions")
+
+
+def side_options(tmp_path, tag, which, regions):
+    """The options of the side outputs `which` and of the listing, every file named after `tag`."""
+    opts = {"eps": ["-e", "-d", str(tmp_path / f"{tag}.eps")], "details": ["--details", str(tmp_path / f"{tag}.details")],
+            "track": ["--track", str(tmp_path / f"{tag}.track")], "support": ["--support", str(tmp_path / f"{tag}.support")],
+            "regions": ["--regions", str(regions), "--regions-out", str(tmp_path / f"{tag}.regions")]}
+    return ["-o", str(tmp_path / f"{tag}.txt"), *[x for w in which for x in opts[w]]]
+
+
+def side_files(tmp_path, tag, which):
+    """What a run wrote: the listing and each side output of `which` (the plots as name -> bytes)."""
+    got = {w: (tmp_path / f"{tag}.{w}").read_bytes() for w in which if w != "eps"}
+    if "eps" in which:   # (the directory is made with the first plot)
+        got["eps"] = {p.name: p.read_bytes() for p in (tmp_path / f"{tag}.eps").glob("*")}
+    return dict(got, txt=(tmp_path / f"{tag}.txt").read_bytes())
+
+
+@pytest.mark.parametrize("flag", ["-r", "-b"], ids=["best_region", "best_only"])
+def test_every_side_output_at_once(tmp_path, flag, capsys):
+    """The side outputs hang off one list of lines per block: with all of them on, each file is the one a run with that option alone writes,
+    in both drivers, across sub-batches dealt to two contexts, and where two contexts split the sample range of a few blocks."""
+    from rnacode_amd import cli
+    from rnacode_amd.synth import to_maf
+    head, doc = write_inputs(tmp_path, "genomic_preprocessed_n100", 64)
+    head = [*head, flag, "-t"]
+    native([*head, "-o", str(tmp_path / "plain.txt")])
+    listed = listing_fields((tmp_path / "plain.txt").read_text())
+    assert len(listed) > 5
+    regions = tmp_path / "in.tsv"
+    regions.write_text(regions_from(listed) + "nobody\t+\t1\t9\n" + f"{listed[0][6]}\t+\t1\n")   # matching, non-matching, malformed
+    native([*head, *side_options(tmp_path, "nat", SIDE_OUTPUTS, regions)])
+    want = side_files(tmp_path, "nat", SIDE_OUTPUTS)
+    assert want["txt"] == (tmp_path / "plain.txt").read_bytes()
+    assert want["eps"] and all(len(want[w].splitlines()) > 1 for w in SIDE_OUTPUTS[1:])   # every output has something in it
+    assert cli.main([*head, *side_options(tmp_path, "py", SIDE_OUTPUTS, regions)]) == 0
+    capsys.readouterr()
+    assert side_files(tmp_path, "py", SIDE_OUTPUTS) == want
+    for w in SIDE_OUTPUTS:
+        native([*head, *side_options(tmp_path, w, [w], regions)])
+        assert side_files(tmp_path, w, [w]) == {w: want[w], "txt": want["txt"]}, w
+    native([*head, *side_options(tmp_path, "dealt", SIDE_OUTPUTS, regions), "--gpus", "2", "--devices", "0,0", "--sub-blocks", "7"])
+    assert side_files(tmp_path, "dealt", SIDE_OUTPUTS) == want
+    # the first two blocks only, with two wavefront groups of samples (at 64 samples there is one group, which two contexts cannot split)
+    blocks = [block_from_golden(e) for e in doc["blocks"][:2]]
+    (tmp_path / "two.maf").write_text(to_maf(blocks))
+    (tmp_path / "two.trees.tsv").write_text("".join(f"{e['ref']['tree']}\t{e['ref']['kappa']!r}\n" for e in doc["blocks"][:2]))
+    head = [str(tmp_path / "two.maf"), "--trees", str(tmp_path / "two.trees.tsv"), "-n", "128", "--seed-base", str(doc["seed_base"]), flag, "-t"]
+    native([*head, *side_options(tmp_path, "one2", SIDE_OUTPUTS, regions)])
+    r = native([*head, *side_options(tmp_path, "split2", SIDE_OUTPUTS, regions), "--gpus", "2", "--devices", "0,0"], RC_CLI_TIMES="1")
+    assert "sample ranges over the GPUs" in r.stderr
+    want = side_files(tmp_path, "one2", SIDE_OUTPUTS)
+    assert side_files(tmp_path, "split2", SIDE_OUTPUTS) == want and len(want["support"].splitlines()) > 1
 
 
 # ---------------------------------------------------------------------------------------------------------------- a hand-made block
