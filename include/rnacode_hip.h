@@ -323,6 +323,31 @@ int rc_batch_track(const rc_batch *b, const int32_t *blks, int32_t n_blks, float
 int rc_batch_segment_scores(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, float *score_out /* n_ranges */,
                             float *pair_out /* may be NULL */, int64_t cap, int64_t *offsets /* n_ranges + 1, may be NULL iff pair_out is NULL */);
 
+/* The null distribution of given segments: the test for a segment NAMED IN ADVANCE (a gene prediction, a Ribo-seq call, a smORF
+ * candidate), where rc_pvalue under the block's fit is the test of the block-wide maximum.  Ranges and their validity rules are
+ * rc_batch_segment_scores's, and score_out[r] has that call's bits.  For every range and every one of the sampleN null alignments of the
+ * batch's parameters -- sample s is the alignment whose maximum rc_batch_maxima reports at [s]: seed seed_base + s, the block's tree and
+ * gap pattern -- the call computes the score of exactly that segment, same codons, frame and strand:
+ *     null[r][s] = max(sum over k of P_k, Delta) / (N - 1)   in the simulated alignment,
+ * the cell S[a][j] the sampling kernels compute for that sample on their way to its maximum, bit for bit.  ge_out[r] is the number of
+ * samples with null[r][s] >= score_out[r] (binary32 compare: a NaN on either side does not count); if null_out is not NULL the values
+ * themselves come back at null_out[r * sampleN + s], and cap < n_ranges * sampleN is RC_ERR_ARG.  All sampleN samples are scored, always:
+ * whatever --stop-early cut from the run, and for a batch that a multi-context run gave a slice of the samples, the samples of that
+ * batch's own parameters.  A range without a step (opt_i < opt_b + 2) has the value fmaxf(0, Delta) / (N - 1) in every sample.
+ * The empirical p is the caller's: (ge + 1) / (sampleN + 1).  It is valid for a segment chosen WITHOUT looking at the scores; it is NOT
+ * valid for a listed HSS, which was selected as a maximum (that is what the fit and rc_pvalue are for).
+ * Errors as for rc_batch_segment_scores: every range is checked before the device is touched, on an error nothing is launched and the
+ * outputs are left alone, rc_last_error names the range.  n_ranges = 0 is RC_OK; a range may repeat.  Works on a batch rc_stream_next
+ * handed out until it is recycled, and leaves the batch's maxima, fit, HSS, timings and rc_batch_clamped as they are.
+ * Only the simulation phase of the null loop is repeated, for the WHOLE of every block that has a range (the run's simulation kernel is
+ * reused as it is), then one row of the recurrence per range and sequence instead of the O(L^2) matrix.  The distinct blocks go in
+ * rounds whose sigma codes fit a budget of device memory, 256 MB by default (RC_SEGNULL_MAX_BYTES overrides; a single block may exceed
+ * it; the result does not depend on it), one simulation and one scoring launch per round; beside the budget the call takes 28 bytes per
+ * range, and 4 bytes x sampleN per range when null_out is asked for.  If the context's MT19937 streams have been dropped or belong to
+ * another seed they are regenerated the way a run does. */
+int rc_batch_segment_null(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, float *score_out /* n_ranges */,
+                          int32_t *ge_out /* n_ranges */, float *null_out /* may be NULL: [n_ranges][sampleN] */, int64_t cap /* floats in null_out */);
+
 /* The substitution matrix and genetic code the scorer uses, for callers that render results
  * (getScoringMatrix() score.c:50-76 and transcode[4][4][4] code.c:28-39, which src/postscript.c:362,412
  * read): pep_out[16a+4b+c] = amino-acid index 0..19 of codon (a,b,c) in A,C,G,T order or -1 for a stop;

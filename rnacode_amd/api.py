@@ -171,6 +171,7 @@ def lib():
         l.rc_batch_backtrack_many.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         l.rc_batch_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         l.rc_batch_segment_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        l.rc_batch_segment_null.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
         l.rc_evd_fit.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         l.rc_mt_stream.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_int32]
         l.rc_pvalue.argtypes = [C.c_float, C.c_float, C.c_float]
@@ -204,7 +205,7 @@ EXPORTED_SYMBOLS = [
     "rc_batch_prep_timing", "rc_host_cpus", "rc_ctx_set_host_threads", "rc_ctx_host_threads", "rc_ctx_fit_exp_mode", "rc_stream_create_v2", "rc_stream_submit", "rc_stream_submit_bound",
     "rc_stream_next", "rc_stream_recycle", "rc_stream_pending", "rc_stream_plan", "rc_stream_destroy", "rc_set_stream_cache", "rc_batch_work", "rc_batch_timing", "rc_batch_null_kernel", "rc_batch_status",
     "rc_batch_models", "rc_batch_maxima", "rc_batch_maxima_all", "rc_batch_fit", "rc_batch_fit_all", "rc_batch_hss", "rc_batch_hss_all", "rc_batch_clamped",
-    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_batch_segment_scores", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
+    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_batch_segment_scores", "rc_batch_segment_null", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
     "rc_code_tables_for", "rc_genetic_code", "rc_species_tree_create", "rc_species_tree_destroy", "rc_species_tree_tips", "rc_species_tree_prune",
     "rc_fit_species_trees", "rc_fit_species_trees_device",
 ]
@@ -703,6 +704,20 @@ class Batch:
         _check(lib().rc_batch_segment_scores(self._h, arr.ctypes.data, n, scores.ctypes.data, vals.ctypes.data, total, offs.ctypes.data))
         o = offs.tolist()
         return scores, [vals[o[r]:o[r + 1]] for r in range(n)]
+
+    def segment_null(self, ranges, matrix: bool = False) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """rc_batch_segment_null: (scores, ge, null) of all `ranges` -- tuples as segment_scores takes, scores with that call's bits.
+        null[r][s] (matrix, else None) is the score of exactly that segment in the batch's null alignment s, float32 [n][sampleN];
+        ge[r] the number of samples with null[r][s] >= scores[r], int32.  segments.empirical_p(ge, sampleN) is the p of a segment
+        named in advance -- not of a listed HSS, which was selected as a maximum."""
+        arr = np.ascontiguousarray(np.asarray(list(ranges), dtype=np.int32).reshape(-1, 4))
+        n, sample_n = arr.shape[0], int(self.params.sampleN)
+        scores = np.zeros(n, dtype=np.float32)
+        ge = np.zeros(n, dtype=np.int32)
+        null = np.zeros((n, sample_n), dtype=np.float32) if matrix else None
+        _check(lib().rc_batch_segment_null(self._h, arr.ctypes.data, n, scores.ctypes.data, ge.ctypes.data,
+                                           null.ctypes.data if matrix else None, n * sample_n if matrix else 0))
+        return scores, ge, null
 
     def results(self, blk: int, with_maxima: bool = False) -> BlockScores:
         st = self.status(blk)

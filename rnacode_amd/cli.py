@@ -4,7 +4,7 @@ Mirrors the reference's command line (src/cmdline.ggo:6-20, src/RNAcode.c:236-37
 options that concern the scoring path and the listings:
 
     python -m rnacode_amd.cli [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S]
-                              [-e [-i CUTOFF] [-d DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE]
+                              [-e [-i CUTOFF] [-d DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null]]
                               [-o OUT] [--trees SIDECAR | --species-tree NEWICK
                               [--species-tree-fit fixed|scale|branches]] [--write-trees SIDECAR] [FILE]
 
@@ -22,7 +22,9 @@ line per listed HSS and aligned sequence (details.py); plots and table of a sub-
 --support FILE (not in the reference) writes, per listed HSS and aligned sequence, the sequence's pair score against the reference row, its
 share of the segment's score and the score without it; --regions FILE with --regions-out FILE scores the segments the file lists (name,
 strand and the listing's Start / End) in every scored block that contains them, whether or not the listing shows them (segments.py; the
-ranges of a sub-batch go in one rc_batch_segment_scores call).
+ranges of a sub-batch go in one rc_batch_segment_scores call); with --regions-null its lines end in null_ge and p_segment, the test for a
+segment named in advance: how many of the -n null alignments score at least as high on exactly that segment (one rc_batch_segment_null call
+per sub-batch), and (null_ge + 1) / (n + 1).
 Quirk kept from the reference: the 4th value of --pars goes to stopPenalty_0 (RNAcode.c:318)."""
 from __future__ import annotations
 
@@ -133,6 +135,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "reference sequence and start / end as the -t listing prints them")
     ap.add_argument("--regions-out", metavar="FILE",
                     help="where the scores of the --regions segments go: one line per region and scored block that contains it")
+    ap.add_argument("--regions-null", action="store_true",
+                    help="with --regions: two more columns in --regions-out, null_ge = how many of the -n null alignments score at least as "
+                         "high on exactly that segment, and p_segment = (null_ge + 1) / (n + 1), the test for a segment named in advance "
+                         "(p is the block-wide test)")
     return ap
 
 
@@ -159,6 +165,8 @@ def _intake(a):
     regions = species = None
     if bool(a.regions) != bool(a.regions_out):
         raise _Refused("--regions and --regions-out go together")
+    if a.regions_null and not a.regions:
+        raise _Refused("--regions-null needs --regions")
     if a.regions:
         try:
             with open(a.regions) as fh:
@@ -269,7 +277,7 @@ def _list_batch(run: _Run, batch, base: int) -> None:
     # --eps / --details: the backtracked paths with ONE call (rc_batch_backtrack_many) -- the segments themselves for the table; for the
     # plots (p below the plot cutoff) the segment and its two extensions.  --support / --regions: the scores and pair scores of every listed
     # HSS, and of every region a block contains, with ONE call (rc_batch_segment_scores)
-    bt, seg, found = _Ranges(), _Ranges(), {}
+    bt, seg, nul, found = _Ranges(), _Ranges(), _Ranges(), {}
     for i in scored:
         b = run.blocks[base + i]
         for h in listed[i]:
@@ -284,11 +292,14 @@ def _list_batch(run: _Run, batch, base: int) -> None:
             for reg in run.regions_of.get(b.rows[0].name, ()):
                 at = segments.locate(reg.strand, reg.start, reg.end, b.rows[0].start, b.rows[0].length, b.ref_len)
                 if isinstance(at, tuple):
-                    found.setdefault(i, []).append((reg, at, seg.add(i, reg.strand, *segments.range_of(*at))))
+                    lo, hi = segments.range_of(*at)
+                    found.setdefault(i, []).append((reg, at, seg.add(i, reg.strand, lo, hi), nul.add(i, reg.strand, lo, hi) if a.regions_null else -1))
     paths = batch.backtrack_many(bt.ranges) if bt.ranges else []
     # --track: the tracks of the blocks the listing covers with ONE call (rc_batch_track)
     tracked = dict(zip(scored, batch.track(scored))) if "track" in side and scored else {}
     seg_scores, seg_pairs = batch.segment_scores(seg.ranges) if seg.ranges else (None, None)
+    # --regions-null: the regions' ranges (not the listed HSS, which were selected as maxima) with ONE call (rc_batch_segment_null)
+    null_ge = batch.segment_null(nul.ranges)[1] if nul.ranges else None
     for i in range(batch.n):
         b = run.blocks[base + i]
         if base + i in run.refused:   # the species tree does not cover the block's rows
@@ -306,9 +317,10 @@ def _list_batch(run: _Run, batch, base: int) -> None:
             rc, mu, lam = batch.getExtremeValuePars(i)
             if i in tracked:
                 side["track"].writelines(track.block_lines(b.rows[0].name, b.rows[0].start, b.rows[0].length, tracked[i], rc, mu, lam, a.cutoff))
-            for reg, (frame, c1, c2), r in found.get(i, ()):
+            for reg, (frame, c1, c2), r, rn in found.get(i, ()):
                 p = api.pvalue(float(seg_scores[r]), mu, lam) if rc == 1 else 99.0
-                side["regions_out"].write(segments.region_line(reg, frame, c1, c2, seg_scores[r], p, seg_pairs[r]))
+                side["regions_out"].write(segments.region_line(reg, frame, c1, c2, seg_scores[r], p, seg_pairs[r],
+                                                               (null_ge[rn], run.params.sampleN) if rn >= 0 else None))
                 reg.matched = True
 
 
@@ -356,7 +368,7 @@ def main(argv=None) -> int:
         for name, header in SIDE_FILES:
             if getattr(a, name):
                 side[name] = files.enter_context(open(getattr(a, name), "w"))
-                side[name].write(header())
+                side[name].write(header(null=True) if name == "regions_out" and a.regions_null else header())
         code = params.genetic_code.decode()
         run = _Run(a, params, code, api.code_tables(a.blosum, code) if a.details else None, blocks, read_index, refused,
                    segments.by_name(regions) if regions is not None else {}, out, fmt, side)

@@ -217,7 +217,7 @@ extern "C" void rc_set_stream_cache(int enabled) { g_no_stream_cache = !enabled;
 
 // U[draw][sample] for seeds seed .. seed + Spad - 1, at least D draws; generated on `st`, other streams order
 // themselves behind U_ready
-static int ensure_mt_stream(rc_ctx *c, rc_batch *b, hipStream_t st, uint32_t seed, int Spad, int D) {
+int ensure_mt_stream(rc_ctx *c, rc_batch *b, hipStream_t st, uint32_t seed, int Spad, int D) {
   b->mtLaunched = false;
   if (c->U_valid && c->U_seed == seed && c->U_Spad == Spad && c->U_D >= D) {
     if (c->U_ready.e) HIP_TRY(hipStreamWaitEvent(st, c->U_ready, 0));

@@ -34,6 +34,8 @@
 // file lists (name, strand, the listing's Start / End) in every scored block that contains them; a region that matches nothing gets a line on
 // stderr at the end of the run.  The ranges of a sub-batch go in ONE rc_batch_segment_scores call (rc_eps.h, support_tail / region_line; the
 // same bytes as python -m rnacode_amd.cli, whose segments.py documents the rules).  With --gpus N the one writer emits both in input order.
+// --regions-null (with --regions): every --regions-out line ends in null_ge and p_segment = (null_ge + 1) / (n + 1), the test for a segment named
+// in advance -- the regions' ranges of a sub-batch in ONE rc_batch_segment_null call (in the sample split one per slice, the counts added).
 //
 // Quirk kept from the reference: the 4th value of --pars goes to stopPenalty_0 (RNAcode.c:318).
 #include <algorithm>
@@ -399,7 +401,7 @@ struct Listing {
 
 void usage() {
   std::fprintf(stderr, "usage: rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]\n"
-                       "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE]\n"
+                       "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null]]\n"
                        "                   [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]\n"
                        "                   [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]\n"
                        "                   [--write-trees SIDECAR] [--dump-blocks] [FILE]\n"
@@ -419,7 +421,10 @@ void usage() {
                        "                             against the reference, its share of the segment's score, the score without that sequence\n"
                        "  --regions FILE             score given segments: tab-separated lines 'name strand start end [id]', name a block's reference\n"
                        "                             sequence, start / end as the -t listing prints them; needs\n"
-                       "  --regions-out FILE         one line per region and scored block that contains it: score, p, supporting sequences\n");
+                       "  --regions-out FILE         one line per region and scored block that contains it: score, p, supporting sequences\n"
+                       "  --regions-null             with --regions: two more columns, null_ge = how many of the -n null alignments score at least as\n"
+                       "                             high on exactly that segment, p_segment = (null_ge + 1) / (n + 1): the test for a segment\n"
+                       "                             named in advance (p is the block-wide test)\n");
 }
 
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -458,6 +463,7 @@ struct Run {
   std::vector<rceps::Region> regions;                     // --regions, in file order
   std::map<std::string, std::vector<int>> regionsOf;      // reference row name -> the regions that can match a block, in file order
   std::vector<char> regionMatched;                        // set by the writer
+  bool regionsNull = false;                               // --regions-null: null_ge and p_segment behind every --regions-out line
   // the writer: one thread, jobs in input order
   std::mutex jm;
   std::condition_variable jcv;
@@ -627,7 +633,9 @@ bool add_track(const Run &R, rc_batch *b, Job &j, std::string &err, const std::v
 
 // --support / --regions for every block the listing covers, while the batch is alive: the scores and pair scores of all listed HSS, and of
 // every region a block contains, with ONE call (rc_batch_segment_scores), then their lines (rc_eps.h, support_tail / region_line).
-bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std::vector<EvdFit> *fits) {
+// --regions-null: the regions' ranges -- not the listed HSS, which were selected as maxima -- in ONE rc_batch_segment_null call more; where
+// the samples were split over several batches (slices: each holds a slice of the samples of every block), one call per batch, the counts added.
+bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std::vector<EvdFit> *fits, const std::vector<rc_batch *> *slices) {
   const int m = static_cast<int>(j.blocks.size());
   struct Listed { int blk; Line *line; int range; };
   struct Found { int blk, region; rceps::SegLoc at; int range; };
@@ -677,11 +685,28 @@ bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std
       l.line->support.push_back(rceps::support_tail(std::string(blk.rows[0].name), std::string(blk.rows[k].name), k, static_cast<char>(h.strand), h.frame, h.startGenomic,
                                                     h.endGenomic, h.score, h.pvalue, p[k - 1], static_cast<float>(nk), loo[k - 1]));
   }
-  for (const Found &f : found) {
+  std::vector<int32_t> nullGe;   // per found region
+  if (R.regionsNull && !found.empty()) {
+    std::vector<rc_bt_range> regs;
+    for (const Found &f : found) regs.push_back(ranges[f.range]);
+    const int nf = static_cast<int>(regs.size());
+    std::vector<float> sc(nf);
+    std::vector<int32_t> ge(nf);
+    nullGe.assign(nf, 0);
+    const std::vector<rc_batch *> one{b};
+    for (rc_batch *sb : slices ? *slices : one) {
+      if (!sb) continue;
+      if (rc_batch_segment_null(sb, regs.data(), nf, sc.data(), ge.data(), nullptr, 0) != RC_OK) { err = rc_last_error(); return false; }
+      for (int k = 0; k < nf; k++) nullGe[k] += ge[k];
+    }
+  }
+  for (size_t k = 0; k < found.size(); k++) {
+    const Found &f = found[k];
     EvdFit fit;
     if (!fit_of(b, fits, f.blk, fit, err)) return false;
     const float p = fit.rc == 1 ? rc_pvalue(scores[f.range], fit.mu, fit.lambda) : 99.0f;
-    j.blocks[f.blk].regions += rceps::region_line(R.regions[f.region], f.at, scores[f.range], p, pairs.data() + offs[f.range], static_cast<int>(offs[f.range + 1] - offs[f.range]));
+    j.blocks[f.blk].regions += rceps::region_line(R.regions[f.region], f.at, scores[f.range], p, pairs.data() + offs[f.range], static_cast<int>(offs[f.range + 1] - offs[f.range]),
+                                                  R.regionsNull ? nullGe[k] : -1, R.par.sampleN);
     j.matched.push_back(f.region);
   }
   return true;
@@ -708,13 +733,14 @@ std::unique_ptr<Job> fetch(rc_batch *b, int seq, const int *blockIdx, std::strin
 
 // Step 2, while the batch is alive: each block's listing arranged -- here and nowhere else --, what goes out beside it made, the job handed
 // to the writer.  fits: as for fit_of; the caller that passes them has filled in the p-values of j->hss as well.
-bool deliver(Run &R, rc_batch *b, std::unique_ptr<Job> j, std::string &err, const std::vector<EvdFit> *fits = nullptr) {
+bool deliver(Run &R, rc_batch *b, std::unique_ptr<Job> j, std::string &err, const std::vector<EvdFit> *fits = nullptr,
+             const std::vector<rc_batch *> *slices = nullptr) {
   for (size_t i = 0; i < j->blocks.size(); i++)
     if (scored(R, j->blocks[i]))
       j->blocks[i].lines = R.list.arrange(std::vector<rc_hss>(j->hss.begin() + j->offs[i], j->hss.begin() + j->offs[i + 1]), j->blocks[i].none);
   if ((R.list.eps || R.list.on(kDetails)) && !annotate(R, b, *j, err)) return false;
   if (R.list.on(kTrack) && !add_track(R, b, *j, err, fits)) return false;
-  if ((R.list.on(kSupport) || R.list.on(kRegions)) && !add_segments(R, b, *j, err, fits)) return false;
+  if ((R.list.on(kSupport) || R.list.on(kRegions)) && !add_segments(R, b, *j, err, fits, slices)) return false;
   post(R, std::move(j));
   return true;
 }
@@ -913,7 +939,7 @@ bool run_sample_split(Run &R, std::vector<Worker> &W, std::string &err) {
     fits[i] = EvdFit{rc, mu32, lam32};
     for (int64_t k = j->offs[i]; k < j->offs[i + 1]; k++) j->hss[k].pvalue = rc == 1 ? rc_pvalue(j->hss[k].score, mu32, lam32) : 99.0f;   // RNAcode.c:180-188
   }
-  const bool ok = deliver(R, batch[0], std::move(j), err, &fits);
+  const bool ok = deliver(R, batch[0], std::move(j), err, &fits, &batch);
   for (rc_batch *b : batch) if (b) rc_batch_destroy(b);
   return ok;
 }
@@ -985,6 +1011,7 @@ int main(int argc, char **argv) {
     else if (o == "--support") list.side[kSupport].path = val();
     else if (o == "--regions") regionsFile = val();
     else if (o == "--regions-out") list.side[kRegions].path = val();
+    else if (o == "--regions-null") R.regionsNull = true;
     else if (!o.empty() && o[0] == '-' && o != "-") { usage(); return 2; }
     else file = o;
   }
@@ -994,6 +1021,8 @@ int main(int argc, char **argv) {
     if (rc_code_tables_for(&par, pep, matrix) != RC_OK) die("--genetic-code: " + std::string(rc_last_error()));
   }
   if (!regionsFile.empty() != list.on(kRegions)) die("--regions and --regions-out go together");   // before any context exists
+  if (R.regionsNull && regionsFile.empty()) die("--regions-null needs --regions");
+  if (R.regionsNull) list.side[kRegions].header = rceps::regions_header_null;
   if (!regionsFile.empty()) {
     std::ifstream in(regionsFile, std::ios::binary);
     if (!in) die("--regions: could not open " + regionsFile);

@@ -415,6 +415,7 @@ inline std::vector<float> leave_one_out(const float *pairs, int nk, float Delta)
 }
 inline const char *support_header() { return "hss\tname\tstrand\tframe\tstart\tend\tscore\tp\trow\trow_name\tpair_score\tshare\tloo_score\n"; }
 inline const char *regions_header() { return "id\tname\tstrand\tframe\tfrom\tto\tstart\tend\tscore\tp\tsupport\trows\n"; }
+inline const char *regions_header_null() { return "id\tname\tstrand\tframe\tfrom\tto\tstart\tend\tscore\tp\tsupport\trows\tnull_ge\tp_segment\n"; }   // --regions-null
 // --support: the columns of row k's line behind the HSS counter (details_tail's head, then the row's pair score, its share and the score without it)
 inline std::string support_tail(const std::string &refName, const std::string &rowName, int k, char strand, int frame, int startGenomic, int endGenomic,
                                 float score, float pvalue, float pair, float nkf, float loo) {
@@ -425,14 +426,20 @@ inline std::string support_tail(const std::string &refName, const std::string &r
   out += "\t" + fmt3(pair) + "\t" + fmt3(share) + "\t" + fmt3(loo) + "\n";
   return out;
 }
-inline std::string region_line(const Region &r, const SegLoc &at, float score, float p, const float *pairs, int nk) {
+// ge >= 0 (--regions-null): two more columns, how many of the n null alignments reach the score on exactly this segment, and (ge + 1) / (n + 1)
+inline std::string region_line(const Region &r, const SegLoc &at, float score, float p, const float *pairs, int nk, int ge = -1, int n = 0) {
   int support = 0;
   for (int k = 0; k < nk; k++) support += pairs[k] > 0.0f;
   std::string out;
   char pe[64];
   if (p != p) std::snprintf(pe, sizeof pe, "nan"); else std::snprintf(pe, sizeof pe, "%.3e", static_cast<double>(p));
-  put(out, "%s\t%s\t%c\t%i\t%i\t%i\t%lld\t%lld\t%s\t%s\t%i\t%i\n", r.id.c_str(), r.name.c_str(), r.strand, at.frame + 1, at.c1 + 1, at.c2 + 1, r.start, r.end,
+  put(out, "%s\t%s\t%c\t%i\t%i\t%i\t%lld\t%lld\t%s\t%s\t%i\t%i", r.id.c_str(), r.name.c_str(), r.strand, at.frame + 1, at.c1 + 1, at.c2 + 1, r.start, r.end,
       fmt3(score).c_str(), pe, support, nk);
+  if (ge >= 0) {
+    if (score != score) put(out, "\t%i\tnan", ge);
+    else put(out, "\t%i\t%.3e", ge, (ge + 1.0) / (n + 1.0));
+  }
+  out += "\n";
   return out;
 }
 

@@ -264,6 +264,26 @@ struct SegArgs {
   float *scores;              // [nRanges]
 };
 void launch_segment_scores(const SegArgs &a, hipStream_t stream);   // both kernels, in that order
+// rc_batch_segment_null (rc_segment_null.hip): the ranges' values in every null sample.  One launch covers a round of distinct blocks whose
+// codes k_generic_sim<false> has left at codesAll (item = position in `blocks` x groups + sample group, codesStride bytes each); position p's
+// ranges are rangeIdx[blkStart[p] .. blkStart[p + 1]) -- indices into `ranges`, `scores`, `ge` and the rows of nullOut, in call order.
+struct SegNullArgs {
+  const uint8_t *blob;
+  const DevBlock *dblocks;
+  const uint32_t *flags;      // per batch index: kFlagNan picks the reference's MAX macro
+  const int *blocks;          // [nBlocks] batch indices of the round
+  const int *blkStart;        // [nBlocks + 1]
+  const int *rangeIdx;
+  const SegRange *ranges;     // every range of the call
+  const float *scores;        // [nRanges] the native scores (k_segment_fold's)
+  int *ge;                    // [nRanges] += samples whose value is >= scores[r]
+  float *nullOut;             // [nRanges][sampleN], or null
+  const uint8_t *codesAll;
+  size_t codesStride;
+  int nBlocks, groups, sampleN;
+};
+constexpr int seg_null_code_words(int L) { return ((L / 3 + 31) >> 2) + 1; }   // GenericLayout::nW (rc_null_generic.h): code words per (strand x frame, row)
+void launch_segment_null(const SegNullArgs &a, hipStream_t stream);   // nBlocks x groups workgroups of one wavefront
 // wider blocks (N > 64): generic kernels with their states in a global scratch (rc_null_generic.h)
 size_t null_generic_lds_bytes(int N, int nnodes);   // packed node states + codon windows of the widest block of the launch
 // the same in two launches (simulation with many light wavefronts, then the DP): bytes of an item's codes / of a DP workgroup's states

@@ -1,5 +1,6 @@
-// rc_results.cpp -- what a finished batch holds: statuses, models, maxima, fits, HSS tables, native S matrices, backtrack paths, per-codon tracks, segment scores.
+// rc_results.cpp -- what a finished batch holds: statuses, models, maxima, fits, HSS tables, native S matrices, backtrack paths, per-codon tracks, segment scores and their null distributions.
 #include "rc_runtime.h"
+#include "rc_segnull_plan.h"
 
 extern "C" {
 
@@ -539,6 +540,113 @@ int rc_batch_segment_scores(const rc_batch *b, const rc_bt_range *ranges, int32_
   }();
   if (rc != RC_OK && launched) (void)hipStreamSynchronize(st);
   return rc;
+}
+
+// The null distribution of many ranges (rc_segment_null.hip): the value of exactly that range in each of the batch's sampleN null alignments,
+// and how many of them reach the range's native score.  The native scores come from rc_batch_segment_scores (its checks are this call's);
+// the ranges are grouped by block, the distinct blocks walked in rounds whose sigma codes fit a budget: per round k_generic_sim<false> -- the
+// run's own simulation, whatever kernels the run took for the block -- writes the codes of every (block, sample group) item, k_segment_null
+// reads them.  Nothing of the batch is written: the simulation gets a scratch word for its clamp count, work counters and a block list of
+// this call's own, and no maxima.
+int rc_batch_segment_null(const rc_batch *bc, const rc_bt_range *ranges, int32_t n_ranges, float *score_out, int32_t *ge_out, float *null_out,
+                          int64_t cap) {
+  rc_batch *b = const_cast<rc_batch *>(bc);
+  if (!b || n_ranges < 0 || (n_ranges > 0 && (!ranges || !score_out || !ge_out))) return fail(RC_ERR_ARG, "bad argument");
+  if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
+  const int sampleN = b->par.sampleN, groups = (sampleN + kWave - 1) / kWave, Spad = groups * kWave;
+  if (null_out && cap < static_cast<int64_t>(n_ranges) * sampleN)
+    return fail(RC_ERR_ARG, "null_out too small: " + std::to_string(static_cast<int64_t>(n_ranges) * sampleN) + " values");
+  // every range is checked there before the device is touched; the scores wait here until the whole call has succeeded
+  std::vector<float> scores(static_cast<size_t>(n_ranges));
+  RC_TRY(rc_batch_segment_scores(b, ranges, n_ranges, scores.data(), nullptr, 0, nullptr));
+  if (n_ranges == 0) return RC_OK;
+  rc_ctx *c = b->ctx;
+  size_t budget = kSegNullMaxBytes;
+  if (const char *e = std::getenv("RC_SEGNULL_MAX_BYTES")) budget = static_cast<size_t>(std::max(1ll, std::atoll(e)));
+  const auto codes_bytes = [&](int blk) { return null_generic_codes_bytes(b->meta[blk].N, b->meta[blk].L, b->db[blk].nnodes); };
+  const SegNullPlan pl = seg_null_plan(n_ranges, [&](int r) { return ranges[r].blk; }, codes_bytes, groups, budget);
+  size_t maxItems = 0, codesNeed = 0;
+  for (const SegNullRound &rd : pl.rounds) {
+    maxItems = std::max(maxItems, static_cast<size_t>(rd.count) * groups);
+    codesNeed = std::max(codesNeed, static_cast<size_t>(rd.count) * groups * rd.stride);
+  }
+  if (maxItems > static_cast<size_t>(INT32_MAX)) return fail(RC_ERR_ARG, "more than 2^31 - 1 (block, sample group) items in one round");
+  for (int blk : pl.blocks)   // k_segment_null finds a sequence's code words by GenericLayout's rule: the two must agree
+    if (codes_bytes(blk) != al256(static_cast<size_t>(6) * b->meta[blk].NK * seg_null_code_words(b->meta[blk].L) * kWave * sizeof(uint32_t)))
+      return fail(RC_ERR_UNSUPPORTED, "internal: the layout of the sigma codes has changed");
+  // one upload: the distinct blocks, the CSR, the ranges, the native scores
+  const size_t nb = pl.blocks.size(), nr = static_cast<size_t>(n_ranges);
+  const size_t oStart = nb, oIdx = oStart + nb + 1, oRanges = oIdx + nr, oScores = oRanges + 4 * nr, upWords = oScores + nr;
+  std::vector<int32_t> up(upWords);
+  std::memcpy(up.data(), pl.blocks.data(), nb * sizeof(int32_t));
+  std::memcpy(up.data() + oStart, pl.blkStart.data(), (nb + 1) * sizeof(int32_t));
+  std::memcpy(up.data() + oIdx, pl.rangeIdx.data(), nr * sizeof(int32_t));
+  std::memcpy(up.data() + oRanges, ranges, nr * sizeof(rc_bt_range));
+  std::memcpy(up.data() + oScores, scores.data(), nr * sizeof(float));
+  std::vector<int32_t> ge(nr);
+  HIP_TRY(hipSetDevice(c->device));
+  RC_STREAM_TRY(st, stream_aux(c));
+  HIP_TRY(hipEventSynchronize(b->evPrep));   // the tables of the blob are made on the device
+  DevBuf d_up, d_ge, d_cnt, d_codes, d_null;
+  for (DevBuf *d : {&d_up, &d_ge, &d_cnt, &d_codes, &d_null}) { d->retired = c->retired.get(); d->pool = c->bufPool.get(); }
+  const uint8_t *blob = b->dblob.as<uint8_t>();
+  constexpr size_t kCntWords = 16;   // the simulation's eight work queues, then (8-aligned) its clamp count: this call's own, read by nobody
+  bool launched = false;
+  // (a lambda: whatever fails in it, nothing returns to the caller -- who owns the outputs, while `up`, `ge` and the buffers die with this
+  // frame -- before the work already queued on the stream has drained)
+  const int rc = [&]() -> int {
+    HIP_TRY(d_up.ensure(up.size() * sizeof(int32_t)));
+    HIP_TRY(d_ge.ensure(nr * sizeof(int32_t)));
+    HIP_TRY(d_cnt.ensure(kCntWords * sizeof(uint32_t)));
+    HIP_TRY(d_codes.ensure(codesNeed));
+    if (null_out) HIP_TRY(d_null.ensure(nr * static_cast<size_t>(sampleN) * sizeof(float)));
+    launched = true;   // from here on something may be in flight
+    // the MT19937 streams of the batch's seeds: the context's cache, or regenerated as a run does (the batch's own record of it stays)
+    const bool mtLaunched = b->mtLaunched;
+    const int mt = ensure_mt_stream(c, b, st, b->par.seed_base, Spad, b->maxDraws);
+    b->mtLaunched = mtLaunched;
+    RC_TRY(mt);
+    HIP_TRY(hipMemcpyAsync(d_up.p, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_ge.p, 0, nr * sizeof(int32_t), st));
+    NullArgs sim{};
+    sim.blob = blob; sim.dblocks = reinterpret_cast<const DevBlock *>(blob + b->oDblocks); sim.flags = b->dflags.as<uint32_t>();
+    sim.gLo = 0; sim.gHi = groups; sim.sampleN = sampleN; sim.Spad = Spad;   // every sample, whatever --stop-early cut from the run (skipMask 0)
+    sim.U = c->d_U; sim.pair = b->tables->ptrs.pair; sim.tieThr = c->tieThr;
+    sim.workCounter = d_cnt.as<unsigned int>(); sim.clampCount = reinterpret_cast<unsigned long long *>(d_cnt.as<uint32_t>() + 8);
+    sim.codesAll = d_codes.as<uint8_t>();
+    SegNullArgs sn{};
+    sn.blob = blob; sn.dblocks = sim.dblocks; sn.flags = sim.flags;
+    sn.rangeIdx = d_up.as<int>() + oIdx; sn.ranges = reinterpret_cast<const SegRange *>(d_up.as<int>() + oRanges);
+    sn.scores = reinterpret_cast<const float *>(d_up.as<int>() + oScores);
+    sn.ge = d_ge.as<int>(); sn.nullOut = null_out ? d_null.as<float>() : nullptr;
+    sn.codesAll = d_codes.as<uint8_t>(); sn.groups = groups; sn.sampleN = sampleN;
+    for (const SegNullRound &rd : pl.rounds) {
+      int maxN = 0, maxNodes = 0;
+      for (int p = rd.first; p < rd.first + rd.count; p++) {
+        maxN = std::max(maxN, b->meta[pl.blocks[p]].N); maxNodes = std::max(maxNodes, b->db[pl.blocks[p]].nnodes);
+      }
+      const size_t lds = null_generic_lds_bytes(maxN, maxNodes);
+      const auto key = std::make_tuple(NullKind::GenericSim, 0, lds);
+      const auto it = c->occ.find(key);
+      const int occ = std::max(1, it != c->occ.end() ? it->second : (c->occ[key] = generic_occupancy(NullKind::GenericSim, lds)));
+      const long long items = static_cast<long long>(rd.count) * groups;
+      HIP_TRY(hipMemsetAsync(d_cnt.p, 0, kCntWords * sizeof(uint32_t), st));   // (behind the round before: one stream)
+      sim.classBlocks = d_up.as<int>() + rd.first; sim.nClassBlocks = rd.count; sim.codesStride = rd.stride;
+      launch_generic(NullKind::GenericSim, sim, static_cast<int>(std::min<long long>(items, static_cast<long long>(c->numCU) * occ)), lds, d_codes.as<uint8_t>(), st);
+      HIP_TRY(hipGetLastError());
+      sn.blocks = sim.classBlocks; sn.blkStart = d_up.as<int>() + oStart + rd.first; sn.nBlocks = rd.count; sn.codesStride = rd.stride;
+      launch_segment_null(sn, st);
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(ge.data(), d_ge.p, nr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (null_out) HIP_TRY(hipMemcpyAsync(null_out, d_null.p, nr * static_cast<size_t>(sampleN) * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // (the streams are non-blocking: nothing else would wait for the copies)
+    return RC_OK;
+  }();
+  if (rc != RC_OK) { if (launched) (void)hipStreamSynchronize(st); return rc; }
+  std::memcpy(score_out, scores.data(), nr * sizeof(float));
+  std::memcpy(ge_out, ge.data(), nr * sizeof(int32_t));
+  return RC_OK;
 }
 
 int rc_code_tables(int32_t blosum, int32_t pep_out[64], int32_t matrix_out[400]) {

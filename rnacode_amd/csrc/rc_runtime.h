@@ -307,6 +307,8 @@ inline size_t al256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 // rc_batch_backtrack_many: device bytes (item descriptors + one byte per sequence and codon step) one launch may take; a call with more
 // walks its ranges in several launches (RC_BT_MAX_BYTES overrides: tests reach the split with it).  A range is never cut.
 constexpr size_t kBtMaxBytes = static_cast<size_t>(256) << 20;
+// rc_batch_segment_null: bytes of sigma codes one round of distinct blocks may take (RC_SEGNULL_MAX_BYTES overrides); a block is never cut
+constexpr size_t kSegNullMaxBytes = static_cast<size_t>(256) << 20;
 
 
 struct TableSet;
@@ -523,6 +525,8 @@ int batch_run_async(rc_batch *b, bool streaming = false);
 int batch_wait(rc_batch *b);
 void trace_device(rc_batch *b);
 extern bool g_no_stream_cache;
+// the context's MT19937 streams U[draw][Spad] for seeds seed .. seed + Spad - 1, at least D draws: the cached ones, or generated on `st`
+int ensure_mt_stream(rc_ctx *c, rc_batch *b, hipStream_t st, uint32_t seed, int Spad, int D);
 size_t native_grid(const rc_ctx *c, size_t items, int smax, int mode = 0);                        // rc_schedule.cpp
 bool fat_class(const rc_batch *b, const rc_ctx *c, int NK, int maxL);
 int launch_native_block(const RunEnv &R);

@@ -11,6 +11,9 @@ regions_read / support_tail / region_line) follows the same rules and writes the
   --regions-out    one line per region and scored block that contains it (locate), COLUMNS_REGIONS; blocks in input order, within a
                    block the regions in file order.  p is rc_pvalue under the block's fit (99 where it failed): the probability that the
                    block-wide MAXIMUM reaches the score, conservative for a segment chosen beforehand.
+  --regions-null   (with --regions) two more columns, null_ge and p_segment: Batch.segment_null (rc_batch_segment_null) scores exactly
+                   that segment in each of the run's n null alignments, null_ge of them reach the segment's score, and p_segment =
+                   (null_ge + 1) / (n + 1) -- the test for a segment named in advance, where p is the block-wide test.
   --support FILE   one line per listed HSS and non-reference row, COLUMNS_SUPPORT: the first ten columns are the --details table's, then
                    the row's pair score, its share float32(pair / float32(N - 1)) of the sum behind the score, and the leave-one-out
                    score -- the segment's score without that row.
@@ -23,6 +26,7 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 COLUMNS_SUPPORT = ("hss", "name", "strand", "frame", "start", "end", "score", "p", "row", "row_name", "pair_score", "share", "loo_score")
+COLUMNS_NULL = ("null_ge", "p_segment")   # --regions-null: behind COLUMNS_REGIONS
 COLUMNS_REGIONS = ("id", "name", "strand", "frame", "from", "to", "start", "end", "score", "p", "support", "rows")
 
 BAD_LENGTH = "length not a multiple of three"
@@ -36,8 +40,13 @@ def support_header() -> str:
     return "\t".join(COLUMNS_SUPPORT) + "\n"
 
 
-def regions_header() -> str:
-    return "\t".join(COLUMNS_REGIONS) + "\n"
+def regions_header(null: bool = False) -> str:
+    return "\t".join(COLUMNS_REGIONS + (COLUMNS_NULL if null else ())) + "\n"
+
+
+def empirical_p(ge, n):
+    """(ge + 1) / (n + 1) in float64: the p of a segment chosen without looking at the scores, ge of whose n null values reach its score."""
+    return (np.asarray(ge, dtype=np.float64) + 1.0) / (np.float64(n) + 1.0)
 
 
 def locate(strand: str, start: int, end: int, ref_start: int, ref_length: int, L: int) -> Union[Tuple[int, int, int], str]:
@@ -150,7 +159,12 @@ def support_lines(counter: int, ref_name: str, h: dict, row_names: Sequence[str]
     return out
 
 
-def region_line(region: Region, frame: int, c1: int, c2: int, score, p, pairs) -> str:
+def region_line(region: Region, frame: int, c1: int, c2: int, score, p, pairs, null: Optional[Tuple[int, int]] = None) -> str:
+    """null: (ge, n) of --regions-null, or None: the line without the two columns."""
     pr = np.asarray(pairs, dtype=np.float32)
-    return "%s\t%s\t%s\t%i\t%i\t%i\t%i\t%i\t%s\t%.3e\t%i\t%i\n" % (region.id, region.name, region.strand, frame + 1, c1 + 1, c2 + 1, region.start,
-                                                              region.end, fmt3(score), float(np.float32(p)), int((pr > 0).sum()), pr.shape[0])
+    line = "%s\t%s\t%s\t%i\t%i\t%i\t%i\t%i\t%s\t%.3e\t%i\t%i" % (region.id, region.name, region.strand, frame + 1, c1 + 1, c2 + 1, region.start,
+                                                            region.end, fmt3(score), float(np.float32(p)), int((pr > 0).sum()), pr.shape[0])
+    if null is not None:
+        ge, n = int(null[0]), int(null[1])
+        line += "\t%i\tnan" % ge if np.isnan(np.float32(score)) else "\t%i\t%.3e" % (ge, (ge + 1.0) / (n + 1.0))
+    return line + "\n"
