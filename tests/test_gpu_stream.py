@@ -294,6 +294,37 @@ def test_native_scan_by_lanes_equals_the_fused_scan_and_the_oracle():
         assert lanes[i] == [(h["strand"], h["frame"], h["start"], h["end"], np.float32(h["score"])) for h in want], i
 
 
+@pytest.mark.parametrize("n,seed", [(17, 41), (34, 42), (64, 43)])
+def test_native_scan_by_lanes_of_wide_row_counts(ctx, n, seed):
+    """k_native_scan is also what batches of >= 64 blocks of MORE than 33 rows get (rc_schedule.cpp, launch_native_block): N-1 = 16 is the last
+    row count with one z register per lane, 33 has three, 63 four.  70 blocks of one row count x 30 columns, the last row -- the top bits of the
+    last z word -- out of frame in every block: as one batch (lane scan, one launch more) and in slices of 40 (fused into k_native_dp<N-1>)
+    the HSS tables are equal, and every tenth block's is the oracle's."""
+    from helpers import hss_table, oracle_block, punch_gap
+    from rnacode_amd import api
+    from rnacode_amd.synth import synth_blocks
+    blocks = [b.upper() for b in synth_blocks(70, n, 30, seed=seed)]
+    for i, b in enumerate(blocks):
+        punch_gap(b, -1, *((10, 1), (20, 2))[i % 2])
+    p = api.default_params(sampleN=64, seed_base=3)
+
+    def tables(sub):
+        batch = api.Batch(ctx, sub, p).run()
+        out = [hss_table(batch.scoreAln(i)) for i in range(len(sub))]
+        launches = batch.timing()[1]["native"]
+        batch.close()
+        return out, launches
+
+    lanes, launches = tables(blocks)
+    first, fused_launches = tables(blocks[:40])
+    second, _ = tables(blocks[40:])
+    assert launches == fused_launches + 1          # the scan was a launch of its own
+    assert lanes == first + second
+    assert sum(len(t) for t in lanes) > len(blocks)
+    for i in range(0, len(blocks), 10):
+        assert lanes[i] == hss_table(oracle_block(blocks[i], 64, 3).hss), i
+
+
 def test_stop_early_runs_fewer_samples_and_agrees_with_the_oracle(monkeypatch):
     """--stop-early (score.c:992,1036-1042): blocks whose first samples already beat the native score more often
     than the cutoff allows are decided (rc = -1) and get no further samples; all others are sampled in full.
