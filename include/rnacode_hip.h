@@ -348,6 +348,29 @@ int rc_batch_segment_scores(const rc_batch *b, const rc_bt_range *ranges, int32_
 int rc_batch_segment_null(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, float *score_out /* n_ranges */,
                           int32_t *ge_out /* n_ranges */, float *null_out /* may be NULL: [n_ranges][sampleN] */, int64_t cap /* floats in null_out */);
 
+/* Decoy listings: the complete HSS listing of null alignments, for an empirical false discovery rate of a whole screen.  For the k-th
+ * listed block (blks[k], or k where blks is NULL; a block may repeat) and decoy d = 0 .. n_decoys - 1 (1 <= n_decoys <= 64) the call
+ * simulates the null alignment of MT19937 seed seed + d under the block's own tree, gap pattern and base frequencies -- the run's own
+ * simulation --, scores it on both strands with the native block's kernels and the block's own gap tables and parameters, and lists its
+ * HSS: out[offsets[k * n_decoys + d] .. offsets[k * n_decoys + d + 1]), sorted as rc_batch_hss sorts, genomic coordinates as for a native
+ * HSS, pvalue from the block's fit (99 where the fit failed).  The total, offsets[n_blks * n_decoys], may exceed cap: records past cap are
+ * not written (cap = 0 sizes the buffer and writes none).  A block that was not scored contributes n_decoys empty lists.  *clamped, if
+ * not NULL, gets the number of clamped draws of the listed decoys' simulations (rc_batch_clamped's count for these alignments).
+ * Decoy d depends on seed + d and the block only, not on n_decoys or on which blocks are listed.
+ *   - With seed = par.seed_base and d < sampleN, decoy d is the alignment behind rc_batch_maxima(...)[d]: the best score of its list has
+ *     those bits, and the list is empty where that value is -1.
+ *   - The drivers pass seed_base + sampleN: the first seeds the fit did not see.
+ *   - Decoys share the null model of the p-values.  They calibrate multiplicity -- how many lines of a listing filtered at p <= t are
+ *     expected to be false: (decoy HSS with p <= t) / n_decoys against (listed HSS with p <= t) --, not model misfit.
+ * A block index out of range, n_decoys outside 1..64 or a batch that has not completed a run returns RC_ERR_ARG; every argument is checked
+ * before the device is touched, and on an error the outputs are left alone.  Works on a batch rc_stream_next handed out until it is
+ * recycled, and leaves the batch's maxima, fit, HSS, timings and rc_batch_clamped as they are.
+ * Cost: one simulation item per listed block (lane = decoy, so 64 decoys cost one simulation), then the native block's DP for every
+ * (block, decoy).  The listed blocks go in rounds under a budget of device memory, 256 MB by default (RC_DECOY_MAX_BYTES overrides, read
+ * per call; a single block may exceed it; the result does not depend on it); one synchronisation and one copy back per call. */
+int rc_batch_decoys(const rc_batch *b, const int32_t *blks, int32_t n_blks, uint32_t seed, int32_t n_decoys, rc_hss *out, int64_t cap,
+                    int64_t *offsets /* n_blks * n_decoys + 1 */, int64_t *clamped /* may be NULL */);
+
 /* The substitution matrix and genetic code the scorer uses, for callers that render results
  * (getScoringMatrix() score.c:50-76 and transcode[4][4][4] code.c:28-39, which src/postscript.c:362,412
  * read): pep_out[16a+4b+c] = amino-acid index 0..19 of codon (a,b,c) in A,C,G,T order or -1 for a stop;

@@ -172,6 +172,8 @@ def lib():
         l.rc_batch_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         l.rc_batch_segment_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.rc_batch_segment_null.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        l.rc_batch_decoys.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(RcHss), C.c_int64,
+                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         l.rc_evd_fit.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         l.rc_mt_stream.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_int32]
         l.rc_pvalue.argtypes = [C.c_float, C.c_float, C.c_float]
@@ -205,12 +207,21 @@ EXPORTED_SYMBOLS = [
     "rc_batch_prep_timing", "rc_host_cpus", "rc_ctx_set_host_threads", "rc_ctx_host_threads", "rc_ctx_fit_exp_mode", "rc_stream_create_v2", "rc_stream_submit", "rc_stream_submit_bound",
     "rc_stream_next", "rc_stream_recycle", "rc_stream_pending", "rc_stream_plan", "rc_stream_destroy", "rc_set_stream_cache", "rc_batch_work", "rc_batch_timing", "rc_batch_null_kernel", "rc_batch_status",
     "rc_batch_models", "rc_batch_maxima", "rc_batch_maxima_all", "rc_batch_fit", "rc_batch_fit_all", "rc_batch_hss", "rc_batch_hss_all", "rc_batch_clamped",
-    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_batch_segment_scores", "rc_batch_segment_null", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
+    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_batch_segment_scores", "rc_batch_segment_null", "rc_batch_decoys", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
     "rc_code_tables_for", "rc_genetic_code", "rc_species_tree_create", "rc_species_tree_destroy", "rc_species_tree_tips", "rc_species_tree_prune",
     "rc_fit_species_trees", "rc_fit_species_trees_device",
 ]
 # the entry points of the older rc_params layout (include/rnacode_hip.h, "Binary compatibility"): exported, no longer declared
 COMPAT_SYMBOLS = ["rc_default_params", "rc_batch_create", "rc_stream_create"]
+
+
+def _hss_dicts(out, total: int) -> List[dict]:
+    """The first `total` records of an RcHss array as the dicts of scoreAln."""
+    a = np.frombuffer(out, dtype=_HSS_DTYPE, count=total)   # columns at once: per-record ctypes access is ~3 us
+    keys = ("strand", "frame", "startSite", "endSite", "start", "end", "startGenomic", "endGenomic", "score", "pvalue")
+    cols = [[chr(v) for v in a["strand"].tolist()]] + [a[k].tolist() for k in keys[1:8]] + \
+           [a["score"].astype(np.float64).tolist(), a["pvalue"].astype(np.float64).tolist()]
+    return [dict(zip(keys, vals)) for vals in zip(*cols)]
 
 
 def _check(code: int) -> int:
@@ -594,13 +605,37 @@ class Batch:
         total = int(offs[self.n])
         out = (RcHss * max(total, 1))()
         _check(lib().rc_batch_hss_all(self._h, out, total, offs))
-        a = np.frombuffer(out, dtype=_HSS_DTYPE, count=total)   # columns at once: per-record ctypes access is ~3 us
-        keys = ("strand", "frame", "startSite", "endSite", "start", "end", "startGenomic", "endGenomic", "score", "pvalue")
-        cols = [[chr(v) for v in a["strand"].tolist()]] + [a[k].tolist() for k in keys[1:8]] + \
-               [a["score"].astype(np.float64).tolist(), a["pvalue"].astype(np.float64).tolist()]
-        recs = [dict(zip(keys, vals)) for vals in zip(*cols)]
+        recs = _hss_dicts(out, total)
         o = list(offs)
         return [recs[o[i]:o[i + 1]] for i in range(self.n)]
+
+    def decoys(self, n_decoys: int, seed: Optional[int] = None, blks=None, with_clamped: bool = False):
+        """rc_batch_decoys: the complete HSS listing of n_decoys (1..64) null alignments per block of `blks` (default: all, in order) --
+        block x decoy x HSS, the dicts of scoreAln, p-values under the block's own fit.  Decoy d is the alignment of MT19937 seed
+        seed + d (default seed_base + sampleN: the first seeds the fit did not see); a block that was not scored has empty lists.
+        with_clamped: (lists, clamped draws of these simulations)."""
+        if seed is None:
+            seed = int(self.params.seed_base) + int(self.params.sampleN)
+        if blks is None:
+            arr, n, ptr = None, self.n, None
+        else:
+            arr = np.ascontiguousarray(np.asarray(list(blks), dtype=np.int32).reshape(-1))
+            n, ptr = arr.shape[0], arr.ctypes.data
+        k = int(n_decoys)
+        offs = (C.c_int64 * (n * max(k, 0) + 1))()
+        clamped = C.c_int64()
+        cap = max(16 * n * max(k, 0), 1)   # (a second call only where the lists are longer than that)
+        while True:
+            out = (RcHss * cap)()
+            _check(lib().rc_batch_decoys(self._h, ptr, n, C.c_uint32(seed & 0xFFFFFFFF), k, out, cap, offs, C.byref(clamped)))
+            total = int(offs[n * k])
+            if total <= cap:
+                break
+            cap = total
+        recs = _hss_dicts(out, total)
+        o = list(offs)
+        lists = [[recs[o[i * k + d]:o[i * k + d + 1]] for d in range(k)] for i in range(n)]
+        return (lists, clamped.value) if with_clamped else lists
 
     def getExtremeValuePars(self, blk: int) -> Tuple[int, float, float]:
         rc, mu, lam = C.c_int32(), C.c_float(), C.c_float()

@@ -5,6 +5,7 @@ options that concern the scoring path and the listings:
 
     python -m rnacode_amd.cli [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S]
                               [-e [-i CUTOFF] [-d DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null]]
+                              [--decoys K --decoys-out FILE]
                               [-o OUT] [--trees SIDECAR | --species-tree NEWICK
                               [--species-tree-fit fixed|scale|branches]] [--write-trees SIDECAR] [FILE]
 
@@ -25,6 +26,9 @@ strand and the listing's Start / End) in every scored block that contains them, 
 ranges of a sub-batch go in one rc_batch_segment_scores call); with --regions-null its lines end in null_ge and p_segment, the test for a
 segment named in advance: how many of the -n null alignments score at least as high on exactly that segment (one rc_batch_segment_null call
 per sub-batch), and (null_ge + 1) / (n + 1).
+--decoys K with --decoys-out FILE (not in the reference) writes the complete listing of K null alignments per scored block, selected by
+--cutoff, -b and -r as the block's own HSS are (decoys.py; one rc_batch_decoys call per sub-batch, seeds seed_base + n ..: the first the
+fit did not see): what `python -m rnacode_amd.decoys` turns into a false discovery rate of the listing.
 Quirk kept from the reference: the 4th value of --pars goes to stopPenalty_0 (RNAcode.c:318)."""
 from __future__ import annotations
 
@@ -38,7 +42,7 @@ from typing import IO, List, Optional
 
 import numpy as np
 
-from . import api, details, eps, report, segments, track
+from . import api, decoys, details, eps, report, segments, track
 from .alnio import AlnBlock, read_alignment_file
 
 
@@ -139,6 +143,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --regions: two more columns in --regions-out, null_ge = how many of the -n null alignments score at least as "
                          "high on exactly that segment, and p_segment = (null_ge + 1) / (n + 1), the test for a segment named in advance "
                          "(p is the block-wide test)")
+    ap.add_argument("--decoys", type=int, metavar="K",
+                    help="with --decoys-out: list the HSS of K (1..64) null alignments per scored block, simulated as the samples behind the "
+                         "p-values are and selected by --cutoff, -b and -r as the block's own; python -m rnacode_amd.decoys turns the two "
+                         "listings into q-values")
+    ap.add_argument("--decoys-out", metavar="FILE", help="where the decoy listing goes: one line per decoy HSS")
     return ap
 
 
@@ -167,6 +176,10 @@ def _intake(a):
         raise _Refused("--regions and --regions-out go together")
     if a.regions_null and not a.regions:
         raise _Refused("--regions-null needs --regions")
+    if (a.decoys is not None) != bool(a.decoys_out):
+        raise _Refused("--decoys and --decoys-out go together")
+    if a.decoys is not None and not 1 <= a.decoys <= 64:
+        raise _Refused("--decoys takes a number of decoys from 1 to 64")
     if a.regions:
         try:
             with open(a.regions) as fh:
@@ -208,7 +221,7 @@ def _trees(a, ctx, blocks, marshalled, species, n_read: int, read_index: List[in
 
 
 SIDE_FILES = (("details", details.header), ("track", track.header), ("support", segments.support_header),
-              ("regions_out", segments.regions_header))   # the option's name in the parsed arguments, its header line
+              ("regions_out", segments.regions_header), ("decoys_out", decoys.header))   # the option's name in the parsed arguments, its header line
 
 
 class _Ranges:
@@ -300,6 +313,8 @@ def _list_batch(run: _Run, batch, base: int) -> None:
     seg_scores, seg_pairs = batch.segment_scores(seg.ranges) if seg.ranges else (None, None)
     # --regions-null: the regions' ranges (not the listed HSS, which were selected as maxima) with ONE call (rc_batch_segment_null)
     null_ge = batch.segment_null(nul.ranges)[1] if nul.ranges else None
+    # --decoys: the decoy listings of the blocks the listing covers with ONE call (rc_batch_decoys)
+    decoyed = dict(zip(scored, batch.decoys(a.decoys, run.params.seed_base + run.params.sampleN, scored))) if "decoys_out" in side and scored else {}
     for i in range(batch.n):
         b = run.blocks[base + i]
         if base + i in run.refused:   # the species tree does not cover the block's rows
@@ -313,6 +328,8 @@ def _list_batch(run: _Run, batch, base: int) -> None:
             print(f"Skipping alignment. Failed to build ML tree. ({batch.block_error(i) or 'not scored'})", file=sys.stderr)
             continue
         _list_block(run, i, b, all_hss[i], bt, paths, seg, seg_pairs)
+        if i in decoyed:
+            side["decoys_out"].writelines(decoys.block_lines(run.read_index[base + i], b.rows[0].name, decoyed[i], a.cutoff, a.best_only, a.best_region))
         if i in tracked or i in found:
             rc, mu, lam = batch.getExtremeValuePars(i)
             if i in tracked:

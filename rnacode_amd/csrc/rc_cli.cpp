@@ -37,6 +37,12 @@
 // --regions-null (with --regions): every --regions-out line ends in null_ge and p_segment = (null_ge + 1) / (n + 1), the test for a segment named
 // in advance -- the regions' ranges of a sub-batch in ONE rc_batch_segment_null call (in the sample split one per slice, the counts added).
 //
+// --decoys K with --decoys-out FILE (not in the reference): the complete listing of K null alignments per scored block -- simulated as the samples
+// behind the p-values are, from the seeds seed_base + n on (the first the fit did not see; n the run's whole -n), selected by -p, -b and -r as
+// the block's own HSS -- one line per decoy HSS: the block's input index, the decoy, then the -t listing's columns.  ONE rc_batch_decoys call per
+// sub-batch (in the sample split one slice computes them, with the p-values of the gathered fit); the same bytes as python -m rnacode_amd.cli,
+// whose decoys.py turns the file and the listing into q-values.  With --gpus N the one writer emits it in input order.
+//
 // Quirk kept from the reference: the 4th value of --pars goes to stopPenalty_0 (RNAcode.c:318).
 #include <algorithm>
 #include <atomic>
@@ -288,14 +294,15 @@ std::vector<Block> read_alignment(FILE *in) {
   return read_maf(text, size);
 }
 
-// A side file (--details, --track, --support, --regions-out): opened and given its header before the first batch, closed and checked
+// A side file (--details, --track, --support, --regions-out, --decoys-out): opened and given its header before the first batch, closed and checked
 // when everything has been listed.  An empty path: the option is off.
 struct SideFile {
   const char *(*header)();
   std::string path;
   FILE *f;
 };
-enum { kDetails, kTrack, kSupport, kRegions, kSides };
+enum { kDetails, kTrack, kSupport, kRegions, kDecoys, kSides };
+const char *decoys_header() { return "block\tdecoy\tstrand\tframe\tlength\tfrom\tto\tname\tstart\tend\tscore\tp\n"; }
 
 // an HSS that gets a line of the listing, and what goes out beside that line
 struct Line {
@@ -314,7 +321,7 @@ struct Listing {
   float epsCutoff = 0.05f;
   std::string epsDir = "eps";
   SideFile side[kSides] = {{rceps::details_header, "", nullptr}, {rceps::track_header, "", nullptr}, {rceps::support_header, "", nullptr},
-                           {rceps::regions_header, "", nullptr}};
+                           {rceps::regions_header, "", nullptr}, {decoys_header, "", nullptr}};
   bool on(int s) const { return !side[s].path.empty(); }
   int hitCounter = 0;
 
@@ -350,6 +357,18 @@ struct Listing {
       if (bestOnly) break;
     }
     return lines;
+  }
+
+  // the -t listing's columns behind the counter (block() below), from the strand on, in its formats: what a line of --decoys-out ends in
+  static std::string tabular_tail(const rc_hss &h, const std::string &refName) {
+    const double p = static_cast<double>(h.pvalue);
+    const char strand[2] = {static_cast<char>(h.strand), 0};
+    char num[160];
+    std::snprintf(num, sizeof num, "\t%s\t%i\t%i\t%i\t%i\t", strand, h.frame + 1, h.endSite - h.startSite + 1, h.startSite + 1, h.endSite + 1);
+    std::string tail = num + refName;
+    if (p < 0.001) std::snprintf(num, sizeof num, "\t%i\t%i\t%7.3f\t% 9.3e\n", h.startGenomic, h.endGenomic, static_cast<double>(h.score), p);
+    else std::snprintf(num, sizeof num, "\t%i\t%i\t%7.3f\t% 9.3f\n", h.startGenomic, h.endGenomic, static_cast<double>(h.score), p);
+    return tail + num;
   }
 
   // a block's part of the listing: its lines as arrange() chose them, each with its plot (misc.c:461-474 writes hss-<counter>.eps in front
@@ -402,6 +421,7 @@ struct Listing {
 void usage() {
   std::fprintf(stderr, "usage: rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]\n"
                        "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null]]\n"
+                       "                   [--decoys K --decoys-out FILE]\n"
                        "                   [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]\n"
                        "                   [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]\n"
                        "                   [--write-trees SIDECAR] [--dump-blocks] [FILE]\n"
@@ -424,7 +444,11 @@ void usage() {
                        "  --regions-out FILE         one line per region and scored block that contains it: score, p, supporting sequences\n"
                        "  --regions-null             with --regions: two more columns, null_ge = how many of the -n null alignments score at least as\n"
                        "                             high on exactly that segment, p_segment = (null_ge + 1) / (n + 1): the test for a segment\n"
-                       "                             named in advance (p is the block-wide test)\n");
+                       "                             named in advance (p is the block-wide test)\n"
+                       "  --decoys K                 with --decoys-out: list the HSS of K (1..64) null alignments per scored block, simulated as the\n"
+                       "                             samples behind the p-values are and selected by -p, -b and -r as the block's own\n"
+                       "  --decoys-out FILE          the decoy listing, one line per decoy HSS: block decoy strand frame length from to name start\n"
+                       "                             end score p (python -m rnacode_amd.decoys turns it and the -t listing into q-values)\n");
 }
 
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -436,7 +460,7 @@ struct BlockOut {
   std::string why;             // why it was not scored
   bool none = true;            // Listing::arrange: nothing significant
   std::vector<Line> lines;     // the HSS that get a line, what goes out beside each attached
-  std::string track, regions;  // its --track / --regions-out lines
+  std::string track, regions, decoys;  // its --track / --regions-out / --decoys-out lines
 };
 
 // results of one sub-batch on their way to the writer
@@ -464,6 +488,7 @@ struct Run {
   std::map<std::string, std::vector<int>> regionsOf;      // reference row name -> the regions that can match a block, in file order
   std::vector<char> regionMatched;                        // set by the writer
   bool regionsNull = false;                               // --regions-null: null_ge and p_segment behind every --regions-out line
+  int decoys = 0;                                         // --decoys: null alignments listed per scored block
   // the writer: one thread, jobs in input order
   std::mutex jm;
   std::condition_variable jcv;
@@ -511,6 +536,7 @@ void writer_thread(Run &R) {
       R.list.block(o.lines, o.none, std::string(blk.rows[0].name));
       if (!o.track.empty()) std::fwrite(o.track.data(), 1, o.track.size(), R.list.side[kTrack].f);
       if (!o.regions.empty()) std::fwrite(o.regions.data(), 1, o.regions.size(), R.list.side[kRegions].f);
+      if (!o.decoys.empty()) std::fwrite(o.decoys.data(), 1, o.decoys.size(), R.list.side[kDecoys].f);
     }
     for (int r : j->matched) R.regionMatched[r] = 1;
     R.tList += now() - t;
@@ -712,6 +738,39 @@ bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std
   return true;
 }
 
+// --decoys for every block the listing covers, while the batch is alive: ONE rc_batch_decoys call (a second one only where the lists are longer
+// than the first one's room), seeds seed_base + n ..: the first the fit did not see, n the run's whole sample count.  Each decoy's HSS are
+// arranged as the block's own are; where the caller made the fits itself (the sample split) the p-values are theirs.
+bool add_decoys(const Run &R, rc_batch *b, Job &j, std::string &err, const std::vector<EvdFit> *fits) {
+  std::vector<int32_t> blks;
+  for (size_t i = 0; i < j.blocks.size(); i++) if (scored(R, j.blocks[i])) blks.push_back(static_cast<int32_t>(i));
+  const int nb = static_cast<int>(blks.size()), K = R.decoys;
+  if (!nb) return true;
+  const size_t nl = static_cast<size_t>(nb) * K;
+  std::vector<int64_t> offs(nl + 1, 0);
+  std::vector<rc_hss> recs(16 * nl);
+  const uint32_t seed = R.par.seed_base + static_cast<uint32_t>(R.par.sampleN);
+  for (;;) {
+    if (rc_batch_decoys(b, blks.data(), nb, seed, K, recs.data(), static_cast<int64_t>(recs.size()), offs.data(), nullptr) != RC_OK) { err = rc_last_error(); return false; }
+    if (offs[nl] <= static_cast<int64_t>(recs.size())) break;
+    recs.resize(static_cast<size_t>(offs[nl]));
+  }
+  for (int k = 0; k < nb; k++) {
+    const int i = blks[k];
+    const Block &blk = R.blocks[j.blocks[i].index];
+    EvdFit fit{-1, 0.0f, 0.0f};
+    if (fits && !fit_of(b, fits, i, fit, err)) return false;
+    for (int d = 0; d < K; d++) {
+      std::vector<rc_hss> list(recs.begin() + offs[static_cast<size_t>(k) * K + d], recs.begin() + offs[static_cast<size_t>(k) * K + d + 1]);
+      if (fits) for (rc_hss &h : list) h.pvalue = fit.rc == 1 ? rc_pvalue(h.score, fit.mu, fit.lambda) : 99.0f;
+      bool none = true;
+      for (const Line &l : R.list.arrange(std::move(list), none))
+        j.blocks[i].decoys += std::to_string(blk.index) + "\t" + std::to_string(d) + Listing::tabular_tail(l.h, std::string(blk.rows[0].name));
+    }
+  }
+  return true;
+}
+
 // From a finished batch to the writer, step 1: the HSS, status and reason of each of its blocks (blockIdx: their input blocks).
 std::unique_ptr<Job> fetch(rc_batch *b, int seq, const int *blockIdx, std::string &err) {
   std::unique_ptr<Job> j(new Job());
@@ -741,6 +800,7 @@ bool deliver(Run &R, rc_batch *b, std::unique_ptr<Job> j, std::string &err, cons
   if ((R.list.eps || R.list.on(kDetails)) && !annotate(R, b, *j, err)) return false;
   if (R.list.on(kTrack) && !add_track(R, b, *j, err, fits)) return false;
   if ((R.list.on(kSupport) || R.list.on(kRegions)) && !add_segments(R, b, *j, err, fits, slices)) return false;
+  if (R.list.on(kDecoys) && !add_decoys(R, b, *j, err, fits)) return false;
   post(R, std::move(j));
   return true;
 }
@@ -960,7 +1020,7 @@ int main(int argc, char **argv) {
   Listing &list = R.list;
   std::string file, outfile, trees, limit, devicesArg, speciesFile, writeTrees, regionsFile;
   int device = 0, subBlocks = 0, gpus = 1;   // subBlocks 0: the library's schedule
-  bool dumpBlocks = false;
+  bool dumpBlocks = false, decoysGiven = false;
   for (int a = 1; a < argc; a++) {
     const std::string o = argv[a];
     auto val = [&]() -> const char * { if (a + 1 >= argc) { usage(); std::exit(2); } return argv[++a]; };
@@ -1012,6 +1072,8 @@ int main(int argc, char **argv) {
     else if (o == "--regions") regionsFile = val();
     else if (o == "--regions-out") list.side[kRegions].path = val();
     else if (o == "--regions-null") R.regionsNull = true;
+    else if (o == "--decoys") { decoysGiven = true; R.decoys = std::atoi(val()); }
+    else if (o == "--decoys-out") list.side[kDecoys].path = val();
     else if (!o.empty() && o[0] == '-' && o != "-") { usage(); return 2; }
     else file = o;
   }
@@ -1023,6 +1085,8 @@ int main(int argc, char **argv) {
   if (!regionsFile.empty() != list.on(kRegions)) die("--regions and --regions-out go together");   // before any context exists
   if (R.regionsNull && regionsFile.empty()) die("--regions-null needs --regions");
   if (R.regionsNull) list.side[kRegions].header = rceps::regions_header_null;
+  if (decoysGiven != list.on(kDecoys)) die("--decoys and --decoys-out go together");
+  if (decoysGiven && (R.decoys < 1 || R.decoys > 64)) die("--decoys takes a number of decoys from 1 to 64");
   if (!regionsFile.empty()) {
     std::ifstream in(regionsFile, std::ios::binary);
     if (!in) die("--regions: could not open " + regionsFile);

@@ -284,6 +284,24 @@ struct SegNullArgs {
 };
 constexpr int seg_null_code_words(int L) { return ((L / 3 + 31) >> 2) + 1; }   // GenericLayout::nW (rc_null_generic.h): code words per (strand x frame, row)
 void launch_segment_null(const SegNullArgs &a, hipStream_t stream);   // nBlocks x groups workgroups of one wavefront
+// rc_batch_decoys (rc_decoys.hip): the codes k_generic_sim<false> has left at codesAll for a round of blocks (position p of `blocks`: one item
+// of one sample group, lane = decoy, at p * codesStride) expanded into native-format sigma tables f32 [2][NK][L + 1], decoy d of position p at
+// sigmaAll + (p * nDecoys + d) * sigmaStride.  vblocks / vflags [p * nDecoys + d]: the block's header with off_sigma aimed at that table, and
+// its flag word -- what the native kernels index with the (block, decoy) number in the block's place.
+struct DecoyArgs {
+  const uint8_t *blob;
+  const DevBlock *dblocks;
+  const uint32_t *flags;
+  const int *blocks;          // [nBlocks] batch indices of the round
+  const uint8_t *codesAll;
+  size_t codesStride;
+  uint8_t *sigmaAll;
+  size_t sigmaStride;         // bytes per (block, decoy): the largest table of the round, 256-aligned
+  DevBlock *vblocks;
+  uint32_t *vflags;
+  int nDecoys;
+};
+void launch_decoy_sigma(const DecoyArgs &a, int nBlocks, int maxNK, hipStream_t stream);   // nBlocks x 2 maxNK workgroups of one wavefront
 // wider blocks (N > 64): generic kernels with their states in a global scratch (rc_null_generic.h)
 size_t null_generic_lds_bytes(int N, int nnodes);   // packed node states + codon windows of the widest block of the launch
 // the same in two launches (simulation with many light wavefronts, then the DP): bytes of an item's codes / of a DP workgroup's states

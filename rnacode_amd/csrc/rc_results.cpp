@@ -1,5 +1,6 @@
 // rc_results.cpp -- what a finished batch holds: statuses, models, maxima, fits, HSS tables, native S matrices, backtrack paths, per-codon tracks, segment scores and their null distributions.
 #include "rc_runtime.h"
+#include "rc_decoy_plan.h"
 #include "rc_segnull_plan.h"
 
 extern "C" {
@@ -135,13 +136,32 @@ static int block_hss_count(const rc_batch *b, int blk) {
   return n;
 }
 
+// a device record as the caller sees it: alignment and genomic coordinates (score.c:921-936), the p-value under the block's fit
+static rc_hss hss_of(const BlockMeta &h, const FitOut &f, const DevHss &d) {
+  const float mu = static_cast<float>(f.mu), lambda = static_cast<float>(f.lambda);
+  rc_hss o{};
+  o.strand = d.strand ? '-' : '+';
+  o.frame = d.frame; o.startSite = d.startSite; o.endSite = d.endSite; o.score = d.score;
+  o.start = d.startSite * 3 + d.frame + 1;                       // score.c:921-922
+  o.end = d.endSite * 3 + d.frame + 3;
+  if (h.ref_start == 0 && h.ref_length == 0) { o.startGenomic = o.start; o.endGenomic = o.end; }   // :925-928
+  else if (!d.strand) {
+    o.startGenomic = h.ref_start + d.startSite * 3 + d.frame;    // :932-933
+    o.endGenomic = h.ref_start + d.endSite * 3 + d.frame + 2;
+  } else {
+    o.endGenomic = (h.ref_start + h.ref_length - 1) - d.startSite * 3 - d.frame;       // :935-936
+    o.startGenomic = (h.ref_start + h.ref_length - 1) - d.endSite * 3 - d.frame - 2;
+  }
+  o.pvalue = (f.rc == 1) ? pvalue_of(d.score, mu, lambda) : 99.0f;   // RNAcode.c:180-188
+  return o;
+}
+
 int rc_batch_hss(const rc_batch *b, int32_t blk, rc_hss *out, int32_t cap) {
   int r = check_blk(b, blk, true);
   if (r) return r;
   const BlockMeta &h = b->meta[blk];
   if (h.status != RC_OK) return h.status;
   const FitOut &f = b->fit[blk];
-  const float mu = static_cast<float>(f.mu), lambda = static_cast<float>(f.lambda);
   std::vector<rc_hss> all;
   for (int combo = 0; combo < 6; combo++) {   // '+' hits then '-' hits, frames ascending (score.c:1107-1127)
     const size_t slot = static_cast<size_t>(blk) * 6 + combo;
@@ -150,21 +170,7 @@ int rc_batch_hss(const rc_batch *b, int32_t blk, rc_hss *out, int32_t cap) {
     for (int i = 0; i < cnt; i++) {
       const DevHss &d = b->hssRec[static_cast<size_t>(b->hssOff[slot]) + i];
       if (!(d.score > 0.0f)) break;           // lists end at the first non-positive score (score.c:1112,1121)
-      rc_hss o{};
-      o.strand = d.strand ? '-' : '+';
-      o.frame = d.frame; o.startSite = d.startSite; o.endSite = d.endSite; o.score = d.score;
-      o.start = d.startSite * 3 + d.frame + 1;                       // score.c:921-922
-      o.end = d.endSite * 3 + d.frame + 3;
-      if (h.ref_start == 0 && h.ref_length == 0) { o.startGenomic = o.start; o.endGenomic = o.end; }   // :925-928
-      else if (!d.strand) {
-        o.startGenomic = h.ref_start + d.startSite * 3 + d.frame;    // :932-933
-        o.endGenomic = h.ref_start + d.endSite * 3 + d.frame + 2;
-      } else {
-        o.endGenomic = (h.ref_start + h.ref_length - 1) - d.startSite * 3 - d.frame;       // :935-936
-        o.startGenomic = (h.ref_start + h.ref_length - 1) - d.endSite * 3 - d.frame - 2;
-      }
-      o.pvalue = (f.rc == 1) ? pvalue_of(d.score, mu, lambda) : 99.0f;   // RNAcode.c:180-188
-      all.push_back(o);
+      all.push_back(hss_of(h, f, d));
     }
   }
   std::stable_sort(all.begin(), all.end(), [](const rc_hss &a, const rc_hss &c) { return a.score > c.score; });
@@ -646,6 +652,259 @@ int rc_batch_segment_null(const rc_batch *bc, const rc_bt_range *ranges, int32_t
   if (rc != RC_OK) { if (launched) (void)hipStreamSynchronize(st); return rc; }
   std::memcpy(score_out, scores.data(), nr * sizeof(float));
   std::memcpy(ge_out, ge.data(), nr * sizeof(int32_t));
+  return RC_OK;
+}
+
+// Decoy listings (rc_decoys.hip): the whole HSS listing of null alignments.  Per listed block one simulation item of k_generic_sim<false> -- the
+// run's own simulation, lane = decoy, MT19937 streams of this call's seeds in a buffer of this call's own -- leaves the sigma codes;
+// k_decoy_sigma expands them into one native-format sigma table per (block, decoy) and writes a copy of the block's header aimed at it; the
+// native block's kernels, unchanged and grouped by row count as launch_native_block groups them, score those copies as if they were blocks.
+// The scored positions go in rounds under a budget (rc_decoy_plan.h); each round's HSS records are packed behind those of the rounds before,
+// and the whole call's come back with one copy behind one synchronisation.  Nothing of the batch is written.
+int rc_batch_decoys(const rc_batch *bc, const int32_t *blks, int32_t n_blks, uint32_t seed, int32_t n_decoys, rc_hss *out, int64_t cap,
+                    int64_t *offsets, int64_t *clamped) {
+  rc_batch *b = const_cast<rc_batch *>(bc);
+  if (!b || !offsets || n_blks < 0 || cap < 0 || (!out && cap > 0)) return fail(RC_ERR_ARG, "bad argument");
+  if (n_decoys < 1 || n_decoys > kWave) return fail(RC_ERR_ARG, "the number of decoys must be 1..64");
+  if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
+  // every index is checked, and the plan made, before anything touches the device (or the caller's arrays)
+  const int K = n_decoys;
+  rc_ctx *c = b->ctx;
+  std::vector<int> posOf(static_cast<size_t>(n_blks), -1);   // listed block k -> its position among the scored ones
+  std::vector<int32_t> up;                                   // one upload: the positions' blocks, then every round's launch lists
+  for (int k = 0; k < n_blks; k++) {
+    const int blk = blks ? blks[k] : k;
+    if (blk < 0 || blk >= b->n) return fail(RC_ERR_ARG, "decoy block " + std::to_string(k) + ": block index out of range");
+    if (b->meta[blk].status != RC_OK) continue;
+    posOf[static_cast<size_t>(k)] = static_cast<int>(up.size());
+    up.push_back(blk);
+  }
+  const size_t P = up.size(), V = P * K, slots = V * 6;
+  if (slots * static_cast<size_t>(b->hssCap) > static_cast<size_t>(INT32_MAX)) return fail(RC_ERR_ARG, "more than 2^31 - 1 HSS slots in one call");
+  std::unique_ptr<uint8_t[]> res;   // what comes back: clamp count u64 | total, pad | counts [slots] | offsets [slots] | packed records (uninitialised: the copy fills it)
+  const size_t resInts = 4 + 2 * slots, packedCap = slots * b->hssCap;
+  size_t total = 0;
+  if (P > 0) {
+    size_t budget = kDecoyMaxBytes;
+    if (const char *e = std::getenv("RC_DECOY_MAX_BYTES")) budget = static_cast<size_t>(std::max(1ll, std::atoll(e)));
+    const auto meta_of = [&](size_t p) -> const BlockMeta & { return b->meta[up[p]]; };
+    const auto wide = [&](const BlockMeta &h, int blk) { return h.N > kTemplRows || block_class(h.N, h.L, b->db[blk].omega, c->rule) == kGenericClass; };
+    const auto codes_bytes = [&](int blk) { return null_generic_codes_bytes(b->meta[blk].N, b->meta[blk].L, b->db[blk].nnodes); };
+    const std::vector<DecoyRound> rounds = decoy_plan(static_cast<int>(P), [&](int p) {
+      const BlockMeta &h = meta_of(p);
+      const size_t smax = static_cast<size_t>(h.L / 3);
+      return DecoyCost{codes_bytes(up[p]), al256(static_cast<size_t>(2) * h.NK * (h.L + 1) * sizeof(float)), 6 * smax * smax * sizeof(float),
+                       static_cast<size_t>(6) * b->hssCap * sizeof(DevHss)};
+    }, K, budget);
+    for (size_t p = 0; p < P; p++) {   // k_decoy_sigma finds a sequence's code words by GenericLayout's rule: the two must agree
+      const BlockMeta &h = meta_of(p);
+      if (codes_bytes(up[p]) != al256(static_cast<size_t>(6) * h.NK * seg_null_code_words(h.L) * kWave * sizeof(uint32_t)))
+        return fail(RC_ERR_UNSUPPORTED, "internal: the layout of the sigma codes has changed");
+    }
+    // a round's launches: its (block, decoy) numbers -- (position in the round) x K + d, what the native kernels take for a block index -- by
+    // row count, the blocks of the generic native kernel in one list
+    struct Launch { int NK; size_t at, count; int smax, maxNK; bool all; };   // NK 0: k_native_dp_generic
+    struct Round { size_t first, nLaunch; int maxN, maxNK, maxNodes; };
+    std::vector<Launch> launches;
+    std::vector<Round> rinfo;
+    const int mode = c->inflight.load() > 0 ? 0 : 1;   // (rc_batch_track's rule)
+    const int chunk = 256;                             // blocks per launch of the generic kernel, which share its scratch (launch_native_block)
+    const auto wide_stride = [](const Launch &l) { return static_cast<size_t>(3) * l.maxNK * kWave + static_cast<size_t>(kWave) * l.smax; };
+    size_t codesNeed = 0, sigmaNeed = 0, tileFloats = 4, scratchFloats = 0, allFloats = 0, maxV = 0;
+    up.reserve(P + V);
+    for (const DecoyRound &rd : rounds) {
+      Round ri{launches.size(), 0, 0, 0, 0};
+      std::map<int, std::vector<int>> byNK;
+      std::vector<int> wides;
+      for (int q = 0; q < rd.count; q++) {
+        const int blk = up[static_cast<size_t>(rd.first + q)];
+        const BlockMeta &h = b->meta[blk];
+        ri.maxN = std::max(ri.maxN, h.N); ri.maxNK = std::max(ri.maxNK, h.NK); ri.maxNodes = std::max(ri.maxNodes, b->db[blk].nnodes);
+        std::vector<int> &v = wide(h, blk) ? wides : byNK[h.NK];
+        for (int d = 0; d < K; d++) v.push_back(q * K + d);
+      }
+      const auto add = [&](int NK, const std::vector<int> &v) {
+        Launch l{NK, up.size(), v.size(), 1, 0, false};
+        for (int vr : v) {
+          const BlockMeta &h = meta_of(static_cast<size_t>(rd.first + vr / K));
+          l.smax = std::max(l.smax, h.L / 3); l.maxNK = std::max(l.maxNK, h.NK);
+        }
+        up.insert(up.end(), v.begin(), v.end());
+        if (NK) {
+          const size_t items = l.count * 6, fl = items * l.smax * l.smax;
+          tileFloats = std::max(tileFloats, native_grid(c, items, l.smax, mode) * kWave * l.smax);
+          // every matrix kept for k_native_scan where the run keeps them (launch_native_block)
+          l.all = fl * sizeof(float) <= c->totalMem / 16 && items >= 6 * 64 && (NK <= 16 || NK > 32);
+          if (l.all) allFloats = std::max(allFloats, fl);
+        } else {
+          scratchFloats = std::max(scratchFloats, wide_stride(l) * 6 * std::min<size_t>(chunk, l.count));
+        }
+        launches.push_back(l);
+      };
+      for (const auto &kv : byNK) add(kv.first, kv.second);
+      if (!wides.empty()) add(0, wides);
+      ri.nLaunch = launches.size() - ri.first;
+      rinfo.push_back(ri);
+      codesNeed = std::max(codesNeed, static_cast<size_t>(rd.count) * rd.stride.codes);
+      sigmaNeed = std::max(sigmaNeed, static_cast<size_t>(rd.count) * K * rd.stride.sigma);
+      maxV = std::max(maxV, static_cast<size_t>(rd.count) * K);
+    }
+    const size_t guess = std::min(packedCap, V * 16);   // records that come with the first copy (batch_wait's rule: normally all of them)
+    const size_t headBytes = resInts * sizeof(int32_t);
+    res.reset(new uint8_t[headBytes + guess * sizeof(DevHss)]);
+    HIP_TRY(hipSetDevice(c->device));
+    RC_STREAM_TRY(st, stream_aux(c));
+    HIP_TRY(hipEventSynchronize(b->evPrep));   // the tables of the blob are made on the device
+    DevBuf d_up, d_U, d_cnt, d_codes, d_sigma, d_vdb, d_vflags, d_tile, d_scratch, d_all, d_hss, d_res;
+    for (DevBuf *d : {&d_up, &d_U, &d_cnt, &d_codes, &d_sigma, &d_vdb, &d_vflags, &d_tile, &d_scratch, &d_all, &d_hss, &d_res}) {
+      d->retired = c->retired.get(); d->pool = c->bufPool.get();
+    }
+    uint8_t *blob = b->dblob.as<uint8_t>();
+    bool launched = false;
+    // (a lambda: whatever fails in it, nothing returns to the caller before the work already queued on the stream has drained -- `up`, `res`
+    // and the buffers die with this frame)
+    const int rc = [&]() -> int {
+      HIP_TRY(d_up.ensure(up.size() * sizeof(int32_t)));
+      HIP_TRY(d_U.ensure(static_cast<size_t>(kWave) * std::max(b->maxDraws, 1) * sizeof(uint32_t)));
+      HIP_TRY(d_cnt.ensure(8 * sizeof(uint32_t)));
+      HIP_TRY(d_codes.ensure(codesNeed));
+      HIP_TRY(d_sigma.ensure(sigmaNeed));
+      HIP_TRY(d_vdb.ensure(maxV * sizeof(DevBlock)));
+      HIP_TRY(d_vflags.ensure(maxV * sizeof(uint32_t)));
+      HIP_TRY(d_tile.ensure(tileFloats * sizeof(float)));
+      if (scratchFloats) HIP_TRY(d_scratch.ensure(scratchFloats * sizeof(float)));
+      if (allFloats) HIP_TRY(d_all.ensure(allFloats * sizeof(float)));
+      HIP_TRY(d_hss.ensure(std::max<size_t>(maxV * 6 * b->hssCap, 1) * sizeof(DevHss)));   // a round's records: packed before the next round
+      HIP_TRY(d_res.ensure(headBytes + packedCap * sizeof(DevHss)));
+      launched = true;   // from here on something may be in flight
+      // the MT19937 streams of the seeds seed .. seed + 63, one per lane: this call's own (the context's cache holds the run's)
+      launch_mt_stream(seed, kWave, std::max(b->maxDraws, 1), d_U.as<uint32_t>(), st);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(d_up.p, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemsetAsync(d_res.p, 0, resInts * sizeof(int32_t), st));   // clamp count, total, and the counts of slots nobody writes
+      int32_t *ri32 = d_res.as<int32_t>();
+      DevHss *packed = reinterpret_cast<DevHss *>(ri32 + resInts);
+      NullArgs sim{};
+      sim.blob = blob; sim.dblocks = reinterpret_cast<const DevBlock *>(blob + b->oDblocks); sim.flags = b->dflags.as<uint32_t>();
+      sim.gLo = 0; sim.gHi = 1; sim.sampleN = K; sim.Spad = kWave;   // one group; the lanes K.. are simulated and never read (their clamps not counted)
+      sim.U = d_U.as<uint32_t>(); sim.pair = b->tables->ptrs.pair; sim.tieThr = c->tieThr;
+      sim.workCounter = d_cnt.as<unsigned int>(); sim.clampCount = reinterpret_cast<unsigned long long *>(ri32);
+      sim.codesAll = d_codes.as<uint8_t>();
+      DecoyArgs da{};
+      da.blob = blob; da.dblocks = sim.dblocks; da.flags = sim.flags; da.codesAll = d_codes.as<uint8_t>(); da.sigmaAll = d_sigma.as<uint8_t>();
+      da.vblocks = d_vdb.as<DevBlock>(); da.vflags = d_vflags.as<uint32_t>(); da.nDecoys = K;
+      NativeArgs na{};
+      na.blob = blob; na.dblocks = d_vdb.as<DevBlock>(); na.flags = d_vflags.as<uint32_t>(); na.pair = sim.pair;
+      na.hssCap = b->hssCap; na.tieThr = c->tieThr;
+      for (size_t r = 0; r < rounds.size(); r++) {
+        const DecoyRound &rd = rounds[r];
+        const Round &ri = rinfo[r];
+        const size_t lds = null_generic_lds_bytes(ri.maxN, ri.maxNodes);
+        const auto key = std::make_tuple(NullKind::GenericSim, 0, lds);
+        const auto it = c->occ.find(key);
+        const int occ = std::max(1, it != c->occ.end() ? it->second : (c->occ[key] = generic_occupancy(NullKind::GenericSim, lds)));
+        HIP_TRY(hipMemsetAsync(d_cnt.p, 0, 8 * sizeof(uint32_t), st));   // (behind the round before: one stream)
+        sim.classBlocks = d_up.as<int>() + rd.first; sim.nClassBlocks = rd.count; sim.codesStride = rd.stride.codes;
+        launch_generic(NullKind::GenericSim, sim, static_cast<int>(std::min<long long>(rd.count, static_cast<long long>(c->numCU) * occ)), lds, d_codes.as<uint8_t>(), st);
+        HIP_TRY(hipGetLastError());
+        da.blocks = sim.classBlocks; da.codesStride = rd.stride.codes; da.sigmaStride = rd.stride.sigma;
+        launch_decoy_sigma(da, rd.count, ri.maxNK, st);
+        HIP_TRY(hipGetLastError());
+        // the round's (block, decoy) numbers start at 0: its counts at the round's place in the call's arrays
+        const size_t v0 = static_cast<size_t>(rd.first) * K;
+        na.hss = d_hss.as<DevHss>(); na.hssCount = ri32 + 4 + v0 * 6;
+        for (size_t x = ri.first; x < ri.first + ri.nLaunch; x++) {
+          const Launch &l = launches[x];
+          NativeArgs nc = na;
+          nc.blocks = d_up.as<int>() + l.at;
+          if (l.NK) {
+            nc.nItems = static_cast<int>(l.count) * 6;
+            nc.tile = d_tile.as<float>(); nc.tileStride = static_cast<size_t>(kWave) * l.smax;
+            if (l.all) { nc.sAll = d_all.as<float>(); nc.sAllSites = l.smax; }
+            if (!launch_native_dp(l.NK, nc, static_cast<int>(native_grid(c, static_cast<size_t>(nc.nItems), l.smax, mode)), st))
+              return fail(RC_ERR_UNSUPPORTED, "no native DP kernel for this number of rows");
+            if (nc.sAll) launch_native_scan(nc, st);
+          } else {
+            for (size_t lo = 0; lo < l.count; lo += chunk) {
+              NativeArgs ng = nc;
+              ng.blocks = nc.blocks + lo;
+              launch_native_dp_generic(ng, static_cast<int>(std::min<size_t>(chunk, l.count - lo)), d_scratch.as<float>(), wide_stride(l), st);
+            }
+          }
+          HIP_TRY(hipGetLastError());
+        }
+        // the round's records behind those of the rounds before (the total runs on): where a slot's records start is offsets[slot]
+        launch_hss_pack(d_hss.as<DevHss>(), na.hssCount, b->hssCap, rd.count * K * 6, packed, ri32 + 4 + slots + v0 * 6, ri32 + 2, st);
+        HIP_TRY(hipGetLastError());
+      }
+      HIP_TRY(hipMemcpyAsync(res.get(), d_res.p, headBytes + guess * sizeof(DevHss), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));   // (the streams are non-blocking: nothing else would wait for the copy)
+      total = static_cast<size_t>(reinterpret_cast<const int32_t *>(res.get())[2]);
+      if (total > guess) {   // (more than 16 records per (block, decoy) on average: the rest with a second copy)
+        const size_t at = headBytes + guess * sizeof(DevHss);
+        std::unique_ptr<uint8_t[]> more(new uint8_t[headBytes + total * sizeof(DevHss)]);
+        std::memcpy(more.get(), res.get(), at);
+        res = std::move(more);
+        HIP_TRY(hipMemcpyAsync(res.get() + at, d_res.as<uint8_t>() + at, (total - guess) * sizeof(DevHss), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+      }
+      return RC_OK;
+    }();
+    if (rc != RC_OK) { if (launched) (void)hipStreamSynchronize(st); return rc; }
+  }
+  // the lists, each as rc_batch_hss makes a block's: the six strand x frame lists up to their first non-positive score, by descending score
+  // (ties in that order), coordinates and p-value.  Two passes over the listed blocks, on host threads where the call is large: the lists'
+  // lengths, then -- their places known -- the records straight into the caller's array.
+  const int32_t *hi = reinterpret_cast<const int32_t *>(res.get());
+  const DevHss *rec = reinterpret_cast<const DevHss *>(res.get() + resInts * sizeof(int32_t));
+  const size_t nLists = static_cast<size_t>(n_blks) * K;
+  std::vector<int64_t> at(nLists + 1, 0);
+  std::atomic<bool> overflow{false};
+  const unsigned threads = V >= 4096 ? static_cast<unsigned>(std::min(16, c->hostThreads > 0 ? c->hostThreads : effective_cpus())) : 1u;
+  const auto slot_len = [&](size_t slot) {   // records of a slot in front of its first non-positive score (score.c:1112,1121)
+    const int cnt = hi[4 + slot];
+    const DevHss *r = rec + hi[4 + slots + slot];
+    int n = 0;
+    while (n < cnt && r[n].score > 0.0f) n++;
+    return n;
+  };
+  parallel_for(n_blks, threads, [&](int k) {
+    if (posOf[static_cast<size_t>(k)] < 0) return;
+    for (int d = 0; d < K; d++) {
+      int64_t n = 0;
+      for (int combo = 0; combo < 6; combo++) {
+        const size_t slot = (static_cast<size_t>(posOf[static_cast<size_t>(k)]) * K + d) * 6 + combo;
+        if (hi[4 + slot] > b->hssCap) { overflow.store(true); return; }
+        n += slot_len(slot);
+      }
+      at[static_cast<size_t>(k) * K + d + 1] = n;
+    }
+  });
+  if (overflow.load()) return fail(RC_ERR_UNSUPPORTED, "HSS buffer overflow");
+  for (size_t l = 0; l < nLists; l++) at[l + 1] += at[l];
+  parallel_for(n_blks, threads, [&](int k) {
+    if (posOf[static_cast<size_t>(k)] < 0) return;
+    const int blk = blks ? blks[k] : k;
+    std::vector<rc_hss> all;
+    for (int d = 0; d < K; d++) {
+      const size_t l = static_cast<size_t>(k) * K + d;
+      if (at[l] >= cap) return;   // (nothing of this list, nor of the block's later ones, has room)
+      all.clear();
+      for (int combo = 0; combo < 6; combo++) {
+        const size_t slot = (static_cast<size_t>(posOf[static_cast<size_t>(k)]) * K + d) * 6 + combo;
+        const DevHss *r = rec + hi[4 + slots + slot];
+        for (int i = 0, n = slot_len(slot); i < n; i++) {
+          // (an insertion sort: what std::stable_sort by descending score leaves, without its buffer -- a list has a handful of records)
+          size_t to = all.size();
+          all.push_back(hss_of(b->meta[blk], b->fit[blk], r[i]));
+          for (; to > 0 && all[to - 1].score < all[to].score; to--) std::swap(all[to - 1], all[to]);
+        }
+      }
+      for (size_t i = 0; i < all.size() && at[l] + static_cast<int64_t>(i) < cap; i++) out[at[l] + static_cast<int64_t>(i)] = all[i];
+    }
+  });
+  std::memcpy(offsets, at.data(), (nLists + 1) * sizeof(int64_t));
+  if (clamped) { *clamped = 0; if (P > 0) std::memcpy(clamped, res.get(), sizeof(int64_t)); }
   return RC_OK;
 }
 

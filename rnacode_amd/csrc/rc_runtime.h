@@ -309,6 +309,8 @@ inline size_t al256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 constexpr size_t kBtMaxBytes = static_cast<size_t>(256) << 20;
 // rc_batch_segment_null: bytes of sigma codes one round of distinct blocks may take (RC_SEGNULL_MAX_BYTES overrides); a block is never cut
 constexpr size_t kSegNullMaxBytes = static_cast<size_t>(256) << 20;
+// rc_batch_decoys: bytes of sigma codes, sigma tables and kept matrices one round of listed blocks may take (RC_DECOY_MAX_BYTES overrides); a block is never cut
+constexpr size_t kDecoyMaxBytes = static_cast<size_t>(256) << 20;
 
 
 struct TableSet;
