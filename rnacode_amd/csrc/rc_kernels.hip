@@ -924,7 +924,7 @@ __global__ __launch_bounds__(256) void k_evd_fit_f64(const double *x, int n, Fit
   if (threadIdx.x == 0) { out->rc = rc; out->mu = rc ? mu : 0; out->lambda = lambda; out->better = 0; }
 }
 
-// getHSS's fold (SampleScan, rc_null_kernel.h) over the S values a ROWS launch of k_null left in its buffers: one wavefront per
+// getHSS's fold (SampleScan, rc_scan_core.h) over the S values a ROWS launch of k_null left in its buffers: one wavefront per
 // (block, 64-sample group, strand x frame), lane = sample, entries in the reference's order (row by row), eight loads ahead of the
 // fold.  The maxima meet those of the other five parts in an atomic max on the preset -1.
 __global__ __launch_bounds__(64) void k_null_rowscan(NullArgs A, const DevBlock *__restrict__ dblocks, const int *__restrict__ classBlocks,
@@ -948,7 +948,6 @@ __global__ __launch_bounds__(64) void k_null_rowscan(NullArgs A, const DevBlock 
   constexpr int kAhead = 64;
   const int total = sites * (sites + 1) / 2;
   int a = 0, slotsLeft = sites;
-  float j2f = 1.0f;
   sample_scan_row_begin(st, best, 0u);
   for (int base = 0; base < total; base += kAhead) {
     float v[kAhead];
@@ -957,11 +956,11 @@ __global__ __launch_bounds__(64) void k_null_rowscan(NullArgs A, const DevBlock 
 #pragma unroll
     for (int u = 0; u < kAhead; u++) {
       if (base + u < total) {
-        if (a < sites - 1) { sample_scan_step(st, v[u], j2f, negTie); j2f += 2.0f; }   // (the last row's one slot: the frame's final entry, never computed)
+        if (a < sites - 1) sample_scan_step(st, v[u], negTie);   // (the last row's one slot: the frame's final entry, never computed)
         if (--slotsLeft == 0) {
-          sample_scan_row_end(st, static_cast<uint32_t>(a));
+          sample_scan_row_end(st, static_cast<uint32_t>(a), static_cast<uint32_t>(a < sites - 1 ? sites : sites - 1));
           a++;
-          if (a < sites) { sample_scan_row_begin(st, best, static_cast<uint32_t>(a)); slotsLeft = sites - a; j2f = static_cast<float>(2 * a + 1); }
+          if (a < sites) { sample_scan_row_begin(st, best, static_cast<uint32_t>(a)); slotsLeft = sites - a; }
         }
       }
     }

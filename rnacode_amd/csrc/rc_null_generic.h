@@ -585,12 +585,12 @@ __device__ __forceinline__ void generic_body(const NullArgs &A, const uint8_t *_
               constexpr int u = decltype(uc)::value;
               if ((validA >> u) & 1u) {   // a <= j0 + u < jendA
                 const float v = fmaxf(sumA.template at<u>(), Delta) / nkf;
-                sample_scan_step(st, v, static_cast<float>(2 * (j0 + u) + 1), negTie);
+                sample_scan_step(st, v, negTie);   // (validA's bits are the row's entries in order, none left out)
               }
               if ((validB >> u) & 1u) rowbuf[static_cast<size_t>(j0 + u) * kWave] = fmaxf(sumB.template at<u>(), Delta) / nkf;
             });
           }
-          sample_scan_row_end(st, static_cast<uint32_t>(a));
+          sample_scan_row_end(st, static_cast<uint32_t>(a), static_cast<uint32_t>(jendA));
           if (b < sites) {   // row a + 1 through the scan, eight entries fetched at a time
             sample_scan_row_begin(st, best, static_cast<uint32_t>(b));
             for (int j = b; j < jendB; j += 8) {
@@ -599,9 +599,9 @@ __device__ __forceinline__ void generic_body(const NullArgs &A, const uint8_t *_
               for (int t = 0; t < 8; t++) v[t] = rowbuf[static_cast<size_t>(j + t < jendB ? j + t : jendB - 1) * kWave];
 #pragma unroll
               for (int t = 0; t < 8; t++)
-                if (j + t < jendB) sample_scan_step(st, v[t], static_cast<float>(2 * (j + t) + 1), negTie);
+                if (j + t < jendB) sample_scan_step(st, v[t], negTie);
             }
-            sample_scan_row_end(st, static_cast<uint32_t>(b));
+            sample_scan_row_end(st, static_cast<uint32_t>(b), static_cast<uint32_t>(jendB));
           }
         }
         sample_scan_last(st, best);

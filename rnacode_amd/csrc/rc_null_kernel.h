@@ -4,7 +4,7 @@
 //
 // In the order of the file:
 //   shared device pieces     ref_max / pair_step (the recurrence), scan_step and native_scan_rows (getHSS for the native block), KRegs and
-//                            static_for (per-sequence registers), div_by_nk, SampleScan (getHSS per null sample)
+//                            static_for (per-sequence registers), div_by_nk (SampleScan, getHSS per null sample: rc_scan_core.h)
 //   null_body                the work queues and the sharing of a launch's last items; phase A (simulation -> sigma codes in the staging
 //                            scratch); phase B per strand x frame: staging of the codes, the fetch_* lambdas and load_words, lookup, finish,
 //                            the cell kinds (fast, pristine, tail, event -- with the reference's maximum for NaN tables), next_event,
@@ -19,6 +19,7 @@
 
 #include "rc_device.h"
 #include "rc_launch.h"
+#include "rc_scan_core.h"
 #include "rc_sim_core.h"
 
 namespace rc {
@@ -142,57 +143,12 @@ template <int NK, bool EXACT> __device__ __forceinline__ float div_by_nk(float x
   }
 }
 
-// getHSS's state machine as the null samples need it (score.c:892-959): only the best emitted score
-// matters.  The serial rule per entry (a, j) with value v > 0 is
-//   open segment ended before row a (segmentEnd < a, currMax > 0)  -> report it, start (v, a, j)
-//   else v > currMax, or |v - currMax| < 1e-4 and j - a >= segmentEnd - segmentStart -> replace.
-// Restated per row so that an entry costs 4 compares and 2 selects:
-//  * A segment that ended before row a can no longer change, and it is reported either at the next
-//    positive entry or at the frame's final entry -- so reporting it at the START of row a and
-//    turning the state into "no segment" (currMax 0, which any positive v replaces through v > currMax)
-//    yields the same set of reported values.
-//  * Within row a the state is either carried in (segment (ss0, se0) with se0 >= a) or was set in
-//    this row at some j' (segment (a, j')).  "j - a >= segmentEnd - segmentStart" is j >= se0 - ss0 + a
-//    for the former and j >= j' (always true later in the row) for the latter: one threshold Q per
-//    lane, kept as 2(se0 - ss0 + a) when carried in and 2j' + 1 when set in this row, compared with
-//    2j + 1; its low bit tells at the end of the row which of the two happened.
-//  * v <= currMax together with |v - currMax| < thr is fl(v - currMax) > -thr.
-struct SampleScan {
-  float cm;        // currMax
-  float Q;         // see above, as a float (integers < 2^24 are exact): valid inside a row
-  uint32_t se;     // segmentEnd, valid between rows
-  uint32_t len;    // segmentEnd - segmentStart, valid between rows
-};
-__device__ __forceinline__ void sample_scan_row_begin(SampleScan &st, float &best, uint32_t a) {
-  const bool done = (st.cm > 0.0f) & (st.se < a);                 // score.c:900
-  best = (done & (st.len >= 2u) & (st.cm > best)) ? st.cm : best;  // minSegmentLength, score.c:902
-  st.cm = done ? 0.0f : st.cm;
-  st.len = done ? 0u : st.len;
-  st.Q = static_cast<float>(2u * (st.len + a));
-}
-// every entry except the frame's final one; j2 = 2j + 1, wave-uniform but held in a VGPR as a float: the
-// caller advances it with a double-rate v_add_f32 instead of copying a scalar counter per entry
+// getHSS's state machine as the null samples need it (score.c:892-959): SampleScan and sample_scan_row_begin / _step / _row_end / _last
+// are in rc_scan_core.h, which the host compiles too (tools/verify_scan_core.cpp), with the proof of the restatement.
 // (Round 6 built the step with a rare-arm branch -- v > currMax and the band test fl(v - currMax) > -thr as two compares into scalar lane masks,
 // the tie rule's other two compares only where some lane sits in the band (score.c:953-954), the two selects written out: same decisions, two
 // v_cmp fewer in the common arm, a scalar and-not, compare and branch more.  Product builds A/B on the headline: 42.68 against 42.80 ms per launch --
 // nothing, and two registers more in the one-row kernels (a wavefront per SIMD lost at 11, 23 and 24 rows).  Taken back; profiles/r06/ab_scan_tie_branch.txt.)
-__device__ __forceinline__ void sample_scan_step(SampleScan &st, float v, float j2, float negTieThr) {
-  const float d = v - st.cm;
-  const bool upd = (v > st.cm) | ((v > 0.0f) & (d > negTieThr) & (st.Q <= j2));   // score.c:953-954
-  st.cm = upd ? v : st.cm;
-  st.Q = upd ? j2 : st.Q;
-}
-__device__ __forceinline__ void sample_scan_row_end(SampleScan &st, uint32_t a) {
-  const uint32_t q = static_cast<uint32_t>(st.Q);
-  const bool inrow = (q & 1u) != 0u;
-  const uint32_t j = q >> 1;
-  st.se = inrow ? j : st.se;
-  st.len = inrow ? j - a : st.len;
-}
-// the final entry of a frame is entered unconditionally and always reports the open segment
-__device__ __forceinline__ void sample_scan_last(const SampleScan &st, float &best) {
-  best = ((st.len >= 2u) & (st.cm > best)) ? st.cm : best;
-}
 
 // Read-only inputs are separate __restrict__ kernel parameters (not members of the by-value
 // argument block) so that the compiler may prove them unclobbered and fetch the wave-uniform
@@ -1027,8 +983,8 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
           return end;
         };
         SampleScan st{0.0f, 0.0f, 0u, 0u};
-        float two_v;
-        asm volatile("v_mov_b32 %0, 2.0" : "=v"(two_v));
+        float negTwo_v;   // what the scan's X moves by from entry to entry, in a register (sample_scan_step)
+        asm volatile("v_mov_b32 %0, -2.0" : "=v"(negTwo_v));
         const float negTie = -A.tieThr;
         // The part of a span j .. e - 1 that lies in front of the suffix cache, in pairs of cells on two register sets (see "Two cells of distance"
         // at the one-row loops below): act(w, jj, jn) is the cell of site jj on the set w, which fetches site jn behind its look-ups.
@@ -1164,14 +1120,12 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
               uint32_t wcur[NCW];
               load_words(a, wcur);
               int j = a;
-              float j2f = static_cast<float>(2 * a + 1);
               float wvA = 0.0f, wvB = 0.0f;
               asm volatile("v_mov_b32 %0, 0" : "=v"(wvA));
               asm volatile("v_mov_b32 %0, 0" : "=v"(wvB));
               {   // row a's first cell (site a: no event)
                 const float v = pristine_cell(wcur, wvA, a + 1, std::true_type{});
-                sample_scan_step(st, v, j2f, negTie);
-                asm volatile("v_add_f32 %0, %1, %0" : "+v"(j2f) : "v"(two_v));
+                sample_scan_step(st, v, negTie, negTwo_v);
                 j = a + 1;
               }
               const int extra = (sites - 1 - a > kBuf) ? sites - 1 - a - kBuf : 0;   // row a + 1 has sites - 1 - a cells: the last kBuf are buffered
@@ -1184,10 +1138,8 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
               auto pair_cell = [&](uint32_t (&w)[NCW], int jj, int jn, auto kd, auto &&fn) {
                 float vB;
                 const float v = fn(w, jn, vB, kd);
-                sample_scan_step(st, v, j2f, negTie);
+                sample_scan_step(st, v, negTie, negTwo_v);
                 keep(vB, jj);
-                const float two_c = two_v;   // (a copy: an asm operand alone does not make a generic lambda capture the variable)
-                asm volatile("v_add_f32 %0, %1, %0" : "+v"(j2f) : "v"(two_c));
               };
               // the cells j .. e - 1 of one kind; codes from L2: in front of the suffix cache with two cells of fetch distance on two register sets
               // (see "Two cells of distance" at the one-row loops below)
@@ -1202,9 +1154,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                   for (const int pe = e < b0 ? e : b0; j < pe; j++) {   // (j < b0 <= sites - 1: the next site exists)
                     float vB;
                     const float v = fn(wcur, j + 1, vB, std::true_type{});
-                    sample_scan_step(st, v, j2f, negTie);
-                    const float two_c = two_v;
-                    asm volatile("v_add_f32 %0, %1, %0" : "+v"(j2f) : "v"(two_c));
+                    sample_scan_step(st, v, negTie, negTwo_v);
                   }
                   const int ge = e < sites - 1 ? e : sites - 1;
                   for (; j + kGroup <= ge; j += kGroup) {
@@ -1213,9 +1163,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                     static_for<kGroup>([&](auto uc) {
                       constexpr int u = decltype(uc)::value;
                       const float v = fn(wcur, StagedSite<u * NCW * kWave * 4>{at}, vB[u], std::true_type{});
-                      sample_scan_step(st, v, j2f, negTie);
-                      const float two_c = two_v;
-                      asm volatile("v_add_f32 %0, %1, %0" : "+v"(j2f) : "v"(two_c));
+                      sample_scan_step(st, v, negTie, negTwo_v);
                     });
                     // the group's values into entries idx .. idx + kGroup - 1 (idx >= 0: j >= b0), one index for all: the scheduling
                     // barriers keep the indexed moves side by side, where one s_set_gpr_idx_on .. off window takes them all
@@ -1266,19 +1214,17 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
               }
 #pragma unroll
               for (int x = 0; x < NCW; x++) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wcur[x]));
-              sample_scan_row_end(st, static_cast<uint32_t>(a));
+              sample_scan_row_end(st, static_cast<uint32_t>(a), static_cast<uint32_t>(sites));
               pendRow = a + 1; pendExtra = extra; pendN = sites - b0;
               a += 2;
             } else {
               // ---- one row: row `a`, or the row left over from a pair (its first pendExtra cells, then its buffered values).  The walk of
-              // the one-row kernels below, without their deep fetches.  (Its span loops stand here and not in a lambda like `span` there,
-              // and j2f in front of the row's begin: either changed, the compiler names every two-row kernel's registers differently --
-              // instruction counts within a few lines, one kernel's register figures moved, speed not measured.  That only matters while a change must leave the machine
-              // code byte for byte as it was; profiles/r07/refactor_isa_identity.txt.)
+              // the one-row kernels below, without their deep fetches.  (Its span loops stand here and not in a lambda like `span` there:
+              // changed, the compiler names every two-row kernel's registers differently -- instruction counts within a few lines, one kernel's
+              // register figures moved, speed not measured; profiles/r07/refactor_isa_identity.txt.)
               const bool pend = pendRow >= 0;
               const int row = pend ? pendRow : a;
               const int jend = pend ? row + pendExtra : ((row == sites - 1) ? sites - 1 : sites);
-              float j2f = static_cast<float>(2 * row + 1);
               sample_scan_row_begin(st, best, static_cast<uint32_t>(row));
               static_for<NK>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
@@ -1288,10 +1234,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
               uint32_t wcur[NCW];
               load_words(row, wcur);
               int j = row;
-              auto take = [&](float v) {
-                sample_scan_step(st, v, j2f, negTie);
-                asm volatile("v_add_f32 %0, %1, %0" : "+v"(j2f) : "v"(two_v));
-              };
+              auto take = [&](float v) { sample_scan_step(st, v, negTie, negTwo_v); };
               auto one = [&](auto &&cell) {   // cell(w, jn, kind) -> S
                 const int jn = j + 1 < sites ? j + 1 : j;
                 take(cell(wcur, jn, std::true_type{}));
@@ -1343,15 +1286,14 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
 #pragma unroll
                   for (int idx = 0; idx < kBuf; idx++) {
                     if (idx >= pendN) return;
-                    sample_scan_step(st, buf[idx], j2f, negTie);
-                    asm volatile("v_add_f32 %0, %1, %0" : "+v"(j2f) : "v"(two_v));
+                    sample_scan_step(st, buf[idx], negTie, negTwo_v);
                   }
                 }();
                 pendRow = -1;
               } else {
                 a += 1;
               }
-              sample_scan_row_end(st, static_cast<uint32_t>(row));
+              sample_scan_row_end(st, static_cast<uint32_t>(row), static_cast<uint32_t>(row == sites - 1 ? sites - 1 : sites));
             }
           }
         } else {
@@ -1386,14 +1328,10 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
             load_words(a, wcur);
             const int jend = (a == sites - 1) ? sites - 1 : sites;   // the frame's final entry is handled below
             int j = a;
-            float j2f = static_cast<float>(2 * a + 1);   // 2j + 1 of the cell being entered
             // what becomes of a cell's S value: the item's buffer (rows split over workgroups), or getHSS's fold
             auto take = [&](float v) {
               if constexpr (ROWS) { *sdst = v; sdst += kWave; }
-              else {
-                sample_scan_step(st, v, j2f, negTie);
-                asm volatile("v_add_f32 %0, %1, %0" : "+v"(j2f) : "v"(two_v));
-              }
+              else sample_scan_step(st, v, negTie, negTwo_v);
             };
             // one cell on wcur: the site whose words are fetched behind the look-ups, EXACT's second register set, the cell, its scan step
             auto one = [&](auto &&cell) {   // cell(w, jn, kind) -> S
@@ -1466,7 +1404,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
               }
             }
             if constexpr (ROWS) { if (a == sites - 1) sdst += kWave; }   // (the frame's final entry has a slot of its own; it is never computed)
-            else sample_scan_row_end(st, static_cast<uint32_t>(a));
+            else sample_scan_row_end(st, static_cast<uint32_t>(a), static_cast<uint32_t>(jend));
           }
         }
         if constexpr (!ROWS) sample_scan_last(st, best);   // entry (sites-1, sites-1): its own value can never be reported

@@ -92,9 +92,9 @@ __device__ __forceinline__ void tiled_body(const NullArgs &A, const uint8_t *__r
     const int sidx = grp * kWave + lane;
     float best = -1.0f;
     const float negTie = -A.tieThr;
-    float omega_v, two_v;
+    float omega_v, negTwo_v;
     asm volatile("v_mov_b32 %0, %1" : "=v"(omega_v) : "s"(omega));   // per-lane copies: a v_add_f32 with two VGPR operands issues at the full rate (tools/microbench.hip)
-    asm volatile("v_mov_b32 %0, 2.0" : "=v"(two_v));
+    asm volatile("v_mov_b32 %0, -2.0" : "=v"(negTwo_v));
     for (int s = 0; s < 2; s++) {
       for (int f = 0; f < 3; f++) {
         const int sites = (L - f) / 3;
@@ -151,7 +151,6 @@ __device__ __forceinline__ void tiled_body(const NullArgs &A, const uint8_t *__r
               const int kk = t * KT + k;
               tab[k * kWave + lane] = kk < NK ? lut[(static_cast<size_t>(s) * NK + kk) * kLutSize + lane] : 0.0f;
             });
-            float j2f = static_cast<float>(2 * a + 1);
             // one cell on the register set (w, pv): the look-ups, the set refilled for the cell after next, `step` on every sequence, the sum onward
             auto cell = [&](int j, uint32_t (&w)[WPT], float &pv, auto &&step) {
               float sig[KT];
@@ -171,8 +170,7 @@ __device__ __forceinline__ void tiled_body(const NullArgs &A, const uint8_t *__r
                 // score.c:843 with S[b][i-1] = S[b][i-2] = 0: max(sum, Delta) / (N - 1).  Only positive values ever reach a sample's result, and for
                 // Delta < 0 a positive one is sum / (N - 1): the maximum is left out (batches with Delta >= 0 take the SEM instantiation)
                 const float v = SEM ? ref_max<true>(sum, Delta) / nkf : sum / nkf;
-                sample_scan_step(st, v, j2f, negTie);
-                asm volatile("v_add_f32 %0, %1, %0" : "+v"(j2f) : "v"(two_v));
+                sample_scan_step(st, v, negTie, negTwo_v);
               } else if (j >= jp) {
                 rowLds[(j - jp) * kWave + lane] = sum;
               } else {
@@ -250,7 +248,7 @@ __device__ __forceinline__ void tiled_body(const NullArgs &A, const uint8_t *__r
               }
             }
           }
-          sample_scan_row_end(st, static_cast<uint32_t>(a));
+          sample_scan_row_end(st, static_cast<uint32_t>(a), static_cast<uint32_t>(jend));
         }
         sample_scan_last(st, best);
       }

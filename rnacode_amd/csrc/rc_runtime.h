@@ -357,6 +357,7 @@ struct rc_ctx {
   float tieThr = 0.0f;
   std::map<std::tuple<NullKind, int, size_t>, int> occ;   // (kind, N-1 or tile size, dynamic LDS bytes) -> resident workgroups per CU (rc_schedule.cpp, occupancy)
   size_t ldsPerCU = 160 * 1024;
+  int dualRows = 1;             // RC_DUAL_ROWS=0: no class takes the two-row k_null, 3..6 rows walk one row per pass like the others (A/B; tests of that walk)
   int rowSplit = 1;             // RC_ROW_SPLIT=0: never split a strand x frame part's rows over workgroups (tiny batches; A/B)
   int highOccupancy = 1;        // RC_HIGH_OCCUPANCY: 1 k_null_occ (one more wavefront per SIMD) for batches of one row-count class, 0 never, 2 always (A/B)
   size_t ldsMaxBytes = 13312;   // per wavefront: >= 12 wavefronts per CU; measured crossover against reading the codes from L2 (cols 150: 52.0 vs 54.0 ms, cols 180: 41.5 vs 39.3 ms)
@@ -514,7 +515,7 @@ struct RunEnv {
   int nativeMode;     // native_grid's mode
   bool fat;           // every class of the batch takes the two-row k_null (fat_class) and nothing runs beside it
   // a class of N-1 other sequences takes the two-row k_null (its codes staged in LDS where they fit, else from L2 when that is faster)
-  bool two_rows(int NK) const { return NK <= kDualRowsMaxNK && (NK == 2 || fat); }
+  bool two_rows(int NK) const { return c->dualRows && NK <= kDualRowsMaxNK && (NK == 2 || fat); }
 };
 
 // functions that cross unit boundaries

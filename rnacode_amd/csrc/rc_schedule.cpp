@@ -23,7 +23,7 @@ size_t native_grid(const rc_ctx *c, size_t items, int smax, int mode) {
 // every sub-batch boundary to be paid back (RC_FAT_STREAM_MIN_ITEMS).  Everything else keeps the one-row instantiations (74 VGPRs)
 // and the small kernels beside them.
 bool fat_class(const rc_batch *b, const rc_ctx *c, int NK, int maxL) {
-  if (NK < 3 || NK > kDualRowsMaxNK || b->allExact) return false;
+  if (!c->dualRows || NK < 3 || NK > kDualRowsMaxNK || b->allExact) return false;
   const size_t lds = static_cast<size_t>(maxL / 3) * ((NK + 4) / 5) * kWave * sizeof(uint32_t);
   return lds <= c->ldsMaxBytes;   // (longer blocks: the two-row kernel from L2 gains 3-4 % on the launch and loses it again to the native-block kernels queued in front)
 }
