@@ -361,7 +361,8 @@ int rc_batch_segment_null(const rc_batch *b, const rc_bt_range *ranges, int32_t 
  *     those bits, and the list is empty where that value is -1.
  *   - The drivers pass seed_base + sampleN: the first seeds the fit did not see.
  *   - Decoys share the null model of the p-values.  They calibrate multiplicity -- how many lines of a listing filtered at p <= t are
- *     expected to be false: (decoy HSS with p <= t) / n_decoys against (listed HSS with p <= t) --, not model misfit.
+ *     expected to be false: (decoy HSS with p <= t) / n_decoys against (listed HSS with p <= t) --, not model misfit: for that, compare
+ *     them with the decoys made from the data itself, rc_batch_decoys_shuffled.
  * A block index out of range, n_decoys outside 1..64 or a batch that has not completed a run returns RC_ERR_ARG; every argument is checked
  * before the device is touched, and on an error the outputs are left alone.  Works on a batch rc_stream_next handed out until it is
  * recycled, and leaves the batch's maxima, fit, HSS, timings and rc_batch_clamped as they are.
@@ -370,6 +371,25 @@ int rc_batch_segment_null(const rc_batch *b, const rc_bt_range *ranges, int32_t 
  * per call; a single block may exceed it; the result does not depend on it); one synchronisation and one copy back per call. */
 int rc_batch_decoys(const rc_batch *b, const int32_t *blks, int32_t n_blks, uint32_t seed, int32_t n_decoys, rc_hss *out, int64_t cap,
                     int64_t *offsets /* n_blks * n_decoys + 1 */, int64_t *clamped /* may be NULL */);
+
+/* Shuffled decoys: the same listing for decoys made from the block itself -- its own columns, permuted among the columns with the same gap
+ * mask -- instead of alignments simulated under the block's model.  Where the p-values' null model fits the data the two kinds of decoy
+ * list alike; where they disagree, the disagreement is the model's misfit (rate heterogeneity, local composition, indel context).
+ * The decoy of a block with `cols` columns and seed s (decoy d of a call: seed + d):
+ *   - mask(c) = the set of rows, the reference included, whose character in column c is '-' (only '-': N, IUPAC letters and lower case
+ *     travel with their column); two columns are in one class iff their masks are equal;
+ *   - fmix(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16 (mod 2^32);
+ *     key(s, c) = fmix(fmix(s) ^ (c * 0x9E3779B1 mod 2^32))   -- key(112, 0) = 0xF8C35C5F;
+ *   - for a class's columns c_1 < .. < c_m and the same columns s_1 .. s_m sorted by (key(s, c), c), decoy column c_t holds, in every
+ *     row, the characters of column s_t; the '-' strand is the reverse complement of the shuffled rows.
+ * Every row keeps its gaps, so the decoy has the block's coordinates, gap tables, base frequencies, tree, score tables and fit; only the
+ * characters a codon's columns hold differ.  The decoy depends on seed + d and the block only (rnacode_amd.decoys.shuffle_columns gives
+ * its rows).  Arguments, outputs, errors, rounds and budget are rc_batch_decoys'; nothing is drawn from a distribution, so there is no
+ * clamp count.  Cost: the class ids of every distinct listed block once per call on the host, one sort of `cols` 64-bit words per
+ * (block, decoy) -- in LDS up to 4096 columns (RC_SHUFFLE_LDS_COLS overrides, 1..8192, read per call; the result does not depend on it),
+ * in device memory above --, then the native block's DP for every (block, decoy). */
+int rc_batch_decoys_shuffled(const rc_batch *b, const int32_t *blks, int32_t n_blks, uint32_t seed, int32_t n_decoys, rc_hss *out, int64_t cap,
+                             int64_t *offsets /* n_blks * n_decoys + 1 */);
 
 /* The substitution matrix and genetic code the scorer uses, for callers that render results
  * (getScoringMatrix() score.c:50-76 and transcode[4][4][4] code.c:28-39, which src/postscript.c:362,412

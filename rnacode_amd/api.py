@@ -174,6 +174,8 @@ def lib():
         l.rc_batch_segment_null.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
         l.rc_batch_decoys.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(RcHss), C.c_int64,
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        l.rc_batch_decoys_shuffled.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(RcHss), C.c_int64,
+                                               C.POINTER(C.c_int64)]
         l.rc_evd_fit.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         l.rc_mt_stream.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_int32]
         l.rc_pvalue.argtypes = [C.c_float, C.c_float, C.c_float]
@@ -201,13 +203,15 @@ def lib():
     return _lib
 
 
+DECOY_KINDS = ("simulated", "shuffled")   # Batch.decoys' kinds, --decoy-kind of both drivers
+
 EXPORTED_SYMBOLS = [
     "rc_default_params_v2", "rc_last_error", "rc_device_count", "rc_ctx_create", "rc_ctx_destroy", "rc_ctx_trim", "rc_batch_create_v2",
     "rc_batch_destroy", "rc_batch_bind_maxima", "rc_batch_run", "rc_batch_run_async", "rc_batch_wait", "rc_batch_size", "rc_batch_block_error",
     "rc_batch_prep_timing", "rc_host_cpus", "rc_ctx_set_host_threads", "rc_ctx_host_threads", "rc_ctx_fit_exp_mode", "rc_stream_create_v2", "rc_stream_submit", "rc_stream_submit_bound",
     "rc_stream_next", "rc_stream_recycle", "rc_stream_pending", "rc_stream_plan", "rc_stream_destroy", "rc_set_stream_cache", "rc_batch_work", "rc_batch_timing", "rc_batch_null_kernel", "rc_batch_status",
     "rc_batch_models", "rc_batch_maxima", "rc_batch_maxima_all", "rc_batch_fit", "rc_batch_fit_all", "rc_batch_hss", "rc_batch_hss_all", "rc_batch_clamped",
-    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_batch_segment_scores", "rc_batch_segment_null", "rc_batch_decoys", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
+    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_batch_segment_scores", "rc_batch_segment_null", "rc_batch_decoys", "rc_batch_decoys_shuffled", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
     "rc_code_tables_for", "rc_genetic_code", "rc_species_tree_create", "rc_species_tree_destroy", "rc_species_tree_tips", "rc_species_tree_prune",
     "rc_fit_species_trees", "rc_fit_species_trees_device",
 ]
@@ -609,11 +613,14 @@ class Batch:
         o = list(offs)
         return [recs[o[i]:o[i + 1]] for i in range(self.n)]
 
-    def decoys(self, n_decoys: int, seed: Optional[int] = None, blks=None, with_clamped: bool = False):
-        """rc_batch_decoys: the complete HSS listing of n_decoys (1..64) null alignments per block of `blks` (default: all, in order) --
-        block x decoy x HSS, the dicts of scoreAln, p-values under the block's own fit.  Decoy d is the alignment of MT19937 seed
-        seed + d (default seed_base + sampleN: the first seeds the fit did not see); a block that was not scored has empty lists.
-        with_clamped: (lists, clamped draws of these simulations)."""
+    def decoys(self, n_decoys: int, seed: Optional[int] = None, blks=None, with_clamped: bool = False, kind: str = "simulated"):
+        """rc_batch_decoys / rc_batch_decoys_shuffled: the complete HSS listing of n_decoys (1..64) decoy alignments per block of `blks`
+        (default: all, in order) -- block x decoy x HSS, the dicts of scoreAln, p-values under the block's own fit.  kind "simulated": decoy d
+        is the null alignment of MT19937 seed seed + d; "shuffled": the block's own columns permuted within their gap classes by seed + d
+        (decoys.shuffle_columns).  The default seed is seed_base + sampleN: the first seeds the fit did not see; a block that was not scored
+        has empty lists.  with_clamped: (lists, clamped draws of these simulations -- 0 for shuffled decoys, which draw nothing)."""
+        if kind not in DECOY_KINDS:
+            raise ValueError(f"decoy kind must be one of {', '.join(DECOY_KINDS)}")
         if seed is None:
             seed = int(self.params.seed_base) + int(self.params.sampleN)
         if blks is None:
@@ -627,7 +634,10 @@ class Batch:
         cap = max(16 * n * max(k, 0), 1)   # (a second call only where the lists are longer than that)
         while True:
             out = (RcHss * cap)()
-            _check(lib().rc_batch_decoys(self._h, ptr, n, C.c_uint32(seed & 0xFFFFFFFF), k, out, cap, offs, C.byref(clamped)))
+            if kind == "shuffled":
+                _check(lib().rc_batch_decoys_shuffled(self._h, ptr, n, C.c_uint32(seed & 0xFFFFFFFF), k, out, cap, offs))
+            else:
+                _check(lib().rc_batch_decoys(self._h, ptr, n, C.c_uint32(seed & 0xFFFFFFFF), k, out, cap, offs, C.byref(clamped)))
             total = int(offs[n * k])
             if total <= cap:
                 break

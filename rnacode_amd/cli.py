@@ -5,7 +5,7 @@ options that concern the scoring path and the listings:
 
     python -m rnacode_amd.cli [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S]
                               [-e [-i CUTOFF] [-d DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null]]
-                              [--decoys K --decoys-out FILE]
+                              [--decoys K --decoys-out FILE [--decoy-kind simulated|shuffled]]
                               [-o OUT] [--trees SIDECAR | --species-tree NEWICK
                               [--species-tree-fit fixed|scale|branches]] [--write-trees SIDECAR] [FILE]
 
@@ -28,7 +28,8 @@ segment named in advance: how many of the -n null alignments score at least as h
 per sub-batch), and (null_ge + 1) / (n + 1).
 --decoys K with --decoys-out FILE (not in the reference) writes the complete listing of K null alignments per scored block, selected by
 --cutoff, -b and -r as the block's own HSS are (decoys.py; one rc_batch_decoys call per sub-batch, seeds seed_base + n ..: the first the
-fit did not see): what `python -m rnacode_amd.decoys` turns into a false discovery rate of the listing.
+fit did not see): what `python -m rnacode_amd.decoys` turns into a false discovery rate of the listing.  --decoy-kind shuffled lists, in
+the same file and with the same seeds, each block's own columns permuted within their gap classes instead (rc_batch_decoys_shuffled).
 Quirk kept from the reference: the 4th value of --pars goes to stopPenalty_0 (RNAcode.c:318)."""
 from __future__ import annotations
 
@@ -148,6 +149,9 @@ def build_parser() -> argparse.ArgumentParser:
                          "p-values are and selected by --cutoff, -b and -r as the block's own; python -m rnacode_amd.decoys turns the two "
                          "listings into q-values")
     ap.add_argument("--decoys-out", metavar="FILE", help="where the decoy listing goes: one line per decoy HSS")
+    ap.add_argument("--decoy-kind", metavar="KIND",
+                    help="with --decoys: simulated (the default: null alignments under the block's model) or shuffled (the block's own columns, "
+                         "permuted among the columns with the same gap pattern: decoys that do not share the p-values' model)")
     return ap
 
 
@@ -180,6 +184,10 @@ def _intake(a):
         raise _Refused("--decoys and --decoys-out go together")
     if a.decoys is not None and not 1 <= a.decoys <= 64:
         raise _Refused("--decoys takes a number of decoys from 1 to 64")
+    if a.decoy_kind is not None and a.decoys is None:
+        raise _Refused("--decoy-kind needs --decoys")
+    if a.decoy_kind is not None and a.decoy_kind not in api.DECOY_KINDS:
+        raise _Refused("--decoy-kind is simulated or shuffled")
     if a.regions:
         try:
             with open(a.regions) as fh:
@@ -314,7 +322,7 @@ def _list_batch(run: _Run, batch, base: int) -> None:
     # --regions-null: the regions' ranges (not the listed HSS, which were selected as maxima) with ONE call (rc_batch_segment_null)
     null_ge = batch.segment_null(nul.ranges)[1] if nul.ranges else None
     # --decoys: the decoy listings of the blocks the listing covers with ONE call (rc_batch_decoys)
-    decoyed = dict(zip(scored, batch.decoys(a.decoys, run.params.seed_base + run.params.sampleN, scored))) if "decoys_out" in side and scored else {}
+    decoyed = dict(zip(scored, batch.decoys(a.decoys, run.params.seed_base + run.params.sampleN, scored, kind=a.decoy_kind or "simulated"))) if "decoys_out" in side and scored else {}
     for i in range(batch.n):
         b = run.blocks[base + i]
         if base + i in run.refused:   # the species tree does not cover the block's rows

@@ -421,7 +421,7 @@ struct Listing {
 void usage() {
   std::fprintf(stderr, "usage: rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]\n"
                        "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null]]\n"
-                       "                   [--decoys K --decoys-out FILE]\n"
+                       "                   [--decoys K --decoys-out FILE [--decoy-kind simulated|shuffled]]\n"
                        "                   [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]\n"
                        "                   [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]\n"
                        "                   [--write-trees SIDECAR] [--dump-blocks] [FILE]\n"
@@ -448,7 +448,9 @@ void usage() {
                        "  --decoys K                 with --decoys-out: list the HSS of K (1..64) null alignments per scored block, simulated as the\n"
                        "                             samples behind the p-values are and selected by -p, -b and -r as the block's own\n"
                        "  --decoys-out FILE          the decoy listing, one line per decoy HSS: block decoy strand frame length from to name start\n"
-                       "                             end score p (python -m rnacode_amd.decoys turns it and the -t listing into q-values)\n");
+                       "                             end score p (python -m rnacode_amd.decoys turns it and the -t listing into q-values)\n"
+                       "  --decoy-kind KIND          with --decoys: simulated (the default) or shuffled -- the block's own columns, permuted among the\n"
+                       "                             columns with the same gap pattern: decoys that do not share the p-values' model\n");
 }
 
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -489,6 +491,7 @@ struct Run {
   std::vector<char> regionMatched;                        // set by the writer
   bool regionsNull = false;                               // --regions-null: null_ge and p_segment behind every --regions-out line
   int decoys = 0;                                         // --decoys: null alignments listed per scored block
+  bool decoysShuffled = false;                            // --decoy-kind shuffled: the block's own columns, permuted within their gap classes, instead
   // the writer: one thread, jobs in input order
   std::mutex jm;
   std::condition_variable jcv;
@@ -738,7 +741,7 @@ bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std
   return true;
 }
 
-// --decoys for every block the listing covers, while the batch is alive: ONE rc_batch_decoys call (a second one only where the lists are longer
+// --decoys for every block the listing covers, while the batch is alive: ONE rc_batch_decoys (--decoy-kind shuffled: rc_batch_decoys_shuffled) call (a second one only where the lists are longer
 // than the first one's room), seeds seed_base + n ..: the first the fit did not see, n the run's whole sample count.  Each decoy's HSS are
 // arranged as the block's own are; where the caller made the fits itself (the sample split) the p-values are theirs.
 bool add_decoys(const Run &R, rc_batch *b, Job &j, std::string &err, const std::vector<EvdFit> *fits) {
@@ -751,7 +754,9 @@ bool add_decoys(const Run &R, rc_batch *b, Job &j, std::string &err, const std::
   std::vector<rc_hss> recs(16 * nl);
   const uint32_t seed = R.par.seed_base + static_cast<uint32_t>(R.par.sampleN);
   for (;;) {
-    if (rc_batch_decoys(b, blks.data(), nb, seed, K, recs.data(), static_cast<int64_t>(recs.size()), offs.data(), nullptr) != RC_OK) { err = rc_last_error(); return false; }
+    const int rc = R.decoysShuffled ? rc_batch_decoys_shuffled(b, blks.data(), nb, seed, K, recs.data(), static_cast<int64_t>(recs.size()), offs.data())
+                                    : rc_batch_decoys(b, blks.data(), nb, seed, K, recs.data(), static_cast<int64_t>(recs.size()), offs.data(), nullptr);
+    if (rc != RC_OK) { err = rc_last_error(); return false; }
     if (offs[nl] <= static_cast<int64_t>(recs.size())) break;
     recs.resize(static_cast<size_t>(offs[nl]));
   }
@@ -1020,7 +1025,8 @@ int main(int argc, char **argv) {
   Listing &list = R.list;
   std::string file, outfile, trees, limit, devicesArg, speciesFile, writeTrees, regionsFile;
   int device = 0, subBlocks = 0, gpus = 1;   // subBlocks 0: the library's schedule
-  bool dumpBlocks = false, decoysGiven = false;
+  bool dumpBlocks = false, decoysGiven = false, decoyKindGiven = false;
+  std::string decoyKind;
   for (int a = 1; a < argc; a++) {
     const std::string o = argv[a];
     auto val = [&]() -> const char * { if (a + 1 >= argc) { usage(); std::exit(2); } return argv[++a]; };
@@ -1074,6 +1080,7 @@ int main(int argc, char **argv) {
     else if (o == "--regions-null") R.regionsNull = true;
     else if (o == "--decoys") { decoysGiven = true; R.decoys = std::atoi(val()); }
     else if (o == "--decoys-out") list.side[kDecoys].path = val();
+    else if (o == "--decoy-kind") { decoyKindGiven = true; decoyKind = val(); }
     else if (!o.empty() && o[0] == '-' && o != "-") { usage(); return 2; }
     else file = o;
   }
@@ -1087,6 +1094,9 @@ int main(int argc, char **argv) {
   if (R.regionsNull) list.side[kRegions].header = rceps::regions_header_null;
   if (decoysGiven != list.on(kDecoys)) die("--decoys and --decoys-out go together");
   if (decoysGiven && (R.decoys < 1 || R.decoys > 64)) die("--decoys takes a number of decoys from 1 to 64");
+  if (decoyKindGiven && !decoysGiven) die("--decoy-kind needs --decoys");
+  if (decoyKindGiven && decoyKind != "simulated" && decoyKind != "shuffled") die("--decoy-kind is simulated or shuffled");
+  R.decoysShuffled = decoyKind == "shuffled";
   if (!regionsFile.empty()) {
     std::ifstream in(regionsFile, std::ios::binary);
     if (!in) die("--regions: could not open " + regionsFile);

@@ -302,6 +302,33 @@ struct DecoyArgs {
   int nDecoys;
 };
 void launch_decoy_sigma(const DecoyArgs &a, int nBlocks, int maxNK, hipStream_t stream);   // nBlocks x 2 maxNK workgroups of one wavefront
+// rc_batch_decoys_shuffled (rc_shuffle.hip): the same tables and header copies for gap-class column shuffles of the blocks themselves
+// (rc_shuffle_plan.h has the definition).  Position p of `blocks` has its class ids u16 [cols] and, behind them, its columns ordered by
+// (class, column) u16 [cols] at cls16 + clsAt[p]; (block, decoy) v = p * nDecoys + d has a slot of permStride bytes at permAll + v * permStride:
+// the permutation u16 [cols] (decoy column c holds the block's column perm[c]), then -- 256-aligned, only where the block has more than
+// ldsCols columns -- the u64 words k_shuffle_perm sorts in global memory; up to ldsCols columns it sorts them in LDS.
+struct ShuffleArgs {
+  const uint8_t *blob;
+  const DevBlock *dblocks;
+  const uint32_t *flags;
+  const int *blocks;          // [nBlocks] batch indices of the round
+  const uint8_t *pair;        // [64][64] codon pair -> sigma code
+  const uint16_t *cls16;
+  const long long *clsAt;     // [nBlocks] of the round, in u16 units
+  uint8_t *permAll;
+  size_t permStride;
+  uint8_t *sigmaAll;
+  size_t sigmaStride;         // bytes per (block, decoy): the largest table of the round, 256-aligned
+  DevBlock *vblocks;
+  uint32_t *vflags;
+  int nDecoys;
+  uint32_t seed;              // decoy d shuffles with seed + d
+  int ldsCols;
+};
+constexpr int kShuffleLdsCols = 4096, kShuffleLdsColsMax = 8192;   // the default bound (32 KB of LDS) and the largest one (64 KB)
+// k_shuffle_perm then k_shuffle_sigma, nBlocks x nDecoys workgroups each; ldsBytes: 8 x the power of two that holds the round's widest block
+// of up to ldsCols columns (0: none), sortThreads: 64 .. 256 by the round's widest block
+void launch_shuffle_sigma(const ShuffleArgs &a, int nBlocks, size_t ldsBytes, int sortThreads, hipStream_t stream);
 // wider blocks (N > 64): generic kernels with their states in a global scratch (rc_null_generic.h)
 size_t null_generic_lds_bytes(int N, int nnodes);   // packed node states + codon windows of the widest block of the launch
 // the same in two launches (simulation with many light wavefronts, then the DP): bytes of an item's codes / of a DP workgroup's states

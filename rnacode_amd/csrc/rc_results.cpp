@@ -2,6 +2,7 @@
 #include "rc_runtime.h"
 #include "rc_decoy_plan.h"
 #include "rc_segnull_plan.h"
+#include "rc_shuffle_plan.h"
 
 extern "C" {
 
@@ -655,20 +656,176 @@ int rc_batch_segment_null(const rc_batch *bc, const rc_bt_range *ranges, int32_t
   return RC_OK;
 }
 
-// Decoy listings (rc_decoys.hip): the whole HSS listing of null alignments.  Per listed block one simulation item of k_generic_sim<false> -- the
-// run's own simulation, lane = decoy, MT19937 streams of this call's seeds in a buffer of this call's own -- leaves the sigma codes;
-// k_decoy_sigma expands them into one native-format sigma table per (block, decoy) and writes a copy of the block's header aimed at it; the
-// native block's kernels, unchanged and grouped by row count as launch_native_block groups them, score those copies as if they were blocks.
-// The scored positions go in rounds under a budget (rc_decoy_plan.h); each round's HSS records are packed behind those of the rounds before,
-// and the whole call's come back with one copy behind one synchronisation.  Nothing of the batch is written.
-int rc_batch_decoys(const rc_batch *bc, const int32_t *blks, int32_t n_blks, uint32_t seed, int32_t n_decoys, rc_hss *out, int64_t cap,
-                    int64_t *offsets, int64_t *clamped) {
-  rc_batch *b = const_cast<rc_batch *>(bc);
-  if (!b || !offsets || n_blks < 0 || cap < 0 || (!out && cap > 0)) return fail(RC_ERR_ARG, "bad argument");
-  if (n_decoys < 1 || n_decoys > kWave) return fail(RC_ERR_ARG, "the number of decoys must be 1..64");
-  if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
+}  // extern "C"
+
+// Decoy listings (rc_decoys.hip, rc_shuffle.hip): the whole HSS listing of decoy alignments of the listed blocks.  Per (block, decoy) a
+// native-format sigma table and a copy of the block's header aimed at it; the native block's kernels, unchanged and grouped by row count as
+// launch_native_block groups them, score those copies as if they were blocks.  The scored positions go in rounds under a budget
+// (rc_decoy_plan.h); each round's HSS records are packed behind those of the rounds before, and the whole call's come back with one copy
+// behind one synchronisation.  Nothing of the batch is written.
+// The two entry points differ in what fills a round's sigma tables and header copies, a Fill:
+//   plan(blocks)        before the device is touched: whatever the filler derives per position on the host; may refuse the call
+//   bytes(p)            what position p takes in the filler's own device buffer, for all its decoys (the plan's cost beside the tables)
+//   ensure(need)        its device buffers, `need` bytes of that buffer for the largest round
+//   begin(st, clamps)   once per call, in front of the first round (clamps: the call's clamp count, zeroed)
+//   round(x)            the launches that leave round x's tables, header copies and flag words
+namespace {
+
+struct DecoyRoundCtx {
+  const DecoyRound *rd;
+  const int *blocks;          // device: the round's batch indices
+  int maxN, maxNK, maxNodes;
+  uint8_t *sigmaAll;
+  DevBlock *vblocks;
+  uint32_t *vflags;
+  hipStream_t st;
+};
+
+inline void adopt_bufs(rc_ctx *c, std::initializer_list<DevBuf *> bufs) {
+  for (DevBuf *d : bufs) { d->retired = c->retired.get(); d->pool = c->bufPool.get(); }
+}
+
+// rc_batch_decoys: per listed block one simulation item of k_generic_sim<false> -- the run's own simulation, lane = decoy, MT19937 streams of
+// this call's seeds in a buffer of this call's own -- leaves the sigma codes; k_decoy_sigma expands them into the tables.
+struct SimFill {
+  rc_batch *b;
+  rc_ctx *c;
+  uint32_t seed;
+  int K;
+  const std::vector<int32_t> *up = nullptr;
+  DevBuf d_U, d_cnt, d_codes;
+  NullArgs sim{};
+  DecoyArgs da{};
+  SimFill(rc_batch *b_, uint32_t seed_, int K_) : b(b_), c(b_->ctx), seed(seed_), K(K_) { adopt_bufs(c, {&d_U, &d_cnt, &d_codes}); }
+  size_t codes_bytes(int blk) const { return null_generic_codes_bytes(b->meta[blk].N, b->meta[blk].L, b->db[blk].nnodes); }
+  int plan(const std::vector<int32_t> &blocks) {   // (the positions: the vector grows behind them later)
+    up = &blocks;
+    for (int32_t blk : blocks) {   // k_decoy_sigma finds a sequence's code words by GenericLayout's rule: the two must agree
+      const BlockMeta &h = b->meta[blk];
+      if (codes_bytes(blk) != al256(static_cast<size_t>(6) * h.NK * seg_null_code_words(h.L) * kWave * sizeof(uint32_t)))
+        return fail(RC_ERR_UNSUPPORTED, "internal: the layout of the sigma codes has changed");
+    }
+    return RC_OK;
+  }
+  size_t bytes(int p) const { return codes_bytes((*up)[static_cast<size_t>(p)]); }
+  int ensure(size_t need) {
+    HIP_TRY(d_U.ensure(static_cast<size_t>(kWave) * std::max(b->maxDraws, 1) * sizeof(uint32_t)));
+    HIP_TRY(d_cnt.ensure(8 * sizeof(uint32_t)));
+    HIP_TRY(d_codes.ensure(need));
+    return RC_OK;
+  }
+  int begin(hipStream_t st, unsigned long long *clamps) {
+    // the MT19937 streams of the seeds seed .. seed + 63, one per lane: this call's own (the context's cache holds the run's)
+    launch_mt_stream(seed, kWave, std::max(b->maxDraws, 1), d_U.as<uint32_t>(), st);
+    HIP_TRY(hipGetLastError());
+    uint8_t *blob = b->dblob.as<uint8_t>();
+    sim.blob = blob; sim.dblocks = reinterpret_cast<const DevBlock *>(blob + b->oDblocks); sim.flags = b->dflags.as<uint32_t>();
+    sim.gLo = 0; sim.gHi = 1; sim.sampleN = K; sim.Spad = kWave;   // one group; the lanes K.. are simulated and never read (their clamps not counted)
+    sim.U = d_U.as<uint32_t>(); sim.pair = b->tables->ptrs.pair; sim.tieThr = c->tieThr;
+    sim.workCounter = d_cnt.as<unsigned int>(); sim.clampCount = clamps;
+    sim.codesAll = d_codes.as<uint8_t>();
+    da.blob = blob; da.dblocks = sim.dblocks; da.flags = sim.flags; da.codesAll = d_codes.as<uint8_t>(); da.nDecoys = K;
+    return RC_OK;
+  }
+  int round(const DecoyRoundCtx &x) {
+    const size_t lds = null_generic_lds_bytes(x.maxN, x.maxNodes);
+    const auto key = std::make_tuple(NullKind::GenericSim, 0, lds);
+    const auto it = c->occ.find(key);
+    const int occ = std::max(1, it != c->occ.end() ? it->second : (c->occ[key] = generic_occupancy(NullKind::GenericSim, lds)));
+    HIP_TRY(hipMemsetAsync(d_cnt.p, 0, 8 * sizeof(uint32_t), x.st));   // (behind the round before: one stream)
+    sim.classBlocks = x.blocks; sim.nClassBlocks = x.rd->count; sim.codesStride = x.rd->stride.codes;
+    launch_generic(NullKind::GenericSim, sim, static_cast<int>(std::min<long long>(x.rd->count, static_cast<long long>(c->numCU) * occ)), lds, d_codes.as<uint8_t>(), x.st);
+    HIP_TRY(hipGetLastError());
+    da.blocks = x.blocks; da.codesStride = x.rd->stride.codes; da.sigmaAll = x.sigmaAll; da.sigmaStride = x.rd->stride.sigma;
+    da.vblocks = x.vblocks; da.vflags = x.vflags;
+    launch_decoy_sigma(da, x.rd->count, x.maxNK, x.st);
+    HIP_TRY(hipGetLastError());
+    return RC_OK;
+  }
+};
+
+// rc_batch_decoys_shuffled: the class ids of every distinct listed block once per call, on the host from the characters the batch's pinned blob
+// still holds (rc_shuffle_plan.h); k_shuffle_perm sorts each (block, decoy)'s permutation, k_shuffle_sigma reads the block's characters
+// through it.  A position's bytes: per decoy the permutation and, above the LDS bound, the words of the sort.
+struct ShuffleFill {
+  rc_batch *b;
+  rc_ctx *c;
+  uint32_t seed;
+  int K, ldsCols = kShuffleLdsCols;
+  size_t P = 0;
+  const std::vector<int32_t> *up = nullptr;
+  std::vector<uint8_t> host;   // what goes up: clsAt long long [P] | per distinct block cls u16 [cols], ord u16 [cols]
+  DevBuf d_cls, d_perm;
+  ShuffleArgs sa{};
+  ShuffleFill(rc_batch *b_, uint32_t seed_, int K_) : b(b_), c(b_->ctx), seed(seed_), K(K_) {
+    adopt_bufs(c, {&d_cls, &d_perm});
+    if (const char *e = std::getenv("RC_SHUFFLE_LDS_COLS")) ldsCols = static_cast<int>(std::min<long long>(kShuffleLdsColsMax, std::max(1ll, std::atoll(e))));
+  }
+  int plan(const std::vector<int32_t> &blocks) {
+    up = &blocks;
+    P = blocks.size();
+    std::map<int, long long> at;   // distinct block -> where its arrays start, in u16 units behind the clsAt array
+    std::vector<int> distinct;
+    std::vector<long long> distinctAt;
+    long long words = 0;
+    std::vector<long long> clsAt(P);
+    for (size_t p = 0; p < P; p++) {
+      const auto ins = at.emplace(blocks[p], words);
+      if (ins.second) { distinct.push_back(blocks[p]); distinctAt.push_back(words); words += 2ll * b->meta[blocks[p]].cols; }
+      clsAt[p] = ins.first->second;
+    }
+    host.resize(P * sizeof(long long) + static_cast<size_t>(words) * sizeof(uint16_t));
+    std::memcpy(host.data(), clsAt.data(), P * sizeof(long long));
+    uint16_t *arrays = reinterpret_cast<uint16_t *>(host.data() + P * sizeof(long long));
+    const uint8_t *hblob = b->hblob.as<uint8_t>();
+    const unsigned threads = distinct.size() >= 1024 ? static_cast<unsigned>(std::min(16, c->hostThreads > 0 ? c->hostThreads : effective_cpus())) : 1u;
+    parallel_for(static_cast<int>(distinct.size()), threads, [&](int q) {
+      const int blk = distinct[static_cast<size_t>(q)];
+      const BlockMeta &h = b->meta[blk];
+      uint16_t *cls = arrays + distinctAt[static_cast<size_t>(q)];
+      shuffle_classes(hblob + b->db[blk].off_chars, h.N, h.cols, cls, cls + h.cols);
+    });
+    return RC_OK;
+  }
+  size_t slot_bytes(int cols) const {
+    return al256(static_cast<size_t>(cols) * sizeof(uint16_t)) + (cols > ldsCols ? static_cast<size_t>(shuffle_pow2(static_cast<uint32_t>(cols))) * sizeof(uint64_t) : 0);
+  }
+  size_t bytes(int p) const { return static_cast<size_t>(K) * slot_bytes(b->meta[(*up)[static_cast<size_t>(p)]].cols); }
+  int ensure(size_t need) {
+    HIP_TRY(d_cls.ensure(std::max<size_t>(host.size(), 8)));
+    HIP_TRY(d_perm.ensure(need));
+    return RC_OK;
+  }
+  int begin(hipStream_t st, unsigned long long *) {
+    HIP_TRY(hipMemcpyAsync(d_cls.p, host.data(), host.size(), hipMemcpyHostToDevice, st));
+    uint8_t *blob = b->dblob.as<uint8_t>();
+    sa.blob = blob; sa.dblocks = reinterpret_cast<const DevBlock *>(blob + b->oDblocks); sa.flags = b->dflags.as<uint32_t>();
+    sa.pair = b->tables->ptrs.pair;
+    sa.cls16 = reinterpret_cast<const uint16_t *>(d_cls.as<uint8_t>() + P * sizeof(long long));
+    sa.permAll = d_perm.as<uint8_t>(); sa.nDecoys = K; sa.seed = seed; sa.ldsCols = ldsCols;
+    return RC_OK;
+  }
+  int round(const DecoyRoundCtx &x) {
+    int ldsMax = 0, colsMax = 0;
+    for (int p = x.rd->first; p < x.rd->first + x.rd->count; p++) {
+      const int cols = b->meta[(*up)[static_cast<size_t>(p)]].cols;
+      colsMax = std::max(colsMax, cols);
+      if (cols <= ldsCols) ldsMax = std::max(ldsMax, cols);
+    }
+    sa.blocks = x.blocks; sa.clsAt = d_cls.as<long long>() + x.rd->first;
+    sa.permStride = x.rd->stride.codes / static_cast<size_t>(K);   // (every position's bytes are K slots)
+    sa.sigmaAll = x.sigmaAll; sa.sigmaStride = x.rd->stride.sigma; sa.vblocks = x.vblocks; sa.vflags = x.vflags;
+    const size_t lds = ldsMax ? static_cast<size_t>(shuffle_pow2(static_cast<uint32_t>(ldsMax))) * sizeof(uint64_t) : 0;
+    const int threads = static_cast<int>(std::min<uint32_t>(256, std::max<uint32_t>(kWave, shuffle_pow2(static_cast<uint32_t>(colsMax)) / 2)));
+    launch_shuffle_sigma(sa, x.rd->count, lds, threads, x.st);
+    HIP_TRY(hipGetLastError());
+    return RC_OK;
+  }
+};
+
+template <typename Fill>
+int decoys_body(rc_batch *b, const int32_t *blks, int32_t n_blks, int K, rc_hss *out, int64_t cap, int64_t *offsets, int64_t *clamped, Fill &fill) {
   // every index is checked, and the plan made, before anything touches the device (or the caller's arrays)
-  const int K = n_decoys;
   rc_ctx *c = b->ctx;
   std::vector<int> posOf(static_cast<size_t>(n_blks), -1);   // listed block k -> its position among the scored ones
   std::vector<int32_t> up;                                   // one upload: the positions' blocks, then every round's launch lists
@@ -689,18 +846,13 @@ int rc_batch_decoys(const rc_batch *bc, const int32_t *blks, int32_t n_blks, uin
     if (const char *e = std::getenv("RC_DECOY_MAX_BYTES")) budget = static_cast<size_t>(std::max(1ll, std::atoll(e)));
     const auto meta_of = [&](size_t p) -> const BlockMeta & { return b->meta[up[p]]; };
     const auto wide = [&](const BlockMeta &h, int blk) { return h.N > kTemplRows || block_class(h.N, h.L, b->db[blk].omega, c->rule) == kGenericClass; };
-    const auto codes_bytes = [&](int blk) { return null_generic_codes_bytes(b->meta[blk].N, b->meta[blk].L, b->db[blk].nnodes); };
+    RC_TRY(fill.plan(up));
     const std::vector<DecoyRound> rounds = decoy_plan(static_cast<int>(P), [&](int p) {
       const BlockMeta &h = meta_of(p);
       const size_t smax = static_cast<size_t>(h.L / 3);
-      return DecoyCost{codes_bytes(up[p]), al256(static_cast<size_t>(2) * h.NK * (h.L + 1) * sizeof(float)), 6 * smax * smax * sizeof(float),
+      return DecoyCost{fill.bytes(p), al256(static_cast<size_t>(2) * h.NK * (h.L + 1) * sizeof(float)), 6 * smax * smax * sizeof(float),
                        static_cast<size_t>(6) * b->hssCap * sizeof(DevHss)};
     }, K, budget);
-    for (size_t p = 0; p < P; p++) {   // k_decoy_sigma finds a sequence's code words by GenericLayout's rule: the two must agree
-      const BlockMeta &h = meta_of(p);
-      if (codes_bytes(up[p]) != al256(static_cast<size_t>(6) * h.NK * seg_null_code_words(h.L) * kWave * sizeof(uint32_t)))
-        return fail(RC_ERR_UNSUPPORTED, "internal: the layout of the sigma codes has changed");
-    }
     // a round's launches: its (block, decoy) numbers -- (position in the round) x K + d, what the native kernels take for a block index -- by
     // row count, the blocks of the generic native kernel in one list
     struct Launch { int NK; size_t at, count; int smax, maxNK; bool all; };   // NK 0: k_native_dp_generic
@@ -710,7 +862,7 @@ int rc_batch_decoys(const rc_batch *bc, const int32_t *blks, int32_t n_blks, uin
     const int mode = c->inflight.load() > 0 ? 0 : 1;   // (rc_batch_track's rule)
     const int chunk = 256;                             // blocks per launch of the generic kernel, which share its scratch (launch_native_block)
     const auto wide_stride = [](const Launch &l) { return static_cast<size_t>(3) * l.maxNK * kWave + static_cast<size_t>(kWave) * l.smax; };
-    size_t codesNeed = 0, sigmaNeed = 0, tileFloats = 4, scratchFloats = 0, allFloats = 0, maxV = 0;
+    size_t fillNeed = 0, sigmaNeed = 0, tileFloats = 4, scratchFloats = 0, allFloats = 0, maxV = 0;
     up.reserve(P + V);
     for (const DecoyRound &rd : rounds) {
       Round ri{launches.size(), 0, 0, 0, 0};
@@ -745,7 +897,7 @@ int rc_batch_decoys(const rc_batch *bc, const int32_t *blks, int32_t n_blks, uin
       if (!wides.empty()) add(0, wides);
       ri.nLaunch = launches.size() - ri.first;
       rinfo.push_back(ri);
-      codesNeed = std::max(codesNeed, static_cast<size_t>(rd.count) * rd.stride.codes);
+      fillNeed = std::max(fillNeed, static_cast<size_t>(rd.count) * rd.stride.codes);
       sigmaNeed = std::max(sigmaNeed, static_cast<size_t>(rd.count) * K * rd.stride.sigma);
       maxV = std::max(maxV, static_cast<size_t>(rd.count) * K);
     }
@@ -755,19 +907,15 @@ int rc_batch_decoys(const rc_batch *bc, const int32_t *blks, int32_t n_blks, uin
     HIP_TRY(hipSetDevice(c->device));
     RC_STREAM_TRY(st, stream_aux(c));
     HIP_TRY(hipEventSynchronize(b->evPrep));   // the tables of the blob are made on the device
-    DevBuf d_up, d_U, d_cnt, d_codes, d_sigma, d_vdb, d_vflags, d_tile, d_scratch, d_all, d_hss, d_res;
-    for (DevBuf *d : {&d_up, &d_U, &d_cnt, &d_codes, &d_sigma, &d_vdb, &d_vflags, &d_tile, &d_scratch, &d_all, &d_hss, &d_res}) {
-      d->retired = c->retired.get(); d->pool = c->bufPool.get();
-    }
+    DevBuf d_up, d_sigma, d_vdb, d_vflags, d_tile, d_scratch, d_all, d_hss, d_res;
+    adopt_bufs(c, {&d_up, &d_sigma, &d_vdb, &d_vflags, &d_tile, &d_scratch, &d_all, &d_hss, &d_res});
     uint8_t *blob = b->dblob.as<uint8_t>();
     bool launched = false;
     // (a lambda: whatever fails in it, nothing returns to the caller before the work already queued on the stream has drained -- `up`, `res`
     // and the buffers die with this frame)
     const int rc = [&]() -> int {
       HIP_TRY(d_up.ensure(up.size() * sizeof(int32_t)));
-      HIP_TRY(d_U.ensure(static_cast<size_t>(kWave) * std::max(b->maxDraws, 1) * sizeof(uint32_t)));
-      HIP_TRY(d_cnt.ensure(8 * sizeof(uint32_t)));
-      HIP_TRY(d_codes.ensure(codesNeed));
+      RC_TRY(fill.ensure(fillNeed));
       HIP_TRY(d_sigma.ensure(sigmaNeed));
       HIP_TRY(d_vdb.ensure(maxV * sizeof(DevBlock)));
       HIP_TRY(d_vflags.ensure(maxV * sizeof(uint32_t)));
@@ -777,39 +925,19 @@ int rc_batch_decoys(const rc_batch *bc, const int32_t *blks, int32_t n_blks, uin
       HIP_TRY(d_hss.ensure(std::max<size_t>(maxV * 6 * b->hssCap, 1) * sizeof(DevHss)));   // a round's records: packed before the next round
       HIP_TRY(d_res.ensure(headBytes + packedCap * sizeof(DevHss)));
       launched = true;   // from here on something may be in flight
-      // the MT19937 streams of the seeds seed .. seed + 63, one per lane: this call's own (the context's cache holds the run's)
-      launch_mt_stream(seed, kWave, std::max(b->maxDraws, 1), d_U.as<uint32_t>(), st);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(d_up.p, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemsetAsync(d_res.p, 0, resInts * sizeof(int32_t), st));   // clamp count, total, and the counts of slots nobody writes
       int32_t *ri32 = d_res.as<int32_t>();
       DevHss *packed = reinterpret_cast<DevHss *>(ri32 + resInts);
-      NullArgs sim{};
-      sim.blob = blob; sim.dblocks = reinterpret_cast<const DevBlock *>(blob + b->oDblocks); sim.flags = b->dflags.as<uint32_t>();
-      sim.gLo = 0; sim.gHi = 1; sim.sampleN = K; sim.Spad = kWave;   // one group; the lanes K.. are simulated and never read (their clamps not counted)
-      sim.U = d_U.as<uint32_t>(); sim.pair = b->tables->ptrs.pair; sim.tieThr = c->tieThr;
-      sim.workCounter = d_cnt.as<unsigned int>(); sim.clampCount = reinterpret_cast<unsigned long long *>(ri32);
-      sim.codesAll = d_codes.as<uint8_t>();
-      DecoyArgs da{};
-      da.blob = blob; da.dblocks = sim.dblocks; da.flags = sim.flags; da.codesAll = d_codes.as<uint8_t>(); da.sigmaAll = d_sigma.as<uint8_t>();
-      da.vblocks = d_vdb.as<DevBlock>(); da.vflags = d_vflags.as<uint32_t>(); da.nDecoys = K;
+      HIP_TRY(hipMemsetAsync(d_res.p, 0, resInts * sizeof(int32_t), st));   // clamp count, total, and the counts of slots nobody writes
+      RC_TRY(fill.begin(st, reinterpret_cast<unsigned long long *>(ri32)));
+      HIP_TRY(hipMemcpyAsync(d_up.p, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
       NativeArgs na{};
-      na.blob = blob; na.dblocks = d_vdb.as<DevBlock>(); na.flags = d_vflags.as<uint32_t>(); na.pair = sim.pair;
+      na.blob = blob; na.dblocks = d_vdb.as<DevBlock>(); na.flags = d_vflags.as<uint32_t>(); na.pair = b->tables->ptrs.pair;
       na.hssCap = b->hssCap; na.tieThr = c->tieThr;
       for (size_t r = 0; r < rounds.size(); r++) {
         const DecoyRound &rd = rounds[r];
         const Round &ri = rinfo[r];
-        const size_t lds = null_generic_lds_bytes(ri.maxN, ri.maxNodes);
-        const auto key = std::make_tuple(NullKind::GenericSim, 0, lds);
-        const auto it = c->occ.find(key);
-        const int occ = std::max(1, it != c->occ.end() ? it->second : (c->occ[key] = generic_occupancy(NullKind::GenericSim, lds)));
-        HIP_TRY(hipMemsetAsync(d_cnt.p, 0, 8 * sizeof(uint32_t), st));   // (behind the round before: one stream)
-        sim.classBlocks = d_up.as<int>() + rd.first; sim.nClassBlocks = rd.count; sim.codesStride = rd.stride.codes;
-        launch_generic(NullKind::GenericSim, sim, static_cast<int>(std::min<long long>(rd.count, static_cast<long long>(c->numCU) * occ)), lds, d_codes.as<uint8_t>(), st);
-        HIP_TRY(hipGetLastError());
-        da.blocks = sim.classBlocks; da.codesStride = rd.stride.codes; da.sigmaStride = rd.stride.sigma;
-        launch_decoy_sigma(da, rd.count, ri.maxNK, st);
-        HIP_TRY(hipGetLastError());
+        RC_TRY(fill.round(DecoyRoundCtx{&rd, d_up.as<int>() + rd.first, ri.maxN, ri.maxNK, ri.maxNodes, d_sigma.as<uint8_t>(), d_vdb.as<DevBlock>(),
+                                        d_vflags.as<uint32_t>(), st}));
         // the round's (block, decoy) numbers start at 0: its counts at the round's place in the call's arrays
         const size_t v0 = static_cast<size_t>(rd.first) * K;
         na.hss = d_hss.as<DevHss>(); na.hssCount = ri32 + 4 + v0 * 6;
@@ -906,6 +1034,32 @@ int rc_batch_decoys(const rc_batch *bc, const int32_t *blks, int32_t n_blks, uin
   std::memcpy(offsets, at.data(), (nLists + 1) * sizeof(int64_t));
   if (clamped) { *clamped = 0; if (P > 0) std::memcpy(clamped, res.get(), sizeof(int64_t)); }
   return RC_OK;
+}
+
+// the arguments both entry points take: checked before the device is touched
+int decoys_args(const rc_batch *b, int32_t n_blks, int32_t n_decoys, const rc_hss *out, int64_t cap, const int64_t *offsets) {
+  if (!b || !offsets || n_blks < 0 || cap < 0 || (!out && cap > 0)) return fail(RC_ERR_ARG, "bad argument");
+  if (n_decoys < 1 || n_decoys > kWave) return fail(RC_ERR_ARG, "the number of decoys must be 1..64");
+  if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
+  return RC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rc_batch_decoys(const rc_batch *bc, const int32_t *blks, int32_t n_blks, uint32_t seed, int32_t n_decoys, rc_hss *out, int64_t cap,
+                    int64_t *offsets, int64_t *clamped) {
+  RC_TRY(decoys_args(bc, n_blks, n_decoys, out, cap, offsets));
+  SimFill fill(const_cast<rc_batch *>(bc), seed, n_decoys);
+  return decoys_body(const_cast<rc_batch *>(bc), blks, n_blks, n_decoys, out, cap, offsets, clamped, fill);
+}
+
+int rc_batch_decoys_shuffled(const rc_batch *bc, const int32_t *blks, int32_t n_blks, uint32_t seed, int32_t n_decoys, rc_hss *out, int64_t cap,
+                             int64_t *offsets) {
+  RC_TRY(decoys_args(bc, n_blks, n_decoys, out, cap, offsets));
+  ShuffleFill fill(const_cast<rc_batch *>(bc), seed, n_decoys);
+  return decoys_body(const_cast<rc_batch *>(bc), blks, n_blks, n_decoys, out, cap, offsets, nullptr, fill);
 }
 
 int rc_code_tables(int32_t blosum, int32_t pep_out[64], int32_t matrix_out[400]) {

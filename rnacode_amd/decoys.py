@@ -10,8 +10,10 @@ block's p-values are -- listed exactly as the block itself: scored, scanned for 
 
 The target-decoy estimate for a listing filtered at p <= t: R(t) listed HSS have p <= t, D(t) decoy HSS have p <= t, K decoys per block, so
 D(t) / K false lines are expected and FDR(t) = min(1, (D(t) / K) / max(R(t), 1)).  The q-value of a line is the smallest FDR over all
-thresholds t >= its p.  Decoys share the null model of the p-values: they calibrate multiplicity (how many lines of a screen are expected
-to be false), not model misfit.
+thresholds t >= its p.  Simulated decoys share the null model of the p-values: they calibrate multiplicity (how many lines of a screen are
+expected to be false), not model misfit.  --decoy-kind shuffled makes the decoys from the data itself instead -- each block's own columns,
+permuted among the columns with the same gap pattern (shuffle_columns) --: the file and the q-values are read the same way, and where the two
+kinds disagree the disagreement is the misfit of the model.
 
     python -m rnacode_amd.decoys [-k K] LISTING.tsv DECOYS.tsv
 
@@ -44,6 +46,44 @@ def block_lines(block: int, ref_name: str, lists: Sequence[List[dict]], cutoff: 
                 best_region: bool = False) -> List[str]:
     """The lines of one block's decoys, decoys ascending, each decoy's HSS selected and ordered as the listing selects the block's own."""
     return [decoy_line(block, d, ref_name, h) for d, hss in enumerate(lists) for h in report.listed_hss(hss, cutoff, best_only, best_region)]
+
+
+def _fmix(x: np.ndarray) -> np.ndarray:
+    """The 32-bit murmur3 finaliser on uint64 arrays holding 32-bit values."""
+    m = np.uint64(0xFFFFFFFF)
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x85EBCA6B)) & m
+    x = x ^ (x >> np.uint64(13))
+    x = (x * np.uint64(0xC2B2AE35)) & m
+    return x ^ (x >> np.uint64(16))
+
+
+def shuffle_key(seed: int, cols) -> np.ndarray:
+    """key(seed, c) = fmix(fmix(seed) ^ (c * 0x9E3779B1 mod 2^32)) for the columns `cols`, as uint32."""
+    m = np.uint64(0xFFFFFFFF)
+    c = np.asarray(cols, dtype=np.uint64)
+    s = _fmix(np.asarray([int(seed) & 0xFFFFFFFF], dtype=np.uint64))
+    return _fmix(s ^ ((c * np.uint64(0x9E3779B1)) & m)).astype(np.uint32)
+
+
+def shuffle_columns(rows: Sequence[str], seed: int) -> List[str]:
+    """The rows of the shuffled decoy of an alignment (Batch.decoys(kind="shuffled"), rc_batch_decoys_shuffled, decoy d of a call: seed + d).
+    Columns are permuted within their gap classes -- two columns are in one class iff the same set of rows holds '-' there (only '-': every
+    other character travels with its column) --: for a class's columns c_1 < .. < c_m and the same columns s_1 .. s_m sorted by
+    (key(seed, c), c), decoy column c_t holds original column s_t.  Every row keeps its gaps; the multiset of columns is the block's."""
+    rows = list(rows)
+    if not rows or not rows[0]:
+        return rows
+    a = np.array([np.frombuffer(r.encode("latin-1"), dtype=np.uint8) for r in rows])
+    cols = a.shape[1]
+    _, cls = np.unique(a == ord("-"), axis=1, return_inverse=True)
+    cls = np.asarray(cls).reshape(-1)
+    c = np.arange(cols)
+    dst = np.lexsort((c, cls))                            # the classes' columns, ascending
+    src = np.lexsort((c, shuffle_key(seed, c), cls))      # the same columns by (key, column) within each class
+    perm = np.empty(cols, dtype=np.int64)
+    perm[dst] = src
+    return [bytes(r).decode("latin-1") for r in a[:, perm]]
 
 
 def qvalues(real_p: Iterable[float], decoy_p: Iterable[float], n_decoys: int) -> np.ndarray:
