@@ -42,6 +42,22 @@ static int check_blk(const rc_batch *b, int blk, bool needRun) {
   return RC_OK;
 }
 
+// a scored block as the native block's plan sees it (rc_native_plan.h): the wide blocks of a query's list share its launches
+static NativeMember native_member(const rc_batch *b, int blk) {
+  const BlockMeta &h = b->meta[blk];
+  return NativeMember{h.NK, h.L, native_wide(h.N, h.L, b->db[blk].omega, b->ctx->rule), 0};
+}
+// ... and the order the queries give their lists for it: by kernel, the generic one's blocks last
+static bool native_before(const NativeMember &x, const NativeMember &y) { return std::make_pair(x.wide, x.NK) < std::make_pair(y.wide, y.NK); }
+
+// k_segment_null and k_decoy_sigma find a sequence's code words in what k_generic_sim left by GenericLayout's rule: the two must agree
+static int check_codes_layout(const rc_batch *b, int blk) {
+  const BlockMeta &h = b->meta[blk];
+  if (null_generic_codes_bytes(h.N, h.L, b->db[blk].nnodes) != al256(static_cast<size_t>(6) * h.NK * seg_null_code_words(h.L) * kWave * sizeof(uint32_t)))
+    return fail(RC_ERR_UNSUPPORTED, "internal: the layout of the sigma codes has changed");
+  return RC_OK;
+}
+
 int rc_batch_status(const rc_batch *b, int32_t blk) {
   int r = check_blk(b, blk, false);
   return r ? r : b->meta[blk].status;
@@ -218,10 +234,9 @@ int rc_batch_native_S(const rc_batch *b, int32_t blk, int32_t strand, int32_t fr
     // the scoring pass never materialises S: recompute this block's six matrices with the same kernel (fullS set: no records written)
     rc_ctx *c = b->ctx;
     DevBuf full, tile, idx;
-    const bool generic = h.N > kTemplRows || block_class(h.N, h.L, b->db[blk].omega, c->rule) == kGenericClass;   // (the tiled classes' native block takes k_native_dp<N-1> up to 64 rows)
-    const size_t tileStride = generic ? static_cast<size_t>(3) * h.NK * kWave + static_cast<size_t>(kWave) * smax : static_cast<size_t>(kWave) * smax;
+    const NativePlan pl = native_plan_on(c, 1, [&](size_t) { return native_member(b, blk); }, native_query_mode(c));
     HIP_TRY(full.ensure(static_cast<size_t>(6) * smax * smax * sizeof(float)));
-    HIP_TRY(tile.ensure(6 * tileStride * sizeof(float)));
+    HIP_TRY(tile.ensure(std::max(pl.tileFloats, pl.scratchFloats) * sizeof(float)));   // (one block: it takes one of the two)
     HIP_TRY(idx.ensure(sizeof(int)));
     const int bi = blk;
     HIP_TRY(hipMemcpy(idx.p, &bi, sizeof(int), hipMemcpyHostToDevice));
@@ -229,11 +244,11 @@ int rc_batch_native_S(const rc_batch *b, int32_t blk, int32_t strand, int32_t fr
     NativeArgs na{};
     const uint8_t *blob = b->dblob.as<uint8_t>();
     na.blob = b->dblob.as<uint8_t>(); na.dblocks = reinterpret_cast<const DevBlock *>(blob + b->oDblocks); na.blocks = idx.as<int>();
-    na.hssCap = b->hssCap; na.tieThr = c->tieThr; na.tile = tile.as<float>(); na.tileStride = tileStride; na.nItems = 6;
+    na.hssCap = b->hssCap; na.tieThr = c->tieThr;
     na.fullS = full.as<float>();
     na.flags = b->dflags.as<uint32_t>();
-    if (generic) launch_native_dp_generic(na, 1, tile.as<float>(), tileStride, nullptr);
-    else if (!launch_native_dp(h.NK, na, 6, nullptr)) return fail(RC_ERR_UNSUPPORTED, "no native DP kernel for this number of rows");
+    const int launches = launch_native_plan(pl, na, idx.as<int>(), NativeBufs{tile.as<float>(), tile.as<float>(), nullptr}, nullptr);
+    if (launches < 0) return launches;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, full.as<float>() + at, sizeof(float) * sites * sites, hipMemcpyDeviceToHost));
   }
@@ -341,7 +356,7 @@ int rc_batch_backtrack_many(const rc_batch *b, const rc_bt_range *ranges, int32_
   RC_STREAM_TRY(st, stream_aux(c));
   HIP_TRY(hipEventSynchronize(b->evPrep));   // the z and sigma tables are made on the device (k_prep_gaps, k_native_sigma)
   DevBuf d_items, d_cells;
-  for (DevBuf *d : {&d_items, &d_cells}) { d->retired = c->retired.get(); d->pool = c->bufPool.get(); }
+  adopt_bufs(c, {&d_items, &d_cells});
   const uint8_t *blob = b->dblob.as<uint8_t>();
   std::vector<BtItem> items;
   items.reserve(nItems);
@@ -385,15 +400,14 @@ int rc_batch_backtrack_many(const rc_batch *b, const rc_bt_range *ranges, int32_
 }
 
 // The per-codon track of the listed blocks: the native block's DP again (rc_track.hip: the scoring kernels with the track's reduction where
-// they have getHSS), one launch per row-count class as in launch_native_block, every array written by the wavefront that owns it into one device
+// they have getHSS), planned and launched as the run's are (rc_native_plan.h), every array written by the wavefront that owns it into one device
 // buffer that comes back with one copy.  Nothing sites x sites exists: a workgroup holds 64 rows of S, an item's track is its output.
 int rc_batch_track(const rc_batch *b, const int32_t *blks, int32_t n_blks, float *out, int64_t cap, int64_t *offsets) {
   if (!b || !offsets || n_blks < 0 || (!out && cap > 0)) return fail(RC_ERR_ARG, "bad argument");
   if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
   // every index is checked, and the layout made, before anything touches the device
-  struct Pos { int blk; long long off; };
-  std::map<int, std::vector<Pos>> byNK;   // N-1 -> positions whose block takes k_native_track<N-1>
-  std::vector<Pos> wide;                  // ... k_native_track_generic
+  struct Pos { int blk; long long off; NativeMember m; };
+  std::vector<Pos> pos;   // the scored blocks and where their arrays start
   rc_ctx *c = b->ctx;
   int64_t total = 0;
   for (int k = 0; k < n_blks; k++) {
@@ -401,10 +415,7 @@ int rc_batch_track(const rc_batch *b, const int32_t *blks, int32_t n_blks, float
     if (blk < 0 || blk >= b->n) return fail(RC_ERR_ARG, "track block " + std::to_string(k) + ": block index out of range");
     const BlockMeta &h = b->meta[blk];
     const bool scored = h.status == RC_OK;
-    if (scored) {   // (the kernels of rc_batch_native_S: the tiled classes' native block takes k_native_dp<N-1> up to 64 rows)
-      const bool generic = h.N > kTemplRows || block_class(h.N, h.L, b->db[blk].omega, c->rule) == kGenericClass;
-      (generic ? wide : byNK[h.NK]).push_back(Pos{blk, static_cast<long long>(total)});
-    }
+    if (scored) pos.push_back(Pos{blk, static_cast<long long>(total), native_member(b, blk)});
     for (int combo = 0; combo < 6; combo++) {
       offsets[6 * static_cast<size_t>(k) + combo] = total;
       if (scored) total += (h.L - combo % 3) / 3;
@@ -415,67 +426,33 @@ int rc_batch_track(const rc_batch *b, const int32_t *blks, int32_t n_blks, float
   HIP_TRY(hipSetDevice(c->device));
   RC_STREAM_TRY(st, stream_aux(c));
   HIP_TRY(hipEventSynchronize(b->evPrep));   // the z and sigma tables are made on the device (k_prep_gaps, k_native_sigma)
-  // the launches' block lists and track offsets, class by class, in one upload: ints, then (8-aligned) the offsets
-  size_t nPos = wide.size();
-  for (const auto &kv : byNK) nPos += kv.second.size();
-  const size_t offAt = (nPos * sizeof(int) + 7) & ~static_cast<size_t>(7);
-  std::vector<uint8_t> lists(offAt + nPos * sizeof(long long));
+  // the launches' block list and track offsets, kernel by kernel, in one upload: ints, then (8-aligned) the offsets
+  std::stable_sort(pos.begin(), pos.end(), [](const Pos &x, const Pos &y) { return native_before(x.m, y.m); });
+  const size_t offAt = (pos.size() * sizeof(int) + 7) & ~static_cast<size_t>(7);
+  std::vector<uint8_t> lists(offAt + pos.size() * sizeof(long long));
   int *hBlocks = reinterpret_cast<int *>(lists.data());
   long long *hOff = reinterpret_cast<long long *>(lists.data() + offAt);
-  struct Launch { int NK; size_t at, count; int smax, maxNK; };   // NK 0: the generic kernel
-  std::vector<Launch> launches;
-  size_t at = 0;
-  auto add = [&](int NK, const std::vector<Pos> &v) {
-    Launch l{NK, at, v.size(), 1, 0};
-    for (const Pos &p : v) {
-      hBlocks[at] = p.blk; hOff[at] = p.off; at++;
-      l.smax = std::max(l.smax, b->meta[p.blk].L / 3); l.maxNK = std::max(l.maxNK, b->meta[p.blk].NK);
-    }
-    launches.push_back(l);
-  };
-  for (const auto &kv : byNK) add(kv.first, kv.second);
-  if (!wide.empty()) add(0, wide);
-  // beside other batches of the context that are being scored: the grid the run's native stage takes beside k_null; else every wavefront slot
-  const int mode = c->inflight.load() > 0 ? 0 : 1;
-  const int chunk = 256;   // blocks per launch of the generic kernel, which share its scratch (launch_native_block)
-  auto wide_stride = [](const Launch &l) { return static_cast<size_t>(3) * l.maxNK * kWave + static_cast<size_t>(kWave) * l.smax; };   // states, then 64 rows of S
-  size_t tileFloats = 4;
-  for (const Launch &l : launches)
-    tileFloats = std::max(tileFloats, l.NK ? native_grid(c, l.count * 6, l.smax, mode) * kWave * l.smax : wide_stride(l) * 6 * std::min<size_t>(chunk, l.count));
+  for (size_t i = 0; i < pos.size(); i++) { hBlocks[i] = pos[i].blk; hOff[i] = pos[i].off; }
+  const NativePlan pl = native_plan_on(c, pos.size(), [&](size_t i) { return pos[i].m; }, native_query_mode(c));
   DevBuf d_lists, d_tile, d_out;
-  for (DevBuf *d : {&d_lists, &d_tile, &d_out}) { d->retired = c->retired.get(); d->pool = c->bufPool.get(); }
+  adopt_bufs(c, {&d_lists, &d_tile, &d_out});
   const uint8_t *blob = b->dblob.as<uint8_t>();
   bool launched = false;
   // (a lambda: whatever fails in it, nothing returns to the caller -- who owns `out`, while `lists` and the buffers die with this frame --
   // before the work already queued on the stream has drained)
   const int rc = [&]() -> int {
     HIP_TRY(d_lists.ensure(lists.size()));
-    HIP_TRY(d_tile.ensure(tileFloats * sizeof(float)));
+    HIP_TRY(d_tile.ensure(std::max<size_t>(std::max(pl.tileFloats, pl.scratchFloats), 4) * sizeof(float)));   // (one buffer for both: one stream)
     HIP_TRY(d_out.ensure(static_cast<size_t>(total) * sizeof(float)));
     launched = true;   // from here on something may be in flight
     HIP_TRY(hipMemcpyAsync(d_lists.p, lists.data(), lists.size(), hipMemcpyHostToDevice, st));
     NativeArgs na{};
     na.blob = b->dblob.as<uint8_t>(); na.dblocks = reinterpret_cast<const DevBlock *>(blob + b->oDblocks);
     na.flags = b->dflags.as<uint32_t>();
-    for (const Launch &l : launches) {
-      NativeArgs nc = na;
-      nc.blocks = d_lists.as<int>() + l.at;
-      const long long *trackOff = reinterpret_cast<const long long *>(d_lists.as<uint8_t>() + offAt) + l.at;
-      if (l.NK) {
-        nc.nItems = static_cast<int>(l.count) * 6;
-        nc.tile = d_tile.as<float>(); nc.tileStride = static_cast<size_t>(kWave) * l.smax;
-        if (!launch_native_track(l.NK, nc, static_cast<int>(native_grid(c, static_cast<size_t>(nc.nItems), l.smax, mode)), d_out.as<float>(), trackOff, st))
-          return fail(RC_ERR_UNSUPPORTED, "no native DP kernel for this number of rows");
-      } else {
-        for (size_t lo = 0; lo < l.count; lo += chunk) {
-          NativeArgs ng = nc;
-          ng.blocks = nc.blocks + lo;
-          launch_native_track_generic(ng, static_cast<int>(std::min<size_t>(chunk, l.count - lo)), d_tile.as<float>(), wide_stride(l), d_out.as<float>(),
-                                      trackOff + lo, st);
-        }
-      }
-      HIP_TRY(hipGetLastError());
-    }
+    const NativeTrack track{d_out.as<float>(), reinterpret_cast<const long long *>(d_lists.as<uint8_t>() + offAt)};
+    const int launches = launch_native_plan(pl, na, d_lists.as<int>(), NativeBufs{d_tile.as<float>(), d_tile.as<float>(), nullptr}, st, &track);
+    if (launches < 0) return launches;
+    HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, d_out.p, static_cast<size_t>(total) * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));   // (the streams are non-blocking: nothing else would wait for the copy)
     return RC_OK;
@@ -522,7 +499,7 @@ int rc_batch_segment_scores(const rc_batch *b, const rc_bt_range *ranges, int32_
   RC_STREAM_TRY(st, stream_aux(c));
   HIP_TRY(hipEventSynchronize(b->evPrep));   // the z and sigma tables are made on the device (k_prep_gaps, k_native_sigma)
   DevBuf d_up, d_pairs, d_scores;
-  for (DevBuf *d : {&d_up, &d_pairs, &d_scores}) { d->retired = c->retired.get(); d->pool = c->bufPool.get(); }
+  adopt_bufs(c, {&d_up, &d_pairs, &d_scores});
   const uint8_t *blob = b->dblob.as<uint8_t>();
   bool launched = false;
   // (a lambda: whatever fails in it, nothing returns to the caller -- who owns the outputs, while `up` and the buffers die with this frame --
@@ -578,9 +555,7 @@ int rc_batch_segment_null(const rc_batch *bc, const rc_bt_range *ranges, int32_t
     codesNeed = std::max(codesNeed, static_cast<size_t>(rd.count) * groups * rd.stride);
   }
   if (maxItems > static_cast<size_t>(INT32_MAX)) return fail(RC_ERR_ARG, "more than 2^31 - 1 (block, sample group) items in one round");
-  for (int blk : pl.blocks)   // k_segment_null finds a sequence's code words by GenericLayout's rule: the two must agree
-    if (codes_bytes(blk) != al256(static_cast<size_t>(6) * b->meta[blk].NK * seg_null_code_words(b->meta[blk].L) * kWave * sizeof(uint32_t)))
-      return fail(RC_ERR_UNSUPPORTED, "internal: the layout of the sigma codes has changed");
+  for (int blk : pl.blocks) RC_TRY(check_codes_layout(b, blk));
   // one upload: the distinct blocks, the CSR, the ranges, the native scores
   const size_t nb = pl.blocks.size(), nr = static_cast<size_t>(n_ranges);
   const size_t oStart = nb, oIdx = oStart + nb + 1, oRanges = oIdx + nr, oScores = oRanges + 4 * nr, upWords = oScores + nr;
@@ -595,7 +570,7 @@ int rc_batch_segment_null(const rc_batch *bc, const rc_bt_range *ranges, int32_t
   RC_STREAM_TRY(st, stream_aux(c));
   HIP_TRY(hipEventSynchronize(b->evPrep));   // the tables of the blob are made on the device
   DevBuf d_up, d_ge, d_cnt, d_codes, d_null;
-  for (DevBuf *d : {&d_up, &d_ge, &d_cnt, &d_codes, &d_null}) { d->retired = c->retired.get(); d->pool = c->bufPool.get(); }
+  adopt_bufs(c, {&d_up, &d_ge, &d_cnt, &d_codes, &d_null});
   const uint8_t *blob = b->dblob.as<uint8_t>();
   constexpr size_t kCntWords = 16;   // the simulation's eight work queues, then (8-aligned) its clamp count: this call's own, read by nobody
   bool launched = false;
@@ -632,15 +607,8 @@ int rc_batch_segment_null(const rc_batch *bc, const rc_bt_range *ranges, int32_t
       for (int p = rd.first; p < rd.first + rd.count; p++) {
         maxN = std::max(maxN, b->meta[pl.blocks[p]].N); maxNodes = std::max(maxNodes, b->db[pl.blocks[p]].nnodes);
       }
-      const size_t lds = null_generic_lds_bytes(maxN, maxNodes);
-      const auto key = std::make_tuple(NullKind::GenericSim, 0, lds);
-      const auto it = c->occ.find(key);
-      const int occ = std::max(1, it != c->occ.end() ? it->second : (c->occ[key] = generic_occupancy(NullKind::GenericSim, lds)));
-      const long long items = static_cast<long long>(rd.count) * groups;
-      HIP_TRY(hipMemsetAsync(d_cnt.p, 0, kCntWords * sizeof(uint32_t), st));   // (behind the round before: one stream)
       sim.classBlocks = d_up.as<int>() + rd.first; sim.nClassBlocks = rd.count; sim.codesStride = rd.stride;
-      launch_generic(NullKind::GenericSim, sim, static_cast<int>(std::min<long long>(items, static_cast<long long>(c->numCU) * occ)), lds, d_codes.as<uint8_t>(), st);
-      HIP_TRY(hipGetLastError());
+      RC_TRY(launch_sim_side(c, sim, static_cast<long long>(rd.count) * groups, maxN, maxNodes, kCntWords, st));
       sn.blocks = sim.classBlocks; sn.blkStart = d_up.as<int>() + oStart + rd.first; sn.nBlocks = rd.count; sn.codesStride = rd.stride;
       launch_segment_null(sn, st);
       HIP_TRY(hipGetLastError());
@@ -659,8 +627,8 @@ int rc_batch_segment_null(const rc_batch *bc, const rc_bt_range *ranges, int32_t
 }  // extern "C"
 
 // Decoy listings (rc_decoys.hip, rc_shuffle.hip): the whole HSS listing of decoy alignments of the listed blocks.  Per (block, decoy) a
-// native-format sigma table and a copy of the block's header aimed at it; the native block's kernels, unchanged and grouped by row count as
-// launch_native_block groups them, score those copies as if they were blocks.  The scored positions go in rounds under a budget
+// native-format sigma table and a copy of the block's header aimed at it; the native block's kernels, unchanged and planned as the run plans
+// them (rc_native_plan.h), score those copies as if they were blocks.  The scored positions go in rounds under a budget
 // (rc_decoy_plan.h); each round's HSS records are packed behind those of the rounds before, and the whole call's come back with one copy
 // behind one synchronisation.  Nothing of the batch is written.
 // The two entry points differ in what fills a round's sigma tables and header copies, a Fill:
@@ -681,10 +649,6 @@ struct DecoyRoundCtx {
   hipStream_t st;
 };
 
-inline void adopt_bufs(rc_ctx *c, std::initializer_list<DevBuf *> bufs) {
-  for (DevBuf *d : bufs) { d->retired = c->retired.get(); d->pool = c->bufPool.get(); }
-}
-
 // rc_batch_decoys: per listed block one simulation item of k_generic_sim<false> -- the run's own simulation, lane = decoy, MT19937 streams of
 // this call's seeds in a buffer of this call's own -- leaves the sigma codes; k_decoy_sigma expands them into the tables.
 struct SimFill {
@@ -700,11 +664,7 @@ struct SimFill {
   size_t codes_bytes(int blk) const { return null_generic_codes_bytes(b->meta[blk].N, b->meta[blk].L, b->db[blk].nnodes); }
   int plan(const std::vector<int32_t> &blocks) {   // (the positions: the vector grows behind them later)
     up = &blocks;
-    for (int32_t blk : blocks) {   // k_decoy_sigma finds a sequence's code words by GenericLayout's rule: the two must agree
-      const BlockMeta &h = b->meta[blk];
-      if (codes_bytes(blk) != al256(static_cast<size_t>(6) * h.NK * seg_null_code_words(h.L) * kWave * sizeof(uint32_t)))
-        return fail(RC_ERR_UNSUPPORTED, "internal: the layout of the sigma codes has changed");
-    }
+    for (int32_t blk : blocks) RC_TRY(check_codes_layout(b, blk));
     return RC_OK;
   }
   size_t bytes(int p) const { return codes_bytes((*up)[static_cast<size_t>(p)]); }
@@ -728,14 +688,8 @@ struct SimFill {
     return RC_OK;
   }
   int round(const DecoyRoundCtx &x) {
-    const size_t lds = null_generic_lds_bytes(x.maxN, x.maxNodes);
-    const auto key = std::make_tuple(NullKind::GenericSim, 0, lds);
-    const auto it = c->occ.find(key);
-    const int occ = std::max(1, it != c->occ.end() ? it->second : (c->occ[key] = generic_occupancy(NullKind::GenericSim, lds)));
-    HIP_TRY(hipMemsetAsync(d_cnt.p, 0, 8 * sizeof(uint32_t), x.st));   // (behind the round before: one stream)
     sim.classBlocks = x.blocks; sim.nClassBlocks = x.rd->count; sim.codesStride = x.rd->stride.codes;
-    launch_generic(NullKind::GenericSim, sim, static_cast<int>(std::min<long long>(x.rd->count, static_cast<long long>(c->numCU) * occ)), lds, d_codes.as<uint8_t>(), x.st);
-    HIP_TRY(hipGetLastError());
+    RC_TRY(launch_sim_side(c, sim, x.rd->count, x.maxN, x.maxNodes, 8, x.st));
     da.blocks = x.blocks; da.codesStride = x.rd->stride.codes; da.sigmaAll = x.sigmaAll; da.sigmaStride = x.rd->stride.sigma;
     da.vblocks = x.vblocks; da.vflags = x.vflags;
     launch_decoy_sigma(da, x.rd->count, x.maxNK, x.st);
@@ -844,59 +798,37 @@ int decoys_body(rc_batch *b, const int32_t *blks, int32_t n_blks, int K, rc_hss 
   if (P > 0) {
     size_t budget = kDecoyMaxBytes;
     if (const char *e = std::getenv("RC_DECOY_MAX_BYTES")) budget = static_cast<size_t>(std::max(1ll, std::atoll(e)));
-    const auto meta_of = [&](size_t p) -> const BlockMeta & { return b->meta[up[p]]; };
-    const auto wide = [&](const BlockMeta &h, int blk) { return h.N > kTemplRows || block_class(h.N, h.L, b->db[blk].omega, c->rule) == kGenericClass; };
     RC_TRY(fill.plan(up));
     const std::vector<DecoyRound> rounds = decoy_plan(static_cast<int>(P), [&](int p) {
-      const BlockMeta &h = meta_of(p);
+      const BlockMeta &h = b->meta[up[static_cast<size_t>(p)]];
       const size_t smax = static_cast<size_t>(h.L / 3);
       return DecoyCost{fill.bytes(p), al256(static_cast<size_t>(2) * h.NK * (h.L + 1) * sizeof(float)), 6 * smax * smax * sizeof(float),
                        static_cast<size_t>(6) * b->hssCap * sizeof(DevHss)};
     }, K, budget);
-    // a round's launches: its (block, decoy) numbers -- (position in the round) x K + d, what the native kernels take for a block index -- by
-    // row count, the blocks of the generic native kernel in one list
-    struct Launch { int NK; size_t at, count; int smax, maxNK; bool all; };   // NK 0: k_native_dp_generic
-    struct Round { size_t first, nLaunch; int maxN, maxNK, maxNodes; };
-    std::vector<Launch> launches;
+    // a round's launch list: its (block, decoy) numbers -- (position in the round) x K + d, what the native kernels take for a block index -- in
+    // the order of the native block's plan, which makes the round's launches of it
+    struct Round { size_t listAt; NativePlan pl; int maxN, maxNK, maxNodes; };
     std::vector<Round> rinfo;
-    const int mode = c->inflight.load() > 0 ? 0 : 1;   // (rc_batch_track's rule)
-    const int chunk = 256;                             // blocks per launch of the generic kernel, which share its scratch (launch_native_block)
-    const auto wide_stride = [](const Launch &l) { return static_cast<size_t>(3) * l.maxNK * kWave + static_cast<size_t>(kWave) * l.smax; };
+    const int mode = native_query_mode(c);
     size_t fillNeed = 0, sigmaNeed = 0, tileFloats = 4, scratchFloats = 0, allFloats = 0, maxV = 0;
     up.reserve(P + V);
+    std::vector<int> order;
+    std::vector<NativeMember> mem;
     for (const DecoyRound &rd : rounds) {
-      Round ri{launches.size(), 0, 0, 0, 0};
-      std::map<int, std::vector<int>> byNK;
-      std::vector<int> wides;
+      Round ri{up.size(), {}, 0, 0, 0};
+      order.resize(static_cast<size_t>(rd.count)); mem.resize(order.size());
       for (int q = 0; q < rd.count; q++) {
         const int blk = up[static_cast<size_t>(rd.first + q)];
-        const BlockMeta &h = b->meta[blk];
-        ri.maxN = std::max(ri.maxN, h.N); ri.maxNK = std::max(ri.maxNK, h.NK); ri.maxNodes = std::max(ri.maxNodes, b->db[blk].nnodes);
-        std::vector<int> &v = wide(h, blk) ? wides : byNK[h.NK];
-        for (int d = 0; d < K; d++) v.push_back(q * K + d);
+        ri.maxN = std::max(ri.maxN, b->meta[blk].N); ri.maxNK = std::max(ri.maxNK, b->meta[blk].NK); ri.maxNodes = std::max(ri.maxNodes, b->db[blk].nnodes);
+        order[static_cast<size_t>(q)] = q; mem[static_cast<size_t>(q)] = native_member(b, blk);
       }
-      const auto add = [&](int NK, const std::vector<int> &v) {
-        Launch l{NK, up.size(), v.size(), 1, 0, false};
-        for (int vr : v) {
-          const BlockMeta &h = meta_of(static_cast<size_t>(rd.first + vr / K));
-          l.smax = std::max(l.smax, h.L / 3); l.maxNK = std::max(l.maxNK, h.NK);
-        }
-        up.insert(up.end(), v.begin(), v.end());
-        if (NK) {
-          const size_t items = l.count * 6, fl = items * l.smax * l.smax;
-          tileFloats = std::max(tileFloats, native_grid(c, items, l.smax, mode) * kWave * l.smax);
-          // every matrix kept for k_native_scan where the run keeps them (launch_native_block)
-          l.all = fl * sizeof(float) <= c->totalMem / 16 && items >= 6 * 64 && (NK <= 16 || NK > 32);
-          if (l.all) allFloats = std::max(allFloats, fl);
-        } else {
-          scratchFloats = std::max(scratchFloats, wide_stride(l) * 6 * std::min<size_t>(chunk, l.count));
-        }
-        launches.push_back(l);
-      };
-      for (const auto &kv : byNK) add(kv.first, kv.second);
-      if (!wides.empty()) add(0, wides);
-      ri.nLaunch = launches.size() - ri.first;
-      rinfo.push_back(ri);
+      std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return native_before(mem[static_cast<size_t>(x)], mem[static_cast<size_t>(y)]); });
+      for (int q : order)
+        for (int d = 0; d < K; d++) up.push_back(q * K + d);
+      ri.pl = native_plan_on(c, order.size() * K, [&](size_t i) { return mem[static_cast<size_t>(order[i / K])]; }, mode);
+      tileFloats = std::max(tileFloats, ri.pl.tileFloats); scratchFloats = std::max(scratchFloats, ri.pl.scratchFloats);
+      allFloats = std::max(allFloats, ri.pl.allFloats);
+      rinfo.push_back(std::move(ri));
       fillNeed = std::max(fillNeed, static_cast<size_t>(rd.count) * rd.stride.codes);
       sigmaNeed = std::max(sigmaNeed, static_cast<size_t>(rd.count) * K * rd.stride.sigma);
       maxV = std::max(maxV, static_cast<size_t>(rd.count) * K);
@@ -941,26 +873,9 @@ int decoys_body(rc_batch *b, const int32_t *blks, int32_t n_blks, int K, rc_hss 
         // the round's (block, decoy) numbers start at 0: its counts at the round's place in the call's arrays
         const size_t v0 = static_cast<size_t>(rd.first) * K;
         na.hss = d_hss.as<DevHss>(); na.hssCount = ri32 + 4 + v0 * 6;
-        for (size_t x = ri.first; x < ri.first + ri.nLaunch; x++) {
-          const Launch &l = launches[x];
-          NativeArgs nc = na;
-          nc.blocks = d_up.as<int>() + l.at;
-          if (l.NK) {
-            nc.nItems = static_cast<int>(l.count) * 6;
-            nc.tile = d_tile.as<float>(); nc.tileStride = static_cast<size_t>(kWave) * l.smax;
-            if (l.all) { nc.sAll = d_all.as<float>(); nc.sAllSites = l.smax; }
-            if (!launch_native_dp(l.NK, nc, static_cast<int>(native_grid(c, static_cast<size_t>(nc.nItems), l.smax, mode)), st))
-              return fail(RC_ERR_UNSUPPORTED, "no native DP kernel for this number of rows");
-            if (nc.sAll) launch_native_scan(nc, st);
-          } else {
-            for (size_t lo = 0; lo < l.count; lo += chunk) {
-              NativeArgs ng = nc;
-              ng.blocks = nc.blocks + lo;
-              launch_native_dp_generic(ng, static_cast<int>(std::min<size_t>(chunk, l.count - lo)), d_scratch.as<float>(), wide_stride(l), st);
-            }
-          }
-          HIP_TRY(hipGetLastError());
-        }
+        const int launches = launch_native_plan(ri.pl, na, d_up.as<int>() + ri.listAt, NativeBufs{d_tile.as<float>(), d_scratch.as<float>(), d_all.as<float>()}, st);
+        if (launches < 0) return launches;
+        HIP_TRY(hipGetLastError());
         // the round's records behind those of the rounds before (the total runs on): where a slot's records start is offsets[slot]
         launch_hss_pack(d_hss.as<DevHss>(), na.hssCount, b->hssCap, rd.count * K * 6, packed, ri32 + 4 + slots + v0 * 6, ri32 + 2, st);
         HIP_TRY(hipGetLastError());

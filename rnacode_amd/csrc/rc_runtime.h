@@ -2,7 +2,7 @@
 // that keeps them between batches, the context, a batch, a stream of batches, and the functions that cross unit boundaries.
 //   rc_context.cpp   contexts: streams, constant tables, host thread pool
 //   rc_batch.cpp     a batch's life: prepare -> upload -> run -> wait
-//   rc_schedule.cpp  which kernels a run launches, with what grids, LDS and scratch (the launch plans)
+//   rc_schedule.cpp  which kernels a run launches, with what grids, LDS and scratch (the launch plans); the native block's launches of every caller
 //   rc_stream.cpp    streams of sub-batches
 //   rc_results.cpp   accessors, backtrack, code tables
 //   rc_trees_api.cpp the tree estimator's entry points, stand-alone fits and the MT19937 accessor
@@ -21,6 +21,7 @@
 #include <cstring>
 #include <deque>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -32,6 +33,7 @@
 #include "../../include/rnacode_hip.h"
 #include "rc_host.h"
 #include "rc_launch.h"
+#include "rc_native_plan.h"
 
 using namespace rc;
 
@@ -383,6 +385,11 @@ struct rc_ctx {
   size_t retiredCapBytes = 0;     // more than this parked while batches are in flight: the next wait drains (and stalls) once; 1/16 of the device memory
 };
 
+// a call's own device buffers: outgrown ones are parked in the context's list, and they come from and go back to its pool
+inline void adopt_bufs(rc_ctx *c, std::initializer_list<DevBuf *> bufs) {
+  for (DevBuf *d : bufs) { d->retired = c->retired.get(); d->pool = c->bufPool.get(); }
+}
+
 // the context's streams, created on first use (see rc_ctx_create); which: 0..2 compute, 3 native, 4 copy, 5 aux, 6 and 7 tree fits
 // nullptr if the stream cannot be created: callers return RC_ERR_DEVICE (a null handle would be the legacy default stream, which
 // does not order against the non-blocking ones)
@@ -531,8 +538,26 @@ extern bool g_no_stream_cache;
 // the context's MT19937 streams U[draw][Spad] for seeds seed .. seed + Spad - 1, at least D draws: the cached ones, or generated on `st`
 int ensure_mt_stream(rc_ctx *c, rc_batch *b, hipStream_t st, uint32_t seed, int Spad, int D);
 size_t native_grid(const rc_ctx *c, size_t items, int smax, int mode = 0);                        // rc_schedule.cpp
+// the plan of rc_native_plan.h with this context's grid rule and device memory
+template <typename MemberOf> NativePlan native_plan_on(const rc_ctx *c, size_t n, MemberOf memberOf, int mode) {
+  return native_plan(n, memberOf, [&](size_t items, int smax) { return native_grid(c, items, smax, mode); }, c->totalMem);
+}
+// a query on a finished batch: beside other batches of the context that are being scored the grid the run's native stage takes beside k_null, else
+// every wavefront slot
+inline int native_query_mode(const rc_ctx *c) { return c->inflight.load() > 0 ? 0 : 1; }
 bool fat_class(const rc_batch *b, const rc_ctx *c, int NK, int maxL);
 int launch_native_block(const RunEnv &R);
+// The launches of a plan (rc_native_plan.h) on `st`: base with blob, dblocks, flags and -- DP -- the HSS fields set; `list` the device list the
+// groups index into; the buffers hold the plan's tileFloats, scratchFloats and allFloats.  track: the track's kernels in place of DP and scan,
+// member i's arrays from out[off[i]] (off on the device, beside `list`).  Returns the number of launches, or an RC_ERR_* code (negative).
+struct NativeBufs { float *tile, *scratch, *all; };
+struct NativeTrack { float *out; const long long *off; };
+int launch_native_plan(const NativePlan &pl, const NativeArgs &base, const int *list, const NativeBufs &buf, hipStream_t st, const NativeTrack *track = nullptr);
+// resident workgroups per CU of a kind's kernel (n: its N-1 or tile size) with lds bytes of dynamic LDS, asked once per context; 0: cannot launch
+int occupancy(rc_ctx *c, NullKind kind, int n, size_t lds);
+// k_generic_sim<false> for a query on a finished batch (rc_batch_segment_null, rc_batch_decoys): sim.workCounter's cntWords words zeroed, then
+// `items` items of blocks of at most maxN rows and maxNodes tree nodes on as many workgroups as stay resident, codes to sim.codesAll
+int launch_sim_side(rc_ctx *c, const NullArgs &sim, long long items, int maxN, int maxNodes, size_t cntWords, hipStream_t st);
 size_t steal_slots(const rc_ctx *c);
 size_t steal_words(const rc_ctx *c);
 // null sampling of the sample groups [gLo, gHi) of every class: what the round's plan takes -- uint32 of staging scratch, the return value,

@@ -42,78 +42,28 @@ int launch_native_block(const RunEnv &R) {
   na.flags = b->dflags.as<uint32_t>();
   HIP_TRY(hipMemsetAsync(b->dhssCount.p, 0, static_cast<size_t>(R.n) * 6 * sizeof(int), st));
   launch_native_sigma(na, static_cast<int>(b->okBlocks.size()), st); b->nl[3]++;
-  // Groups of blocks with one row count, each a contiguous piece of its class's list: a per-row-count class is one group; a tiled class (row
-  // counts mixed, its list sorted by row count: rc_batch.cpp) one per row count -- the native block of its blocks goes through k_native_dp<N-1>
-  // like any block of up to 64 rows (k_native_dp_generic, one wavefront per matrix with its states in memory, took 7 ms for 1662 blocks of
-  // 40 x 150 where k_native_dp<39> takes 0.4).
-  struct Group { int NK; const int *list; size_t count; int smax; };
-  std::vector<Group> groups;
-  for (auto &kv : b->classes) {
-    if (kv.first == kGenericClass) continue;
-    const int *list = R.classList + b->classOff[kv.first];
-    const auto &mem = kv.second;
-    for (size_t at = 0; at < mem.size();) {
-      size_t end = at;
-      int smax = 1;
-      const int nk = b->meta[mem[at]].NK;
-      while (end < mem.size() && b->meta[mem[end]].NK == nk) { smax = std::max(smax, b->meta[mem[end]].L / 3); end++; }
-      groups.push_back(Group{nk, list + at, end - at, smax});
-      at = end;
+  // The class lists, one behind the other as the device has them (rc_batch.cpp): a per-row-count class is one group; a tiled class (row counts
+  // mixed, its list sorted by row count) one per row count, those of more than 64 rows wide; the generic class one wide group.  The key: the
+  // class, and in any but the generic one the row count -- a group never holds blocks of two classes, whatever their row counts.  (Classes
+  // are 2 and up, so class x kMaxRows + N - 1 is 1000 at the least and never the generic class's own number, 64.)  Wide as native_wide has
+  // it, read off the class the block is already in.
+  std::vector<NativeMember> mem;
+  mem.reserve(b->okBlocks.size());
+  for (const auto &kv : b->classes) {
+    const bool generic = kv.first == kGenericClass;
+    for (int bi : kv.second) {
+      const BlockMeta &m = b->meta[bi];
+      mem.push_back(NativeMember{m.NK, m.L, generic || m.N > kTemplRows, generic ? kv.first : kv.first * kMaxRows + m.NK});
     }
   }
-  {   // one 64-row buffer per persistent workgroup, shared by the group launches (same stream)
-    size_t need = 0;
-    for (const Group &g : groups) if (g.NK < kTemplRows) need = std::max(need, native_grid(c, g.count * 6, g.smax, R.nativeMode) * kWave * g.smax);
-    HIP_TRY(b->dnativeTile.ensure(std::max<size_t>(need, 4) * sizeof(float)));
-  }
-  {   // more than 64 rows: states in a scratch, at most 256 blocks per launch share it -- the generic class, and the blocks of that width in the tiled ones
-    struct Wide { const int *list; size_t count; int maxNK, smax; };
-    std::vector<Wide> wides;
-    if (b->classes.count(kGenericClass)) {
-      const auto &mem = b->classes[kGenericClass];
-      Wide w{R.classList + b->classOff[kGenericClass], mem.size(), 0, 1};
-      for (int bi : mem) { w.maxNK = std::max(w.maxNK, b->meta[bi].NK); w.smax = std::max(w.smax, b->meta[bi].L / 3); }
-      wides.push_back(w);
-    }
-    for (const Group &g : groups) if (g.NK >= kTemplRows) wides.push_back(Wide{g.list, g.count, g.NK, g.smax});
-    const int chunk = 256;
-    auto stride_of = [](const Wide &w) { return static_cast<size_t>(3) * w.maxNK * kWave + static_cast<size_t>(kWave) * w.smax; };   // states, then 64 rows of S
-    size_t scratchFloats = 0;
-    for (const Wide &w : wides) scratchFloats = std::max(scratchFloats, stride_of(w) * 6 * std::min<size_t>(chunk, w.count));
-    if (scratchFloats) HIP_TRY(b->dnativeScratch.ensure(scratchFloats * sizeof(float)));   // (once: the launches below share it in stream order)
-    for (const Wide &w : wides) {
-      NativeArgs nc = na;
-      nc.blocks = w.list;
-      const size_t stride = stride_of(w);
-      for (size_t at = 0; at < w.count; at += chunk) {
-        NativeArgs ng = nc;
-        ng.blocks = nc.blocks + at;
-        launch_native_dp_generic(ng, static_cast<int>(std::min<size_t>(chunk, w.count - at)), b->dnativeScratch.as<float>(), stride, st);
-        b->nl[3]++;
-      }
-    }
-  }
-  for (const Group &g : groups) {
-    if (g.NK >= kTemplRows) continue;   // (above)
-    // up to 64 rows: DP and getHSS fused, 64 rows of one matrix at a time through a per-workgroup buffer (persistent grid)
-    NativeArgs nc = na;
-    nc.blocks = g.list;
-    nc.nItems = static_cast<int>(g.count) * 6;
-    nc.tileStride = static_cast<size_t>(kWave) * g.smax;
-    const int grid = static_cast<int>(native_grid(c, static_cast<size_t>(nc.nItems), g.smax, R.nativeMode));
-    nc.tile = b->dnativeTile.as<float>();
-    // every matrix of the group kept for a scan with one lane per matrix, where that fits in a sixteenth of the device memory
-    // (headline: 10 000 blocks x 6 x 40 x 40 floats = 384 MB); otherwise DP and scan fused, 64 rows at a time
-    const size_t allFloats = static_cast<size_t>(nc.nItems) * g.smax * g.smax;
-    if (allFloats * sizeof(float) <= c->totalMem / 16 && nc.nItems >= 6 * 64 && (g.NK <= 16 || g.NK > 32)) {   // (17..32: see k_native_dp)
-      HIP_TRY(b->dnativeAll.ensure(std::max<size_t>(allFloats, 4) * sizeof(float)));
-      nc.sAll = b->dnativeAll.as<float>(); nc.sAllSites = g.smax;
-    }
-    if (!launch_native_dp(g.NK, nc, grid, st))
-      return fail(RC_ERR_UNSUPPORTED, "no native DP kernel for this number of rows");
-    b->nl[3]++;
-    if (nc.sAll) { launch_native_scan(nc, st); b->nl[3]++; }
-  }
+  const NativePlan pl = native_plan(mem.size(), [&](size_t i) { return mem[i]; },
+                                    [&](size_t items, int smax) { return native_grid(c, items, smax, R.nativeMode); }, c->totalMem);
+  HIP_TRY(b->dnativeTile.ensure(std::max<size_t>(pl.tileFloats, 4) * sizeof(float)));
+  if (pl.scratchFloats) HIP_TRY(b->dnativeScratch.ensure(pl.scratchFloats * sizeof(float)));
+  if (pl.allFloats) HIP_TRY(b->dnativeAll.ensure(std::max<size_t>(pl.allFloats, 4) * sizeof(float)));
+  const int launches = launch_native_plan(pl, na, R.classList, NativeBufs{b->dnativeTile.as<float>(), b->dnativeScratch.as<float>(), b->dnativeAll.as<float>()}, st);
+  if (launches < 0) return launches;
+  b->nl[3] += launches;
   HIP_TRY(hipMemsetAsync(b->dhssOffsets.as<int>() + R.slots, 0, sizeof(int), st));
   launch_hss_pack(b->dhss.as<DevHss>(), b->dhssCount.as<int>(), b->hssCap, R.slots, b->dhssPacked.as<DevHss>(), b->dhssOffsets.as<int>(),
                   b->dhssOffsets.as<int>() + R.slots, st);
@@ -121,12 +71,51 @@ int launch_native_block(const RunEnv &R) {
   return RC_OK;
 }
 
+// The wide groups first -- their chunks share the scratch in stream order --, then a k_native_dp<N-1> per group over a persistent grid, DP and
+// getHSS fused, 64 rows of one matrix at a time through a per-workgroup buffer; k_native_scan behind it where the group keeps its matrices.
+int launch_native_plan(const NativePlan &pl, const NativeArgs &base, const int *list, const NativeBufs &buf, hipStream_t st, const NativeTrack *track) {
+  int launches = 0;
+  for (const NativeGroup &g : pl.groups) {
+    if (g.NK) continue;
+    NativeArgs na = base;
+    const size_t stride = native_wide_stride(g.maxNK, g.smax);
+    for (size_t lo = 0; lo < g.count; lo += kNativeWideChunk, launches++) {
+      na.blocks = list + g.at + lo;
+      const int blocks = static_cast<int>(native_wide_chunk(g.count, lo));
+      if (track) launch_native_track_generic(na, blocks, buf.scratch, stride, track->out, track->off + g.at + lo, st);
+      else launch_native_dp_generic(na, blocks, buf.scratch, stride, st);
+    }
+  }
+  for (const NativeGroup &g : pl.groups) {
+    if (!g.NK) continue;
+    NativeArgs na = base;
+    na.blocks = list + g.at; na.nItems = static_cast<int>(g.count) * 6;
+    na.tile = buf.tile; na.tileStride = static_cast<size_t>(kWave) * g.smax;
+    if (g.keepAll && !track) { na.sAll = buf.all; na.sAllSites = g.smax; }
+    if (!(track ? launch_native_track(g.NK, na, static_cast<int>(g.grid), track->out, track->off + g.at, st) : launch_native_dp(g.NK, na, static_cast<int>(g.grid), st)))
+      return fail(RC_ERR_UNSUPPORTED, "no native DP kernel for this number of rows");
+    launches++;
+    if (na.sAll) { launch_native_scan(na, st); launches++; }
+  }
+  return launches;
+}
+
+// k_generic_sim<false> outside a run: a query's own simulation of blocks of a finished batch
+int launch_sim_side(rc_ctx *c, const NullArgs &sim, long long items, int maxN, int maxNodes, size_t cntWords, hipStream_t st) {
+  const size_t lds = null_generic_lds_bytes(maxN, maxNodes);
+  const int occ = std::max(1, occupancy(c, NullKind::GenericSim, 0, lds));
+  HIP_TRY(hipMemsetAsync(sim.workCounter, 0, cntWords * sizeof(uint32_t), st));   // (behind the round before: one stream)
+  launch_generic(NullKind::GenericSim, sim, static_cast<int>(std::min<long long>(items, static_cast<long long>(c->numCU) * occ)), lds, sim.codesAll, st);
+  HIP_TRY(hipGetLastError());
+  return RC_OK;
+}
+
 // tail sharing of k_null (rc_null_kernel.h): per launch one claim word and a (block, group) pair per workgroup
 size_t steal_slots(const rc_ctx *c) { return static_cast<size_t>(c->numCU) * 32; }
 size_t steal_words(const rc_ctx *c) { return 16 + 4 * steal_slots(c); }   // header, claim words, (block, group) pairs, list of published slots
 
-// resident workgroups per CU of a kind's kernel (n: its N-1 or tile size) with lds bytes of dynamic LDS, asked once per context; 0: cannot launch
-static int occupancy(rc_ctx *c, NullKind kind, int n, size_t lds) {
+// (rc_runtime.h) the answer of the kernel's family, kept per context
+int occupancy(rc_ctx *c, NullKind kind, int n, size_t lds) {
   const auto key = std::make_tuple(kind, n, lds);
   auto it = c->occ.find(key);
   if (it != c->occ.end()) return it->second;
