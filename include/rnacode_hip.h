@@ -391,6 +391,30 @@ int rc_batch_decoys(const rc_batch *b, const int32_t *blks, int32_t n_blks, uint
 int rc_batch_decoys_shuffled(const rc_batch *b, const int32_t *blks, int32_t n_blks, uint32_t seed, int32_t n_decoys, rc_hss *out, int64_t cap,
                              int64_t *offsets /* n_blks * n_decoys + 1 */);
 
+/* The shuffle null: the p-values' null distribution made from the block itself instead of simulated under its model.  For the k-th listed
+ * block (blks[k], or k where blks is NULL; a block may repeat) and d = 0 .. n_shuffles - 1 (1 <= n_shuffles <= 65536) the call scores the
+ * gap-class column shuffle of seed seed + d -- rc_batch_decoys_shuffled's definition, key function and seeds: shuffle d of this call IS
+ * shuffled decoy d -- with the block's own models, gap tables and parameters, as a null sample of the run is scored:
+ *   - maxima_out[k * n_shuffles + d] (may be NULL) = the value rc_batch_maxima would hold for that alignment: the score of the
+ *     first-or-greater entry of its HSS list, or -1 where it has none.  With the same seed it has the bits of the best score of list d of
+ *     rc_batch_decoys_shuffled (-1 where that list is empty);
+ *   - fit_out[4 k + {0, 1, 2, 3}] = {evd_rc (1 / -1), mu, lambda of the Gumbel fit of the block's n_shuffles maxima -- the run's fit: the
+ *     same kernel, exp and binary32 inputs, so a fit of few values does what the run's does with as few --, the number of shuffles whose
+ *     maximum is >= the block's best native score}: rc_batch_fit_all's record.  rc_pvalue(score, mu, lambda) is the p-value of an HSS of
+ *     the block under this null.  A block that was not scored gets {its status, 0, 0, 0} and maxima of -1.
+ * Shuffle d depends on seed + d and the block only: not on n_shuffles, on which blocks are listed, on the budget or on RC_SHUFFLE_LDS_COLS.
+ * A block where no gap class has two columns has only the identity shuffle: all its maxima are equal.
+ * A block index out of range, n_shuffles outside 1..65536 or a batch that has not completed a run returns RC_ERR_ARG; every argument is
+ * checked before the device is touched, and on an error the outputs are left alone.  Works on a batch rc_stream_next handed out until it
+ * is recycled, and leaves the batch's maxima, fit, HSS, timings and rc_batch_clamped as they are.
+ * Cost: the class ids of every distinct listed block once per call on the host; per (block, shuffle) one sort as for a shuffled decoy;
+ * per (block, group of 64 shuffles) one wavefront that reads the block's characters through the group's permutations and leaves sigma
+ * codes where the wide-block sampling path leaves a null sample's, and that path's DP (lane = shuffle) on them.  The distinct blocks go
+ * in rounds under a budget of device memory, 2 GB by default (RC_SHUFFLE_NULL_MAX_BYTES overrides, read per call; a single block may
+ * exceed it; the result does not depend on it); one synchronisation and one copy back per call. */
+int rc_batch_shuffle_null(const rc_batch *b, const int32_t *blks, int32_t n_blks, uint32_t seed, int32_t n_shuffles,
+                          float *fit_out /* 4 n_blks */, float *maxima_out /* n_blks * n_shuffles, may be NULL */);
+
 /* The substitution matrix and genetic code the scorer uses, for callers that render results
  * (getScoringMatrix() score.c:50-76 and transcode[4][4][4] code.c:28-39, which src/postscript.c:362,412
  * read): pep_out[16a+4b+c] = amino-acid index 0..19 of codon (a,b,c) in A,C,G,T order or -1 for a stop;

@@ -176,6 +176,7 @@ def lib():
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         l.rc_batch_decoys_shuffled.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(RcHss), C.c_int64,
                                                C.POINTER(C.c_int64)]
+        l.rc_batch_shuffle_null.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p]
         l.rc_evd_fit.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         l.rc_mt_stream.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_int32]
         l.rc_pvalue.argtypes = [C.c_float, C.c_float, C.c_float]
@@ -211,7 +212,7 @@ EXPORTED_SYMBOLS = [
     "rc_batch_prep_timing", "rc_host_cpus", "rc_ctx_set_host_threads", "rc_ctx_host_threads", "rc_ctx_fit_exp_mode", "rc_stream_create_v2", "rc_stream_submit", "rc_stream_submit_bound",
     "rc_stream_next", "rc_stream_recycle", "rc_stream_pending", "rc_stream_plan", "rc_stream_destroy", "rc_set_stream_cache", "rc_batch_work", "rc_batch_timing", "rc_batch_null_kernel", "rc_batch_status",
     "rc_batch_models", "rc_batch_maxima", "rc_batch_maxima_all", "rc_batch_fit", "rc_batch_fit_all", "rc_batch_hss", "rc_batch_hss_all", "rc_batch_clamped",
-    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_batch_segment_scores", "rc_batch_segment_null", "rc_batch_decoys", "rc_batch_decoys_shuffled", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
+    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_batch_segment_scores", "rc_batch_segment_null", "rc_batch_decoys", "rc_batch_decoys_shuffled", "rc_batch_shuffle_null", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
     "rc_code_tables_for", "rc_genetic_code", "rc_species_tree_create", "rc_species_tree_destroy", "rc_species_tree_tips", "rc_species_tree_prune",
     "rc_fit_species_trees", "rc_fit_species_trees_device",
 ]
@@ -646,6 +647,24 @@ class Batch:
         o = list(offs)
         lists = [[recs[o[i * k + d]:o[i * k + d + 1]] for d in range(k)] for i in range(n)]
         return (lists, clamped.value) if with_clamped else lists
+
+    def shuffle_null(self, n_shuffles: int, seed: Optional[int] = None, blks=None, maxima: bool = True):
+        """rc_batch_shuffle_null: the null distribution made from each block of `blks` (default: all, in order) itself -- the maxima of
+        n_shuffles (1..65536) gap-class column shuffles (decoys.shuffle_columns, seeds seed + d: shuffle d is shuffled decoy d) and their
+        Gumbel fit.  -> (fits [n, 4] float32: evd_rc or the block's status, mu, lambda, shuffles whose maximum is >= the block's best
+        native score; maxima [n, n_shuffles] float32, or None with maxima=False).  The default seed is seed_base + sampleN."""
+        if seed is None:
+            seed = int(self.params.seed_base) + int(self.params.sampleN)
+        if blks is None:
+            arr, n, ptr = None, self.n, None
+        else:
+            arr = np.ascontiguousarray(np.asarray(list(blks), dtype=np.int32).reshape(-1))
+            n, ptr = arr.shape[0], arr.ctypes.data
+        k = int(n_shuffles)
+        fits = np.zeros((n, 4), dtype=np.float32)
+        mx = np.zeros((n, max(k, 0)), dtype=np.float32) if maxima else None
+        _check(lib().rc_batch_shuffle_null(self._h, ptr, n, C.c_uint32(seed & 0xFFFFFFFF), k, fits.ctypes.data, None if mx is None else mx.ctypes.data))
+        return fits, mx
 
     def getExtremeValuePars(self, blk: int) -> Tuple[int, float, float]:
         rc, mu, lam = C.c_int32(), C.c_float(), C.c_float()

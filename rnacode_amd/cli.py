@@ -5,7 +5,7 @@ options that concern the scoring path and the listings:
 
     python -m rnacode_amd.cli [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S]
                               [-e [-i CUTOFF] [-d DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null]]
-                              [--decoys K --decoys-out FILE [--decoy-kind simulated|shuffled]]
+                              [--decoys K --decoys-out FILE [--decoy-kind simulated|shuffled]] [--shuffle-null N --shuffle-null-out FILE]
                               [-o OUT] [--trees SIDECAR | --species-tree NEWICK
                               [--species-tree-fit fixed|scale|branches]] [--write-trees SIDECAR] [FILE]
 
@@ -30,6 +30,9 @@ per sub-batch), and (null_ge + 1) / (n + 1).
 --cutoff, -b and -r as the block's own HSS are (decoys.py; one rc_batch_decoys call per sub-batch, seeds seed_base + n ..: the first the
 fit did not see): what `python -m rnacode_amd.decoys` turns into a false discovery rate of the listing.  --decoy-kind shuffled lists, in
 the same file and with the same seeds, each block's own columns permuted within their gap classes instead (rc_batch_decoys_shuffled).
+--shuffle-null N with --shuffle-null-out FILE (not in the reference) writes, per listed HSS, its p-value under the null made from the block
+itself: the Gumbel fit of the maxima of N such shuffles of the block (the same seeds: shuffle d is shuffled decoy d), and the empirical count
+behind it (shuffle_null.py; one rc_batch_shuffle_null call per sub-batch).
 Quirk kept from the reference: the 4th value of --pars goes to stopPenalty_0 (RNAcode.c:318)."""
 from __future__ import annotations
 
@@ -43,7 +46,7 @@ from typing import IO, List, Optional
 
 import numpy as np
 
-from . import api, decoys, details, eps, report, segments, track
+from . import api, decoys, details, eps, report, segments, shuffle_null, track
 from .alnio import AlnBlock, read_alignment_file
 
 
@@ -152,6 +155,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--decoy-kind", metavar="KIND",
                     help="with --decoys: simulated (the default: null alignments under the block's model) or shuffled (the block's own columns, "
                          "permuted among the columns with the same gap pattern: decoys that do not share the p-values' model)")
+    ap.add_argument("--shuffle-null", type=int, metavar="N",
+                    help="with --shuffle-null-out: score N (1..65536) shuffles of every listed block -- its own columns, permuted among the "
+                         "columns with the same gap pattern -- and fit their maxima as -n's are fitted")
+    ap.add_argument("--shuffle-null-out", metavar="FILE",
+                    help="one line per listed HSS: its p under that fit (p_shuffled), how many of the N maxima reach its score (ge), and the "
+                         "columns a shuffle can move (movable)")
     return ap
 
 
@@ -188,6 +197,10 @@ def _intake(a):
         raise _Refused("--decoy-kind needs --decoys")
     if a.decoy_kind is not None and a.decoy_kind not in api.DECOY_KINDS:
         raise _Refused("--decoy-kind is simulated or shuffled")
+    if (a.shuffle_null is not None) != bool(a.shuffle_null_out):
+        raise _Refused("--shuffle-null and --shuffle-null-out go together")
+    if a.shuffle_null is not None and not 1 <= a.shuffle_null <= 65536:
+        raise _Refused("--shuffle-null takes a number of shuffles from 1 to 65536")
     if a.regions:
         try:
             with open(a.regions) as fh:
@@ -229,7 +242,8 @@ def _trees(a, ctx, blocks, marshalled, species, n_read: int, read_index: List[in
 
 
 SIDE_FILES = (("details", details.header), ("track", track.header), ("support", segments.support_header),
-              ("regions_out", segments.regions_header), ("decoys_out", decoys.header))   # the option's name in the parsed arguments, its header line
+              ("regions_out", segments.regions_header), ("decoys_out", decoys.header),
+              ("shuffle_null_out", shuffle_null.header))   # the option's name in the parsed arguments, its header line
 
 
 class _Ranges:
@@ -262,8 +276,9 @@ class _Run:
     state: report.ReportState = field(default_factory=report.ReportState)
 
 
-def _list_block(run: _Run, i: int, b: AlnBlock, hss: List[dict], bt: _Ranges, paths, seg: _Ranges, seg_pairs) -> None:
-    """One scored block's part of the listing, and of --eps, --details and --support beside each of its lines."""
+def _list_block(run: _Run, i: int, b: AlnBlock, hss: List[dict], bt: _Ranges, paths, seg: _Ranges, seg_pairs, shuffled=None) -> None:
+    """One scored block's part of the listing, and of --eps, --details, --support and --shuffle-null-out beside each of its lines.
+    shuffled: the block's (fit, maxima, movable columns) of --shuffle-null."""
     a, side = run.a, run.side
 
     def plot(counter, h):   # misc.c:461-474: hss-<counter>.eps for every listed HSS with p below the plot cutoff
@@ -280,9 +295,11 @@ def _list_block(run: _Run, i: int, b: AlnBlock, hss: List[dict], bt: _Ranges, pa
         if "support" in side:
             side["support"].writelines(segments.support_lines(counter, b.rows[0].name, h, [r.name for r in b.rows], seg_pairs[seg.at[key]],
                                                               run.params.Delta))
+        if shuffled is not None:
+            side["shuffle_null_out"].writelines(shuffle_null.block_lines([counter], b.rows[0].name, [h], *shuffled))
 
     report.print_results(run.out, run.fmt, hss, b.rows[0].name, run.state, cutoff=a.cutoff, best_only=a.best_only, best_region=a.best_region,
-                         eps=plot if a.eps else None, eps_cutoff=a.eps_cutoff, listed=tables if "details" in side or "support" in side else None)
+                         eps=plot if a.eps else None, eps_cutoff=a.eps_cutoff, listed=tables if "details" in side or "support" in side or shuffled is not None else None)
 
 
 def _list_batch(run: _Run, batch, base: int) -> None:
@@ -323,6 +340,11 @@ def _list_batch(run: _Run, batch, base: int) -> None:
     null_ge = batch.segment_null(nul.ranges)[1] if nul.ranges else None
     # --decoys: the decoy listings of the blocks the listing covers with ONE call (rc_batch_decoys)
     decoyed = dict(zip(scored, batch.decoys(a.decoys, run.params.seed_base + run.params.sampleN, scored, kind=a.decoy_kind or "simulated"))) if "decoys_out" in side and scored else {}
+    # --shuffle-null: the shuffle maxima and their fit for the blocks the listing covers with ONE call (rc_batch_shuffle_null)
+    shuffled = {}
+    if "shuffle_null_out" in side and scored:
+        fits, maxima = batch.shuffle_null(a.shuffle_null, run.params.seed_base + run.params.sampleN, scored)
+        shuffled = {i: (fits[k], maxima[k], shuffle_null.movable([r.seq for r in run.blocks[base + i].rows])) for k, i in enumerate(scored)}
     for i in range(batch.n):
         b = run.blocks[base + i]
         if base + i in run.refused:   # the species tree does not cover the block's rows
@@ -335,7 +357,7 @@ def _list_batch(run: _Run, batch, base: int) -> None:
         if status[i] != api.RC_OK:         # RNAcode.c:153-156: the reference has no tree for this block either
             print(f"Skipping alignment. Failed to build ML tree. ({batch.block_error(i) or 'not scored'})", file=sys.stderr)
             continue
-        _list_block(run, i, b, all_hss[i], bt, paths, seg, seg_pairs)
+        _list_block(run, i, b, all_hss[i], bt, paths, seg, seg_pairs, shuffled.get(i))
         if i in decoyed:
             side["decoys_out"].writelines(decoys.block_lines(run.read_index[base + i], b.rows[0].name, decoyed[i], a.cutoff, a.best_only, a.best_region))
         if i in tracked or i in found:

@@ -43,6 +43,12 @@
 // sub-batch (in the sample split one slice computes them, with the p-values of the gathered fit); the same bytes as python -m rnacode_amd.cli,
 // whose decoys.py turns the file and the listing into q-values.  With --gpus N the one writer emits it in input order.
 //
+// --shuffle-null N with --shuffle-null-out FILE (not in the reference): per listed HSS its p-value under the null made from the block itself -- the
+// Gumbel fit of the maxima of N gap-class column shuffles of the block, seeds seed_base + n .. (shuffle d is shuffled decoy d) -- and the
+// empirical count behind it: hss name strand frame start end score p p_shuffled ge n movable.  ONE rc_batch_shuffle_null call per sub-batch,
+// for the blocks the listing covers; the same bytes as python -m rnacode_amd.cli (shuffle_null.py).  With --gpus N the one writer emits it
+// in input order.
+//
 // Quirk kept from the reference: the 4th value of --pars goes to stopPenalty_0 (RNAcode.c:318).
 #include <algorithm>
 #include <atomic>
@@ -294,21 +300,23 @@ std::vector<Block> read_alignment(FILE *in) {
   return read_maf(text, size);
 }
 
-// A side file (--details, --track, --support, --regions-out, --decoys-out): opened and given its header before the first batch, closed and checked
+// A side file (--details, --track, --support, --regions-out, --decoys-out, --shuffle-null-out): opened and given its header before the first batch, closed and checked
 // when everything has been listed.  An empty path: the option is off.
 struct SideFile {
   const char *(*header)();
   std::string path;
   FILE *f;
 };
-enum { kDetails, kTrack, kSupport, kRegions, kDecoys, kSides };
+enum { kDetails, kTrack, kSupport, kRegions, kDecoys, kShuffleNull, kSides };
 const char *decoys_header() { return "block\tdecoy\tstrand\tframe\tlength\tfrom\tto\tname\tstart\tend\tscore\tp\n"; }
+const char *shuffle_null_header() { return "hss\tname\tstrand\tframe\tstart\tend\tscore\tp\tp_shuffled\tge\tn\tmovable\n"; }
 
 // an HSS that gets a line of the listing, and what goes out beside that line
 struct Line {
   rc_hss h;
   std::string eps;                             // --eps: the plot's text, or empty (drawn while the block's batch was alive)
   std::vector<std::string> details, support;   // its --details / --support lines, one per row, without the counter in front
+  std::string shuffleNull;                     // its --shuffle-null-out line, without the counter in front
 };
 
 // printResults (misc.c:392-552); the HSS counter runs across blocks and is not advanced after a --best-only line
@@ -321,7 +329,7 @@ struct Listing {
   float epsCutoff = 0.05f;
   std::string epsDir = "eps";
   SideFile side[kSides] = {{rceps::details_header, "", nullptr}, {rceps::track_header, "", nullptr}, {rceps::support_header, "", nullptr},
-                           {rceps::regions_header, "", nullptr}, {decoys_header, "", nullptr}};
+                           {rceps::regions_header, "", nullptr}, {decoys_header, "", nullptr}, {shuffle_null_header, "", nullptr}};
   bool on(int s) const { return !side[s].path.empty(); }
   int hitCounter = 0;
 
@@ -395,6 +403,7 @@ struct Listing {
       }
       for (const std::string &tail : l.details) std::fprintf(side[kDetails].f, "%i\t%s", hitCounter, tail.c_str());
       for (const std::string &tail : l.support) std::fprintf(side[kSupport].f, "%i\t%s", hitCounter, tail.c_str());
+      if (!l.shuffleNull.empty()) std::fprintf(side[kShuffleNull].f, "%i\t%s", hitCounter, l.shuffleNull.c_str());
       const int length = h.endSite - h.startSite + 1;
       const char strand[2] = {static_cast<char>(h.strand), 0};
       if (fmt == 0) {
@@ -421,7 +430,7 @@ struct Listing {
 void usage() {
   std::fprintf(stderr, "usage: rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]\n"
                        "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null]]\n"
-                       "                   [--decoys K --decoys-out FILE [--decoy-kind simulated|shuffled]]\n"
+                       "                   [--decoys K --decoys-out FILE [--decoy-kind simulated|shuffled]] [--shuffle-null N --shuffle-null-out FILE]\n"
                        "                   [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]\n"
                        "                   [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]\n"
                        "                   [--write-trees SIDECAR] [--dump-blocks] [FILE]\n"
@@ -450,7 +459,11 @@ void usage() {
                        "  --decoys-out FILE          the decoy listing, one line per decoy HSS: block decoy strand frame length from to name start\n"
                        "                             end score p (python -m rnacode_amd.decoys turns it and the -t listing into q-values)\n"
                        "  --decoy-kind KIND          with --decoys: simulated (the default) or shuffled -- the block's own columns, permuted among the\n"
-                       "                             columns with the same gap pattern: decoys that do not share the p-values' model\n");
+                       "                             columns with the same gap pattern: decoys that do not share the p-values' model\n"
+                       "  --shuffle-null N           with --shuffle-null-out: score N (1..65536) shuffles of every listed block -- its own columns,\n"
+                       "                             permuted among the columns with the same gap pattern -- and fit their maxima as -n's are fitted\n"
+                       "  --shuffle-null-out FILE    one line per listed HSS: hss name strand frame start end score p p_shuffled ge n movable --\n"
+                       "                             its p under that fit, how many of the N maxima reach its score, the columns a shuffle can move\n");
 }
 
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -492,6 +505,7 @@ struct Run {
   bool regionsNull = false;                               // --regions-null: null_ge and p_segment behind every --regions-out line
   int decoys = 0;                                         // --decoys: null alignments listed per scored block
   bool decoysShuffled = false;                            // --decoy-kind shuffled: the block's own columns, permuted within their gap classes, instead
+  int shuffleNull = 0;                                    // --shuffle-null: shuffles scored per listed block
   // the writer: one thread, jobs in input order
   std::mutex jm;
   std::condition_variable jcv;
@@ -776,6 +790,57 @@ bool add_decoys(const Run &R, rc_batch *b, Job &j, std::string &err, const std::
   return true;
 }
 
+// the number of columns that lie in a gap class of two or more (shuffle_null.movable): what a shuffle can move
+int movable_columns(const Block &blk) {
+  const size_t cols = blk.rows.empty() ? 0 : blk.rows[0].seq.size();
+  std::map<std::string, int> classes;
+  std::string mask(blk.rows.size(), '.');
+  for (size_t c = 0; c < cols; c++) {
+    for (size_t r = 0; r < blk.rows.size(); r++) mask[r] = blk.rows[r].seq[c] == '-' ? '-' : '.';
+    classes[mask]++;
+  }
+  int n = 0;
+  for (const auto &kv : classes) if (kv.second >= 2) n += kv.second;
+  return n;
+}
+
+// --shuffle-null for every block the listing covers, while the batch is alive: ONE rc_batch_shuffle_null call, seeds seed_base + n .. (the
+// shuffled decoys' own).  Each listed HSS gets its p under the block's shuffle fit (99 where that fit failed) and the count of the N maxima
+// that reach its score, in binary32 (a NaN counts for nothing).
+bool add_shuffle_null(const Run &R, rc_batch *b, Job &j, std::string &err) {
+  std::vector<int32_t> blks;
+  for (size_t i = 0; i < j.blocks.size(); i++) if (scored(R, j.blocks[i])) blks.push_back(static_cast<int32_t>(i));
+  const int nb = static_cast<int>(blks.size()), N = R.shuffleNull;
+  if (!nb) return true;
+  std::vector<float> fit(static_cast<size_t>(4) * nb), maxima(static_cast<size_t>(nb) * N);
+  const uint32_t seed = R.par.seed_base + static_cast<uint32_t>(R.par.sampleN);
+  if (rc_batch_shuffle_null(b, blks.data(), nb, seed, N, fit.data(), maxima.data()) != RC_OK) { err = rc_last_error(); return false; }
+  for (int k = 0; k < nb; k++) {
+    const int i = blks[k];
+    if (j.blocks[i].lines.empty()) continue;
+    const Block &blk = R.blocks[j.blocks[i].index];
+    const int mov = movable_columns(blk);
+    const float *f = fit.data() + 4 * static_cast<size_t>(k), *mx = maxima.data() + static_cast<size_t>(k) * N;
+    for (Line &l : j.blocks[i].lines) {
+      const rc_hss &h = l.h;
+      const float ps = f[0] == 1.0f ? rc_pvalue(h.score, f[1], f[2]) : 99.0f;
+      int ge = 0;
+      for (int d = 0; d < N; d++) ge += mx[d] >= h.score ? 1 : 0;
+      const char strand[2] = {static_cast<char>(h.strand), 0};
+      char num[200];
+      std::snprintf(num, sizeof num, "\t%s\t%i\t%i\t%i\t%7.3f\t", strand, h.frame + 1, h.startGenomic, h.endGenomic, static_cast<double>(h.score));
+      l.shuffleNull = std::string(blk.rows[0].name) + num;
+      for (const double p : {static_cast<double>(h.pvalue), static_cast<double>(ps)}) {
+        std::snprintf(num, sizeof num, p < 0.001 ? "% 9.3e\t" : "% 9.3f\t", p);
+        l.shuffleNull += num;
+      }
+      std::snprintf(num, sizeof num, "%i\t%i\t%i\n", ge, N, mov);
+      l.shuffleNull += num;
+    }
+  }
+  return true;
+}
+
 // From a finished batch to the writer, step 1: the HSS, status and reason of each of its blocks (blockIdx: their input blocks).
 std::unique_ptr<Job> fetch(rc_batch *b, int seq, const int *blockIdx, std::string &err) {
   std::unique_ptr<Job> j(new Job());
@@ -806,6 +871,7 @@ bool deliver(Run &R, rc_batch *b, std::unique_ptr<Job> j, std::string &err, cons
   if (R.list.on(kTrack) && !add_track(R, b, *j, err, fits)) return false;
   if ((R.list.on(kSupport) || R.list.on(kRegions)) && !add_segments(R, b, *j, err, fits, slices)) return false;
   if (R.list.on(kDecoys) && !add_decoys(R, b, *j, err, fits)) return false;
+  if (R.list.on(kShuffleNull) && !add_shuffle_null(R, b, *j, err)) return false;
   post(R, std::move(j));
   return true;
 }
@@ -1025,7 +1091,7 @@ int main(int argc, char **argv) {
   Listing &list = R.list;
   std::string file, outfile, trees, limit, devicesArg, speciesFile, writeTrees, regionsFile;
   int device = 0, subBlocks = 0, gpus = 1;   // subBlocks 0: the library's schedule
-  bool dumpBlocks = false, decoysGiven = false, decoyKindGiven = false;
+  bool dumpBlocks = false, decoysGiven = false, decoyKindGiven = false, shuffleNullGiven = false;
   std::string decoyKind;
   for (int a = 1; a < argc; a++) {
     const std::string o = argv[a];
@@ -1081,6 +1147,8 @@ int main(int argc, char **argv) {
     else if (o == "--decoys") { decoysGiven = true; R.decoys = std::atoi(val()); }
     else if (o == "--decoys-out") list.side[kDecoys].path = val();
     else if (o == "--decoy-kind") { decoyKindGiven = true; decoyKind = val(); }
+    else if (o == "--shuffle-null") { shuffleNullGiven = true; R.shuffleNull = std::atoi(val()); }
+    else if (o == "--shuffle-null-out") list.side[kShuffleNull].path = val();
     else if (!o.empty() && o[0] == '-' && o != "-") { usage(); return 2; }
     else file = o;
   }
@@ -1097,6 +1165,8 @@ int main(int argc, char **argv) {
   if (decoyKindGiven && !decoysGiven) die("--decoy-kind needs --decoys");
   if (decoyKindGiven && decoyKind != "simulated" && decoyKind != "shuffled") die("--decoy-kind is simulated or shuffled");
   R.decoysShuffled = decoyKind == "shuffled";
+  if (shuffleNullGiven != list.on(kShuffleNull)) die("--shuffle-null and --shuffle-null-out go together");
+  if (shuffleNullGiven && (R.shuffleNull < 1 || R.shuffleNull > 65536)) die("--shuffle-null takes a number of shuffles from 1 to 65536");
   if (!regionsFile.empty()) {
     std::ifstream in(regionsFile, std::ios::binary);
     if (!in) die("--regions: could not open " + regionsFile);

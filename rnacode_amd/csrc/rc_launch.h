@@ -329,6 +329,40 @@ constexpr int kShuffleLdsCols = 4096, kShuffleLdsColsMax = 8192;   // the defaul
 // k_shuffle_perm then k_shuffle_sigma, nBlocks x nDecoys workgroups each; ldsBytes: 8 x the power of two that holds the round's widest block
 // of up to ldsCols columns (0: none), sortThreads: 64 .. 256 by the round's widest block
 void launch_shuffle_sigma(const ShuffleArgs &a, int nBlocks, size_t ldsBytes, int sortThreads, hipStream_t stream);
+void launch_shuffle_perm(const ShuffleArgs &a, int nBlocks, size_t ldsBytes, int sortThreads, hipStream_t stream);   // k_shuffle_perm alone
+// rc_batch_shuffle_null (rc_shuffle_null.hip): the sigma codes of column shuffles where k_generic_sim<false> would have left a null sample's,
+// lane = shuffle, so that k_generic_dp -- unchanged -- leaves each shuffle's maximum.  Item u = (position p of `blocks`) x groups + g holds the
+// shuffles 64 g .. 64 g + 63 of block blocks[p], its codes at codesAll + u * codesStride; the permutation of (p, shuffle d) is the slot
+// shuffle_null_slot(p, d, nBlocks, nShuffles) of permStride bytes at permAll (rc_shuffle_null_plan.h), left there by k_shuffle_perm.
+struct ShuffleNullArgs {
+  const uint8_t *blob;
+  const DevBlock *dblocks;
+  const int *blocks;          // [nBlocks] batch indices of the round
+  const uint8_t *pair;        // [64][64] codon pair -> sigma code
+  const uint8_t *permAll;
+  size_t permStride;
+  uint8_t *codesAll;
+  size_t codesStride;
+  int nBlocks, groups, nShuffles;
+};
+void launch_shuffle_codes(const ShuffleNullArgs &a, int seqParts, hipStream_t stream);   // nBlocks x groups workgroups of one wavefront, times seqParts shares of the sequences
+// The headers k_generic_dp and k_evd_fit index for a call's positions: vblocks[blocks[p]] = the block's own with out_index = p and off_chain
+// aimed at chainAll + chainAt[p], filled here with k_prep_lut's loop (which fills it for the generic class only); vflags[blocks[p]] = the
+// block's kFlagNan bit.  One thread per position.
+struct ShuffleNullHeadArgs {
+  const uint8_t *blob;
+  const DevBlock *dblocks;
+  const uint32_t *flags;
+  const int *blocks;          // [nBlocks] the call's distinct scored blocks
+  const long long *chainAt;   // [nBlocks] in floats
+  float *chainAll;
+  DevBlock *vblocks;          // indexed by batch index
+  uint32_t *vflags;
+  int nBlocks;
+};
+void launch_shuffle_null_heads(const ShuffleNullHeadArgs &a, hipStream_t stream);
+// ge[out_index] = how many of a.sampleN maxima of the position are >= the block's best native score (a: as for launch_evd_fit)
+void launch_shuffle_null_ge(const FitArgs &a, int nblocks, int *ge, hipStream_t stream);
 // wider blocks (N > 64): generic kernels with their states in a global scratch (rc_null_generic.h)
 size_t null_generic_lds_bytes(int N, int nnodes);   // packed node states + codon windows of the widest block of the launch
 // the same in two launches (simulation with many light wavefronts, then the DP): bytes of an item's codes / of a DP workgroup's states

@@ -3,6 +3,7 @@
 #include "rc_decoy_plan.h"
 #include "rc_segnull_plan.h"
 #include "rc_shuffle_plan.h"
+#include "rc_shuffle_null_plan.h"
 
 extern "C" {
 
@@ -975,6 +976,205 @@ int rc_batch_decoys_shuffled(const rc_batch *bc, const int32_t *blks, int32_t n_
   RC_TRY(decoys_args(bc, n_blks, n_decoys, out, cap, offsets));
   ShuffleFill fill(const_cast<rc_batch *>(bc), seed, n_decoys);
   return decoys_body(const_cast<rc_batch *>(bc), blks, n_blks, n_decoys, out, cap, offsets, nullptr, fill);
+}
+
+// The shuffle null (rc_shuffle_null.hip): the maximum of n_shuffles gap-class column shuffles of every listed block, and their Gumbel fit.
+// The distinct scored blocks go in rounds under a budget (rc_shuffle_null_plan.h); per round k_shuffle_perm leaves every (block, shuffle)'s
+// permutation -- the classes from the host, as for the shuffled decoys --, k_shuffle_codes the sigma codes of every (block, group of 64
+// shuffles) item where k_generic_sim<false> would have left a null sample's, and k_generic_dp, sized as the run's scheduler sizes it, each
+// shuffle's maximum.  The run's fit follows on the call's maxima; everything comes back with one copy behind one synchronisation.  Nothing of
+// the batch is written: the DP and the fit index header copies whose chain table is the call's own.
+int rc_batch_shuffle_null(const rc_batch *bc, const int32_t *blks, int32_t n_blks, uint32_t seed, int32_t n_shuffles, float *fit_out,
+                          float *maxima_out) {
+  rc_batch *b = const_cast<rc_batch *>(bc);
+  if (!b || n_blks < 0 || (n_blks > 0 && !fit_out)) return fail(RC_ERR_ARG, "bad argument");
+  if (n_shuffles < 1 || n_shuffles > kShuffleNullMax) return fail(RC_ERR_ARG, "the number of shuffles must be 1..65536");
+  if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
+  const int n = n_shuffles, groups = (n + kWave - 1) / kWave;
+  std::vector<int> posOf(static_cast<size_t>(b->n), -1);   // block -> its position among the call's distinct scored blocks
+  std::vector<int32_t> blocks;
+  for (int k = 0; k < n_blks; k++) {
+    const int blk = blks ? blks[k] : k;
+    if (blk < 0 || blk >= b->n) return fail(RC_ERR_ARG, "shuffle-null block " + std::to_string(k) + ": block index out of range");
+    if (b->meta[blk].status != RC_OK || posOf[static_cast<size_t>(blk)] >= 0) continue;
+    posOf[static_cast<size_t>(blk)] = static_cast<int>(blocks.size());
+    blocks.push_back(blk);
+  }
+  const size_t P = blocks.size();
+  // what comes back: FitOut [P] | ge int [P] | maxima float [P][n]
+  const size_t oGe = al256(P * sizeof(FitOut)), oMax = al256(oGe + P * sizeof(int32_t)), maxBytes = P * static_cast<size_t>(n) * sizeof(float);
+  const size_t backBytes = maxima_out ? oMax + maxBytes : oMax;
+  std::unique_ptr<uint8_t[]> res;
+  if (P > 0) {
+    rc_ctx *c = b->ctx;
+    size_t budget = kShuffleNullMaxBytes;
+    if (const char *e = std::getenv("RC_SHUFFLE_NULL_MAX_BYTES")) budget = static_cast<size_t>(std::max(1ll, std::atoll(e)));
+    ShuffleFill fill(b, seed, 1);   // the classes of every block, on the host
+    RC_TRY(fill.plan(blocks));
+    for (int32_t blk : blocks) RC_TRY(check_codes_layout(b, blk));
+    const std::vector<ShuffleNullRound> rounds = shuffle_null_plan(static_cast<int>(P), [&](int p) {
+      const int blk = blocks[static_cast<size_t>(p)];
+      return ShuffleNullCost{null_generic_codes_bytes(b->meta[blk].N, b->meta[blk].L, b->db[blk].nnodes), fill.slot_bytes(b->meta[blk].cols)};
+    }, n, budget, static_cast<size_t>(INT32_MAX / 6));
+    // one upload: the blocks, then (8-aligned) where each position's chain table starts
+    const size_t oChainAt = (P + 1) & ~static_cast<size_t>(1), upWords = oChainAt + 2 * P;
+    std::vector<int32_t> up(upWords, 0);
+    std::memcpy(up.data(), blocks.data(), P * sizeof(int32_t));
+    long long chainFloats = 0;
+    for (size_t p = 0; p < P; p++) {
+      std::memcpy(up.data() + oChainAt + 2 * p, &chainFloats, sizeof(long long));
+      chainFloats += b->meta[blocks[p]].L / 3 + 40;
+    }
+    // a round's launches: the sort as ShuffleFill::round sizes it, the DP as size_two_launches (rc_schedule.cpp) sizes a round of the generic class
+    struct Round { size_t sortLds; int sortThreads, seqParts, comboSplit, grid; size_t dpLds, stateBytes; };
+    std::vector<Round> rinfo;
+    size_t permNeed = 0, codesNeed = 0, stateNeed = 0;
+    HIP_TRY(hipSetDevice(c->device));
+    for (const ShuffleNullRound &rd : rounds) {
+      int ldsMax = 0, colsMax = 0, maxN = 0, maxL = 0, maxNK = 0, maxNodes = 0;
+      for (int p = rd.first; p < rd.first + rd.count; p++) {
+        const int blk = blocks[static_cast<size_t>(p)];
+        const BlockMeta &h = b->meta[blk];
+        colsMax = std::max(colsMax, h.cols);
+        if (h.cols <= fill.ldsCols) ldsMax = std::max(ldsMax, h.cols);
+        maxN = std::max(maxN, h.N); maxL = std::max(maxL, h.L); maxNK = std::max(maxNK, h.NK); maxNodes = std::max(maxNodes, b->db[blk].nnodes);
+      }
+      Round ri{};
+      ri.sortLds = ldsMax ? static_cast<size_t>(shuffle_pow2(static_cast<uint32_t>(ldsMax))) * sizeof(uint64_t) : 0;
+      ri.sortThreads = static_cast<int>(std::min<uint32_t>(256, std::max<uint32_t>(kWave, shuffle_pow2(static_cast<uint32_t>(colsMax)) / 2)));
+      const long long items = static_cast<long long>(rd.count) * groups;
+      // few items: the sequences of an item over several workgroups of k_shuffle_codes
+      ri.seqParts = static_cast<int>(std::max<long long>(1, std::min<long long>({static_cast<long long>(maxNK), 64, static_cast<long long>(c->numCU) * 8 / items})));
+      ri.dpLds = null_generic_lds_bytes(maxN, maxNodes);
+      ri.stateBytes = null_generic_state_bytes(maxN, maxL, maxNodes);
+      const long long slots = static_cast<long long>(c->numCU) * std::max(1, occupancy(c, NullKind::GenericDp, 0, ri.dpLds));
+      ri.comboSplit = (static_cast<double>(items) <= c->splitFactor * static_cast<double>(slots) || items < 8 * slots) ? 1 : 0;
+      ri.grid = static_cast<int>(std::min<long long>(items * (ri.comboSplit ? 6 : 1), slots));
+      rinfo.push_back(ri);
+      permNeed = std::max(permNeed, static_cast<size_t>(rd.count) * n * rd.permStride);
+      codesNeed = std::max(codesNeed, static_cast<size_t>(items) * rd.codesStride);
+      stateNeed = std::max(stateNeed, static_cast<size_t>(ri.grid) * ri.stateBytes);
+    }
+    res.reset(new uint8_t[backBytes]);
+    RC_STREAM_TRY(st, stream_aux(c));
+    HIP_TRY(hipEventSynchronize(b->evPrep));   // the tables of the blob are made on the device
+    DevBuf d_up, d_codes, d_state, d_vdb, d_vflags, d_chain, d_cnt, d_res;
+    adopt_bufs(c, {&d_up, &d_codes, &d_state, &d_vdb, &d_vflags, &d_chain, &d_cnt, &d_res});
+    const uint8_t *blob = b->dblob.as<uint8_t>();
+    bool launched = false;
+    // RC_SHUFFLE_NULL_TIMING=1 (tools/time_shuffle_null.py): events between the phases of every round, their sums on stderr
+    const bool timing = std::getenv("RC_SHUFFLE_NULL_TIMING") != nullptr;
+    std::vector<hipEvent_t> marks;   // per round: in front of the sort, behind it, behind the codes, behind the DP; then around the fit
+    const auto mark = [&]() -> int {
+      if (!timing) return RC_OK;
+      hipEvent_t e = nullptr;
+      HIP_TRY(hipEventCreate(&e));
+      marks.push_back(e);
+      HIP_TRY(hipEventRecord(e, st));
+      return RC_OK;
+    };
+    // (a lambda: whatever fails in it, nothing returns to the caller before the work already queued on the stream has drained -- `up`, `res`
+    // and the buffers die with this frame)
+    const int rc = [&]() -> int {
+      HIP_TRY(d_up.ensure(up.size() * sizeof(int32_t)));
+      RC_TRY(fill.ensure(permNeed));
+      HIP_TRY(d_codes.ensure(codesNeed));
+      HIP_TRY(d_state.ensure(std::max<size_t>(stateNeed, 256)));
+      HIP_TRY(d_vdb.ensure(static_cast<size_t>(b->n) * sizeof(DevBlock)));
+      HIP_TRY(d_vflags.ensure(static_cast<size_t>(b->n) * sizeof(uint32_t)));
+      HIP_TRY(d_chain.ensure(static_cast<size_t>(chainFloats) * sizeof(float)));
+      HIP_TRY(d_cnt.ensure(8 * sizeof(uint32_t)));
+      HIP_TRY(d_res.ensure(oMax + maxBytes));
+      launched = true;   // from here on something may be in flight
+      RC_TRY(fill.begin(st, nullptr));   // the class arrays go up
+      HIP_TRY(hipMemcpyAsync(d_up.p, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+      float *d_max = reinterpret_cast<float *>(d_res.as<uint8_t>() + oMax);
+      // -1 everywhere first: an item split into its strand x frame parts meets in an atomic max
+      HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_max), 0xBF800000u, P * static_cast<size_t>(n), st));
+      ShuffleNullHeadArgs ha{};
+      ha.blob = blob; ha.dblocks = reinterpret_cast<const DevBlock *>(blob + b->oDblocks); ha.flags = b->dflags.as<uint32_t>();
+      ha.blocks = d_up.as<int>(); ha.chainAt = reinterpret_cast<const long long *>(d_up.as<int>() + oChainAt); ha.chainAll = d_chain.as<float>();
+      ha.vblocks = d_vdb.as<DevBlock>(); ha.vflags = d_vflags.as<uint32_t>(); ha.nBlocks = static_cast<int>(P);
+      launch_shuffle_null_heads(ha, st);
+      HIP_TRY(hipGetLastError());
+      ShuffleArgs sa = fill.sa;
+      ShuffleNullArgs ca{};
+      ca.blob = blob; ca.dblocks = ha.dblocks; ca.pair = b->tables->ptrs.pair; ca.permAll = fill.d_perm.as<uint8_t>(); ca.codesAll = d_codes.as<uint8_t>();
+      ca.groups = groups; ca.nShuffles = n;
+      NullArgs dp{};   // this call's own: its work counters, its maxima, every group of every block (skipMask 0)
+      dp.blob = blob; dp.dblocks = d_vdb.as<DevBlock>(); dp.flags = d_vflags.as<uint32_t>();
+      dp.gLo = 0; dp.gHi = groups; dp.sampleN = n; dp.Spad = groups * kWave;
+      dp.pair = ca.pair; dp.tieThr = c->tieThr; dp.maxima = d_max;
+      dp.workCounter = d_cnt.as<unsigned int>(); dp.codesAll = d_codes.as<uint8_t>();
+      for (size_t r = 0; r < rounds.size(); r++) {
+        const ShuffleNullRound &rd = rounds[r];
+        const Round &ri = rinfo[r];
+        sa.blocks = d_up.as<int>() + rd.first; sa.clsAt = fill.d_cls.as<long long>() + rd.first; sa.permStride = rd.permStride;
+        RC_TRY(mark());
+        for (int piece = 0; piece * kShuffleNullPiece < n; piece++) {
+          sa.permAll = fill.d_perm.as<uint8_t>() + shuffle_null_piece_at(rd.count, piece) * rd.permStride;
+          sa.nDecoys = shuffle_null_piece_count(n, piece);
+          sa.seed = seed + static_cast<uint32_t>(piece) * kShuffleNullPiece;
+          launch_shuffle_perm(sa, rd.count, ri.sortLds, ri.sortThreads, st);
+          HIP_TRY(hipGetLastError());
+        }
+        RC_TRY(mark());
+        ca.blocks = sa.blocks; ca.nBlocks = rd.count; ca.permStride = rd.permStride; ca.codesStride = rd.codesStride;
+        launch_shuffle_codes(ca, ri.seqParts, st);
+        HIP_TRY(hipGetLastError());
+        RC_TRY(mark());
+        HIP_TRY(hipMemsetAsync(d_cnt.p, 0, 8 * sizeof(uint32_t), st));   // (behind the round before: one stream)
+        dp.classBlocks = sa.blocks; dp.nClassBlocks = rd.count; dp.codesStride = rd.codesStride;
+        dp.scratchStride = ri.stateBytes; dp.comboSplit = ri.comboSplit;
+        launch_generic(NullKind::GenericDp, dp, ri.grid, ri.dpLds, d_state.as<uint8_t>(), st);
+        HIP_TRY(hipGetLastError());
+        RC_TRY(mark());
+      }
+      RC_TRY(mark());
+      FitArgs fa{};   // the run's fit (rc_batch.cpp), on this call's maxima; --stop-early is the sampling loop's, not this null's
+      fa.dblocks = d_vdb.as<DevBlock>(); fa.blocks = d_up.as<int>(); fa.maxima = d_max; fa.hss = b->dhss.as<DevHss>();
+      fa.hssCount = b->dhssCount.as<int>(); fa.hssCap = b->hssCap; fa.out = d_res.as<FitOut>(); fa.flags = d_vflags.as<uint32_t>();
+      fa.sampleN = n; fa.expMode = c->expMode;
+      launch_evd_fit(fa, static_cast<int>(P), c->inflight.load() == 0, st);
+      HIP_TRY(hipGetLastError());
+      launch_shuffle_null_ge(fa, static_cast<int>(P), reinterpret_cast<int *>(d_res.as<uint8_t>() + oGe), st);
+      HIP_TRY(hipGetLastError());
+      RC_TRY(mark());
+      HIP_TRY(hipMemcpyAsync(res.get(), d_res.p, backBytes, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));   // (the streams are non-blocking: nothing else would wait for the copy)
+      return RC_OK;
+    }();
+    if (rc != RC_OK && launched) (void)hipStreamSynchronize(st);
+    if (rc == RC_OK && marks.size() == 4 * rounds.size() + 2) {
+      float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f}, t = 0.0f;
+      for (size_t r = 0; r < rounds.size(); r++)
+        for (int ph = 0; ph < 3; ph++)
+          if (hipEventElapsedTime(&t, marks[4 * r + ph], marks[4 * r + ph + 1]) == hipSuccess) ms[ph] += t;
+      if (hipEventElapsedTime(&t, marks[4 * rounds.size()], marks[4 * rounds.size() + 1]) == hipSuccess) ms[3] = t;
+      std::fprintf(stderr, "[rc] shuffle_null: blocks=%zu shuffles=%d rounds=%zu k_shuffle_perm=%.3f k_shuffle_codes=%.3f k_generic_dp=%.3f fit=%.3f ms\n", P, n,
+                   rounds.size(), ms[0], ms[1], ms[2], ms[3]);
+    }
+    for (hipEvent_t e : marks) (void)hipEventDestroy(e);
+    if (rc != RC_OK) return rc;
+  }
+  const FitOut *fits = reinterpret_cast<const FitOut *>(res.get());
+  const int32_t *ge = reinterpret_cast<const int32_t *>(res.get() + oGe);
+  const float *mx = reinterpret_cast<const float *>(res.get() + oMax);
+  for (int k = 0; k < n_blks; k++) {
+    const int blk = blks ? blks[k] : k;
+    float *o = fit_out + 4 * static_cast<size_t>(k);
+    float *m = maxima_out ? maxima_out + static_cast<size_t>(k) * n : nullptr;
+    const int p = posOf[static_cast<size_t>(blk)];
+    if (p < 0) {   // not scored: rc_batch_fit_all's record of such a block, maxima of -1
+      o[0] = static_cast<float>(b->meta[blk].status); o[1] = o[2] = o[3] = 0.0f;
+      if (m) std::fill(m, m + n, -1.0f);
+      continue;
+    }
+    const FitOut &f = fits[p];
+    o[0] = static_cast<float>(f.rc); o[1] = static_cast<float>(f.mu); o[2] = static_cast<float>(f.lambda); o[3] = static_cast<float>(ge[p]);
+    if (m) std::memcpy(m, mx + static_cast<size_t>(p) * n, static_cast<size_t>(n) * sizeof(float));
+  }
+  return RC_OK;
 }
 
 int rc_code_tables(int32_t blosum, int32_t pep_out[64], int32_t matrix_out[400]) {

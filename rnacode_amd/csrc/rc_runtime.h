@@ -313,6 +313,9 @@ constexpr size_t kBtMaxBytes = static_cast<size_t>(256) << 20;
 constexpr size_t kSegNullMaxBytes = static_cast<size_t>(256) << 20;
 // rc_batch_decoys: bytes of sigma codes, sigma tables and kept matrices one round of listed blocks may take (RC_DECOY_MAX_BYTES overrides); a block is never cut
 constexpr size_t kDecoyMaxBytes = static_cast<size_t>(256) << 20;
+// rc_batch_shuffle_null: bytes of sigma codes and permutations one round of blocks may take (RC_SHUFFLE_NULL_MAX_BYTES overrides); a block is
+// never cut.  (An item of 6 x 120 is 138 KB of codes: 2 GiB are some 15 000 items, the chip's wavefront slots a few times over.)
+constexpr size_t kShuffleNullMaxBytes = static_cast<size_t>(2) << 30;
 
 
 struct TableSet;

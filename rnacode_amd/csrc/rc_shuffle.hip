@@ -101,4 +101,11 @@ void launch_shuffle_sigma(const ShuffleArgs &a, int nBlocks, size_t ldsBytes, in
   hipLaunchKernelGGL(k_shuffle_sigma, grid, dim3(256), 0, stream, a);
 }
 
+// the permutations alone (rc_batch_shuffle_null: k_shuffle_codes reads the block's characters through them)
+void launch_shuffle_perm(const ShuffleArgs &a, int nBlocks, size_t ldsBytes, int sortThreads, hipStream_t stream) {
+  if (nBlocks <= 0 || a.nDecoys <= 0) return;
+  const dim3 grid(static_cast<unsigned>(nBlocks), static_cast<unsigned>(a.nDecoys));
+  hipLaunchKernelGGL(k_shuffle_perm, grid, dim3(static_cast<unsigned>(sortThreads)), ldsBytes, stream, a);
+}
+
 }  // namespace rc
