@@ -415,6 +415,37 @@ int rc_batch_decoys_shuffled(const rc_batch *b, const int32_t *blks, int32_t n_b
 int rc_batch_shuffle_null(const rc_batch *b, const int32_t *blks, int32_t n_blks, uint32_t seed, int32_t n_shuffles,
                           float *fit_out /* 4 n_blks */, float *maxima_out /* n_blks * n_shuffles, may be NULL */);
 
+/* Given segments under the shuffle null: the test for a segment NAMED IN ADVANCE against a null made from its own block's columns --
+ * rc_batch_segment_null's question asked of rc_batch_shuffle_null's alignments.  Ranges and their validity rules are
+ * rc_batch_segment_scores's, and score_out[r] has that call's bits.  For every range and d = 0 .. n_shuffles - 1
+ * (1 <= n_shuffles <= 65536) the call computes the score of exactly that segment, same codons, frame and strand,
+ *     null[r][d] = max(sum over k of P_k, Delta) / (N - 1)
+ * in the gap-class column shuffle of seed seed + d of the range's block -- rc_batch_decoys_shuffled's definition, key function and seeds:
+ * shuffle d of this call IS shuffled decoy d and shuffle d of rc_batch_shuffle_null --, scored with the block's own models, gap tables and
+ * parameters: the cell S[a][j] rc_batch_shuffle_null's DP passes on its way to maxima[d], bit for bit.  ge_out[r] is the number of
+ * shuffles with null[r][d] >= score_out[r] (binary32 compare: a NaN on either side does not count); if null_out is not NULL the values
+ * themselves come back at null_out[r * n_shuffles + d], and cap < n_ranges * n_shuffles is RC_ERR_ARG.  A range without a step
+ * (opt_i < opt_b + 2) has the value fmaxf(0, Delta) / (N - 1) in every shuffle.  Shuffle d depends on seed + d and the block only: not
+ * on n_shuffles, on which ranges are listed, on the budget or on RC_SHUFFLE_LDS_COLS.  A block where no gap class has two columns has
+ * only the identity shuffle: every value is the range's own score, and ge_out[r] = n_shuffles.
+ * The empirical p is the caller's: (ge + 1) / (n_shuffles + 1).  It is valid for a segment chosen WITHOUT looking at the scores; it is NOT
+ * valid for a listed HSS, which was selected as a maximum (that is what rc_batch_shuffle_null's fit is for).
+ * n_shuffles outside 1..65536 returns RC_ERR_ARG; the other errors are rc_batch_segment_null's: every range is checked before the device
+ * is touched, rc_last_error names the range, a range on a block that was not scored returns that block's status, a batch that has not
+ * completed a run RC_ERR_ARG, and on any error nothing is launched and the outputs are left alone.  n_ranges = 0 is RC_OK; a range may
+ * repeat.  Works on a batch rc_stream_next handed out until it is recycled, and leaves the batch's maxima, fit, HSS, timings and
+ * rc_batch_clamped as they are.
+ * Cost: the class ids of every distinct block that has a range once per call on the host; per (block, shuffle) one sort as for a
+ * shuffled decoy; per (block, group of 64 shuffles) one wavefront that goes from the group's permutations and the block's own rows
+ * straight to the ranges' values, one row of the recurrence per range and sequence -- no sigma code is stored, no DP matrix made, no
+ * MT19937 stream touched.  The distinct blocks go in rounds whose permutations fit a budget of device memory, 256 MB by default
+ * (RC_SEGSHUFFLE_MAX_BYTES overrides, read per call; a single block may exceed it; the result does not depend on it), the sorts and
+ * one scoring launch per round; beside the permutations the call takes 28 bytes per range, and 4 bytes x n_shuffles per range when
+ * null_out is asked for.  One synchronisation, and one copy back per output array. */
+int rc_batch_segment_shuffle_null(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, uint32_t seed, int32_t n_shuffles,
+                                  float *score_out /* n_ranges */, int32_t *ge_out /* n_ranges */,
+                                  float *null_out /* may be NULL: [n_ranges][n_shuffles] */, int64_t cap /* floats in null_out */);
+
 /* The substitution matrix and genetic code the scorer uses, for callers that render results
  * (getScoringMatrix() score.c:50-76 and transcode[4][4][4] code.c:28-39, which src/postscript.c:362,412
  * read): pep_out[16a+4b+c] = amino-acid index 0..19 of codon (a,b,c) in A,C,G,T order or -1 for a stop;

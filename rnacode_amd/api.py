@@ -177,6 +177,7 @@ def lib():
         l.rc_batch_decoys_shuffled.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(RcHss), C.c_int64,
                                                C.POINTER(C.c_int64)]
         l.rc_batch_shuffle_null.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p]
+        l.rc_batch_segment_shuffle_null.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
         l.rc_evd_fit.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         l.rc_mt_stream.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_int32]
         l.rc_pvalue.argtypes = [C.c_float, C.c_float, C.c_float]
@@ -212,7 +213,7 @@ EXPORTED_SYMBOLS = [
     "rc_batch_prep_timing", "rc_host_cpus", "rc_ctx_set_host_threads", "rc_ctx_host_threads", "rc_ctx_fit_exp_mode", "rc_stream_create_v2", "rc_stream_submit", "rc_stream_submit_bound",
     "rc_stream_next", "rc_stream_recycle", "rc_stream_pending", "rc_stream_plan", "rc_stream_destroy", "rc_set_stream_cache", "rc_batch_work", "rc_batch_timing", "rc_batch_null_kernel", "rc_batch_status",
     "rc_batch_models", "rc_batch_maxima", "rc_batch_maxima_all", "rc_batch_fit", "rc_batch_fit_all", "rc_batch_hss", "rc_batch_hss_all", "rc_batch_clamped",
-    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_batch_segment_scores", "rc_batch_segment_null", "rc_batch_decoys", "rc_batch_decoys_shuffled", "rc_batch_shuffle_null", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
+    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_batch_segment_scores", "rc_batch_segment_null", "rc_batch_decoys", "rc_batch_decoys_shuffled", "rc_batch_shuffle_null", "rc_batch_segment_shuffle_null", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
     "rc_code_tables_for", "rc_genetic_code", "rc_species_tree_create", "rc_species_tree_destroy", "rc_species_tree_tips", "rc_species_tree_prune",
     "rc_fit_species_trees", "rc_fit_species_trees_device",
 ]
@@ -781,6 +782,24 @@ class Batch:
         null = np.zeros((n, sample_n), dtype=np.float32) if matrix else None
         _check(lib().rc_batch_segment_null(self._h, arr.ctypes.data, n, scores.ctypes.data, ge.ctypes.data,
                                            null.ctypes.data if matrix else None, n * sample_n if matrix else 0))
+        return scores, ge, null
+
+    def segment_shuffle_null(self, ranges, n_shuffles: int, seed: Optional[int] = None,
+                             matrix: bool = False) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """rc_batch_segment_shuffle_null: (scores, ge, null) of all `ranges` -- tuples as segment_scores takes, scores with that call's
+        bits.  null[r][d] (matrix, else None) is the score of exactly that segment in the gap-class column shuffle of seed seed + d of its
+        block (decoys.shuffle_columns: shuffle d is shuffled decoy d and shuffle d of shuffle_null), float32 [n][n_shuffles]; ge[r] the
+        number of shuffles with null[r][d] >= scores[r], int32.  segments.empirical_p(ge, n_shuffles) is the p of a segment named in
+        advance against its block's own columns -- not of a listed HSS.  The default seed is seed_base + sampleN."""
+        if seed is None:
+            seed = int(self.params.seed_base) + int(self.params.sampleN)
+        arr = np.ascontiguousarray(np.asarray(list(ranges), dtype=np.int32).reshape(-1, 4))
+        n, k = arr.shape[0], int(n_shuffles)
+        scores = np.zeros(n, dtype=np.float32)
+        ge = np.zeros(n, dtype=np.int32)
+        null = np.zeros((n, max(k, 0)), dtype=np.float32) if matrix else None
+        _check(lib().rc_batch_segment_shuffle_null(self._h, arr.ctypes.data, n, C.c_uint32(seed & 0xFFFFFFFF), k, scores.ctypes.data, ge.ctypes.data,
+                                                   null.ctypes.data if matrix else None, n * max(k, 0) if matrix else 0))
         return scores, ge, null
 
     def results(self, blk: int, with_maxima: bool = False) -> BlockScores:

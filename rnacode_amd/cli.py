@@ -4,7 +4,7 @@ Mirrors the reference's command line (src/cmdline.ggo:6-20, src/RNAcode.c:236-37
 options that concern the scoring path and the listings:
 
     python -m rnacode_amd.cli [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S]
-                              [-e [-i CUTOFF] [-d DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null]]
+                              [-e [-i CUTOFF] [-d DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null] [--regions-shuffle-null N]]
                               [--decoys K --decoys-out FILE [--decoy-kind simulated|shuffled]] [--shuffle-null N --shuffle-null-out FILE]
                               [-o OUT] [--trees SIDECAR | --species-tree NEWICK
                               [--species-tree-fit fixed|scale|branches]] [--write-trees SIDECAR] [FILE]
@@ -25,7 +25,10 @@ share of the segment's score and the score without it; --regions FILE with --reg
 strand and the listing's Start / End) in every scored block that contains them, whether or not the listing shows them (segments.py; the
 ranges of a sub-batch go in one rc_batch_segment_scores call); with --regions-null its lines end in null_ge and p_segment, the test for a
 segment named in advance: how many of the -n null alignments score at least as high on exactly that segment (one rc_batch_segment_null call
-per sub-batch), and (null_ge + 1) / (n + 1).
+per sub-batch), and (null_ge + 1) / (n + 1); with --regions-shuffle-null N they end in shuffle_ge, p_segment_shuffled and movable, the same
+test against a null made from the block itself: how many of N gap-class column shuffles of the block (the shuffles of --shuffle-null, seeds
+seed_base + n ..) score at least as high on exactly that segment (one rc_batch_segment_shuffle_null call per sub-batch), (shuffle_ge + 1) /
+(N + 1), and the columns a shuffle can move.
 --decoys K with --decoys-out FILE (not in the reference) writes the complete listing of K null alignments per scored block, selected by
 --cutoff, -b and -r as the block's own HSS are (decoys.py; one rc_batch_decoys call per sub-batch, seeds seed_base + n ..: the first the
 fit did not see): what `python -m rnacode_amd.decoys` turns into a false discovery rate of the listing.  --decoy-kind shuffled lists, in
@@ -147,6 +150,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --regions: two more columns in --regions-out, null_ge = how many of the -n null alignments score at least as "
                          "high on exactly that segment, and p_segment = (null_ge + 1) / (n + 1), the test for a segment named in advance "
                          "(p is the block-wide test)")
+    ap.add_argument("--regions-shuffle-null", type=int, metavar="N",
+                    help="with --regions: three more columns in --regions-out, shuffle_ge = how many of N (1..65536) shuffles of the block -- "
+                         "its own columns, permuted among the columns with the same gap pattern -- score at least as high on exactly that "
+                         "segment, p_segment_shuffled = (shuffle_ge + 1) / (N + 1), and movable = the columns a shuffle can move")
     ap.add_argument("--decoys", type=int, metavar="K",
                     help="with --decoys-out: list the HSS of K (1..64) null alignments per scored block, simulated as the samples behind the "
                          "p-values are and selected by --cutoff, -b and -r as the block's own; python -m rnacode_amd.decoys turns the two "
@@ -189,6 +196,10 @@ def _intake(a):
         raise _Refused("--regions and --regions-out go together")
     if a.regions_null and not a.regions:
         raise _Refused("--regions-null needs --regions")
+    if a.regions_shuffle_null is not None and not a.regions:
+        raise _Refused("--regions-shuffle-null needs --regions")
+    if a.regions_shuffle_null is not None and not 1 <= a.regions_shuffle_null <= 65536:
+        raise _Refused("--regions-shuffle-null takes a number of shuffles from 1 to 65536")
     if (a.decoys is not None) != bool(a.decoys_out):
         raise _Refused("--decoys and --decoys-out go together")
     if a.decoys is not None and not 1 <= a.decoys <= 64:
@@ -315,7 +326,7 @@ def _list_batch(run: _Run, batch, base: int) -> None:
     # --eps / --details: the backtracked paths with ONE call (rc_batch_backtrack_many) -- the segments themselves for the table; for the
     # plots (p below the plot cutoff) the segment and its two extensions.  --support / --regions: the scores and pair scores of every listed
     # HSS, and of every region a block contains, with ONE call (rc_batch_segment_scores)
-    bt, seg, nul, found = _Ranges(), _Ranges(), _Ranges(), {}
+    bt, seg, nul, shf, found = _Ranges(), _Ranges(), _Ranges(), _Ranges(), {}
     for i in scored:
         b = run.blocks[base + i]
         for h in listed[i]:
@@ -331,13 +342,16 @@ def _list_batch(run: _Run, batch, base: int) -> None:
                 at = segments.locate(reg.strand, reg.start, reg.end, b.rows[0].start, b.rows[0].length, b.ref_len)
                 if isinstance(at, tuple):
                     lo, hi = segments.range_of(*at)
-                    found.setdefault(i, []).append((reg, at, seg.add(i, reg.strand, lo, hi), nul.add(i, reg.strand, lo, hi) if a.regions_null else -1))
+                    found.setdefault(i, []).append((reg, at, seg.add(i, reg.strand, lo, hi), nul.add(i, reg.strand, lo, hi) if a.regions_null else -1,
+                                                    shf.add(i, reg.strand, lo, hi) if a.regions_shuffle_null is not None else -1))
     paths = batch.backtrack_many(bt.ranges) if bt.ranges else []
     # --track: the tracks of the blocks the listing covers with ONE call (rc_batch_track)
     tracked = dict(zip(scored, batch.track(scored))) if "track" in side and scored else {}
     seg_scores, seg_pairs = batch.segment_scores(seg.ranges) if seg.ranges else (None, None)
     # --regions-null: the regions' ranges (not the listed HSS, which were selected as maxima) with ONE call (rc_batch_segment_null)
     null_ge = batch.segment_null(nul.ranges)[1] if nul.ranges else None
+    # --regions-shuffle-null: the same ranges in the block's own column shuffles with ONE call (rc_batch_segment_shuffle_null)
+    shuffle_ge = batch.segment_shuffle_null(shf.ranges, a.regions_shuffle_null, run.params.seed_base + run.params.sampleN)[1] if shf.ranges else None
     # --decoys: the decoy listings of the blocks the listing covers with ONE call (rc_batch_decoys)
     decoyed = dict(zip(scored, batch.decoys(a.decoys, run.params.seed_base + run.params.sampleN, scored, kind=a.decoy_kind or "simulated"))) if "decoys_out" in side and scored else {}
     # --shuffle-null: the shuffle maxima and their fit for the blocks the listing covers with ONE call (rc_batch_shuffle_null)
@@ -364,10 +378,12 @@ def _list_batch(run: _Run, batch, base: int) -> None:
             rc, mu, lam = batch.getExtremeValuePars(i)
             if i in tracked:
                 side["track"].writelines(track.block_lines(b.rows[0].name, b.rows[0].start, b.rows[0].length, tracked[i], rc, mu, lam, a.cutoff))
-            for reg, (frame, c1, c2), r, rn in found.get(i, ()):
+            movable = shuffle_null.movable([r.seq for r in b.rows]) if i in found and a.regions_shuffle_null is not None else 0
+            for reg, (frame, c1, c2), r, rn, rs in found.get(i, ()):
                 p = api.pvalue(float(seg_scores[r]), mu, lam) if rc == 1 else 99.0
                 side["regions_out"].write(segments.region_line(reg, frame, c1, c2, seg_scores[r], p, seg_pairs[r],
-                                                               (null_ge[rn], run.params.sampleN) if rn >= 0 else None))
+                                                               (null_ge[rn], run.params.sampleN) if rn >= 0 else None,
+                                                               (shuffle_ge[rs], a.regions_shuffle_null, movable) if rs >= 0 else None))
                 reg.matched = True
 
 
@@ -415,7 +431,7 @@ def main(argv=None) -> int:
         for name, header in SIDE_FILES:
             if getattr(a, name):
                 side[name] = files.enter_context(open(getattr(a, name), "w"))
-                side[name].write(header(null=True) if name == "regions_out" and a.regions_null else header())
+                side[name].write(header(null=a.regions_null, shuffle=a.regions_shuffle_null is not None) if name == "regions_out" else header())
         code = params.genetic_code.decode()
         run = _Run(a, params, code, api.code_tables(a.blosum, code) if a.details else None, blocks, read_index, refused,
                    segments.by_name(regions) if regions is not None else {}, out, fmt, side)

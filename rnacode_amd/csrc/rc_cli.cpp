@@ -36,6 +36,10 @@
 // same bytes as python -m rnacode_amd.cli, whose segments.py documents the rules).  With --gpus N the one writer emits both in input order.
 // --regions-null (with --regions): every --regions-out line ends in null_ge and p_segment = (null_ge + 1) / (n + 1), the test for a segment named
 // in advance -- the regions' ranges of a sub-batch in ONE rc_batch_segment_null call (in the sample split one per slice, the counts added).
+// --regions-shuffle-null N (with --regions): every --regions-out line ends in shuffle_ge, p_segment_shuffled = (shuffle_ge + 1) / (N + 1) and movable,
+// the same test against a null made from the block itself -- the regions' ranges of a sub-batch in N gap-class column shuffles of their blocks,
+// seeds seed_base + n .. (the shuffles of --shuffle-null), in ONE rc_batch_segment_shuffle_null call (in the sample split one slice's batch
+// gets it with all N shuffles: nothing is added over slices).
 //
 // --decoys K with --decoys-out FILE (not in the reference): the complete listing of K null alignments per scored block -- simulated as the samples
 // behind the p-values are, from the seeds seed_base + n on (the first the fit did not see; n the run's whole -n), selected by -p, -b and -r as
@@ -429,7 +433,8 @@ struct Listing {
 
 void usage() {
   std::fprintf(stderr, "usage: rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]\n"
-                       "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null]]\n"
+                       "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null]\n"
+                       "                   [--regions-shuffle-null N]]\n"
                        "                   [--decoys K --decoys-out FILE [--decoy-kind simulated|shuffled]] [--shuffle-null N --shuffle-null-out FILE]\n"
                        "                   [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]\n"
                        "                   [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]\n"
@@ -454,6 +459,10 @@ void usage() {
                        "  --regions-null             with --regions: two more columns, null_ge = how many of the -n null alignments score at least as\n"
                        "                             high on exactly that segment, p_segment = (null_ge + 1) / (n + 1): the test for a segment\n"
                        "                             named in advance (p is the block-wide test)\n"
+                       "  --regions-shuffle-null N   with --regions: three more columns, shuffle_ge = how many of N (1..65536) shuffles of the block -- its\n"
+                       "                             own columns, permuted among the columns with the same gap pattern -- score at least as high\n"
+                       "                             on exactly that segment, p_segment_shuffled = (shuffle_ge + 1) / (N + 1), movable = the columns\n"
+                       "                             a shuffle can move\n"
                        "  --decoys K                 with --decoys-out: list the HSS of K (1..64) null alignments per scored block, simulated as the\n"
                        "                             samples behind the p-values are and selected by -p, -b and -r as the block's own\n"
                        "  --decoys-out FILE          the decoy listing, one line per decoy HSS: block decoy strand frame length from to name start\n"
@@ -505,6 +514,7 @@ struct Run {
   bool regionsNull = false;                               // --regions-null: null_ge and p_segment behind every --regions-out line
   int decoys = 0;                                         // --decoys: null alignments listed per scored block
   bool decoysShuffled = false;                            // --decoy-kind shuffled: the block's own columns, permuted within their gap classes, instead
+  int regionsShuffleNull = 0;                             // --regions-shuffle-null: shuffles scored per region's block (0: off)
   int shuffleNull = 0;                                    // --shuffle-null: shuffles scored per listed block
   // the writer: one thread, jobs in input order
   std::mutex jm;
@@ -678,6 +688,9 @@ bool add_track(const Run &R, rc_batch *b, Job &j, std::string &err, const std::v
 // every region a block contains, with ONE call (rc_batch_segment_scores), then their lines (rc_eps.h, support_tail / region_line).
 // --regions-null: the regions' ranges -- not the listed HSS, which were selected as maxima -- in ONE rc_batch_segment_null call more; where
 // the samples were split over several batches (slices: each holds a slice of the samples of every block), one call per batch, the counts added.
+// --regions-shuffle-null: the same ranges in ONE rc_batch_segment_shuffle_null call on `b` -- every shuffle is made from the block, not from the
+// samples: one batch has them all, whatever slice of the samples it holds.
+int movable_columns(const Block &blk);
 bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std::vector<EvdFit> *fits, const std::vector<rc_batch *> *slices) {
   const int m = static_cast<int>(j.blocks.size());
   struct Listed { int blk; Line *line; int range; };
@@ -743,13 +756,27 @@ bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std
       for (int k = 0; k < nf; k++) nullGe[k] += ge[k];
     }
   }
+  std::vector<int32_t> shuffleGe;   // per found region
+  std::map<int, int> movableOf;     // block of the batch -> the columns a shuffle can move
+  if (R.regionsShuffleNull > 0 && !found.empty()) {
+    std::vector<rc_bt_range> regs;
+    for (const Found &f : found) regs.push_back(ranges[f.range]);
+    const int nf = static_cast<int>(regs.size());
+    std::vector<float> sc(nf);
+    shuffleGe.assign(nf, 0);
+    const uint32_t seed = R.par.seed_base + static_cast<uint32_t>(R.par.sampleN);
+    if (rc_batch_segment_shuffle_null(b, regs.data(), nf, seed, R.regionsShuffleNull, sc.data(), shuffleGe.data(), nullptr, 0) != RC_OK) { err = rc_last_error(); return false; }
+    for (const Found &f : found)
+      if (!movableOf.count(f.blk)) movableOf[f.blk] = movable_columns(R.blocks[j.blocks[f.blk].index]);
+  }
   for (size_t k = 0; k < found.size(); k++) {
     const Found &f = found[k];
     EvdFit fit;
     if (!fit_of(b, fits, f.blk, fit, err)) return false;
     const float p = fit.rc == 1 ? rc_pvalue(scores[f.range], fit.mu, fit.lambda) : 99.0f;
     j.blocks[f.blk].regions += rceps::region_line(R.regions[f.region], f.at, scores[f.range], p, pairs.data() + offs[f.range], static_cast<int>(offs[f.range + 1] - offs[f.range]),
-                                                  R.regionsNull ? nullGe[k] : -1, R.par.sampleN);
+                                                  R.regionsNull ? nullGe[k] : -1, R.par.sampleN, R.regionsShuffleNull > 0 ? shuffleGe[k] : -1, R.regionsShuffleNull,
+                                                  R.regionsShuffleNull > 0 ? movableOf[f.blk] : 0);
     j.matched.push_back(f.region);
   }
   return true;
@@ -1091,7 +1118,7 @@ int main(int argc, char **argv) {
   Listing &list = R.list;
   std::string file, outfile, trees, limit, devicesArg, speciesFile, writeTrees, regionsFile;
   int device = 0, subBlocks = 0, gpus = 1;   // subBlocks 0: the library's schedule
-  bool dumpBlocks = false, decoysGiven = false, decoyKindGiven = false, shuffleNullGiven = false;
+  bool dumpBlocks = false, decoysGiven = false, decoyKindGiven = false, shuffleNullGiven = false, regionsShuffleGiven = false;
   std::string decoyKind;
   for (int a = 1; a < argc; a++) {
     const std::string o = argv[a];
@@ -1144,6 +1171,7 @@ int main(int argc, char **argv) {
     else if (o == "--regions") regionsFile = val();
     else if (o == "--regions-out") list.side[kRegions].path = val();
     else if (o == "--regions-null") R.regionsNull = true;
+    else if (o == "--regions-shuffle-null") { regionsShuffleGiven = true; R.regionsShuffleNull = std::atoi(val()); }
     else if (o == "--decoys") { decoysGiven = true; R.decoys = std::atoi(val()); }
     else if (o == "--decoys-out") list.side[kDecoys].path = val();
     else if (o == "--decoy-kind") { decoyKindGiven = true; decoyKind = val(); }
@@ -1159,7 +1187,10 @@ int main(int argc, char **argv) {
   }
   if (!regionsFile.empty() != list.on(kRegions)) die("--regions and --regions-out go together");   // before any context exists
   if (R.regionsNull && regionsFile.empty()) die("--regions-null needs --regions");
-  if (R.regionsNull) list.side[kRegions].header = rceps::regions_header_null;
+  if (regionsShuffleGiven && regionsFile.empty()) die("--regions-shuffle-null needs --regions");
+  if (regionsShuffleGiven && (R.regionsShuffleNull < 1 || R.regionsShuffleNull > 65536)) die("--regions-shuffle-null takes a number of shuffles from 1 to 65536");
+  if (R.regionsNull) list.side[kRegions].header = regionsShuffleGiven ? rceps::regions_header_null_shuffle : rceps::regions_header_null;
+  else if (regionsShuffleGiven) list.side[kRegions].header = rceps::regions_header_shuffle;
   if (decoysGiven != list.on(kDecoys)) die("--decoys and --decoys-out go together");
   if (decoysGiven && (R.decoys < 1 || R.decoys > 64)) die("--decoys takes a number of decoys from 1 to 64");
   if (decoyKindGiven && !decoysGiven) die("--decoy-kind needs --decoys");

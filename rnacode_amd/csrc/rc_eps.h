@@ -416,6 +416,11 @@ inline std::vector<float> leave_one_out(const float *pairs, int nk, float Delta)
 inline const char *support_header() { return "hss\tname\tstrand\tframe\tstart\tend\tscore\tp\trow\trow_name\tpair_score\tshare\tloo_score\n"; }
 inline const char *regions_header() { return "id\tname\tstrand\tframe\tfrom\tto\tstart\tend\tscore\tp\tsupport\trows\n"; }
 inline const char *regions_header_null() { return "id\tname\tstrand\tframe\tfrom\tto\tstart\tend\tscore\tp\tsupport\trows\tnull_ge\tp_segment\n"; }   // --regions-null
+// --regions-shuffle-null: shuffle_ge, p_segment_shuffled and movable behind them
+inline const char *regions_header_shuffle() { return "id\tname\tstrand\tframe\tfrom\tto\tstart\tend\tscore\tp\tsupport\trows\tshuffle_ge\tp_segment_shuffled\tmovable\n"; }
+inline const char *regions_header_null_shuffle() {
+  return "id\tname\tstrand\tframe\tfrom\tto\tstart\tend\tscore\tp\tsupport\trows\tnull_ge\tp_segment\tshuffle_ge\tp_segment_shuffled\tmovable\n";
+}
 // --support: the columns of row k's line behind the HSS counter (details_tail's head, then the row's pair score, its share and the score without it)
 inline std::string support_tail(const std::string &refName, const std::string &rowName, int k, char strand, int frame, int startGenomic, int endGenomic,
                                 float score, float pvalue, float pair, float nkf, float loo) {
@@ -427,7 +432,10 @@ inline std::string support_tail(const std::string &refName, const std::string &r
   return out;
 }
 // ge >= 0 (--regions-null): two more columns, how many of the n null alignments reach the score on exactly this segment, and (ge + 1) / (n + 1)
-inline std::string region_line(const Region &r, const SegLoc &at, float score, float p, const float *pairs, int nk, int ge = -1, int n = 0) {
+// sge >= 0 (--regions-shuffle-null): three more, how many of the sn column shuffles of the block reach it, (sge + 1) / (sn + 1), and the columns a
+// shuffle can move
+inline std::string region_line(const Region &r, const SegLoc &at, float score, float p, const float *pairs, int nk, int ge = -1, int n = 0, int sge = -1,
+                               int sn = 0, int movable = 0) {
   int support = 0;
   for (int k = 0; k < nk; k++) support += pairs[k] > 0.0f;
   std::string out;
@@ -438,6 +446,10 @@ inline std::string region_line(const Region &r, const SegLoc &at, float score, f
   if (ge >= 0) {
     if (score != score) put(out, "\t%i\tnan", ge);
     else put(out, "\t%i\t%.3e", ge, (ge + 1.0) / (n + 1.0));
+  }
+  if (sge >= 0) {
+    if (score != score) put(out, "\t%i\tnan\t%i", sge, movable);
+    else put(out, "\t%i\t%.3e\t%i", sge, (sge + 1.0) / (sn + 1.0), movable);
   }
   out += "\n";
   return out;

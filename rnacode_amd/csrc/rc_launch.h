@@ -346,6 +346,26 @@ struct ShuffleNullArgs {
   int nBlocks, groups, nShuffles;
 };
 void launch_shuffle_codes(const ShuffleNullArgs &a, int seqParts, hipStream_t stream);   // nBlocks x groups workgroups of one wavefront, times seqParts shares of the sequences
+// rc_batch_segment_shuffle_null (rc_segment_shuffle.hip): the ranges' values in every column shuffle, from the permutations k_shuffle_perm has
+// left at permAll (the slot of (position p of `blocks`, shuffle d): shuffle_null_slot(p, d, nBlocks, nShuffles), permStride bytes each) and
+// the block's own rows and tables; no codes.  Position p's ranges are rangeIdx[blkStart[p] .. blkStart[p + 1]), as for SegNullArgs.
+struct SegShuffleArgs {
+  const uint8_t *blob;
+  const DevBlock *dblocks;
+  const uint32_t *flags;      // per batch index: kFlagNan picks the reference's MAX macro
+  const int *blocks;          // [nBlocks] batch indices of the round
+  const int *blkStart;        // [nBlocks + 1]
+  const int *rangeIdx;
+  const SegRange *ranges;     // every range of the call
+  const float *scores;        // [nRanges] the native scores (k_segment_fold's)
+  const uint8_t *pair;        // [64][64] codon pair -> sigma code
+  int *ge;                    // [nRanges] += shuffles whose value is >= scores[r]
+  float *nullOut;             // [nRanges][nShuffles], or null
+  const uint8_t *permAll;
+  size_t permStride;
+  int nBlocks, groups, nShuffles;
+};
+void launch_segment_shuffle(const SegShuffleArgs &a, hipStream_t stream);   // nBlocks x groups workgroups of one wavefront
 // The headers k_generic_dp and k_evd_fit index for a call's positions: vblocks[blocks[p]] = the block's own with out_index = p and off_chain
 // aimed at chainAll + chainAt[p], filled here with k_prep_lut's loop (which fills it for the generic class only); vflags[blocks[p]] = the
 // block's kFlagNan bit.  One thread per position.

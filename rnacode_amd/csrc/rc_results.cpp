@@ -746,6 +746,18 @@ struct ShuffleFill {
     return al256(static_cast<size_t>(cols) * sizeof(uint16_t)) + (cols > ldsCols ? static_cast<size_t>(shuffle_pow2(static_cast<uint32_t>(cols))) * sizeof(uint64_t) : 0);
   }
   size_t bytes(int p) const { return static_cast<size_t>(K) * slot_bytes(b->meta[(*up)[static_cast<size_t>(p)]].cols); }
+  // k_shuffle_perm's launch for the positions [first, first + count): the dynamic LDS of the widest block it sorts there (up to ldsCols
+  // columns; 0: none), and its threads by the widest block of all
+  void sort_launch(int first, int count, size_t &lds, int &threads) const {
+    int ldsMax = 0, colsMax = 0;
+    for (int p = first; p < first + count; p++) {
+      const int cols = b->meta[(*up)[static_cast<size_t>(p)]].cols;
+      colsMax = std::max(colsMax, cols);
+      if (cols <= ldsCols) ldsMax = std::max(ldsMax, cols);
+    }
+    lds = ldsMax ? static_cast<size_t>(shuffle_pow2(static_cast<uint32_t>(ldsMax))) * sizeof(uint64_t) : 0;
+    threads = static_cast<int>(std::min<uint32_t>(256, std::max<uint32_t>(kWave, shuffle_pow2(static_cast<uint32_t>(colsMax)) / 2)));
+  }
   int ensure(size_t need) {
     HIP_TRY(d_cls.ensure(std::max<size_t>(host.size(), 8)));
     HIP_TRY(d_perm.ensure(need));
@@ -761,17 +773,12 @@ struct ShuffleFill {
     return RC_OK;
   }
   int round(const DecoyRoundCtx &x) {
-    int ldsMax = 0, colsMax = 0;
-    for (int p = x.rd->first; p < x.rd->first + x.rd->count; p++) {
-      const int cols = b->meta[(*up)[static_cast<size_t>(p)]].cols;
-      colsMax = std::max(colsMax, cols);
-      if (cols <= ldsCols) ldsMax = std::max(ldsMax, cols);
-    }
+    size_t lds = 0;
+    int threads = 0;
+    sort_launch(x.rd->first, x.rd->count, lds, threads);
     sa.blocks = x.blocks; sa.clsAt = d_cls.as<long long>() + x.rd->first;
     sa.permStride = x.rd->stride.codes / static_cast<size_t>(K);   // (every position's bytes are K slots)
     sa.sigmaAll = x.sigmaAll; sa.sigmaStride = x.rd->stride.sigma; sa.vblocks = x.vblocks; sa.vflags = x.vflags;
-    const size_t lds = ldsMax ? static_cast<size_t>(shuffle_pow2(static_cast<uint32_t>(ldsMax))) * sizeof(uint64_t) : 0;
-    const int threads = static_cast<int>(std::min<uint32_t>(256, std::max<uint32_t>(kWave, shuffle_pow2(static_cast<uint32_t>(colsMax)) / 2)));
     launch_shuffle_sigma(sa, x.rd->count, lds, threads, x.st);
     HIP_TRY(hipGetLastError());
     return RC_OK;
@@ -1031,17 +1038,14 @@ int rc_batch_shuffle_null(const rc_batch *bc, const int32_t *blks, int32_t n_blk
     size_t permNeed = 0, codesNeed = 0, stateNeed = 0;
     HIP_TRY(hipSetDevice(c->device));
     for (const ShuffleNullRound &rd : rounds) {
-      int ldsMax = 0, colsMax = 0, maxN = 0, maxL = 0, maxNK = 0, maxNodes = 0;
+      int maxN = 0, maxL = 0, maxNK = 0, maxNodes = 0;
       for (int p = rd.first; p < rd.first + rd.count; p++) {
         const int blk = blocks[static_cast<size_t>(p)];
         const BlockMeta &h = b->meta[blk];
-        colsMax = std::max(colsMax, h.cols);
-        if (h.cols <= fill.ldsCols) ldsMax = std::max(ldsMax, h.cols);
         maxN = std::max(maxN, h.N); maxL = std::max(maxL, h.L); maxNK = std::max(maxNK, h.NK); maxNodes = std::max(maxNodes, b->db[blk].nnodes);
       }
       Round ri{};
-      ri.sortLds = ldsMax ? static_cast<size_t>(shuffle_pow2(static_cast<uint32_t>(ldsMax))) * sizeof(uint64_t) : 0;
-      ri.sortThreads = static_cast<int>(std::min<uint32_t>(256, std::max<uint32_t>(kWave, shuffle_pow2(static_cast<uint32_t>(colsMax)) / 2)));
+      fill.sort_launch(rd.first, rd.count, ri.sortLds, ri.sortThreads);
       const long long items = static_cast<long long>(rd.count) * groups;
       // few items: the sequences of an item over several workgroups of k_shuffle_codes
       ri.seqParts = static_cast<int>(std::max<long long>(1, std::min<long long>({static_cast<long long>(maxNK), 64, static_cast<long long>(c->numCU) * 8 / items})));
@@ -1174,6 +1178,129 @@ int rc_batch_shuffle_null(const rc_batch *bc, const int32_t *blks, int32_t n_blk
     o[0] = static_cast<float>(f.rc); o[1] = static_cast<float>(f.mu); o[2] = static_cast<float>(f.lambda); o[3] = static_cast<float>(ge[p]);
     if (m) std::memcpy(m, mx + static_cast<size_t>(p) * n, static_cast<size_t>(n) * sizeof(float));
   }
+  return RC_OK;
+}
+
+// Given segments under the shuffle null (rc_segment_shuffle.hip): the value of every range in n_shuffles gap-class column shuffles of its
+// block, and how many of them reach the range's native score.  The native scores come from rc_batch_segment_scores (its checks are this
+// call's); the ranges are grouped by block as for rc_batch_segment_null (rc_segnull_plan.h), the distinct blocks walked in rounds whose
+// permutations fit a budget: per round k_shuffle_perm leaves every (block, shuffle)'s permutation -- the classes from the host, the sort in
+// pieces, the slots where rc_batch_shuffle_null has them -- and k_segment_shuffle goes from them straight to the ranges' values.  No sigma
+// code, DP state or header copy is made, no MT19937 stream touched, and nothing of the batch written.
+int rc_batch_segment_shuffle_null(const rc_batch *bc, const rc_bt_range *ranges, int32_t n_ranges, uint32_t seed, int32_t n_shuffles,
+                                  float *score_out, int32_t *ge_out, float *null_out, int64_t cap) {
+  rc_batch *b = const_cast<rc_batch *>(bc);
+  if (!b || n_ranges < 0 || (n_ranges > 0 && (!ranges || !score_out || !ge_out))) return fail(RC_ERR_ARG, "bad argument");
+  if (n_shuffles < 1 || n_shuffles > kShuffleNullMax) return fail(RC_ERR_ARG, "the number of shuffles must be 1..65536");
+  if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
+  const int n = n_shuffles, groups = (n + kWave - 1) / kWave;
+  if (null_out && cap < static_cast<int64_t>(n_ranges) * n)
+    return fail(RC_ERR_ARG, "null_out too small: " + std::to_string(static_cast<int64_t>(n_ranges) * n) + " values");
+  // every range is checked there before the device is touched; the scores wait here until the whole call has succeeded
+  std::vector<float> scores(static_cast<size_t>(n_ranges));
+  RC_TRY(rc_batch_segment_scores(b, ranges, n_ranges, scores.data(), nullptr, 0, nullptr));
+  if (n_ranges == 0) return RC_OK;
+  rc_ctx *c = b->ctx;
+  size_t budget = kSegShuffleMaxBytes;
+  if (const char *e = std::getenv("RC_SEGSHUFFLE_MAX_BYTES")) budget = static_cast<size_t>(std::max(1ll, std::atoll(e)));
+  ShuffleFill fill(b, seed, 1);
+  // a (block, group of 64 shuffles) item's permutations: 64 slots
+  const SegNullPlan pl = seg_null_plan(n_ranges, [&](int r) { return ranges[r].blk; },
+                                       [&](int blk) { return static_cast<size_t>(kWave) * fill.slot_bytes(b->meta[blk].cols); }, groups, budget);
+  RC_TRY(fill.plan(pl.blocks));   // the classes of every distinct block, on the host
+  struct Round { size_t sortLds, permStride; int sortThreads; };
+  std::vector<Round> rinfo;
+  size_t permNeed = 0;
+  for (const SegNullRound &rd : pl.rounds) {
+    if (static_cast<size_t>(rd.count) * groups > static_cast<size_t>(INT32_MAX)) return fail(RC_ERR_ARG, "more than 2^31 - 1 (block, shuffle group) items in one round");
+    Round ri{};
+    fill.sort_launch(rd.first, rd.count, ri.sortLds, ri.sortThreads);
+    ri.permStride = rd.stride / kWave;
+    rinfo.push_back(ri);
+    permNeed = std::max(permNeed, static_cast<size_t>(rd.count) * n * ri.permStride);
+  }
+  // one upload: the distinct blocks, the CSR, the ranges, the native scores
+  const size_t nb = pl.blocks.size(), nr = static_cast<size_t>(n_ranges);
+  const size_t oStart = nb, oIdx = oStart + nb + 1, oRanges = oIdx + nr, oScores = oRanges + 4 * nr, upWords = oScores + nr;
+  std::vector<int32_t> up(upWords);
+  std::memcpy(up.data(), pl.blocks.data(), nb * sizeof(int32_t));
+  std::memcpy(up.data() + oStart, pl.blkStart.data(), (nb + 1) * sizeof(int32_t));
+  std::memcpy(up.data() + oIdx, pl.rangeIdx.data(), nr * sizeof(int32_t));
+  std::memcpy(up.data() + oRanges, ranges, nr * sizeof(rc_bt_range));
+  std::memcpy(up.data() + oScores, scores.data(), nr * sizeof(float));
+  std::vector<int32_t> ge(nr);
+  HIP_TRY(hipSetDevice(c->device));
+  RC_STREAM_TRY(st, stream_aux(c));
+  HIP_TRY(hipEventSynchronize(b->evPrep));   // the tables of the blob are made on the device
+  DevBuf d_up, d_ge, d_null;
+  adopt_bufs(c, {&d_up, &d_ge, &d_null});
+  const uint8_t *blob = b->dblob.as<uint8_t>();
+  bool launched = false;
+  // RC_SEGSHUFFLE_TIMING=1 (tools/time_segment_shuffle.py): events between the phases of every round, their sums on stderr
+  const bool timing = std::getenv("RC_SEGSHUFFLE_TIMING") != nullptr;
+  std::vector<hipEvent_t> marks;   // per round: in front of the sort, behind it, behind the segment kernel
+  const auto mark = [&]() -> int {
+    if (!timing) return RC_OK;
+    hipEvent_t e = nullptr;
+    HIP_TRY(hipEventCreate(&e));
+    marks.push_back(e);
+    HIP_TRY(hipEventRecord(e, st));
+    return RC_OK;
+  };
+  // (a lambda: whatever fails in it, nothing returns to the caller -- who owns the outputs, while `up`, `ge` and the buffers die with this
+  // frame -- before the work already queued on the stream has drained)
+  const int rc = [&]() -> int {
+    HIP_TRY(d_up.ensure(up.size() * sizeof(int32_t)));
+    HIP_TRY(d_ge.ensure(nr * sizeof(int32_t)));
+    RC_TRY(fill.ensure(permNeed));
+    if (null_out) HIP_TRY(d_null.ensure(nr * static_cast<size_t>(n) * sizeof(float)));
+    launched = true;   // from here on something may be in flight
+    RC_TRY(fill.begin(st, nullptr));   // the class arrays go up
+    HIP_TRY(hipMemcpyAsync(d_up.p, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_ge.p, 0, nr * sizeof(int32_t), st));
+    ShuffleArgs sa = fill.sa;
+    SegShuffleArgs ss{};
+    ss.blob = blob; ss.dblocks = sa.dblocks; ss.flags = sa.flags; ss.pair = sa.pair;
+    ss.rangeIdx = d_up.as<int>() + oIdx; ss.ranges = reinterpret_cast<const SegRange *>(d_up.as<int>() + oRanges);
+    ss.scores = reinterpret_cast<const float *>(d_up.as<int>() + oScores);
+    ss.ge = d_ge.as<int>(); ss.nullOut = null_out ? d_null.as<float>() : nullptr;
+    ss.permAll = fill.d_perm.as<uint8_t>(); ss.groups = groups; ss.nShuffles = n;
+    for (size_t r = 0; r < pl.rounds.size(); r++) {
+      const SegNullRound &rd = pl.rounds[r];
+      const Round &ri = rinfo[r];
+      sa.blocks = d_up.as<int>() + rd.first; sa.clsAt = fill.d_cls.as<long long>() + rd.first; sa.permStride = ri.permStride;
+      RC_TRY(mark());
+      for (int piece = 0; piece * kShuffleNullPiece < n; piece++) {
+        sa.permAll = fill.d_perm.as<uint8_t>() + shuffle_null_piece_at(rd.count, piece) * ri.permStride;
+        sa.nDecoys = shuffle_null_piece_count(n, piece);
+        sa.seed = seed + static_cast<uint32_t>(piece) * kShuffleNullPiece;
+        launch_shuffle_perm(sa, rd.count, ri.sortLds, ri.sortThreads, st);
+        HIP_TRY(hipGetLastError());
+      }
+      RC_TRY(mark());
+      ss.blocks = sa.blocks; ss.blkStart = d_up.as<int>() + oStart + rd.first; ss.nBlocks = rd.count; ss.permStride = ri.permStride;
+      launch_segment_shuffle(ss, st);
+      HIP_TRY(hipGetLastError());
+      RC_TRY(mark());
+    }
+    HIP_TRY(hipMemcpyAsync(ge.data(), d_ge.p, nr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (null_out) HIP_TRY(hipMemcpyAsync(null_out, d_null.p, nr * static_cast<size_t>(n) * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // (the streams are non-blocking: nothing else would wait for the copies)
+    return RC_OK;
+  }();
+  if (rc != RC_OK && launched) (void)hipStreamSynchronize(st);
+  if (rc == RC_OK && marks.size() == 3 * pl.rounds.size()) {
+    float ms[2] = {0.0f, 0.0f}, t = 0.0f;
+    for (size_t r = 0; r < pl.rounds.size(); r++)
+      for (int ph = 0; ph < 2; ph++)
+        if (hipEventElapsedTime(&t, marks[3 * r + ph], marks[3 * r + ph + 1]) == hipSuccess) ms[ph] += t;
+    std::fprintf(stderr, "[rc] segment_shuffle: ranges=%d blocks=%zu shuffles=%d rounds=%zu k_shuffle_perm=%.3f k_segment_shuffle=%.3f ms\n", n_ranges, nb, n,
+                 pl.rounds.size(), ms[0], ms[1]);
+  }
+  for (hipEvent_t e : marks) (void)hipEventDestroy(e);
+  if (rc != RC_OK) return rc;
+  std::memcpy(score_out, scores.data(), nr * sizeof(float));
+  std::memcpy(ge_out, ge.data(), nr * sizeof(int32_t));
   return RC_OK;
 }
 

@@ -316,6 +316,8 @@ constexpr size_t kDecoyMaxBytes = static_cast<size_t>(256) << 20;
 // rc_batch_shuffle_null: bytes of sigma codes and permutations one round of blocks may take (RC_SHUFFLE_NULL_MAX_BYTES overrides); a block is
 // never cut.  (An item of 6 x 120 is 138 KB of codes: 2 GiB are some 15 000 items, the chip's wavefront slots a few times over.)
 constexpr size_t kShuffleNullMaxBytes = static_cast<size_t>(2) << 30;
+// rc_batch_segment_shuffle_null: bytes of permutations one round of distinct blocks may take (RC_SEGSHUFFLE_MAX_BYTES overrides); a block is never cut
+constexpr size_t kSegShuffleMaxBytes = static_cast<size_t>(256) << 20;
 
 
 struct TableSet;

@@ -13,12 +13,13 @@
 //
 // The permutations of a group are permStride bytes apart: a lane does not gather its own from global memory.  The wavefront reads a chunk of
 // kShuffleNullChunk columns of each of the 64 permutations with one coalesced load (lane = column pair) and transposes it into LDS, u16
-// [column][lane]; a strand's columns ascend ('+') or descend ('-') with the position, so a block longer than a chunk loads each chunk once per
+// [column][lane] (rc_shuffle_chunk.h: the loader k_segment_shuffle shares); a strand's columns ascend ('+') or descend ('-') with the position, so a block longer than a chunk loads each chunk once per
 // strand and sequence.  The codon-pair table lies in LDS beside it.  The per-lane arithmetic is rc_shuffle_null_plan.h's.
 #include <hip/hip_runtime.h>
 
 #include "rc_device.h"
 #include "rc_launch.h"
+#include "rc_shuffle_chunk.h"   // shuffle_load_chunk
 #include "rc_shuffle_null_plan.h"
 
 namespace rc {
@@ -39,16 +40,7 @@ __global__ __launch_bounds__(64) void k_shuffle_codes(ShuffleNullArgs A) {
   const uint8_t *__restrict__ slot0 = A.permAll + shuffle_null_slot(p, d0, A.nBlocks, A.nShuffles) * A.permStride;
   int curBase = -1;   // the first column of the chunk in LDS
   const auto load_chunk = [&](int base) {
-    __syncthreads();
-    const bool in = base + 2 * lane < cols;   // (an odd cols: the pair's second half is the slot's padding, and no column)
-#pragma unroll 8
-    for (int l = 0; l < kWave; l++) {
-      const uint32_t *src = reinterpret_cast<const uint32_t *>(slot0 + static_cast<size_t>(l < live ? l : live - 1) * A.permStride) + (base >> 1);
-      const uint32_t w = in ? src[lane] : 0u;
-      permLds[(2 * lane) * kShuffleNullPitch + l] = static_cast<uint16_t>(w & 0xFFFFu);
-      permLds[(2 * lane + 1) * kShuffleNullPitch + l] = static_cast<uint16_t>(w >> 16);
-    }
-    __syncthreads();
+    shuffle_load_chunk(permLds, slot0, A.permStride, live, cols, base, lane);
     curBase = base;
   };
   const uint32_t codeZero = static_cast<uint32_t>(db->code_zero);

@@ -14,6 +14,12 @@ regions_read / support_tail / region_line) follows the same rules and writes the
   --regions-null   (with --regions) two more columns, null_ge and p_segment: Batch.segment_null (rc_batch_segment_null) scores exactly
                    that segment in each of the run's n null alignments, null_ge of them reach the segment's score, and p_segment =
                    (null_ge + 1) / (n + 1) -- the test for a segment named in advance, where p is the block-wide test.
+  --regions-shuffle-null N   (with --regions) three more columns, shuffle_ge, p_segment_shuffled and movable, behind --regions-null's where
+                   both are given: Batch.segment_shuffle_null (rc_batch_segment_shuffle_null) scores exactly that segment in N gap-class
+                   column shuffles of its block (seeds seed_base + n ..: the shuffles --shuffle-null scores), shuffle_ge of them reach
+                   the segment's score, and p_segment_shuffled = (shuffle_ge + 1) / (N + 1) -- the test for a segment named in advance
+                   against a null made from the block's own columns, where p_segment's null is simulated under the block's model.
+                   movable is shuffle_null.movable of the block: with 0 the only shuffle is the block itself, shuffle_ge = N and p = 1.
   --support FILE   one line per listed HSS and non-reference row, COLUMNS_SUPPORT: the first ten columns are the --details table's, then
                    the row's pair score, its share float32(pair / float32(N - 1)) of the sum behind the score, and the leave-one-out
                    score -- the segment's score without that row.
@@ -27,6 +33,7 @@ import numpy as np
 
 COLUMNS_SUPPORT = ("hss", "name", "strand", "frame", "start", "end", "score", "p", "row", "row_name", "pair_score", "share", "loo_score")
 COLUMNS_NULL = ("null_ge", "p_segment")   # --regions-null: behind COLUMNS_REGIONS
+COLUMNS_SHUFFLE = ("shuffle_ge", "p_segment_shuffled", "movable")   # --regions-shuffle-null: behind COLUMNS_NULL
 COLUMNS_REGIONS = ("id", "name", "strand", "frame", "from", "to", "start", "end", "score", "p", "support", "rows")
 
 BAD_LENGTH = "length not a multiple of three"
@@ -40,8 +47,8 @@ def support_header() -> str:
     return "\t".join(COLUMNS_SUPPORT) + "\n"
 
 
-def regions_header(null: bool = False) -> str:
-    return "\t".join(COLUMNS_REGIONS + (COLUMNS_NULL if null else ())) + "\n"
+def regions_header(null: bool = False, shuffle: bool = False) -> str:
+    return "\t".join(COLUMNS_REGIONS + (COLUMNS_NULL if null else ()) + (COLUMNS_SHUFFLE if shuffle else ())) + "\n"
 
 
 def empirical_p(ge, n):
@@ -159,12 +166,17 @@ def support_lines(counter: int, ref_name: str, h: dict, row_names: Sequence[str]
     return out
 
 
-def region_line(region: Region, frame: int, c1: int, c2: int, score, p, pairs, null: Optional[Tuple[int, int]] = None) -> str:
-    """null: (ge, n) of --regions-null, or None: the line without the two columns."""
+def region_line(region: Region, frame: int, c1: int, c2: int, score, p, pairs, null: Optional[Tuple[int, int]] = None,
+                shuffle: Optional[Tuple[int, int, int]] = None) -> str:
+    """null: (ge, n) of --regions-null, or None: the line without the two columns; shuffle: (ge, n, movable) of --regions-shuffle-null, or
+    None: the line without the three."""
     pr = np.asarray(pairs, dtype=np.float32)
     line = "%s\t%s\t%s\t%i\t%i\t%i\t%i\t%i\t%s\t%.3e\t%i\t%i" % (region.id, region.name, region.strand, frame + 1, c1 + 1, c2 + 1, region.start,
                                                             region.end, fmt3(score), float(np.float32(p)), int((pr > 0).sum()), pr.shape[0])
     if null is not None:
         ge, n = int(null[0]), int(null[1])
         line += "\t%i\tnan" % ge if np.isnan(np.float32(score)) else "\t%i\t%.3e" % (ge, (ge + 1.0) / (n + 1.0))
+    if shuffle is not None:
+        ge, n, movable = int(shuffle[0]), int(shuffle[1]), int(shuffle[2])
+        line += "\t%i\tnan\t%i" % (ge, movable) if np.isnan(np.float32(score)) else "\t%i\t%.3e\t%i" % (ge, (ge + 1.0) / (n + 1.0), movable)
     return line + "\n"
