@@ -348,6 +348,33 @@ int rc_batch_segment_scores(const rc_batch *b, const rc_bt_range *ranges, int32_
 int rc_batch_segment_null(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, float *score_out /* n_ranges */,
                           int32_t *ge_out /* n_ranges */, float *null_out /* may be NULL: [n_ranges][sampleN] */, int64_t cap /* floats in null_out */);
 
+/* The same call with the per-row scores kept: a test per (named segment, species) -- in which rows is the segment conserved as coding?
+ * Ranges, validity rules, errors, rounds, budget (RC_SEGNULL_MAX_BYTES), seeds and samples are rc_batch_segment_null's; score_out and
+ * ge_out have its bits and values.  offsets (n_ranges + 1 entries, required) and pair_out[offsets[r] + k - 1] are
+ * rc_batch_segment_scores's: P_k of row k = 1 .. n_rows - 1 against the reference row in the block itself.  New:
+ *     pair_ge_out[offsets[r] + k - 1] = the number of null alignments s whose P_k over exactly that range is >= the block's own P_k
+ * (binary32 compare: a NaN on either side does not count), and -- if pair_null_out is not NULL -- the values themselves,
+ *     pair_null_out[(offsets[r] + k - 1) * n + s] = P_k of row k over range r in null alignment s,   n = sampleN.
+ * The defining property: take the column s of a range's rows, pair_null_out[(offsets[r] + k - 1) * n + s] for k = 1 .. n_rows - 1, and
+ * fold it the way rc_batch_segment_scores documents -- binary32 additions from 0.0f in row order, fmaxf with Delta, division by
+ * (float)(N - 1) --: the result has the bits of null_out[r * n + s] of rc_batch_segment_null.  Folding a subset of the rows the same way
+ * (division by the subset's size) gives the null distribution of the segment restricted to the reference and those rows: a clade's
+ * test, or with all rows but k the null of the leave-one-out score, without another kernel.
+ * The empirical p of row k is the caller's: (pair_ge + 1) / (n + 1).  It tests this row's codon content against the reference over
+ * exactly this segment under the block's tree and gap pattern; it is valid for a segment AND a row named in advance, not for a listed
+ * HSS.  A row identical to the reference over the segment has P_k = 0 in the block: no evidence either way.  A range without a step has
+ * P_k = 0 in every alignment: its counts are n.
+ * cap < offsets[n_ranges], or (with pair_null_out) null_cap < offsets[n_ranges] * n, returns RC_ERR_ARG; offsets[n_ranges] is the sum of
+ * n_rows - 1 over the ranges, known beforehand.  On any error nothing is launched and every output, offsets included, is left alone.
+ * n_ranges = 0 is RC_OK (offsets[0] = 0).  Leaves the batch as rc_batch_segment_null does.  Cost: that call's, with k_segment_null_pairs in
+ * k_segment_null's place -- per (range, row, group of 64 samples) one compare, one ballot and one atomic add more, and one 256-byte
+ * store where the matrix is asked for --; device memory beside it: 8 bytes per (range, row), and 4 bytes x n per (range, row) with
+ * the matrix. */
+int rc_batch_segment_null_pairs(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, float *score_out /* n_ranges */,
+                                int32_t *ge_out /* n_ranges */, float *pair_out, int32_t *pair_ge_out, int64_t cap /* entries in each */,
+                                int64_t *offsets /* n_ranges + 1 */, float *pair_null_out /* may be NULL: [offsets[n_ranges]][sampleN] */,
+                                int64_t null_cap /* floats in pair_null_out */);
+
 /* Decoy listings: the complete HSS listing of null alignments, for an empirical false discovery rate of a whole screen.  For the k-th
  * listed block (blks[k], or k where blks is NULL; a block may repeat) and decoy d = 0 .. n_decoys - 1 (1 <= n_decoys <= 64) the call
  * simulates the null alignment of MT19937 seed seed + d under the block's own tree, gap pattern and base frequencies -- the run's own
@@ -445,6 +472,23 @@ int rc_batch_shuffle_null(const rc_batch *b, const int32_t *blks, int32_t n_blks
 int rc_batch_segment_shuffle_null(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, uint32_t seed, int32_t n_shuffles,
                                   float *score_out /* n_ranges */, int32_t *ge_out /* n_ranges */,
                                   float *null_out /* may be NULL: [n_ranges][n_shuffles] */, int64_t cap /* floats in null_out */);
+
+/* The same call with the per-row scores kept: rc_batch_segment_null_pairs' outputs under the shuffle null, n = n_shuffles.  Ranges,
+ * validity rules, errors, rounds, budget (RC_SEGSHUFFLE_MAX_BYTES), seeds and shuffles are rc_batch_segment_shuffle_null's; score_out and
+ * ge_out have its bits and values; offsets and pair_out are rc_batch_segment_scores's.  pair_ge_out[offsets[r] + k - 1] is the number of
+ * shuffles d whose P_k over exactly range r is >= the block's own P_k (binary32 compare: a NaN on either side does not count), and
+ * pair_null_out[(offsets[r] + k - 1) * n + d], if not NULL, is that P_k.  The defining property is rc_batch_segment_null_pairs': the column
+ * d of a range's rows, folded as rc_batch_segment_scores documents (binary32 additions from 0.0f in row order, fmaxf with Delta, division
+ * by (float)(N - 1)), has the bits of null_out[r * n + d] of rc_batch_segment_shuffle_null.  The empirical p of row k, (pair_ge + 1) /
+ * (n + 1), tests this row's codon content against the reference over exactly this segment under the block's own columns in another
+ * order; valid for a segment and a row named in advance.  A range without a step has counts of n; so has every range of a block where
+ * no gap class has two columns, whose every shuffle value is the block's own P_k.  cap < offsets[n_ranges], or (with pair_null_out)
+ * null_cap < offsets[n_ranges] * n, returns RC_ERR_ARG; on any error nothing is launched and every output is left alone.  Cost: that
+ * call's, with k_segment_shuffle_pairs in k_segment_shuffle's place. */
+int rc_batch_segment_shuffle_null_pairs(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, uint32_t seed, int32_t n_shuffles,
+                                        float *score_out /* n_ranges */, int32_t *ge_out /* n_ranges */, float *pair_out, int32_t *pair_ge_out,
+                                        int64_t cap /* entries in each */, int64_t *offsets /* n_ranges + 1 */,
+                                        float *pair_null_out /* may be NULL: [offsets[n_ranges]][n_shuffles] */, int64_t null_cap /* floats in pair_null_out */);
 
 /* The substitution matrix and genetic code the scorer uses, for callers that render results
  * (getScoringMatrix() score.c:50-76 and transcode[4][4][4] code.c:28-39, which src/postscript.c:362,412

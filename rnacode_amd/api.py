@@ -178,6 +178,10 @@ def lib():
                                                C.POINTER(C.c_int64)]
         l.rc_batch_shuffle_null.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p]
         l.rc_batch_segment_shuffle_null.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        l.rc_batch_segment_null_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                  C.c_void_p, C.c_int64]
+        l.rc_batch_segment_shuffle_null_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
         l.rc_evd_fit.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         l.rc_mt_stream.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_int32]
         l.rc_pvalue.argtypes = [C.c_float, C.c_float, C.c_float]
@@ -213,7 +217,7 @@ EXPORTED_SYMBOLS = [
     "rc_batch_prep_timing", "rc_host_cpus", "rc_ctx_set_host_threads", "rc_ctx_host_threads", "rc_ctx_fit_exp_mode", "rc_stream_create_v2", "rc_stream_submit", "rc_stream_submit_bound",
     "rc_stream_next", "rc_stream_recycle", "rc_stream_pending", "rc_stream_plan", "rc_stream_destroy", "rc_set_stream_cache", "rc_batch_work", "rc_batch_timing", "rc_batch_null_kernel", "rc_batch_status",
     "rc_batch_models", "rc_batch_maxima", "rc_batch_maxima_all", "rc_batch_fit", "rc_batch_fit_all", "rc_batch_hss", "rc_batch_hss_all", "rc_batch_clamped",
-    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_batch_segment_scores", "rc_batch_segment_null", "rc_batch_decoys", "rc_batch_decoys_shuffled", "rc_batch_shuffle_null", "rc_batch_segment_shuffle_null", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
+    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_batch_segment_scores", "rc_batch_segment_null", "rc_batch_decoys", "rc_batch_decoys_shuffled", "rc_batch_shuffle_null", "rc_batch_segment_shuffle_null", "rc_batch_segment_null_pairs", "rc_batch_segment_shuffle_null_pairs", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
     "rc_code_tables_for", "rc_genetic_code", "rc_species_tree_create", "rc_species_tree_destroy", "rc_species_tree_tips", "rc_species_tree_prune",
     "rc_fit_species_trees", "rc_fit_species_trees_device",
 ]
@@ -801,6 +805,43 @@ class Batch:
         _check(lib().rc_batch_segment_shuffle_null(self._h, arr.ctypes.data, n, C.c_uint32(seed & 0xFFFFFFFF), k, scores.ctypes.data, ge.ctypes.data,
                                                    null.ctypes.data if matrix else None, n * max(k, 0) if matrix else 0))
         return scores, ge, null
+
+    def _segment_pairs_call(self, call, ranges, n_null: int, matrix: bool):
+        """The outputs both *_pairs calls share: call(ranges, n_ranges, scores, ge, pairs, pair_ge, cap, offsets, pair_null, null_cap)."""
+        arr = np.ascontiguousarray(np.asarray(list(ranges), dtype=np.int32).reshape(-1, 4))
+        n, k = arr.shape[0], max(int(n_null), 0)
+        scores = np.zeros(n, dtype=np.float32)
+        ge = np.zeros(n, dtype=np.int32)
+        # the layout is known beforehand: n_rows - 1 pair scores per range (a bad block index is the library's to report)
+        total = sum(self.blocks[b].n - 1 for b in arr[:, 0].tolist() if 0 <= b < self.n)
+        vals = np.zeros(max(total, 1), dtype=np.float32)
+        pair_ge = np.zeros(max(total, 1), dtype=np.int32)
+        offs = np.zeros(n + 1, dtype=np.int64)
+        null = np.zeros((max(total, 1), k), dtype=np.float32) if matrix else None
+        _check(call(arr.ctypes.data, n, scores.ctypes.data, ge.ctypes.data, vals.ctypes.data, pair_ge.ctypes.data, total, offs.ctypes.data,
+                    null.ctypes.data if matrix else None, total * k if matrix else 0))
+        o = offs.tolist()
+        return (scores, ge, [vals[o[r]:o[r + 1]] for r in range(n)], [pair_ge[o[r]:o[r + 1]] for r in range(n)],
+                [null[o[r]:o[r + 1]] for r in range(n)] if matrix else None)
+
+    def segment_null_pairs(self, ranges, matrix: bool = False):
+        """rc_batch_segment_null_pairs: (scores, ge, pairs, pair_ge, pair_null) of all `ranges` -- scores and ge with segment_null's bits and
+        values, pairs with segment_scores'.  pair_ge[r][k - 1] is the number of the batch's null alignments whose pair score P_k of row k
+        over exactly that segment is >= pairs[r][k - 1]: segments.empirical_p(pair_ge[r], sampleN) is the per-species p of a segment and
+        a row named in advance.  pair_null[r] (matrix, else None) holds the values, float32 [n_rows - 1][sampleN]; segments.group_null
+        folds rows of it into the null of the segment restricted to those rows."""
+        sample_n = int(self.params.sampleN)
+        return self._segment_pairs_call(lambda *a: lib().rc_batch_segment_null_pairs(self._h, *a), ranges, sample_n, matrix)
+
+    def segment_shuffle_null_pairs(self, ranges, n_shuffles: int, seed: Optional[int] = None, matrix: bool = False):
+        """rc_batch_segment_shuffle_null_pairs: the same five outputs under the shuffle null -- scores and ge with segment_shuffle_null's
+        bits and values, pair_ge and pair_null over the n_shuffles gap-class column shuffles of seed seed + d of each range's block.  The
+        default seed is seed_base + sampleN."""
+        if seed is None:
+            seed = int(self.params.seed_base) + int(self.params.sampleN)
+        k = int(n_shuffles)
+        return self._segment_pairs_call(lambda *a: lib().rc_batch_segment_shuffle_null_pairs(self._h, a[0], a[1], C.c_uint32(seed & 0xFFFFFFFF), k, *a[2:]),
+                                        ranges, k, matrix)
 
     def results(self, blk: int, with_maxima: bool = False) -> BlockScores:
         st = self.status(blk)

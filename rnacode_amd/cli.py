@@ -28,7 +28,10 @@ segment named in advance: how many of the -n null alignments score at least as h
 per sub-batch), and (null_ge + 1) / (n + 1); with --regions-shuffle-null N they end in shuffle_ge, p_segment_shuffled and movable, the same
 test against a null made from the block itself: how many of N gap-class column shuffles of the block (the shuffles of --shuffle-null, seeds
 seed_base + n ..) score at least as high on exactly that segment (one rc_batch_segment_shuffle_null call per sub-batch), (shuffle_ge + 1) /
-(N + 1), and the columns a shuffle can move.
+(N + 1), and the columns a shuffle can move.  --regions-support FILE (with --regions) writes the --support table for the named segments,
+one line per region, block and non-reference row; with --regions-null / --regions-shuffle-null each line ends in that null's count for the
+row's pair score and p_pair = (count + 1) / (n + 1), the per-species test of a segment named in advance (segments.py; the sub-batch's one
+call per null becomes rc_batch_segment_null_pairs / rc_batch_segment_shuffle_null_pairs).
 --decoys K with --decoys-out FILE (not in the reference) writes the complete listing of K null alignments per scored block, selected by
 --cutoff, -b and -r as the block's own HSS are (decoys.py; one rc_batch_decoys call per sub-batch, seeds seed_base + n ..: the first the
 fit did not see): what `python -m rnacode_amd.decoys` turns into a false discovery rate of the listing.  --decoy-kind shuffled lists, in
@@ -154,6 +157,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --regions: three more columns in --regions-out, shuffle_ge = how many of N (1..65536) shuffles of the block -- "
                          "its own columns, permuted among the columns with the same gap pattern -- score at least as high on exactly that "
                          "segment, p_segment_shuffled = (shuffle_ge + 1) / (N + 1), and movable = the columns a shuffle can move")
+    ap.add_argument("--regions-support", metavar="FILE",
+                    help="with --regions: write a tab-separated table with one line per region, scored block that contains it and aligned "
+                         "sequence: the sequence's pair score against the reference over exactly that segment, its share and the score "
+                         "without it; with --regions-null also pair_null_ge = how many of the -n null alignments have a pair score at "
+                         "least as high for that sequence, and p_pair = (pair_null_ge + 1) / (n + 1); with --regions-shuffle-null N also "
+                         "pair_shuffle_ge and p_pair_shuffled, the same under the N shuffles")
     ap.add_argument("--decoys", type=int, metavar="K",
                     help="with --decoys-out: list the HSS of K (1..64) null alignments per scored block, simulated as the samples behind the "
                          "p-values are and selected by --cutoff, -b and -r as the block's own; python -m rnacode_amd.decoys turns the two "
@@ -200,6 +209,8 @@ def _intake(a):
         raise _Refused("--regions-shuffle-null needs --regions")
     if a.regions_shuffle_null is not None and not 1 <= a.regions_shuffle_null <= 65536:
         raise _Refused("--regions-shuffle-null takes a number of shuffles from 1 to 65536")
+    if a.regions_support and not a.regions:
+        raise _Refused("--regions-support needs --regions")
     if (a.decoys is not None) != bool(a.decoys_out):
         raise _Refused("--decoys and --decoys-out go together")
     if a.decoys is not None and not 1 <= a.decoys <= 64:
@@ -253,7 +264,7 @@ def _trees(a, ctx, blocks, marshalled, species, n_read: int, read_index: List[in
 
 
 SIDE_FILES = (("details", details.header), ("track", track.header), ("support", segments.support_header),
-              ("regions_out", segments.regions_header), ("decoys_out", decoys.header),
+              ("regions_out", segments.regions_header), ("regions_support", segments.region_support_header), ("decoys_out", decoys.header),
               ("shuffle_null_out", shuffle_null.header))   # the option's name in the parsed arguments, its header line
 
 
@@ -349,9 +360,17 @@ def _list_batch(run: _Run, batch, base: int) -> None:
     tracked = dict(zip(scored, batch.track(scored))) if "track" in side and scored else {}
     seg_scores, seg_pairs = batch.segment_scores(seg.ranges) if seg.ranges else (None, None)
     # --regions-null: the regions' ranges (not the listed HSS, which were selected as maxima) with ONE call (rc_batch_segment_null)
-    null_ge = batch.segment_null(nul.ranges)[1] if nul.ranges else None
+    # --regions-support: the same call with every row's count kept (rc_batch_segment_null_pairs) in its place
+    pair_null_ge = pair_shuffle_ge = None
+    if nul.ranges and "regions_support" in side:
+        _, null_ge, _, pair_null_ge, _ = batch.segment_null_pairs(nul.ranges)
+    else:
+        null_ge = batch.segment_null(nul.ranges)[1] if nul.ranges else None
     # --regions-shuffle-null: the same ranges in the block's own column shuffles with ONE call (rc_batch_segment_shuffle_null)
-    shuffle_ge = batch.segment_shuffle_null(shf.ranges, a.regions_shuffle_null, run.params.seed_base + run.params.sampleN)[1] if shf.ranges else None
+    if shf.ranges and "regions_support" in side:
+        _, shuffle_ge, _, pair_shuffle_ge, _ = batch.segment_shuffle_null_pairs(shf.ranges, a.regions_shuffle_null, run.params.seed_base + run.params.sampleN)
+    else:
+        shuffle_ge = batch.segment_shuffle_null(shf.ranges, a.regions_shuffle_null, run.params.seed_base + run.params.sampleN)[1] if shf.ranges else None
     # --decoys: the decoy listings of the blocks the listing covers with ONE call (rc_batch_decoys)
     decoyed = dict(zip(scored, batch.decoys(a.decoys, run.params.seed_base + run.params.sampleN, scored, kind=a.decoy_kind or "simulated"))) if "decoys_out" in side and scored else {}
     # --shuffle-null: the shuffle maxima and their fit for the blocks the listing covers with ONE call (rc_batch_shuffle_null)
@@ -384,6 +403,11 @@ def _list_batch(run: _Run, batch, base: int) -> None:
                 side["regions_out"].write(segments.region_line(reg, frame, c1, c2, seg_scores[r], p, seg_pairs[r],
                                                                (null_ge[rn], run.params.sampleN) if rn >= 0 else None,
                                                                (shuffle_ge[rs], a.regions_shuffle_null, movable) if rs >= 0 else None))
+                if "regions_support" in side:
+                    side["regions_support"].writelines(segments.region_support_lines(
+                        reg, frame, c1, c2, seg_scores[r], [row.name for row in b.rows], seg_pairs[r], run.params.Delta,
+                        (pair_null_ge[rn], run.params.sampleN) if rn >= 0 else None,
+                        (pair_shuffle_ge[rs], a.regions_shuffle_null) if rs >= 0 else None))
                 reg.matched = True
 
 
@@ -431,7 +455,7 @@ def main(argv=None) -> int:
         for name, header in SIDE_FILES:
             if getattr(a, name):
                 side[name] = files.enter_context(open(getattr(a, name), "w"))
-                side[name].write(header(null=a.regions_null, shuffle=a.regions_shuffle_null is not None) if name == "regions_out" else header())
+                side[name].write(header(null=a.regions_null, shuffle=a.regions_shuffle_null is not None) if name in ("regions_out", "regions_support") else header())
         code = params.genetic_code.decode()
         run = _Run(a, params, code, api.code_tables(a.blosum, code) if a.details else None, blocks, read_index, refused,
                    segments.by_name(regions) if regions is not None else {}, out, fmt, side)

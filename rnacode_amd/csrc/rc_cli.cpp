@@ -36,6 +36,9 @@
 // same bytes as python -m rnacode_amd.cli, whose segments.py documents the rules).  With --gpus N the one writer emits both in input order.
 // --regions-null (with --regions): every --regions-out line ends in null_ge and p_segment = (null_ge + 1) / (n + 1), the test for a segment named
 // in advance -- the regions' ranges of a sub-batch in ONE rc_batch_segment_null call (in the sample split one per slice, the counts added).
+// --regions-support FILE (with --regions): the --support table for named segments, one line per region, scored block that contains it and
+// non-reference row (rc_eps.h, region_support_lines); with --regions-null / --regions-shuffle-null each line ends in that null's count for the
+// row and p_pair = (count + 1) / (n + 1), from rc_batch_segment_null_pairs / rc_batch_segment_shuffle_null_pairs in the plain calls' place.
 // --regions-shuffle-null N (with --regions): every --regions-out line ends in shuffle_ge, p_segment_shuffled = (shuffle_ge + 1) / (N + 1) and movable,
 // the same test against a null made from the block itself -- the regions' ranges of a sub-batch in N gap-class column shuffles of their blocks,
 // seeds seed_base + n .. (the shuffles of --shuffle-null), in ONE rc_batch_segment_shuffle_null call (in the sample split one slice's batch
@@ -311,7 +314,7 @@ struct SideFile {
   std::string path;
   FILE *f;
 };
-enum { kDetails, kTrack, kSupport, kRegions, kDecoys, kShuffleNull, kSides };
+enum { kDetails, kTrack, kSupport, kRegions, kDecoys, kShuffleNull, kRegionSupport, kSides };
 const char *decoys_header() { return "block\tdecoy\tstrand\tframe\tlength\tfrom\tto\tname\tstart\tend\tscore\tp\n"; }
 const char *shuffle_null_header() { return "hss\tname\tstrand\tframe\tstart\tend\tscore\tp\tp_shuffled\tge\tn\tmovable\n"; }
 
@@ -333,7 +336,8 @@ struct Listing {
   float epsCutoff = 0.05f;
   std::string epsDir = "eps";
   SideFile side[kSides] = {{rceps::details_header, "", nullptr}, {rceps::track_header, "", nullptr}, {rceps::support_header, "", nullptr},
-                           {rceps::regions_header, "", nullptr}, {decoys_header, "", nullptr}, {shuffle_null_header, "", nullptr}};
+                           {rceps::regions_header, "", nullptr}, {decoys_header, "", nullptr}, {shuffle_null_header, "", nullptr},
+                           {rceps::region_support_header, "", nullptr}};
   bool on(int s) const { return !side[s].path.empty(); }
   int hitCounter = 0;
 
@@ -434,7 +438,7 @@ struct Listing {
 void usage() {
   std::fprintf(stderr, "usage: rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]\n"
                        "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null]\n"
-                       "                   [--regions-shuffle-null N]]\n"
+                       "                   [--regions-shuffle-null N] [--regions-support FILE]]\n"
                        "                   [--decoys K --decoys-out FILE [--decoy-kind simulated|shuffled]] [--shuffle-null N --shuffle-null-out FILE]\n"
                        "                   [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]\n"
                        "                   [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]\n"
@@ -463,6 +467,11 @@ void usage() {
                        "                             own columns, permuted among the columns with the same gap pattern -- score at least as high\n"
                        "                             on exactly that segment, p_segment_shuffled = (shuffle_ge + 1) / (N + 1), movable = the columns\n"
                        "                             a shuffle can move\n"
+                       "  --regions-support FILE     with --regions: one line per region, scored block that contains it and aligned sequence: the\n"
+                       "                             sequence's pair score against the reference over exactly that segment, its share, the score\n"
+                       "                             without it; with --regions-null also pair_null_ge = how many of the -n null alignments have a\n"
+                       "                             pair score at least as high for that sequence, p_pair = (pair_null_ge + 1) / (n + 1); with\n"
+                       "                             --regions-shuffle-null N also pair_shuffle_ge and p_pair_shuffled, the same under the N shuffles\n"
                        "  --decoys K                 with --decoys-out: list the HSS of K (1..64) null alignments per scored block, simulated as the\n"
                        "                             samples behind the p-values are and selected by -p, -b and -r as the block's own\n"
                        "  --decoys-out FILE          the decoy listing, one line per decoy HSS: block decoy strand frame length from to name start\n"
@@ -485,6 +494,7 @@ struct BlockOut {
   bool none = true;            // Listing::arrange: nothing significant
   std::vector<Line> lines;     // the HSS that get a line, what goes out beside each attached
   std::string track, regions, decoys;  // its --track / --regions-out / --decoys-out lines
+  std::string regionSupport;           // its --regions-support lines
 };
 
 // results of one sub-batch on their way to the writer
@@ -563,6 +573,7 @@ void writer_thread(Run &R) {
       R.list.block(o.lines, o.none, std::string(blk.rows[0].name));
       if (!o.track.empty()) std::fwrite(o.track.data(), 1, o.track.size(), R.list.side[kTrack].f);
       if (!o.regions.empty()) std::fwrite(o.regions.data(), 1, o.regions.size(), R.list.side[kRegions].f);
+      if (!o.regionSupport.empty()) std::fwrite(o.regionSupport.data(), 1, o.regionSupport.size(), R.list.side[kRegionSupport].f);
       if (!o.decoys.empty()) std::fwrite(o.decoys.data(), 1, o.decoys.size(), R.list.side[kDecoys].f);
     }
     for (int r : j->matched) R.regionMatched[r] = 1;
@@ -741,6 +752,15 @@ bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std
       l.line->support.push_back(rceps::support_tail(std::string(blk.rows[0].name), std::string(blk.rows[k].name), k, static_cast<char>(h.strand), h.frame, h.startGenomic,
                                                     h.endGenomic, h.score, h.pvalue, p[k - 1], static_cast<float>(nk), loo[k - 1]));
   }
+  // --regions-support: the *_pairs calls in the plain ones' place, which keep every row's count beside the segment's: the block's
+  // simulation and permutations are not made twice.  Their rows are the found regions', in that order: pairOffs[k] of found[k].
+  const bool rowCounts = R.list.on(kRegionSupport);
+  std::vector<int64_t> pairOffs(found.size() + 1, 0);
+  for (size_t k = 0; k < found.size(); k++) pairOffs[k + 1] = pairOffs[k] + rowsOf[found[k].range];
+  const int64_t pairTotal = pairOffs[found.size()];
+  std::vector<int32_t> pairNullGe, pairShuffleGe;   // per (found region, row)
+  std::vector<float> pr(rowCounts ? static_cast<size_t>(pairTotal) : 0);
+  std::vector<int32_t> pg(pr.size());
   std::vector<int32_t> nullGe;   // per found region
   if (R.regionsNull && !found.empty()) {
     std::vector<rc_bt_range> regs;
@@ -749,11 +769,15 @@ bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std
     std::vector<float> sc(nf);
     std::vector<int32_t> ge(nf);
     nullGe.assign(nf, 0);
+    if (rowCounts) pairNullGe.assign(static_cast<size_t>(pairTotal), 0);
     const std::vector<rc_batch *> one{b};
     for (rc_batch *sb : slices ? *slices : one) {
       if (!sb) continue;
-      if (rc_batch_segment_null(sb, regs.data(), nf, sc.data(), ge.data(), nullptr, 0) != RC_OK) { err = rc_last_error(); return false; }
+      const int rc = rowCounts ? rc_batch_segment_null_pairs(sb, regs.data(), nf, sc.data(), ge.data(), pr.data(), pg.data(), pairTotal, pairOffs.data(), nullptr, 0)
+                               : rc_batch_segment_null(sb, regs.data(), nf, sc.data(), ge.data(), nullptr, 0);
+      if (rc != RC_OK) { err = rc_last_error(); return false; }
       for (int k = 0; k < nf; k++) nullGe[k] += ge[k];
+      for (size_t t = 0; t < pairNullGe.size(); t++) pairNullGe[t] += pg[t];
     }
   }
   std::vector<int32_t> shuffleGe;   // per found region
@@ -765,7 +789,11 @@ bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std
     std::vector<float> sc(nf);
     shuffleGe.assign(nf, 0);
     const uint32_t seed = R.par.seed_base + static_cast<uint32_t>(R.par.sampleN);
-    if (rc_batch_segment_shuffle_null(b, regs.data(), nf, seed, R.regionsShuffleNull, sc.data(), shuffleGe.data(), nullptr, 0) != RC_OK) { err = rc_last_error(); return false; }
+    if (rowCounts) pairShuffleGe.assign(static_cast<size_t>(pairTotal), 0);
+    const int rc = rowCounts ? rc_batch_segment_shuffle_null_pairs(b, regs.data(), nf, seed, R.regionsShuffleNull, sc.data(), shuffleGe.data(), pr.data(),
+                                                                   pairShuffleGe.data(), pairTotal, pairOffs.data(), nullptr, 0)
+                             : rc_batch_segment_shuffle_null(b, regs.data(), nf, seed, R.regionsShuffleNull, sc.data(), shuffleGe.data(), nullptr, 0);
+    if (rc != RC_OK) { err = rc_last_error(); return false; }
     for (const Found &f : found)
       if (!movableOf.count(f.blk)) movableOf[f.blk] = movable_columns(R.blocks[j.blocks[f.blk].index]);
   }
@@ -777,6 +805,15 @@ bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std
     j.blocks[f.blk].regions += rceps::region_line(R.regions[f.region], f.at, scores[f.range], p, pairs.data() + offs[f.range], static_cast<int>(offs[f.range + 1] - offs[f.range]),
                                                   R.regionsNull ? nullGe[k] : -1, R.par.sampleN, R.regionsShuffleNull > 0 ? shuffleGe[k] : -1, R.regionsShuffleNull,
                                                   R.regionsShuffleNull > 0 ? movableOf[f.blk] : 0);
+    if (rowCounts) {
+      const Block &blk = R.blocks[j.blocks[f.blk].index];
+      std::vector<std::string> names;
+      for (const Row &row : blk.rows) names.emplace_back(row.name);
+      j.blocks[f.blk].regionSupport += rceps::region_support_lines(R.regions[f.region], f.at, scores[f.range], names, pairs.data() + offs[f.range],
+                                                                  static_cast<int>(offs[f.range + 1] - offs[f.range]), R.par.Delta,
+                                                                  R.regionsNull ? pairNullGe.data() + pairOffs[k] : nullptr, R.par.sampleN,
+                                                                  R.regionsShuffleNull > 0 ? pairShuffleGe.data() + pairOffs[k] : nullptr, R.regionsShuffleNull);
+    }
     j.matched.push_back(f.region);
   }
   return true;
@@ -1170,6 +1207,7 @@ int main(int argc, char **argv) {
     else if (o == "--support") list.side[kSupport].path = val();
     else if (o == "--regions") regionsFile = val();
     else if (o == "--regions-out") list.side[kRegions].path = val();
+    else if (o == "--regions-support") list.side[kRegionSupport].path = val();
     else if (o == "--regions-null") R.regionsNull = true;
     else if (o == "--regions-shuffle-null") { regionsShuffleGiven = true; R.regionsShuffleNull = std::atoi(val()); }
     else if (o == "--decoys") { decoysGiven = true; R.decoys = std::atoi(val()); }
@@ -1188,9 +1226,12 @@ int main(int argc, char **argv) {
   if (!regionsFile.empty() != list.on(kRegions)) die("--regions and --regions-out go together");   // before any context exists
   if (R.regionsNull && regionsFile.empty()) die("--regions-null needs --regions");
   if (regionsShuffleGiven && regionsFile.empty()) die("--regions-shuffle-null needs --regions");
+  if (list.on(kRegionSupport) && regionsFile.empty()) die("--regions-support needs --regions");
   if (regionsShuffleGiven && (R.regionsShuffleNull < 1 || R.regionsShuffleNull > 65536)) die("--regions-shuffle-null takes a number of shuffles from 1 to 65536");
   if (R.regionsNull) list.side[kRegions].header = regionsShuffleGiven ? rceps::regions_header_null_shuffle : rceps::regions_header_null;
   else if (regionsShuffleGiven) list.side[kRegions].header = rceps::regions_header_shuffle;
+  if (R.regionsNull) list.side[kRegionSupport].header = regionsShuffleGiven ? rceps::region_support_header_null_shuffle : rceps::region_support_header_null;
+  else if (regionsShuffleGiven) list.side[kRegionSupport].header = rceps::region_support_header_shuffle;
   if (decoysGiven != list.on(kDecoys)) die("--decoys and --decoys-out go together");
   if (decoysGiven && (R.decoys < 1 || R.decoys > 64)) die("--decoys takes a number of decoys from 1 to 64");
   if (decoyKindGiven && !decoysGiven) die("--decoy-kind needs --decoys");

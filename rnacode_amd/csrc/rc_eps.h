@@ -455,6 +455,39 @@ inline std::string region_line(const Region &r, const SegLoc &at, float score, f
   return out;
 }
 
+// --regions-support: the --support table for named segments, one line per region, scored block that contains it and non-reference row;
+// behind it --regions-null's pair of columns, then --regions-shuffle-null's (segments.py, region_support_lines)
+#define RC_REGION_SUPPORT_COLUMNS "id\tname\tstrand\tframe\tfrom\tto\tstart\tend\tscore\trow\trow_name\tpair_score\tshare\tloo_score"
+inline const char *region_support_header() { return RC_REGION_SUPPORT_COLUMNS "\n"; }
+inline const char *region_support_header_null() { return RC_REGION_SUPPORT_COLUMNS "\tpair_null_ge\tp_pair\n"; }
+inline const char *region_support_header_shuffle() { return RC_REGION_SUPPORT_COLUMNS "\tpair_shuffle_ge\tp_pair_shuffled\n"; }
+inline const char *region_support_header_null_shuffle() { return RC_REGION_SUPPORT_COLUMNS "\tpair_null_ge\tp_pair\tpair_shuffle_ge\tp_pair_shuffled\n"; }
+// rowNames: the block's row names, the reference's first; ge (n null alignments) / sge (sn shuffles): per row how many have a pair score at
+// least the row's own over exactly this segment, or nullptr: the lines without those two columns.  p = (count + 1) / (n + 1), `nan` where
+// the row's pair score is NaN.
+inline std::string region_support_lines(const Region &r, const SegLoc &at, float score, const std::vector<std::string> &rowNames, const float *pairs, int nk,
+                                        float Delta, const int32_t *ge = nullptr, int n = 0, const int32_t *sge = nullptr, int sn = 0) {
+  const std::vector<float> loo = leave_one_out(pairs, nk, Delta);
+  const float nkf = static_cast<float>(nk);
+  std::string head, out;
+  put(head, "%s\t%s\t%c\t%i\t%i\t%i\t%lld\t%lld\t%s", r.id.c_str(), r.name.c_str(), r.strand, at.frame + 1, at.c1 + 1, at.c2 + 1, r.start, r.end, fmt3(score).c_str());
+  for (int k = 1; k <= nk; k++) {
+    const float pair = pairs[k - 1], share = pair / nkf;
+    put(out, "%s\t%i\t%s", head.c_str(), k, rowNames[static_cast<size_t>(k)].c_str());
+    out += "\t" + fmt3(pair) + "\t" + fmt3(share) + "\t" + fmt3(loo[static_cast<size_t>(k) - 1]);
+    const int32_t *counts[2] = {ge, sge};
+    const int of[2] = {n, sn};
+    for (int c = 0; c < 2; c++) {
+      if (!counts[c]) continue;
+      const int g = counts[c][k - 1];
+      if (pair != pair) put(out, "\t%i\tnan", g);
+      else put(out, "\t%i\t%.3e", g, (g + 1.0) / (of[c] + 1.0));
+    }
+    out += "\n";
+  }
+  return out;
+}
+
 // colorAln, postscript.c:38-332: the EPS text for one high-scoring segment of a block (rows upper-cased, as RNAcode.c:121-128 leaves them)
 inline std::string color_aln(const std::vector<Row> &block, const Hss &hss, const Backtrack &backtrack, const Tables &t) {
   std::vector<std::string> rows;

@@ -284,6 +284,15 @@ struct SegNullArgs {
 };
 constexpr int seg_null_code_words(int L) { return ((L / 3 + 31) >> 2) + 1; }   // GenericLayout::nW (rc_null_generic.h): code words per (strand x frame, row)
 void launch_segment_null(const SegNullArgs &a, hipStream_t stream);   // nBlocks x groups workgroups of one wavefront
+// rc_batch_segment_null_pairs / rc_batch_segment_shuffle_null_pairs: what the *_pairs kernels keep of every (range, row) item beside the
+// arguments above.  Item t = prefix[r] + k is row k + 1 of range r, rc_batch_segment_scores' layout (SegArgs); n = the call's null alignments.
+struct SegPairArgs {
+  const int *prefix;          // [nRanges] the sum of N-1 over the ranges before r
+  const float *pairs;         // [nItems] the block's own P_k (k_segment_pairs')
+  int *pairGe;                // [nItems] += null alignments whose P_k is >= pairs[t]
+  float *pairNull;            // [nItems][n], or null
+};
+void launch_segment_null_pairs(const SegNullArgs &a, const SegPairArgs &pa, hipStream_t stream);   // k_segment_null_pairs, the same grid
 // rc_batch_decoys (rc_decoys.hip): the codes k_generic_sim<false> has left at codesAll for a round of blocks (position p of `blocks`: one item
 // of one sample group, lane = decoy, at p * codesStride) expanded into native-format sigma tables f32 [2][NK][L + 1], decoy d of position p at
 // sigmaAll + (p * nDecoys + d) * sigmaStride.  vblocks / vflags [p * nDecoys + d]: the block's header with off_sigma aimed at that table, and
@@ -366,6 +375,7 @@ struct SegShuffleArgs {
   int nBlocks, groups, nShuffles;
 };
 void launch_segment_shuffle(const SegShuffleArgs &a, hipStream_t stream);   // nBlocks x groups workgroups of one wavefront
+void launch_segment_shuffle_pairs(const SegShuffleArgs &a, const SegPairArgs &pa, hipStream_t stream);   // k_segment_shuffle_pairs, the same grid
 // The headers k_generic_dp and k_evd_fit index for a call's positions: vblocks[blocks[p]] = the block's own with out_index = p and off_chain
 // aimed at chainAll + chainAt[p], filled here with k_prep_lut's loop (which fills it for the generic class only); vflags[blocks[p]] = the
 // block's kFlagNan bit.  One thread per position.

@@ -533,18 +533,70 @@ int rc_batch_segment_scores(const rc_batch *b, const rc_bt_range *ranges, int32_
 // run's own simulation, whatever kernels the run took for the block -- writes the codes of every (block, sample group) item, k_segment_null
 // reads them.  Nothing of the batch is written: the simulation gets a scratch word for its clamp count, work counters and a block list of
 // this call's own, and no maxima.
-int rc_batch_segment_null(const rc_batch *bc, const rc_bt_range *ranges, int32_t n_ranges, float *score_out, int32_t *ge_out, float *null_out,
-                          int64_t cap) {
+//
+// The *_pairs entry points (rc_batch_segment_null_pairs, rc_batch_segment_shuffle_null_pairs) are the same calls with every (range, row)'s P_k
+// kept: `po` names their extra outputs, SegPairsHost holds them until the whole call has succeeded.  The block's own P_k come from the same
+// rc_batch_segment_scores call as the scores and go up with the ranges; the kernels are k_segment_null_pairs / k_segment_shuffle_pairs.
+struct SegPairsOut {
+  float *pair;
+  int32_t *pairGe;
+  int64_t cap;
+  int64_t *offsets;
+  float *pairNull;
+  int64_t nullCap;
+};
+struct SegPairsHost {
+  std::vector<float> pairs;
+  std::vector<int64_t> offs;
+  std::vector<int32_t> prefix, ge;
+  int64_t total = 0;
+};
+// the arguments and the two caps, before anything is launched; n: the call's null alignments.  (A block index out of range leaves the total
+// unknown: rc_batch_segment_scores refuses that call and names the range.)
+static int seg_pairs_check(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, int n, const SegPairsOut &po, SegPairsHost &ph) {
+  if (!po.offsets || (n_ranges > 0 && (!po.pair || !po.pairGe))) return fail(RC_ERR_ARG, "bad argument");
+  bool known = true;
+  for (int r = 0; r < n_ranges; r++) {
+    if (ranges[r].blk < 0 || ranges[r].blk >= b->n) { known = false; break; }
+    ph.total += b->meta[ranges[r].blk].NK;
+  }
+  if (known && po.cap < ph.total) return fail(RC_ERR_ARG, "pair_out too small: " + std::to_string(ph.total) + " pair scores");
+  if (known && po.pairNull && po.nullCap / n < ph.total)
+    return fail(RC_ERR_ARG, "pair_null_out too small: " + std::to_string(ph.total) + " x " + std::to_string(n) + " values");
+  ph.pairs.resize(static_cast<size_t>(std::max<int64_t>(ph.total, 1)));
+  ph.offs.resize(static_cast<size_t>(n_ranges) + 1);
+  return RC_OK;
+}
+// the native scores of the ranges -- and the pair scores, where asked for -- with every check rc_batch_segment_scores makes
+static int seg_native_scores(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, float *scores, SegPairsHost *ph) {
+  if (!ph) return rc_batch_segment_scores(b, ranges, n_ranges, scores, nullptr, 0, nullptr);
+  RC_TRY(rc_batch_segment_scores(b, ranges, n_ranges, scores, ph->pairs.data(), ph->total, ph->offs.data()));
+  ph->prefix.assign(ph->offs.begin(), ph->offs.begin() + n_ranges);
+  ph->ge.resize(static_cast<size_t>(ph->total));
+  return RC_OK;
+}
+static void seg_pairs_deliver(const SegPairsOut &po, const SegPairsHost &ph, int32_t n_ranges) {
+  std::memcpy(po.offsets, ph.offs.data(), (static_cast<size_t>(n_ranges) + 1) * sizeof(int64_t));
+  if (ph.total) {
+    std::memcpy(po.pair, ph.pairs.data(), static_cast<size_t>(ph.total) * sizeof(float));
+    std::memcpy(po.pairGe, ph.ge.data(), static_cast<size_t>(ph.total) * sizeof(int32_t));
+  }
+}
+
+static int segment_null_call(const rc_batch *bc, const rc_bt_range *ranges, int32_t n_ranges, float *score_out, int32_t *ge_out, float *null_out,
+                             int64_t cap, const SegPairsOut *po) {
   rc_batch *b = const_cast<rc_batch *>(bc);
   if (!b || n_ranges < 0 || (n_ranges > 0 && (!ranges || !score_out || !ge_out))) return fail(RC_ERR_ARG, "bad argument");
   if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
   const int sampleN = b->par.sampleN, groups = (sampleN + kWave - 1) / kWave, Spad = groups * kWave;
   if (null_out && cap < static_cast<int64_t>(n_ranges) * sampleN)
     return fail(RC_ERR_ARG, "null_out too small: " + std::to_string(static_cast<int64_t>(n_ranges) * sampleN) + " values");
+  SegPairsHost ph;
+  if (po) RC_TRY(seg_pairs_check(b, ranges, n_ranges, sampleN, *po, ph));
   // every range is checked there before the device is touched; the scores wait here until the whole call has succeeded
   std::vector<float> scores(static_cast<size_t>(n_ranges));
-  RC_TRY(rc_batch_segment_scores(b, ranges, n_ranges, scores.data(), nullptr, 0, nullptr));
-  if (n_ranges == 0) return RC_OK;
+  RC_TRY(seg_native_scores(b, ranges, n_ranges, scores.data(), po ? &ph : nullptr));
+  if (n_ranges == 0) { if (po) po->offsets[0] = 0; return RC_OK; }
   rc_ctx *c = b->ctx;
   size_t budget = kSegNullMaxBytes;
   if (const char *e = std::getenv("RC_SEGNULL_MAX_BYTES")) budget = static_cast<size_t>(std::max(1ll, std::atoll(e)));
@@ -559,8 +611,13 @@ int rc_batch_segment_null(const rc_batch *bc, const rc_bt_range *ranges, int32_t
   for (int blk : pl.blocks) RC_TRY(check_codes_layout(b, blk));
   // one upload: the distinct blocks, the CSR, the ranges, the native scores
   const size_t nb = pl.blocks.size(), nr = static_cast<size_t>(n_ranges);
-  const size_t oStart = nb, oIdx = oStart + nb + 1, oRanges = oIdx + nr, oScores = oRanges + 4 * nr, upWords = oScores + nr;
+  const size_t oStart = nb, oIdx = oStart + nb + 1, oRanges = oIdx + nr, oScores = oRanges + 4 * nr;
+  const size_t nItems = static_cast<size_t>(ph.total), oPrefix = oScores + nr, oPairs = oPrefix + nr, upWords = po ? oPairs + nItems : oPrefix;   // (*_pairs: the prefix and the own P_k behind them)
   std::vector<int32_t> up(upWords);
+  if (po) {
+    std::memcpy(up.data() + oPrefix, ph.prefix.data(), nr * sizeof(int32_t));
+    std::memcpy(up.data() + oPairs, ph.pairs.data(), nItems * sizeof(float));
+  }
   std::memcpy(up.data(), pl.blocks.data(), nb * sizeof(int32_t));
   std::memcpy(up.data() + oStart, pl.blkStart.data(), (nb + 1) * sizeof(int32_t));
   std::memcpy(up.data() + oIdx, pl.rangeIdx.data(), nr * sizeof(int32_t));
@@ -570,8 +627,8 @@ int rc_batch_segment_null(const rc_batch *bc, const rc_bt_range *ranges, int32_t
   HIP_TRY(hipSetDevice(c->device));
   RC_STREAM_TRY(st, stream_aux(c));
   HIP_TRY(hipEventSynchronize(b->evPrep));   // the tables of the blob are made on the device
-  DevBuf d_up, d_ge, d_cnt, d_codes, d_null;
-  adopt_bufs(c, {&d_up, &d_ge, &d_cnt, &d_codes, &d_null});
+  DevBuf d_up, d_ge, d_cnt, d_codes, d_null, d_pge, d_pnull;
+  adopt_bufs(c, {&d_up, &d_ge, &d_cnt, &d_codes, &d_null, &d_pge, &d_pnull});
   const uint8_t *blob = b->dblob.as<uint8_t>();
   constexpr size_t kCntWords = 16;   // the simulation's eight work queues, then (8-aligned) its clamp count: this call's own, read by nobody
   bool launched = false;
@@ -583,6 +640,8 @@ int rc_batch_segment_null(const rc_batch *bc, const rc_bt_range *ranges, int32_t
     HIP_TRY(d_cnt.ensure(kCntWords * sizeof(uint32_t)));
     HIP_TRY(d_codes.ensure(codesNeed));
     if (null_out) HIP_TRY(d_null.ensure(nr * static_cast<size_t>(sampleN) * sizeof(float)));
+    if (po) HIP_TRY(d_pge.ensure(nItems * sizeof(int32_t)));
+    if (po && po->pairNull) HIP_TRY(d_pnull.ensure(nItems * static_cast<size_t>(sampleN) * sizeof(float)));
     launched = true;   // from here on something may be in flight
     // the MT19937 streams of the batch's seeds: the context's cache, or regenerated as a run does (the batch's own record of it stays)
     const bool mtLaunched = b->mtLaunched;
@@ -591,6 +650,7 @@ int rc_batch_segment_null(const rc_batch *bc, const rc_bt_range *ranges, int32_t
     RC_TRY(mt);
     HIP_TRY(hipMemcpyAsync(d_up.p, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(d_ge.p, 0, nr * sizeof(int32_t), st));
+    if (po) HIP_TRY(hipMemsetAsync(d_pge.p, 0, nItems * sizeof(int32_t), st));
     NullArgs sim{};
     sim.blob = blob; sim.dblocks = reinterpret_cast<const DevBlock *>(blob + b->oDblocks); sim.flags = b->dflags.as<uint32_t>();
     sim.gLo = 0; sim.gHi = groups; sim.sampleN = sampleN; sim.Spad = Spad;   // every sample, whatever --stop-early cut from the run (skipMask 0)
@@ -603,6 +663,11 @@ int rc_batch_segment_null(const rc_batch *bc, const rc_bt_range *ranges, int32_t
     sn.scores = reinterpret_cast<const float *>(d_up.as<int>() + oScores);
     sn.ge = d_ge.as<int>(); sn.nullOut = null_out ? d_null.as<float>() : nullptr;
     sn.codesAll = d_codes.as<uint8_t>(); sn.groups = groups; sn.sampleN = sampleN;
+    SegPairArgs pa{};
+    if (po) {
+      pa.prefix = d_up.as<int>() + oPrefix; pa.pairs = reinterpret_cast<const float *>(d_up.as<int>() + oPairs);
+      pa.pairGe = d_pge.as<int>(); pa.pairNull = po->pairNull ? d_pnull.as<float>() : nullptr;
+    }
     for (const SegNullRound &rd : pl.rounds) {
       int maxN = 0, maxNodes = 0;
       for (int p = rd.first; p < rd.first + rd.count; p++) {
@@ -611,18 +676,33 @@ int rc_batch_segment_null(const rc_batch *bc, const rc_bt_range *ranges, int32_t
       sim.classBlocks = d_up.as<int>() + rd.first; sim.nClassBlocks = rd.count; sim.codesStride = rd.stride;
       RC_TRY(launch_sim_side(c, sim, static_cast<long long>(rd.count) * groups, maxN, maxNodes, kCntWords, st));
       sn.blocks = sim.classBlocks; sn.blkStart = d_up.as<int>() + oStart + rd.first; sn.nBlocks = rd.count; sn.codesStride = rd.stride;
-      launch_segment_null(sn, st);
+      if (po) launch_segment_null_pairs(sn, pa, st); else launch_segment_null(sn, st);
       HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemcpyAsync(ge.data(), d_ge.p, nr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (null_out) HIP_TRY(hipMemcpyAsync(null_out, d_null.p, nr * static_cast<size_t>(sampleN) * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (po && nItems) HIP_TRY(hipMemcpyAsync(ph.ge.data(), d_pge.p, nItems * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (po && po->pairNull && nItems)
+      HIP_TRY(hipMemcpyAsync(po->pairNull, d_pnull.p, nItems * static_cast<size_t>(sampleN) * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));   // (the streams are non-blocking: nothing else would wait for the copies)
     return RC_OK;
   }();
   if (rc != RC_OK) { if (launched) (void)hipStreamSynchronize(st); return rc; }
   std::memcpy(score_out, scores.data(), nr * sizeof(float));
   std::memcpy(ge_out, ge.data(), nr * sizeof(int32_t));
+  if (po) seg_pairs_deliver(*po, ph, n_ranges);
   return RC_OK;
+}
+
+int rc_batch_segment_null(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, float *score_out, int32_t *ge_out, float *null_out,
+                          int64_t cap) {
+  return segment_null_call(b, ranges, n_ranges, score_out, ge_out, null_out, cap, nullptr);
+}
+
+int rc_batch_segment_null_pairs(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, float *score_out, int32_t *ge_out, float *pair_out,
+                                int32_t *pair_ge_out, int64_t cap, int64_t *offsets, float *pair_null_out, int64_t null_cap) {
+  const SegPairsOut po{pair_out, pair_ge_out, cap, offsets, pair_null_out, null_cap};
+  return segment_null_call(b, ranges, n_ranges, score_out, ge_out, nullptr, 0, &po);
 }
 
 }  // extern "C"
@@ -1187,8 +1267,8 @@ int rc_batch_shuffle_null(const rc_batch *bc, const int32_t *blks, int32_t n_blk
 // permutations fit a budget: per round k_shuffle_perm leaves every (block, shuffle)'s permutation -- the classes from the host, the sort in
 // pieces, the slots where rc_batch_shuffle_null has them -- and k_segment_shuffle goes from them straight to the ranges' values.  No sigma
 // code, DP state or header copy is made, no MT19937 stream touched, and nothing of the batch written.
-int rc_batch_segment_shuffle_null(const rc_batch *bc, const rc_bt_range *ranges, int32_t n_ranges, uint32_t seed, int32_t n_shuffles,
-                                  float *score_out, int32_t *ge_out, float *null_out, int64_t cap) {
+static int segment_shuffle_call(const rc_batch *bc, const rc_bt_range *ranges, int32_t n_ranges, uint32_t seed, int32_t n_shuffles,
+                                float *score_out, int32_t *ge_out, float *null_out, int64_t cap, const SegPairsOut *po) {
   rc_batch *b = const_cast<rc_batch *>(bc);
   if (!b || n_ranges < 0 || (n_ranges > 0 && (!ranges || !score_out || !ge_out))) return fail(RC_ERR_ARG, "bad argument");
   if (n_shuffles < 1 || n_shuffles > kShuffleNullMax) return fail(RC_ERR_ARG, "the number of shuffles must be 1..65536");
@@ -1196,10 +1276,12 @@ int rc_batch_segment_shuffle_null(const rc_batch *bc, const rc_bt_range *ranges,
   const int n = n_shuffles, groups = (n + kWave - 1) / kWave;
   if (null_out && cap < static_cast<int64_t>(n_ranges) * n)
     return fail(RC_ERR_ARG, "null_out too small: " + std::to_string(static_cast<int64_t>(n_ranges) * n) + " values");
+  SegPairsHost ph;
+  if (po) RC_TRY(seg_pairs_check(b, ranges, n_ranges, n, *po, ph));
   // every range is checked there before the device is touched; the scores wait here until the whole call has succeeded
   std::vector<float> scores(static_cast<size_t>(n_ranges));
-  RC_TRY(rc_batch_segment_scores(b, ranges, n_ranges, scores.data(), nullptr, 0, nullptr));
-  if (n_ranges == 0) return RC_OK;
+  RC_TRY(seg_native_scores(b, ranges, n_ranges, scores.data(), po ? &ph : nullptr));
+  if (n_ranges == 0) { if (po) po->offsets[0] = 0; return RC_OK; }
   rc_ctx *c = b->ctx;
   size_t budget = kSegShuffleMaxBytes;
   if (const char *e = std::getenv("RC_SEGSHUFFLE_MAX_BYTES")) budget = static_cast<size_t>(std::max(1ll, std::atoll(e)));
@@ -1221,8 +1303,13 @@ int rc_batch_segment_shuffle_null(const rc_batch *bc, const rc_bt_range *ranges,
   }
   // one upload: the distinct blocks, the CSR, the ranges, the native scores
   const size_t nb = pl.blocks.size(), nr = static_cast<size_t>(n_ranges);
-  const size_t oStart = nb, oIdx = oStart + nb + 1, oRanges = oIdx + nr, oScores = oRanges + 4 * nr, upWords = oScores + nr;
+  const size_t oStart = nb, oIdx = oStart + nb + 1, oRanges = oIdx + nr, oScores = oRanges + 4 * nr;
+  const size_t nItems = static_cast<size_t>(ph.total), oPrefix = oScores + nr, oPairs = oPrefix + nr, upWords = po ? oPairs + nItems : oPrefix;   // (*_pairs: the prefix and the own P_k behind them)
   std::vector<int32_t> up(upWords);
+  if (po) {
+    std::memcpy(up.data() + oPrefix, ph.prefix.data(), nr * sizeof(int32_t));
+    std::memcpy(up.data() + oPairs, ph.pairs.data(), nItems * sizeof(float));
+  }
   std::memcpy(up.data(), pl.blocks.data(), nb * sizeof(int32_t));
   std::memcpy(up.data() + oStart, pl.blkStart.data(), (nb + 1) * sizeof(int32_t));
   std::memcpy(up.data() + oIdx, pl.rangeIdx.data(), nr * sizeof(int32_t));
@@ -1232,8 +1319,8 @@ int rc_batch_segment_shuffle_null(const rc_batch *bc, const rc_bt_range *ranges,
   HIP_TRY(hipSetDevice(c->device));
   RC_STREAM_TRY(st, stream_aux(c));
   HIP_TRY(hipEventSynchronize(b->evPrep));   // the tables of the blob are made on the device
-  DevBuf d_up, d_ge, d_null;
-  adopt_bufs(c, {&d_up, &d_ge, &d_null});
+  DevBuf d_up, d_ge, d_null, d_pge, d_pnull;
+  adopt_bufs(c, {&d_up, &d_ge, &d_null, &d_pge, &d_pnull});
   const uint8_t *blob = b->dblob.as<uint8_t>();
   bool launched = false;
   // RC_SEGSHUFFLE_TIMING=1 (tools/time_segment_shuffle.py): events between the phases of every round, their sums on stderr
@@ -1254,10 +1341,13 @@ int rc_batch_segment_shuffle_null(const rc_batch *bc, const rc_bt_range *ranges,
     HIP_TRY(d_ge.ensure(nr * sizeof(int32_t)));
     RC_TRY(fill.ensure(permNeed));
     if (null_out) HIP_TRY(d_null.ensure(nr * static_cast<size_t>(n) * sizeof(float)));
+    if (po) HIP_TRY(d_pge.ensure(nItems * sizeof(int32_t)));
+    if (po && po->pairNull) HIP_TRY(d_pnull.ensure(nItems * static_cast<size_t>(n) * sizeof(float)));
     launched = true;   // from here on something may be in flight
     RC_TRY(fill.begin(st, nullptr));   // the class arrays go up
     HIP_TRY(hipMemcpyAsync(d_up.p, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(d_ge.p, 0, nr * sizeof(int32_t), st));
+    if (po) HIP_TRY(hipMemsetAsync(d_pge.p, 0, nItems * sizeof(int32_t), st));
     ShuffleArgs sa = fill.sa;
     SegShuffleArgs ss{};
     ss.blob = blob; ss.dblocks = sa.dblocks; ss.flags = sa.flags; ss.pair = sa.pair;
@@ -1265,6 +1355,11 @@ int rc_batch_segment_shuffle_null(const rc_batch *bc, const rc_bt_range *ranges,
     ss.scores = reinterpret_cast<const float *>(d_up.as<int>() + oScores);
     ss.ge = d_ge.as<int>(); ss.nullOut = null_out ? d_null.as<float>() : nullptr;
     ss.permAll = fill.d_perm.as<uint8_t>(); ss.groups = groups; ss.nShuffles = n;
+    SegPairArgs pa{};
+    if (po) {
+      pa.prefix = d_up.as<int>() + oPrefix; pa.pairs = reinterpret_cast<const float *>(d_up.as<int>() + oPairs);
+      pa.pairGe = d_pge.as<int>(); pa.pairNull = po->pairNull ? d_pnull.as<float>() : nullptr;
+    }
     for (size_t r = 0; r < pl.rounds.size(); r++) {
       const SegNullRound &rd = pl.rounds[r];
       const Round &ri = rinfo[r];
@@ -1279,12 +1374,15 @@ int rc_batch_segment_shuffle_null(const rc_batch *bc, const rc_bt_range *ranges,
       }
       RC_TRY(mark());
       ss.blocks = sa.blocks; ss.blkStart = d_up.as<int>() + oStart + rd.first; ss.nBlocks = rd.count; ss.permStride = ri.permStride;
-      launch_segment_shuffle(ss, st);
+      if (po) launch_segment_shuffle_pairs(ss, pa, st); else launch_segment_shuffle(ss, st);
       HIP_TRY(hipGetLastError());
       RC_TRY(mark());
     }
     HIP_TRY(hipMemcpyAsync(ge.data(), d_ge.p, nr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (null_out) HIP_TRY(hipMemcpyAsync(null_out, d_null.p, nr * static_cast<size_t>(n) * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (po && nItems) HIP_TRY(hipMemcpyAsync(ph.ge.data(), d_pge.p, nItems * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (po && po->pairNull && nItems)
+      HIP_TRY(hipMemcpyAsync(po->pairNull, d_pnull.p, nItems * static_cast<size_t>(n) * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));   // (the streams are non-blocking: nothing else would wait for the copies)
     return RC_OK;
   }();
@@ -1301,7 +1399,20 @@ int rc_batch_segment_shuffle_null(const rc_batch *bc, const rc_bt_range *ranges,
   if (rc != RC_OK) return rc;
   std::memcpy(score_out, scores.data(), nr * sizeof(float));
   std::memcpy(ge_out, ge.data(), nr * sizeof(int32_t));
+  if (po) seg_pairs_deliver(*po, ph, n_ranges);
   return RC_OK;
+}
+
+int rc_batch_segment_shuffle_null(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, uint32_t seed, int32_t n_shuffles,
+                                  float *score_out, int32_t *ge_out, float *null_out, int64_t cap) {
+  return segment_shuffle_call(b, ranges, n_ranges, seed, n_shuffles, score_out, ge_out, null_out, cap, nullptr);
+}
+
+int rc_batch_segment_shuffle_null_pairs(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, uint32_t seed, int32_t n_shuffles,
+                                        float *score_out, int32_t *ge_out, float *pair_out, int32_t *pair_ge_out, int64_t cap, int64_t *offsets,
+                                        float *pair_null_out, int64_t null_cap) {
+  const SegPairsOut po{pair_out, pair_ge_out, cap, offsets, pair_null_out, null_cap};
+  return segment_shuffle_call(b, ranges, n_ranges, seed, n_shuffles, score_out, ge_out, nullptr, 0, &po);
 }
 
 int rc_code_tables(int32_t blosum, int32_t pep_out[64], int32_t matrix_out[400]) {

@@ -20,6 +20,13 @@ regions_read / support_tail / region_line) follows the same rules and writes the
                    the segment's score, and p_segment_shuffled = (shuffle_ge + 1) / (N + 1) -- the test for a segment named in advance
                    against a null made from the block's own columns, where p_segment's null is simulated under the block's model.
                    movable is shuffle_null.movable of the block: with 0 the only shuffle is the block itself, shuffle_ge = N and p = 1.
+  --regions-support FILE   (with --regions) one line per region, scored block that contains it and non-reference row,
+                   COLUMNS_REGION_SUPPORT: the --support table for named segments.  With --regions-null two more columns, pair_null_ge
+                   and p_pair: Batch.segment_null_pairs (rc_batch_segment_null_pairs) keeps every row's pair score P_k over exactly that
+                   segment in each null alignment, pair_null_ge of them reach the row's own, p_pair = (pair_null_ge + 1) / (n + 1) -- in
+                   which species is the segment conserved as coding?  With --regions-shuffle-null N two more behind them,
+                   pair_shuffle_ge and p_pair_shuffled, the same under the block's column shuffles.  Valid for a segment and a row named
+                   in advance; an identical pair has P_k = 0 in the block and is no evidence either way.
   --support FILE   one line per listed HSS and non-reference row, COLUMNS_SUPPORT: the first ten columns are the --details table's, then
                    the row's pair score, its share float32(pair / float32(N - 1)) of the sum behind the score, and the leave-one-out
                    score -- the segment's score without that row.
@@ -35,6 +42,10 @@ COLUMNS_SUPPORT = ("hss", "name", "strand", "frame", "start", "end", "score", "p
 COLUMNS_NULL = ("null_ge", "p_segment")   # --regions-null: behind COLUMNS_REGIONS
 COLUMNS_SHUFFLE = ("shuffle_ge", "p_segment_shuffled", "movable")   # --regions-shuffle-null: behind COLUMNS_NULL
 COLUMNS_REGIONS = ("id", "name", "strand", "frame", "from", "to", "start", "end", "score", "p", "support", "rows")
+# --regions-support: the --support table for named segments; behind it --regions-null's pair, then --regions-shuffle-null's
+COLUMNS_REGION_SUPPORT = ("id", "name", "strand", "frame", "from", "to", "start", "end", "score", "row", "row_name", "pair_score", "share", "loo_score")
+COLUMNS_PAIR_NULL = ("pair_null_ge", "p_pair")
+COLUMNS_PAIR_SHUFFLE = ("pair_shuffle_ge", "p_pair_shuffled")
 
 BAD_LENGTH = "length not a multiple of three"
 OUTSIDE = "outside the block"
@@ -146,6 +157,23 @@ def leave_one_out(pairs, Delta) -> np.ndarray:
         return (np.fmax(acc, np.float32(Delta)) / np.float32(nk - 1)).astype(np.float32)
 
 
+def group_null(pair_null, rows, Delta) -> np.ndarray:
+    """The null values of a segment restricted to the reference row plus the rows `rows` -- row numbers k = 1 .. n_rows - 1 as the `row`
+    column prints them, each once -- from pair_null, the [n_rows - 1][n] matrix Batch.segment_null_pairs / segment_shuffle_null_pairs give
+    for the segment (row k's values at pair_null[k - 1]): per null alignment the selected rows' pair scores summed in ascending row order
+    from 0, float32 throughout, then fmax(sum, Delta) / float32(len(rows)).  With all rows that is the segment's `null` bit for bit; with
+    all rows but k it is the null distribution of leave_one_out's value for row k; a clade's rows give the clade's test."""
+    pn = np.ascontiguousarray(pair_null, dtype=np.float32)
+    ks = sorted(int(k) for k in rows)
+    if not ks or ks[0] < 1 or ks[-1] > pn.shape[0] or len(set(ks)) != len(ks):
+        raise ValueError("rows: distinct row numbers from 1 to %i" % pn.shape[0])
+    acc = np.zeros(pn.shape[1], dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for k in ks:
+            acc = acc + pn[k - 1]
+        return (np.fmax(acc, np.float32(Delta)) / np.float32(len(ks))).astype(np.float32)
+
+
 def fmt3(x) -> str:
     """%.3f of a float32; a NaN is `nan` whatever its sign."""
     v = float(np.float32(x))
@@ -163,6 +191,32 @@ def support_lines(counter: int, ref_name: str, h: dict, row_names: Sequence[str]
             head = "%i\t%s\t%s\t%i\t%i\t%i\t%.2f\t%.3e\t%i\t%s" % (counter, ref_name, h["strand"], h["frame"] + 1, h["startGenomic"], h["endGenomic"],
                                                                  h["score"], float(np.float32(h["pvalue"])), k, row_names[k])   # details.format_line's head
             out.append("%s\t%s\t%s\t%s\n" % (head, fmt3(p[k - 1]), fmt3(np.float32(p[k - 1] / nkf)), fmt3(loo[k - 1])))
+    return out
+
+
+def region_support_header(null: bool = False, shuffle: bool = False) -> str:
+    return "\t".join(COLUMNS_REGION_SUPPORT + (COLUMNS_PAIR_NULL if null else ()) + (COLUMNS_PAIR_SHUFFLE if shuffle else ())) + "\n"
+
+
+def region_support_lines(region: Region, frame: int, c1: int, c2: int, score, row_names: Sequence[str], pairs, Delta,
+                         null: Optional[Tuple[Sequence[int], int]] = None, shuffle: Optional[Tuple[Sequence[int], int]] = None) -> List[str]:
+    """The --regions-support lines of one region in one block: one per non-reference row (row_names: the block's row names, the
+    reference's first).  null: (pair_ge, n) of --regions-null -- per row how many of the n null alignments have a pair score at least
+    the row's own over exactly this segment --, or None: the lines without pair_null_ge and p_pair; shuffle: the same of
+    --regions-shuffle-null.  p = (ge + 1) / (n + 1), `nan` where the row's pair score is NaN."""
+    p = np.ascontiguousarray(pairs, dtype=np.float32)
+    nkf = np.float32(p.shape[0])
+    loo = leave_one_out(p, Delta)
+    head = "%s\t%s\t%s\t%i\t%i\t%i\t%i\t%i\t%s" % (region.id, region.name, region.strand, frame + 1, c1 + 1, c2 + 1, region.start, region.end, fmt3(score))
+    out = []
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(1, p.shape[0] + 1):
+            line = "%s\t%i\t%s\t%s\t%s\t%s" % (head, k, row_names[k], fmt3(p[k - 1]), fmt3(np.float32(p[k - 1] / nkf)), fmt3(loo[k - 1]))
+            for counts in (null, shuffle):
+                if counts is not None:
+                    ge, n = int(counts[0][k - 1]), int(counts[1])
+                    line += "\t%i\tnan" % ge if np.isnan(p[k - 1]) else "\t%i\t%.3e" % (ge, (ge + 1.0) / (n + 1.0))
+            out.append(line + "\n")
     return out
 
 
