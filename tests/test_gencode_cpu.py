@@ -88,6 +88,18 @@ def test_code_tables_follow_the_code():
     assert api.default_params().genetic_code == b""
 
 
+def test_details_codon_classes_follow_the_code():
+    """--details classifies an in-frame codon pair with the run's own tables: TGA / TGG are both Trp under table 2, where AGA is a stop."""
+    from rnacode_amd import details
+    mito, standard = api.code_tables(62, 2), api.code_tables(62)
+    assert details.codon_kind("TGA", "TGG", *mito) == "synonymous" and details.codon_kind("TGG", "TGA", *mito) == "synonymous"
+    assert details.codon_kind("TGA", "TGA", *mito) == "identical"
+    assert details.codon_kind("AGA", "AGA", *mito) == "stop" and details.codon_kind("CGT", "AGA", *mito) == "stop"
+    assert details.codon_kind("TGA", "TGG", *standard) == "stop" and details.codon_kind("TGA", "TGA", *standard) == "stop"
+    assert details.codon_kind("AGA", "AGA", *standard) == "identical" and details.codon_kind("CGT", "AGA", *standard) == "synonymous"
+    assert details.codon_kind("AGA", "AAA", *standard) == "conservative"   # Arg / Lys: BLOSUM62 +2
+
+
 @pytest.mark.parametrize("what", sorted(BAD_CODES))
 def test_bad_codes_are_rejected_on_the_host(what):
     with pytest.raises(api.RnacodeError) as ei:

@@ -40,10 +40,12 @@ def make_blocks():
     return [synth_blocks(1, n, cols, seed)[0].upper() for n, cols, seed in SHAPES]
 
 
-def oracle_decoys(b, seeds):
-    """([per seed: the oracle's HSS list in rc_batch_hss's order], clamped draws)."""
-    from oracle import binding as ob
-    p = ob.default_params(SAMPLES)
+def oracle_decoys(b, seeds, ob=None, blosum=62):
+    """([per seed: the oracle's HSS list in rc_batch_hss's order], clamped draws).  ob: the oracle module (default: the stock one); blosum: 62
+    or 90."""
+    if ob is None:
+        from oracle import binding as ob
+    p = ob.default_params(SAMPLES, blosum)
     rows, names = [r.seq for r in b.rows], [r.name for r in b.rows]
     models, models_rev = ob.get_models(b.tree, rows, names, b.kappa, p.blosum), ob.get_models(b.tree, ob.rev_aln(rows), names, b.kappa, p.blosum)
     freqs = list(models[0].freqs)

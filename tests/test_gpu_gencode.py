@@ -265,8 +265,9 @@ def test_drivers_under_code_2(tmp_path):
         assert (nd / f).read_bytes() == (pd / f).read_bytes(), f
 
 
-def test_mitochondrial_orf_with_tga_is_one_segment_under_code_2(ctx):
-    """A conserved ORF with an in-frame TGA: under code 2 (TGA = Trp) one HSS spans it with p < 0.05; under code 1 none does."""
+def mito_block():
+    """A hand-made conserved ORF of 80 codons, six rows, with TGA as codon 40 of the reference row (TGA or TGG in the others); no sense
+    codon is a stop under table 1 or table 2.  The tree is the block's own fit (host code)."""
     from rnacode_amd import api
     from rnacode_amd.alnio import AlnBlock, AlnRow
     rng = np.random.RandomState(17)
@@ -288,6 +289,13 @@ def test_mitochondrial_orf_with_tga_is_one_segment_under_code_2(ctx):
     blk = AlnBlock([AlnRow(nm, s, 0, len(s), "+", len(s)) for nm, s in zip(names, rows)], 0, None, None)
     tree, kappa = api.fit_tree(blk)
     blk.tree, blk.kappa = tree, kappa
+    return blk
+
+
+def test_mitochondrial_orf_with_tga_is_one_segment_under_code_2(ctx):
+    """A conserved ORF with an in-frame TGA: under code 2 (TGA = Trp) one HSS spans it with p < 0.05; under code 1 none does."""
+    from rnacode_amd import api
+    blk = mito_block()
     tga = 3 * 40 + 1   # 1-based position of the T
     spans = {}
     for code in (1, 2):

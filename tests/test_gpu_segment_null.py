@@ -52,11 +52,12 @@ def ranges_of_block(i, b):
     return out + [(i, 1, *NO_STEP)]
 
 
-def oracle_null(b, ranges, samples, seed_base, Delta=None):
+def oracle_null(b, ranges, samples, seed_base, Delta=None, ob=None, blosum=62):
     """([len(ranges)][samples] float32, clamped draws): the ranges' values (all of block b; their block index is not looked at) in the null
-    alignments of seeds seed_base .. seed_base + samples - 1."""
-    from oracle import binding as ob
-    p = ob.default_params(samples)
+    alignments of seeds seed_base .. seed_base + samples - 1.  ob: the oracle module (default: the stock one); blosum: 62 or 90."""
+    if ob is None:
+        from oracle import binding as ob
+    p = ob.default_params(samples, blosum)
     if Delta is not None:
         p.Delta = Delta
     rows, names = [r.seq for r in b.rows], [r.name for r in b.rows]

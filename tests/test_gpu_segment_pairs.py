@@ -26,11 +26,13 @@ SEED_BASE = 42
 SEED = SEED_BASE + SAMPLES
 
 
-def oracle_pairs(b, ranges, alignments, samples=SAMPLES):
+def oracle_pairs(b, ranges, alignments, samples=SAMPLES, ob=None, blosum=62):
     """[sum of n_rows - 1 over `ranges`][len(alignments)] float32: P_k of every (range, row) of block b in each of `alignments` (lists of
-    rows with b's gap pattern), ranges in order and rows ascending within a range."""
-    from oracle import binding as ob
-    p = ob.default_params(samples)
+    rows with b's gap pattern), ranges in order and rows ascending within a range.  ob: the oracle module (default: the stock one); blosum:
+    62 or 90."""
+    if ob is None:
+        from oracle import binding as ob
+    p = ob.default_params(samples, blosum)
     rows, names = [r.seq for r in b.rows], [r.name for r in b.rows]
     m, mr = ob.get_models(b.tree, rows, names, b.kappa, p.blosum), ob.get_models(b.tree, ob.rev_aln(rows), names, b.kappa, p.blosum)
     nk = b.n - 1
@@ -43,11 +45,12 @@ def oracle_pairs(b, ranges, alignments, samples=SAMPLES):
     return out
 
 
-def simulated(b, seeds):
+def simulated(b, seeds, ob=None, blosum=62):
     """(the null alignments of `seeds`, clamped draws)"""
-    from oracle import binding as ob
+    if ob is None:
+        from oracle import binding as ob
     rows, names = [r.seq for r in b.rows], [r.name for r in b.rows]
-    models = ob.get_models(b.tree, rows, names, b.kappa, 62)
+    models = ob.get_models(b.tree, rows, names, b.kappa, blosum)
     out, clamped = [], 0
     for s in seeds:
         sim, cl = ob.simulate_null(b.tree, rows, names, list(models[0].freqs), models[0].kappa, s)

@@ -54,10 +54,12 @@ def shuffled(rows, seed):
     return ["".join(r[s] for s in src) for r in rows]
 
 
-def oracle_shuffles(b, ranges, seeds, samples=SAMPLES):
-    """[len(ranges)][len(seeds)] float32: the ranges' values (all of block b; their block index is not looked at) in the shuffles of `seeds`."""
-    from oracle import binding as ob
-    p = ob.default_params(samples)
+def oracle_shuffles(b, ranges, seeds, samples=SAMPLES, ob=None, blosum=62):
+    """[len(ranges)][len(seeds)] float32: the ranges' values (all of block b; their block index is not looked at) in the shuffles of `seeds`.
+    ob: the oracle module (default: the stock one); blosum: 62 or 90."""
+    if ob is None:
+        from oracle import binding as ob
+    p = ob.default_params(samples, blosum)
     rows, names = [r.seq for r in b.rows], [r.name for r in b.rows]
     models, models_rev = ob.get_models(b.tree, rows, names, b.kappa, p.blosum), ob.get_models(b.tree, ob.rev_aln(rows), names, b.kappa, p.blosum)
     out = np.zeros((len(ranges), len(seeds)), dtype=np.float32)

@@ -85,10 +85,12 @@ def make_blocks():
     return out
 
 
-def oracle_decoys(b, seeds):
-    """[per seed: the oracle's HSS list of the shuffled rows in rc_batch_hss's order]."""
-    from oracle import binding as ob
-    p = ob.default_params(SAMPLES)
+def oracle_decoys(b, seeds, ob=None, blosum=62):
+    """[per seed: the oracle's HSS list of the shuffled rows in rc_batch_hss's order].  ob: the oracle module (default: the stock one);
+    blosum: 62 or 90."""
+    if ob is None:
+        from oracle import binding as ob
+    p = ob.default_params(SAMPLES, blosum)
     rows, names = [r.seq for r in b.rows], [r.name for r in b.rows]
     models, models_rev = ob.get_models(b.tree, rows, names, b.kappa, p.blosum), ob.get_models(b.tree, ob.rev_aln(rows), names, b.kappa, p.blosum)
     out = []

@@ -41,9 +41,10 @@ def tile_blocks():
     return blocks
 
 
-def oracle_params(pars, samples=SAMPLES):
-    from oracle import binding as ob
-    p = ob.default_params(samples)
+def oracle_params(pars, samples=SAMPLES, ob=None, blosum=62):
+    if ob is None:
+        from oracle import binding as ob
+    p = ob.default_params(samples, blosum)
     for k, v in pars.items():
         setattr(p, k, v)
     return p
@@ -64,14 +65,15 @@ def reduce_matrix(S, L, f):
     return np.fmax.reduce(R, axis=0)
 
 
-def oracle_track(block, pars):
-    """[strand][frame] tracks of one block from ob.score_matrix."""
-    from oracle import binding as ob
+def oracle_track(block, pars, ob=None, blosum=62):
+    """[strand][frame] tracks of one block from ob.score_matrix.  ob: the oracle module (default: the stock one); blosum: 62 or 90."""
+    if ob is None:
+        from oracle import binding as ob
     rows, names = [r.seq for r in block.rows], [r.name for r in block.rows]
-    p = oracle_params(pars)
+    p = oracle_params(pars, ob=ob, blosum=blosum)
     out = []
     for srows in (rows, ob.rev_aln(rows)):
-        S = ob.score_matrix(srows, ob.get_models(block.tree, srows, names, block.kappa, 62), p)
+        S = ob.score_matrix(srows, ob.get_models(block.tree, srows, names, block.kappa, blosum), p)
         out.append([reduce_matrix(S, block.ref_len, f) for f in range(3)])
     return out
 
