@@ -636,7 +636,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
 
     // ---- phase B: both strands x 3 frames: DP over (start a, end j) + serial HSS scan
     float best = -1.0f;
-    unsigned long long statCells = 0, statNoPos = 0, statPosLanes = 0, statPristine = 0, statEvent = 0, statTail = 0;   // RC_PROFILING builds only
+    unsigned long long statCells = 0, statNoPos = 0, statPosLanes = 0, statPristine = 0, statEvent = 0, statTail = 0, statGateTested = 0, statGateSkipped = 0;   // RC_PROFILING builds only
     // omega and Delta as per-lane values: v_add_f32 with two VGPR operands issues at the full rate,
     // with an SGPR operand at ~60 % of it (tools/microbench.hip)
     float omega_v, Delta_v = 0.0f;
@@ -1018,6 +1018,11 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
           typedef float RowBuf __attribute__((ext_vector_type(32)));
           constexpr int kBuf = 32;
           constexpr int kGroup = 4;   // cells per group in the span loops (codes staged in LDS)
+          // entries of the buffered row per test of the scan's gate (rc_scan_core.h).  Measured at 2, 4 and 8 (profiles/r10): chunks of two are
+          // passed over more often (76 % against 65 and 50, tools/scan_gate_stats.py) and pay a test and a branch per two entries -- no gain at
+          // all; eight gain two thirds of what four do.
+          constexpr int kGateChunk = 4;
+          static_assert(kGateChunk >= 2 && kBuf % kGateChunk == 0, "whole chunks fill the buffer");
           RowBuf buf = {};
           Regs RB;   // row a + 1 (its lut members are not used)
           auto pristine2 = [&](uint32_t (&w)[NCW], float &wvA, float &wvB, auto jn, float &vB, auto kd) -> float {
@@ -1184,6 +1189,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                 for (; j < e; j++) pair_cell(wcur, j, j + 1 < sites ? j + 1 : j, std::true_type{}, fn);
               };
               {
+                if constexpr (kProfiling) statPristine += 1 + 2 * (next_event(j, sites) - j);   // (row a's first cell; a pair is two cells)
                 dspan(next_event(j, sites), [&](uint32_t (&w)[NCW], auto jn, float &vB, auto kd) { return pristine2(w, wvA, wvB, jn, vB, kd); });
                 static_for<NK>([&](auto kc) {
                   constexpr int k = decltype(kc)::value;
@@ -1196,6 +1202,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
               while (j < sites) {
                 if ((zany[j >> 6] >> (j & 63)) & 1ull) {
                   const int jev = j;
+                  if constexpr (kProfiling) statEvent += 2;
                   pair_cell(wcur, j, j + 1 < sites ? j + 1 : j, std::true_type{}, [&](uint32_t (&w)[NCW], int jn, float &vB, auto) { return event2(w, jev, jn, vB); });
                   j++;
                 }
@@ -1208,6 +1215,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                     auto &rb = RB.template at<k>();
                     rb.s1 = fmaxf(rb.s1, rb.s2);
                   });
+                  if constexpr (kProfiling) statTail += 2 * (e - j);
                   dspan(e, [&](uint32_t (&w)[NCW], auto jn, float &vB, auto kd) { return tail2(w, jn, vB, kd); });
                 }
                 dspan(e, [&](uint32_t (&w)[NCW], auto jn, float &vB, auto kd) { return fast2(w, jn, vB, kd); });
@@ -1282,13 +1290,48 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
               if (pend) {
                 // the buffered values, entry 0 first: unrolled, so that every entry is a register operand of its scan step (an
                 // indexed read costs three instructions and 9 cycles of the SIMD, tools/microbench_gpr_idx.hip)
-                [&]() {
+                if constexpr (!EXACT) {
+                  // ... in chunks of kGateChunk entries behind the gate of rc_scan_core.h: the chunk's maximum per lane, one compare with
+                  // the lane's G, one wave-uniform branch.  A chunk no lane needs costs the maximum, the compare and one addition to X;
+                  // one that some lane needs goes through the steps as before, and G follows the state they leave.  G is taken behind
+                  // this row's sample_scan_row_begin and its first cells, so a reset is in it.  The entries behind the last whole chunk:
+                  // one at a time.
+                  float G = sample_scan_gate(st, best, negTie);
+                  [&]() {
 #pragma unroll
-                  for (int idx = 0; idx < kBuf; idx++) {
-                    if (idx >= pendN) return;
-                    sample_scan_step(st, buf[idx], negTie, negTwo_v);
-                  }
-                }();
+                    for (int c0 = 0; c0 < kBuf; c0 += kGateChunk) {
+                      if (c0 + kGateChunk > pendN) {
+#pragma unroll
+                        for (int u = 0; u < kGateChunk - 1; u++) {
+                          if (c0 + u >= pendN) return;
+                          sample_scan_step(st, buf[c0 + u], negTie, negTwo_v);
+                        }
+                        return;
+                      }
+                      float m = buf[c0];
+#pragma unroll
+                      for (int u = 1; u + 1 < kGateChunk; u += 2) m = scan_max3(m, buf[c0 + u], buf[c0 + u + 1]);
+                      if constexpr (kGateChunk % 2 == 0) m = scan_max(m, buf[c0 + kGateChunk - 1]);
+                      if constexpr (kProfiling) statGateTested++;
+                      if (__builtin_amdgcn_ballot_w64(sample_scan_gate_pass(m, G)) != 0ull) {
+#pragma unroll
+                        for (int u = 0; u < kGateChunk; u++) sample_scan_step(st, buf[c0 + u], negTie, negTwo_v);
+                        G = sample_scan_gate(st, best, negTie);
+                      } else {
+                        if constexpr (kProfiling) statGateSkipped++;
+                        sample_scan_skip(st, kGateChunk);
+                      }
+                    }
+                  }();
+                } else {
+                  [&]() {
+#pragma unroll
+                    for (int idx = 0; idx < kBuf; idx++) {
+                      if (idx >= pendN) return;
+                      sample_scan_step(st, buf[idx], negTie, negTwo_v);
+                    }
+                  }();
+                }
                 pendRow = -1;
               } else {
                 a += 1;
@@ -1414,6 +1457,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
       if (A.cellStats && lane == 0) {
         atomicAdd(A.cellStats, statCells); atomicAdd(A.cellStats + 1, statNoPos); atomicAdd(A.cellStats + 2, statPosLanes);
         atomicAdd(A.cellStats + 3, statPristine); atomicAdd(A.cellStats + 4, statEvent); atomicAdd(A.cellStats + 5, statTail);
+        atomicAdd(A.cellStats + 6, statGateTested); atomicAdd(A.cellStats + 7, statGateSkipped);
       }
     }
     if (!ROWS && sidx < A.sampleN) {   // (ROWS: k_null_rowscan writes the maxima)
@@ -1438,7 +1482,8 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
 // what to aim for, the register allocator fits them into 78 / 89 / 94 again without a single spill.
 // Two rows per pass: four wavefronts per SIMD (16 per CU is what the staged codes' LDS allows).  The cell groups of the span loops took
 // k_null<5, true, false, true> from 127 to 129 VGPRs on their own; held to four, it fits 128 with nothing spilled.
-constexpr int null_min_waves(int NK, bool EXACT, bool DUAL, int MODE) { return DUAL ? 4 : (EXACT || MODE != 0) ? 1 : NK == 6 ? 6 : (NK == 9 || NK == 10) ? 5 : (NK >= 16 && NK <= 21) ? 4 : (NK >= 24 && NK <= 29) ? 3 : 1; }
+// (Two rows of two sequences fit five: the gate's G took k_null<2, true, false, true> from 96 to 97 VGPRs; held to five it stays at 96, nothing spilled.)
+constexpr int null_min_waves(int NK, bool EXACT, bool DUAL, int MODE) { return DUAL ? (NK == 2 && MODE == 0 ? 5 : 4) :(EXACT || MODE != 0) ? 1 : NK == 6 ? 6 : (NK == 9 || NK == 10) ? 5 : (NK >= 16 && NK <= 21) ? 4 : (NK >= 24 && NK <= 29) ? 3 : 1; }
 template <int NK, bool LDSC, bool EXACT, bool DUAL = false, int MODE = 0>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(null_min_waves(NK, EXACT, DUAL, MODE))))
 void k_null(NullArgs A, const uint8_t *__restrict__ blob,

@@ -29,6 +29,7 @@
 //    with jn the entry behind the last one scanned, Q = X + 2 jn + 2: X odd means set in this row, at j' = jn + (X + 1) / 2; X even
 //    means carried, and its length is jn - a + X / 2 + 1.
 #pragma once
+#include <cmath>
 #include <cstdint>
 
 #if defined(__HIPCC__)
@@ -101,5 +102,63 @@ RC_SCAN_D void sample_scan_row_end(SampleScan &st, uint32_t a, uint32_t jn) {
 RC_SCAN_D void sample_scan_last(const SampleScan &st, float &best) {
   best = ((st.len >= 2u) & (st.cm > best)) ? st.cm : best;
 }
+
+// ---- The gate: entries that may be left out of the fold (k_null's buffered row; tools/verify_scan_gate.cpp, tests/test_scan_gate_cpu.py).
+// Values of a row that wait in registers can be looked at several at once before any of them is folded.  With
+//   c = max(cm, best)   (>= 0: cm >= 0),      G = med3(0, fl(c - 2 thr), fl(c k)),  k = 1 - 2^-22
+// an entry v <= G of this lane changes nothing the lane's final `best` depends on, so a chunk whose values are <= G in every lane
+// is passed over with X moved on by -2 per entry (an even integer, exact in binary32 like every other X).
+//  * G = max(0, min(fl(c - 2 thr), fl(c k))): fl(c k) >= 0, and the median of 0, x, y with y >= 0 is 0 for x < 0 and min(x, y) otherwise.
+//    So v <= G gives v <= 0, or 0 < v <= fl(c - 2 thr) and v <= fl(c k).  v <= 0 fails the step's v > 0.  c = 0 gives G = 0.
+//  * Lemma: 0 < v <= G gives fl(v - c') <= -thr for every c' >= c.  Rounding is monotone, so fl(v - c') <= fl(g - c) for g either bound.
+//    - c <= 2^24 thr, g = fl(c - 2 thr) = (c - 2 thr)(1 + e), |e| <= 2^-24 (a sum of two floats has no underflow error):
+//      g - c = -2 thr + e (c - 2 thr) <= -2 thr + 2^-24 |c - 2 thr| <= -thr, and thr is a float, so fl(g - c) <= -thr.
+//    - c > 2^24 thr / 3 (far above the denormals: thr >= 2^-100 is all this needs), g = fl(c k) <= c k (1 + 2^-24):
+//      g - c <= c (k + 2^-24 - 1) = -3 c 2^-24 < -thr.
+//    The two ranges overlap; c = +inf gives G = +inf, every v passes under it (v = +inf: d is a NaN, the step's own compare fails).
+//  * (i) c = cm >= best.  d = fl(v - cm) <= -thr <= t: the step's upd is false, and leaving the entry out IS the step.
+//  * (ii) c = best > cm.  Call a state with cm <= best HARMLESS: whatever becomes of it, it is reported (row_begin, last) only through
+//    cm > best, so it never changes `best`.  Claim: the fold that sees every entry (O) and the one that leaves entries out (F) are, in
+//    front of every entry and every row, in identical states or both in harmless ones, with the same `best`.
+//    - identical, (i) applies: identical afterwards.  Identical and harmless, or both harmless, entry left out by F: v <= G < best, so O's cm
+//      stays <= best whether it takes v or not.
+//    - both harmless, entry seen by both: v > best >= cm replaces cm in both (v > cm is the rule's first arm) and sets X = -1 in both --
+//      cm and X identical, and row_end derives se and len from X alone where X is odd: identical.  v <= best: each cm stays <= best.
+//    - row_begin: a harmless state that is reported leaves best alone and becomes cm = 0 <= best (states differ only once O has taken
+//      a v > 0 that F left out, and then best > v > 0).  cm > best is reported from identical states only: best stays common.
+//    - entries F does not look at through the gate (row a's, in the cell loops) are entries seen by both.
+//    `best` only grows and a smaller one gives a smaller G: a part of a work item that starts from best = -1 filters less, its own
+//    maximum is exact, and the atomic max joins the parts as before.
+//  * A NaN v never passes: fmaxf drops it from the chunk's maximum, and a chunk of NaNs alone fails the compare.  (The kernels that
+//    can see NaN states are not gated.)
+// The maximum as the gate takes it: v_max_f32 / v_max3_f32 return the other operand for a quiet NaN, like fmaxf.  Written as
+// instructions because fmaxf on a value the compiler has not seen computed costs a canonicalising v_max_f32 x, x per operand (S values
+// and states are results of arithmetic: never signalling).
+RC_SCAN_D float scan_max(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  float r;
+  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+#else
+  return fmaxf(a, b);
+#endif
+}
+RC_SCAN_D float scan_max3(float a, float b, float c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  float r;
+  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+#else
+  return fmaxf(fmaxf(a, b), c);
+#endif
+}
+RC_SCAN_D float sample_scan_gate(const SampleScan &st, float best, float negTieThr) {
+  const float c = scan_max(st.cm, best);
+  return scan_med3(0.0f, c + 2.0f * negTieThr, c * 0.99999976158142089844f);   // k = 1 - 2^-22 = 0x1.fffff8p-1
+}
+// some entry of the chunk (m: the maximum of its values in this lane) has to go through the step
+RC_SCAN_D bool sample_scan_gate_pass(float m, float G) { return m > G; }
+// n entries left out
+RC_SCAN_D void sample_scan_skip(SampleScan &st, int n) { st.X = st.X + static_cast<float>(-2 * n); }
 
 }  // namespace rc
