@@ -104,14 +104,16 @@ void rc_ctx_destroy(rc_ctx *c) {
   c->bufPool->drain(true);
   c->pool.reset();
   if (kProfiling && c->d_cellStats.p) {
-    unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long st[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (hipMemcpy(st, c->d_cellStats.p, sizeof st, hipMemcpyDeviceToHost) == hipSuccess && st[0])
       std::fprintf(stderr, "[rc cell stats] wavefront-cells %llu, with no positive lane %llu (%.4f %%), positive lane-cells %.2f %%\n", st[0], st[1],
                    100.0 * st[1] / st[0], 100.0 * st[2] / (64.0 * st[0])),
       std::fprintf(stderr, "[rc cell stats] before the row's first event %.1f %%, event codons %.1f %%, after its last event %.1f %%, between events %.1f %%\n",
                    100.0 * st[3] / st[0], 100.0 * st[4] / st[0], 100.0 * st[5] / st[0], 100.0 * (st[0] - st[3] - st[4] - st[5]) / st[0]),
       std::fprintf(stderr, "[rc cell stats] buffered row: chunks tested against the scan's gate %llu, passed over %llu (%.2f %%)\n", st[6], st[7],
-                   st[6] ? 100.0 * st[7] / st[6] : 0.0);
+                   st[6] ? 100.0 * st[7] / st[6] : 0.0),
+      std::fprintf(stderr, "[rc cell stats] row a: groups of four tested against the gate on sums %llu, passed over %llu (%.2f %%)\n", st[8], st[9],
+                   st[8] ? 100.0 * st[9] / st[8] : 0.0);
   }
   if (c->d_U) (void)hipFree(c->d_U);
   for (hipStream_t st : c->compute) if (st) (void)hipStreamDestroy(st);
@@ -214,8 +216,8 @@ int rc_ctx_create(int device, rc_ctx **out) {
 #ifdef RC_PROFILING   // these two switches exist in profiling builds only (tools/mk_ab.sh): RC_DEBUG_SKIP gives wrong results
   if (const char *e = std::getenv("RC_DEBUG_SKIP")) c->debugSkip = std::atoi(e);
   if (std::getenv("RC_CELL_STATS")) {
-    HIP_TRY(c->d_cellStats.ensure(8 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(c->d_cellStats.p, 0, 8 * sizeof(unsigned long long)));
+    HIP_TRY(c->d_cellStats.ensure(10 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(c->d_cellStats.p, 0, 10 * sizeof(unsigned long long)));
   }
 #endif
   c->hostThreads = std::min(effective_cpus(), 32);

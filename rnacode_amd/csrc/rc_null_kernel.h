@@ -132,14 +132,11 @@ template <int NK, typename F> __device__ __forceinline__ void static_for(F &&f) 
 // the EXACT instantiation, which uses '/'.
 template <int NK, bool EXACT> __device__ __forceinline__ float div_by_nk(float x, float nkf) {
   if constexpr ((NK & (NK - 1)) == 0) {
-    return x * (1.0f / static_cast<float>(NK));
+    return scan_div_nk(x, 1.0f / static_cast<float>(NK), -static_cast<float>(NK), true);
   } else if constexpr (EXACT) {
     return x / nkf;
   } else {
-    constexpr float y = 1.0f / static_cast<float>(NK);
-    const float q0 = x * y;
-    const float r = __builtin_fmaf(-static_cast<float>(NK), q0, x);
-    return __builtin_fmaf(r, y, q0);
+    return scan_div_nk(x, 1.0f / static_cast<float>(NK), -static_cast<float>(NK), false);   // (rc_scan_core.h: the host's verifiers compile the same text)
   }
 }
 
@@ -636,7 +633,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
 
     // ---- phase B: both strands x 3 frames: DP over (start a, end j) + serial HSS scan
     float best = -1.0f;
-    unsigned long long statCells = 0, statNoPos = 0, statPosLanes = 0, statPristine = 0, statEvent = 0, statTail = 0, statGateTested = 0, statGateSkipped = 0;   // RC_PROFILING builds only
+    unsigned long long statCells = 0, statNoPos = 0, statPosLanes = 0, statPristine = 0, statEvent = 0, statTail = 0, statGateTested = 0, statGateSkipped = 0, statGroupTested = 0, statGroupSkipped = 0;   // RC_PROFILING builds only
     // omega and Delta as per-lane values: v_add_f32 with two VGPR operands issues at the full rate,
     // with an SGPR operand at ~60 % of it (tools/microbench.hip)
     float omega_v, Delta_v = 0.0f;
@@ -886,22 +883,25 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
         // instantiation skips the MAX3 with Delta; blocks with Delta >= 0 are routed to EXACT.
         // the constants of the constant-divisor division as per-lane registers: a literal operand goes over the constant bus like an
         // SGPR, and such VALU instructions issue at the single rate (tools/microbench.hip)
-        auto finish = [&](float sum) -> float {
+        auto seen = [&](float sum) {
           if constexpr (kProfiling) {   // how often a wave-uniform "no lane has sum > 0" test could skip the division and the scan step
             const unsigned long long pos = __ballot(sum > 0.0f);
             statCells++; statNoPos += (pos == 0ull); statPosLanes += __builtin_popcountll(pos);
           }
+        };
+        auto divide = [&](float sum) -> float {
           if constexpr (EXACT) {
             const float top = (sum > Delta_v) ? sum : Delta_v;
             return div_by_nk<NK, EXACT>(top, nkf);
           } else {
             if constexpr ((NK & (NK - 1)) == 0) return div_by_nk<NK, EXACT>(sum, nkf);
-            else {   // div_by_nk's sequence on register operands
-              const float q0 = sum * rcpNk_v;
-              const float r = __builtin_fmaf(negNk_v, q0, sum);
-              return __builtin_fmaf(r, rcpNk_v, q0);
-            }
+            else return scan_div_nk(sum, rcpNk_v, negNk_v, false);   // div_by_nk's sequence on register operands
           }
+        };
+        // (the two-row walk takes a cell apart: `seen` where the sum is made, `divide` where -- and if -- its S value is needed)
+        auto finish = [&](float sum) -> float {
+          seen(sum);
+          return divide(sum);
         };
         // codon without a frame shift in any sequence (z == 0 for all k, score.c:506-510): straight-line
         auto fast_cell = [&](uint32_t (&w)[NCW], int jn, auto kind) -> float {
@@ -1025,6 +1025,12 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
           static_assert(kGateChunk >= 2 && kBuf % kGateChunk == 0, "whole chunks fill the buffer");
           RowBuf buf = {};
           Regs RB;   // row a + 1 (its lut members are not used)
+          // The four kinds of cell pair hand out both rows' SUMS, undivided (the return value is row a's): the division -- a v_mul and two v_fma per
+          // cell -- is paid where an S value is needed.  Row a + 1's sums go into the buffer as they are and are tested against the gate on sums
+          // (rc_scan_core.h: sample_scan_gate_sum) when the row's turn comes; only the chunks that some lane needs are divided.  In the cell
+          // groups of the staged span loops row a's four sums are a chunk of the same gate (dspan).  The cells in front of b0, whose row a + 1
+          // values are thrown away, divide nothing for that row.
+          constexpr float kNkF = static_cast<float>(NK);
           auto pristine2 = [&](uint32_t (&w)[NCW], float &wvA, float &wvB, auto jn, float &vB, auto kd) -> float {
             float sig[NK];
             lookup(w, sig, jn, std::false_type{}, kd);
@@ -1042,8 +1048,10 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
               const float mb = fmaxf(rb.s0, wvB);
               sumB = (k == 0) ? mb : sumB + mb;
             });
-            vB = finish(sumB);
-            return finish(sumA);
+            seen(sumB);
+            seen(sumA);
+            vB = sumB;
+            return sumA;
           };
           auto fast2 = [&](uint32_t (&w)[NCW], auto jn, float &vB, auto kd) -> float {
             float sig[NK];
@@ -1064,8 +1072,10 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
               const float mb = fmaxf(fmaxf(rb.s0, rb.s1), rb.s2);
               sumB = (k == 0) ? mb : sumB + mb;
             });
-            vB = finish(sumB);
-            return finish(sumA);
+            seen(sumB);
+            seen(sumA);
+            vB = sumB;
+            return sumA;
           };
           auto tail2 = [&](uint32_t (&w)[NCW], auto jn, float &vB, auto kd) -> float {
             float sig[NK];
@@ -1084,8 +1094,10 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
               const float mb = fmaxf(rb.s0, rb.s1);
               sumB = (k == 0) ? mb : sumB + mb;
             });
-            vB = finish(sumB);
-            return finish(sumA);
+            seen(sumB);
+            seen(sumA);
+            vB = sumB;
+            return sumA;
           };
           auto event2 = [&](uint32_t (&w)[NCW], int j, int jn, float &vB) -> float {
             float sig[NK];
@@ -1106,8 +1118,10 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
               const float mb = fmaxf(fmaxf(rb.s0, rb.s1), rb.s2);
               sumB = (k == 0) ? mb : sumB + mb;
             });
-            vB = finish(sumB);
-            return finish(sumA);
+            seen(sumB);
+            seen(sumA);
+            vB = sumB;
+            return sumA;
           };
           int a = 0;
           int pendRow = -1, pendExtra = 0, pendN = 0;   // row a + 1 of the last pair: its first pendExtra cells are still to be made, then pendN buffered values to scan
@@ -1135,16 +1149,16 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
               }
               const int extra = (sites - 1 - a > kBuf) ? sites - 1 - a - kBuf : 0;   // row a + 1 has sites - 1 - a cells: the last kBuf are buffered
               const int b0 = a + 1 + extra;
-              auto keep = [&](float vB, int jj) {   // (a cell before b0 lands in entry 0 and is overwritten by the one that belongs there)
+              auto keep = [&](float sB, int jj) {   // (a cell before b0 lands in entry 0 and is overwritten by the one that belongs there)
                 const int idx = jj > b0 ? jj - b0 : 0;
-                buf[idx] = vB;
+                buf[idx] = sB;
               };
-              // one cell pair (rows a and a + 1 at site jj) on the register set w: row a's value through the scan, row a + 1's into the buffer
+              // one cell pair (rows a and a + 1 at site jj) on the register set w: row a's value through the scan, row a + 1's sum into the buffer
               auto pair_cell = [&](uint32_t (&w)[NCW], int jj, int jn, auto kd, auto &&fn) {
-                float vB;
-                const float v = fn(w, jn, vB, kd);
+                float sB;
+                const float v = divide(fn(w, jn, sB, kd));
                 sample_scan_step(st, v, negTie, negTwo_v);
-                keep(vB, jj);
+                keep(sB, jj);
               };
               // the cells j .. e - 1 of one kind; codes from L2: in front of the suffix cache with two cells of fetch distance on two register sets
               // (see "Two cells of distance" at the one-row loops below)
@@ -1157,33 +1171,64 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                   // are thrown away (in front of b0) go first, without a buffer write; a group never reaches the frame's final site (whose
                   // cell fetches no further site), so no cell of a group needs the clamp of the next site.  The rest: one cell at a time.
                   for (const int pe = e < b0 ? e : b0; j < pe; j++) {   // (j < b0 <= sites - 1: the next site exists)
-                    float vB;
-                    const float v = fn(wcur, j + 1, vB, std::true_type{});
+                    float sB;
+                    const float v = divide(fn(wcur, j + 1, sB, std::true_type{}));
                     sample_scan_step(st, v, negTie, negTwo_v);
                   }
+                  // Row a's four entries of a group are a chunk of the gate on sums: the cells hand out row a's sums undivided, the group takes
+                  // their maximum, Gs from the state as it stands (no step has touched it since the last group that was taken, or since the
+                  // cell in front: Gs is made anew in every group from cm and best, six vector instructions, and lives in no register across
+                  // groups), one compare, and X moved on by -8.  The loop's one branch goes back while no lane needs the chunk AND another whole
+                  // group follows -- the trip test is folded into the ballot's mask (written as a boolean && the compiler gives each condition
+                  // a branch of its own).  A chunk that some lane needs is taken behind the loop: X put back (small integers: exact), four
+                  // divisions, four literal steps, and the loop is entered again if groups remain.  The guard in front of the loop and the
+                  // loop's exit meet at the test of `need`, which the compiler must not see through: the taken path is then a block of its own
+                  // behind the loop and not a tail of the group's block (tests/test_codegen_group_gate.py).
                   const int ge = e < sites - 1 ? e : sites - 1;
-                  for (; j + kGroup <= ge; j += kGroup) {
-                    const uint32_t at = ldsLane + static_cast<uint32_t>(j + 1) * (NCW * kWave * 4u);
-                    float vB[kGroup];
-                    static_for<kGroup>([&](auto uc) {
-                      constexpr int u = decltype(uc)::value;
-                      const float v = fn(wcur, StagedSite<u * NCW * kWave * 4>{at}, vB[u], std::true_type{});
-                      sample_scan_step(st, v, negTie, negTwo_v);
-                    });
-                    // the group's values into entries idx .. idx + kGroup - 1 (idx >= 0: j >= b0), one index for all: the scheduling
-                    // barriers keep the indexed moves side by side, where one s_set_gpr_idx_on .. off window takes them all
-                    // (the index settled in an SGPR of its own and known not to be negative -- the mask changes no value, 0 <= idx <= kBuf - kGroup
-                    // - 1 -- lets u fold into the moves' register operand: on a base that might be negative the compiler adds each index anew,
-                    // and the windows stay apart)
-                    int idxRaw = j - b0;
-                    asm volatile("" : "+s"(idxRaw));
-                    const int idx = idxRaw & (kBuf - 1);
-                    __builtin_amdgcn_sched_barrier(0);
-                    static_for<kGroup>([&](auto uc) {
-                      constexpr int u = decltype(uc)::value;
-                      buf[idx + u] = vB[u];
-                    });
-                    __builtin_amdgcn_sched_barrier(0);
+                  static_assert(kGroup == 4, "a group's maximum: v_max3 + v_max");
+                  float sA[kGroup] = {};
+                  unsigned long long need = 0ull;
+                  asm volatile("" : "+s"(need));
+                  for (;;) {
+                    if (j + kGroup <= ge) {
+                      unsigned long long stop;
+                      do {
+                        const uint32_t at = ldsLane + static_cast<uint32_t>(j + 1) * (NCW * kWave * 4u);
+                        float vB[kGroup];
+                        static_for<kGroup>([&](auto uc) {
+                          constexpr int u = decltype(uc)::value;
+                          sA[u] = fn(wcur, StagedSite<u * NCW * kWave * 4>{at}, vB[u], std::true_type{});
+                        });
+                        // the group's values into entries idx .. idx + kGroup - 1 (idx >= 0: j >= b0), one index for all: the scheduling
+                        // barriers keep the indexed moves side by side, where one s_set_gpr_idx_on .. off window takes them all
+                        // (the index settled in an SGPR of its own and known not to be negative -- the mask changes no value, 0 <= idx <= kBuf - kGroup
+                        // - 1 -- lets u fold into the moves' register operand: on a base that might be negative the compiler adds each index anew,
+                        // and the windows stay apart)
+                        int idxRaw = j - b0;
+                        asm volatile("" : "+s"(idxRaw));
+                        const int idx = idxRaw & (kBuf - 1);
+                        __builtin_amdgcn_sched_barrier(0);
+                        static_for<kGroup>([&](auto uc) {
+                          constexpr int u = decltype(uc)::value;
+                          buf[idx + u] = vB[u];
+                        });
+                        __builtin_amdgcn_sched_barrier(0);
+                        const float m = scan_max(scan_max3(sA[0], sA[1], sA[2]), sA[3]);
+                        const float Gs = sample_scan_gate_sum(st, best, negTie, kNkF);
+                        sample_scan_skip(st, kGroup);
+                        j += kGroup;
+                        need = __builtin_amdgcn_ballot_w64(sample_scan_gate_pass(m, Gs));
+                        if constexpr (kProfiling) { statGroupTested++; statGroupSkipped += (need == 0ull); }
+                        const unsigned long long last = static_cast<unsigned long long>(static_cast<long long>(ge - kGroup - j) >> 63);   // all ones behind the last whole group
+                        stop = need | last;
+                      } while (stop == 0ull);
+                    }
+                    if (need == 0ull) break;
+                    need = 0ull;
+                    asm volatile("" : "+s"(need));   // (opaque: or the compiler threads the guard's exit past the join)
+                    sample_scan_skip(st, -kGroup);
+#pragma unroll
+                    for (int u = 0; u < kGroup; u++) sample_scan_step(st, divide(sA[u]), negTie, negTwo_v);
                   }
                 }
                 for (; j < e; j++) pair_cell(wcur, j, j + 1 < sites ? j + 1 : j, std::true_type{}, fn);
@@ -1296,7 +1341,9 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                   // one that some lane needs goes through the steps as before, and G follows the state they leave.  G is taken behind
                   // this row's sample_scan_row_begin and its first cells, so a reset is in it.  The entries behind the last whole chunk:
                   // one at a time.
-                  float G = sample_scan_gate(st, best, negTie);
+                  // The buffer holds SUMS: the gate is the one on sums (sample_scan_gate_sum), and an entry is divided only where it goes
+                  // through a step -- in the chunks that some lane needs and behind the last whole chunk.
+                  float G = sample_scan_gate_sum(st, best, negTie, kNkF);
                   [&]() {
 #pragma unroll
                     for (int c0 = 0; c0 < kBuf; c0 += kGateChunk) {
@@ -1304,7 +1351,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
 #pragma unroll
                         for (int u = 0; u < kGateChunk - 1; u++) {
                           if (c0 + u >= pendN) return;
-                          sample_scan_step(st, buf[c0 + u], negTie, negTwo_v);
+                          sample_scan_step(st, divide(buf[c0 + u]), negTie, negTwo_v);
                         }
                         return;
                       }
@@ -1315,8 +1362,8 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                       if constexpr (kProfiling) statGateTested++;
                       if (__builtin_amdgcn_ballot_w64(sample_scan_gate_pass(m, G)) != 0ull) {
 #pragma unroll
-                        for (int u = 0; u < kGateChunk; u++) sample_scan_step(st, buf[c0 + u], negTie, negTwo_v);
-                        G = sample_scan_gate(st, best, negTie);
+                        for (int u = 0; u < kGateChunk; u++) sample_scan_step(st, divide(buf[c0 + u]), negTie, negTwo_v);
+                        G = sample_scan_gate_sum(st, best, negTie, kNkF);
                       } else {
                         if constexpr (kProfiling) statGateSkipped++;
                         sample_scan_skip(st, kGateChunk);
@@ -1328,7 +1375,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
 #pragma unroll
                     for (int idx = 0; idx < kBuf; idx++) {
                       if (idx >= pendN) return;
-                      sample_scan_step(st, buf[idx], negTie, negTwo_v);
+                      sample_scan_step(st, divide(buf[idx]), negTie, negTwo_v);
                     }
                   }();
                 }
@@ -1458,6 +1505,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
         atomicAdd(A.cellStats, statCells); atomicAdd(A.cellStats + 1, statNoPos); atomicAdd(A.cellStats + 2, statPosLanes);
         atomicAdd(A.cellStats + 3, statPristine); atomicAdd(A.cellStats + 4, statEvent); atomicAdd(A.cellStats + 5, statTail);
         atomicAdd(A.cellStats + 6, statGateTested); atomicAdd(A.cellStats + 7, statGateSkipped);
+        atomicAdd(A.cellStats + 8, statGroupTested); atomicAdd(A.cellStats + 9, statGroupSkipped);
       }
     }
     if (!ROWS && sidx < A.sampleN) {   // (ROWS: k_null_rowscan writes the maxima)

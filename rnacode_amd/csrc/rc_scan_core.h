@@ -161,4 +161,41 @@ RC_SCAN_D bool sample_scan_gate_pass(float m, float G) { return m > G; }
 // n entries left out
 RC_SCAN_D void sample_scan_skip(SampleScan &st, int n) { st.X = st.X + static_cast<float>(-2 * n); }
 
+// ---- The gate on undivided sums (k_null's two-row walk; tools/verify_sum_gate.cpp, tests/test_sum_gate_cpu.py).
+// An S value is v = finish(s) = s / NK, the sum s of a cell's NK maxima divided the way the fast instantiations divide: exact scaling for a
+// power of two, otherwise Markstein's two-FMA correction of s * RN(1 / NK) -- scan_div_nk below is that text, and the kernels call it.  It is
+// the correctly rounded quotient RN(s / NK) for NK in 2..31 and every s in D = {0} U +-[2^-100, 2^100) (tools/verify_const_div.c, by exhaustion);
+// blocks whose sums could leave D are scored by the EXACT launch, which is not gated.  A chunk can therefore be tested BEFORE it is divided:
+//   Gs = fl(fl(G NK) k),  k = 1 - 2^-22,  G = sample_scan_gate(...)       and        s <= Gs, s in D   gives   finish(s) <= G.
+//  * It is enough that Gs <= G NK in real arithmetic: then s / NK <= Gs / NK <= G, G is a float and rounding to nearest is monotone, so
+//    finish(s) = RN(s / NK) <= RN(G) = G.  The division need only be right at s, which is in D; nothing is asked of it at Gs.
+//  * P = fl(G NK) a normal number: P <= G NK (1 + 2^-24).  Gs = RN(P k) with P k = P (1 - 2^-22).
+//    - P k normal: Gs <= P k (1 + 2^-24) <= G NK (1 + 2^-24)^2 (1 - 2^-22) < G NK (1 + 2^-23 + 2^-48 - 2^-22) < G NK.  This is the case of both
+//      ranges of the lemma above (c <= 2^24 thr and c > 2^24 thr / 3): either way G is a float in [0, c], and only its value enters here.
+//    - P k a denormal (P < 2^-126 / k): Gs <= P k + 2^-150 = P - P 2^-22 + 2^-150 <= P - 2^-148 + 2^-150, and G NK >= P / (1 + 2^-24) > P - P 2^-24
+//      > P - 2^-149: again Gs < G NK.
+//  * P a denormal or 0 (G NK < 2^-126, so G is a denormal or 0: NK >= 2): a denormal times an integer below 2^-126 is a multiple of 2^-149 and is
+//    exact, P = G NK.  P k < P, P is a float, rounding is monotone: Gs = RN(P k) <= P = G NK.  G = 0 gives Gs = 0.
+//  * P = +inf.  G = +inf: every finish(s) <= G.  G finite: G NK >= 2^128 (1 - 2^-25), so G > 2^122, while s in D gives finish(s) < 2^99.
+//    (Gs = +inf then passes every chunk over; Gs = 0 is what a caller may always use instead -- G >= 0 -- and what a caller with sums
+//    outside D would have to use: nothing else here relies on D.)
+//  * s < 0 or s = +-0 needs none of this: finish(s) <= 0 <= G.  A NaN s never passes under Gs, as above; the gated kernels see none.
+// So a chunk of sums whose maximum is <= Gs in every lane holds only entries v <= G and is passed over as before; one that some lane needs is
+// divided entry by entry and goes through the literal steps.  Gs is taken from the state the chunk sees, like G: anew behind every literal
+// step and every sample_scan_row_begin (a tie replacement can lower cm; a stale gate is not covered by the proof).
+// The entries this gate looks at are row a + 1's, buffered as sums, and row a's in the cell groups of the staged span loops: a group of
+// four cells is a chunk, entries "seen by both folds" in the proof above are then the ones of the single cells, the event cells and the
+// chunks that pass.
+// x / NK of the fast instantiations on register operands (rcpNk = RN(1 / NK), negNk = -NK): a v_mul and two v_fma, or the v_mul alone
+RC_SCAN_D float scan_div_nk(float x, float rcpNk, float negNk, bool pow2) {
+  const float q0 = x * rcpNk;
+  if (pow2) return q0;
+  const float r = __builtin_fmaf(negNk, q0, x);
+  return __builtin_fmaf(r, rcpNk, q0);
+}
+RC_SCAN_D float scan_gate_sum_of(float G, float nk) { return (G * nk) * 0.99999976158142089844f; }   // G >= 0, nk = NK as a float
+RC_SCAN_D float sample_scan_gate_sum(const SampleScan &st, float best, float negTieThr, float nk) {
+  return scan_gate_sum_of(sample_scan_gate(st, best, negTieThr), nk);
+}
+
 }  // namespace rc

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """k_null's own counters for the bench batch: the cell mix of the row walks (before a row's first event / event codons / after its
-last event / between events) and the scan gate's chunks of the buffered row (tested / passed over), from a profiling build.
+last event / between events), the scan gate's chunks of the buffered row (tested / passed over) and row a's groups of four cells
+in the staged span loops (tested against the gate on sums / passed over), from a profiling build.
 
     tools/mk_ab.sh                      # tools/ab_B.so: the working tree with -DRC_PROFILING
     python tools/cell_stats.py [--lib tools/ab_B.so] [--blocks 10000] [--cols 120] [--seqs 6] [--samples 1000]
