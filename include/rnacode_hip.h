@@ -375,6 +375,51 @@ int rc_batch_segment_null_pairs(const rc_batch *b, const rc_bt_range *ranges, in
                                 int64_t *offsets /* n_ranges + 1 */, float *pair_null_out /* may be NULL: [offsets[n_ranges]][sampleN] */,
                                 int64_t null_cap /* floats in pair_null_out */);
 
+/* Named windows: does an interval NAMED IN ADVANCE -- an exon of a lncRNA, a Ribo-seq covered stretch, an intergenic gap, whose ORF nobody
+ * knows -- contain a conserved coding segment, and how surprising is its best one?  The call sits between rc_batch_segment_null (one cell)
+ * and the block's fit (all cells of both strands).  A window is (blk, strand, lo, hi) in an rc_bt_range, lo = opt_b and hi = opt_i: positions
+ * 1 <= lo <= hi, 1-based in the strand's ungapped reference row, the coordinates of an HSS's start / end (rc_bt_range above).  No
+ * divisibility rule applies.  Its cells are the cells S[a][j] of the three frame matrices rc_batch_native_S documents with
+ *     3 a + f + 1 >= lo,   3 j + f + 3 <= hi,   a <= j:
+ * all segments of whole codons of frame f that lie inside the window (hi beyond the row's end counts as the row's end).  The value of a window
+ * in an alignment is the maximum of its cells that are numbers, NaN where every cell is NaN (fmaxf's maximum).
+ * rc_batch_window_best: for every window w, in the block itself,
+ *     score_out[w]                      the window's value,
+ *     frame_out, opt_b_out, opt_i_out   the first cell, in the order frame, a, j ascending, whose value equals score_out[w] -- frame f,
+ *                                       opt_b = 3 a + f + 1, opt_i = 3 j + f + 3, what rc_batch_segment_scores and rc_batch_backtrack_many
+ *                                       take as a range; the window's first cell where the score is NaN,
+ *     cells_out[w]                      the number of cells.
+ * Every cell has the bits of rc_batch_native_S and rc_batch_segment_scores.  Any output but score_out may be NULL.
+ * rc_batch_window_null: the same five outputs, and for every one of the sampleN null alignments of the batch's parameters -- sample s is the
+ * alignment behind rc_batch_maxima(...)[s]; seeds, samples and --stop-early as for rc_batch_segment_null --
+ *     null[w][s] = the window's value in null alignment s,
+ * every cell with the bits rc_batch_segment_null gives it.  ge_out[w] is the number of samples with null[w][s] >= score_out[w] (binary32
+ * compare: a NaN on either side does not count); if null_out is not NULL the values come back at null_out[w * sampleN + s], and
+ * cap < n_windows * sampleN is RC_ERR_ARG.  With the two whole strands of a block as windows, the fmaxf M of their two null rows is the maximum
+ * of ALL cells of sample s, and m = rc_batch_maxima(...)[s], the best HSS of getHSS's list, is -1 (no HSS) or 0 < m <= M; m == M bit for bit
+ * wherever M is positive, belongs to a segment of three or more codons and leads every other cell by more than getHSS's tie margin.
+ * The empirical p is the caller's: p_window = (ge + 1) / (sampleN + 1).  It is valid for a window chosen WITHOUT looking at the scores; it is
+ * NOT valid for an interval picked around a listed HSS, which was selected as a maximum (that is what the fit and rc_pvalue are for).
+ * rc_pvalue(score, mu, lambda) under the block's fit is conservative for a window, not wrong: the window holds a part of the block's cells.
+ * Samples of different blocks are independent simulations: for windows in several blocks (the exons of one transcript) the element-wise
+ * fmaxf of their null rows is the null of the fmaxf of their scores.
+ * Errors: a window without a cell -- hi < lo + 2, or lo behind every frame's last whole codon -- a strand outside 0..1, lo < 1 or a block
+ * index out of range return RC_ERR_ARG and rc_last_error names the window's index; a window on a block that was not scored returns that
+ * block's status; a batch that has not completed a run RC_ERR_ARG.  Every window is checked before the device is touched: on any of these
+ * errors nothing is launched and the outputs are left alone.  n_windows = 0 is RC_OK; a window may repeat.  Works on a batch rc_stream_next
+ * handed out until it is recycled, and leaves the batch's maxima, fit, HSS, timings and rc_batch_clamped as they are.
+ * Cost: the block's own side is one launch, one wavefront per window, about W^3 / 6 steps of the recurrence per frame and row for a window
+ * of W codons.  The null side repeats the simulation phase for the WHOLE of every block that has a window, in rc_batch_segment_null's rounds
+ * under its budget (RC_SEGNULL_MAX_BYTES; the result does not depend on it), then walks every row of the window's triangles: about
+ * 3 (N - 1) W^2 / 2 steps per sample, the windows and chunks of 512 cells of a window side by side on the device.  Device memory beside the
+ * budget: 48 bytes per window, 32 bytes and 256 x ceil(sampleN / 64) bytes per chunk of the largest round, 4 bytes x sampleN per window when
+ * null_out is asked for, and up to 110 MB of scratch for rounds with blocks of more than 22 rows. */
+int rc_batch_window_best(const rc_batch *b, const rc_bt_range *windows, int32_t n_windows, float *score_out /* n_windows */,
+                         int32_t *frame_out, int32_t *opt_b_out, int32_t *opt_i_out, int64_t *cells_out);
+int rc_batch_window_null(const rc_batch *b, const rc_bt_range *windows, int32_t n_windows, float *score_out /* n_windows */,
+                         int32_t *frame_out, int32_t *opt_b_out, int32_t *opt_i_out, int64_t *cells_out, int32_t *ge_out /* n_windows */,
+                         float *null_out /* may be NULL: [n_windows][sampleN] */, int64_t cap /* floats in null_out */);
+
 /* Decoy listings: the complete HSS listing of null alignments, for an empirical false discovery rate of a whole screen.  For the k-th
  * listed block (blks[k], or k where blks is NULL; a block may repeat) and decoy d = 0 .. n_decoys - 1 (1 <= n_decoys <= 64) the call
  * simulates the null alignment of MT19937 seed seed + d under the block's own tree, gap pattern and base frequencies -- the run's own

@@ -32,6 +32,12 @@ seed_base + n ..) score at least as high on exactly that segment (one rc_batch_s
 one line per region, block and non-reference row; with --regions-null / --regions-shuffle-null each line ends in that null's count for the
 row's pair score and p_pair = (count + 1) / (n + 1), the per-species test of a segment named in advance (segments.py; the sub-batch's one
 call per null becomes rc_batch_segment_null_pairs / rc_batch_segment_shuffle_null_pairs).
+--windows FILE with --windows-out FILE (not in the reference) finds the best segment inside intervals named in advance -- the --regions
+format, any length, any frame; a window is cut to every scored block that overlaps it -- and writes the cut window, that segment, its
+score, the block-wide p and the number of segments the window holds (windows.py; one rc_batch_window_best call per sub-batch).
+--windows-null adds null_ge and p_window = (null_ge + 1) / (n + 1): how many of the -n null alignments hold a segment inside the same window
+that scores at least as high (rc_batch_window_null in that call's place); --windows-summary FILE (with --windows-null) writes one line per
+window id over all its pieces in the run, the exons of a transcript in whatever blocks they lie (windows.group_p's rule).
 --decoys K with --decoys-out FILE (not in the reference) writes the complete listing of K null alignments per scored block, selected by
 --cutoff, -b and -r as the block's own HSS are (decoys.py; one rc_batch_decoys call per sub-batch, seeds seed_base + n ..: the first the
 fit did not see): what `python -m rnacode_amd.decoys` turns into a false discovery rate of the listing.  --decoy-kind shuffled lists, in
@@ -52,7 +58,7 @@ from typing import IO, List, Optional
 
 import numpy as np
 
-from . import api, decoys, details, eps, report, segments, shuffle_null, track
+from . import api, decoys, details, eps, report, segments, shuffle_null, track, windows
 from .alnio import AlnBlock, read_alignment_file
 
 
@@ -163,6 +169,19 @@ def build_parser() -> argparse.ArgumentParser:
                          "without it; with --regions-null also pair_null_ge = how many of the -n null alignments have a pair score at "
                          "least as high for that sequence, and p_pair = (pair_null_ge + 1) / (n + 1); with --regions-shuffle-null N also "
                          "pair_shuffle_ge and p_pair_shuffled, the same under the N shuffles")
+    ap.add_argument("--windows", metavar="FILE",
+                    help="find the best segment inside given windows (with --windows-out): tab-separated lines 'name strand start end [id]' "
+                         "as --regions takes them, of any length and in any frame; a window is cut to the block that overlaps it")
+    ap.add_argument("--windows-out", metavar="FILE",
+                    help="where the windows' results go: one line per window and scored block that overlaps it -- the cut window, its best "
+                         "segment of whole codons, that segment's score and block-wide p, and the number of segments the window holds")
+    ap.add_argument("--windows-null", action="store_true",
+                    help="with --windows: two more columns in --windows-out, null_ge = how many of the -n null alignments hold a segment "
+                         "inside the same window that scores at least as high, and p_window = (null_ge + 1) / (n + 1), the test for a "
+                         "window named in advance (not for an interval picked around a listed HSS)")
+    ap.add_argument("--windows-summary", metavar="FILE",
+                    help="with --windows-null: one line per window id over all its pieces in the run (the exons of a transcript, in "
+                         "whatever blocks they lie): the best score, null_ge and p_window of the pieces taken together")
     ap.add_argument("--decoys", type=int, metavar="K",
                     help="with --decoys-out: list the HSS of K (1..64) null alignments per scored block, simulated as the samples behind the "
                          "p-values are and selected by --cutoff, -b and -r as the block's own; python -m rnacode_amd.decoys turns the two "
@@ -185,8 +204,8 @@ class _Refused(Exception):
 
 
 def _intake(a):
-    """What the options name, checked and read before any context exists: the parameters, the --regions (or None) and the --species-tree
-    (or None)."""
+    """What the options name, checked and read before any context exists: the parameters, the --regions (or None), the --species-tree
+    (or None) and the --windows (or None)."""
     if a.blosum not in (62, 90):
         raise _Refused("Currently only BLOSUM62 and BLOSUM90 are supported.")
     kw = dict(sampleN=a.num_samples, cutoff=a.cutoff, stopEarly=int(a.stop_early), blosum=a.blosum, seed_base=a.seed_base)
@@ -200,7 +219,13 @@ def _intake(a):
         params = api.default_params(**kw)
     except api.RnacodeError as e:
         raise _Refused(f"--genetic-code: {str(e).split(': ', 1)[-1]}")
-    regions = species = None
+    regions = species = wins = None
+    if bool(a.windows) != bool(a.windows_out):
+        raise _Refused("--windows and --windows-out go together")
+    if a.windows_null and not a.windows:
+        raise _Refused("--windows-null needs --windows")
+    if a.windows_summary and not a.windows_null:
+        raise _Refused("--windows-summary needs --windows-null")
     if bool(a.regions) != bool(a.regions_out):
         raise _Refused("--regions and --regions-out go together")
     if a.regions_null and not a.regions:
@@ -229,6 +254,12 @@ def _intake(a):
                 regions = segments.read_regions(fh.readlines())
         except OSError as e:
             raise _Refused(f"--regions: {e}")
+    if a.windows:
+        try:
+            with open(a.windows) as fh:
+                wins = windows.read_windows(fh.readlines())
+        except OSError as e:
+            raise _Refused(f"--windows: {e}")
     if a.species_tree:
         if a.trees:
             raise _Refused("--species-tree and --trees cannot be used together")
@@ -237,7 +268,7 @@ def _intake(a):
                 species = api.SpeciesTree(fh.read())
         except (OSError, api.RnacodeError) as e:
             raise _Refused(f"--species-tree: {str(e).split(': ', 1)[-1]}")
-    return params, regions, species
+    return params, regions, species, wins
 
 
 def _trees(a, ctx, blocks, marshalled, species, n_read: int, read_index: List[int]):
@@ -265,7 +296,7 @@ def _trees(a, ctx, blocks, marshalled, species, n_read: int, read_index: List[in
 
 SIDE_FILES = (("details", details.header), ("track", track.header), ("support", segments.support_header),
               ("regions_out", segments.regions_header), ("regions_support", segments.region_support_header), ("decoys_out", decoys.header),
-              ("shuffle_null_out", shuffle_null.header))   # the option's name in the parsed arguments, its header line
+              ("shuffle_null_out", shuffle_null.header), ("windows_out", windows.header), ("windows_summary", windows.summary_header))   # the option's name in the parsed arguments, its header line
 
 
 class _Ranges:
@@ -295,6 +326,8 @@ class _Run:
     out: IO[str]
     fmt: int
     side: dict                 # the side files that are on: option name -> open file, header written
+    windows_of: dict = field(default_factory=dict)   # --windows: reference row name -> its windows
+    summary: Optional[windows.Summary] = None        # --windows-summary: what the ids have so far
     state: report.ReportState = field(default_factory=report.ReportState)
 
 
@@ -355,6 +388,25 @@ def _list_batch(run: _Run, batch, base: int) -> None:
                     lo, hi = segments.range_of(*at)
                     found.setdefault(i, []).append((reg, at, seg.add(i, reg.strand, lo, hi), nul.add(i, reg.strand, lo, hi) if a.regions_null else -1,
                                                     shf.add(i, reg.strand, lo, hi) if a.regions_shuffle_null is not None else -1))
+    # --windows: the windows that overlap a block, cut to it, with ONE call (rc_batch_window_best, or rc_batch_window_null with --windows-null;
+    # a window is no range of the other calls, and is not shared with them)
+    win_found, win_ranges = {}, []
+    if "windows_out" in side:
+        for i in scored:
+            b = run.blocks[base + i]
+            for w in run.windows_of.get(b.rows[0].name, ()):
+                at = windows.clip(w.strand, w.start, w.end, b.rows[0].start, b.rows[0].length, b.ref_len)
+                if isinstance(at, tuple):
+                    win_found.setdefault(i, []).append((w, at, len(win_ranges)))
+                    win_ranges.append((i, 0 if w.strand == "+" else 1, at[0], at[1]))
+                elif at == windows.NO_CODON:
+                    w.reason = at   # (what the window's stderr line says if no block has a whole codon for it)
+    win_best = win_ge = win_null = None
+    if win_ranges:
+        if a.windows_null:
+            win_best, win_ge, win_null = batch.window_null(win_ranges, matrix=run.summary is not None)
+        else:
+            win_best = batch.window_best(win_ranges)
     paths = batch.backtrack_many(bt.ranges) if bt.ranges else []
     # --track: the tracks of the blocks the listing covers with ONE call (rc_batch_track)
     tracked = dict(zip(scored, batch.track(scored))) if "track" in side and scored else {}
@@ -393,7 +445,7 @@ def _list_batch(run: _Run, batch, base: int) -> None:
         _list_block(run, i, b, all_hss[i], bt, paths, seg, seg_pairs, shuffled.get(i))
         if i in decoyed:
             side["decoys_out"].writelines(decoys.block_lines(run.read_index[base + i], b.rows[0].name, decoyed[i], a.cutoff, a.best_only, a.best_region))
-        if i in tracked or i in found:
+        if i in tracked or i in found or i in win_found:
             rc, mu, lam = batch.getExtremeValuePars(i)
             if i in tracked:
                 side["track"].writelines(track.block_lines(b.rows[0].name, b.rows[0].start, b.rows[0].length, tracked[i], rc, mu, lam, a.cutoff))
@@ -409,12 +461,22 @@ def _list_batch(run: _Run, batch, base: int) -> None:
                         (pair_null_ge[rn], run.params.sampleN) if rn >= 0 else None,
                         (pair_shuffle_ge[rs], a.regions_shuffle_null) if rs >= 0 else None))
                 reg.matched = True
+            for w, (_, _, cut_start, cut_end), k in win_found.get(i, ()):
+                rec = win_best[k]
+                frame, c1, c2 = int(rec["frame"]), (int(rec["opt_b"]) - 1) // 3, (int(rec["opt_i"]) - 3) // 3
+                _, _, sg, eg = track.run_coords(w.strand, frame, c1, c2, b.rows[0].start, b.rows[0].length)
+                p = api.pvalue(float(rec["score"]), mu, lam) if rc == 1 else 99.0
+                side["windows_out"].write(windows.window_line(w, cut_start, cut_end, frame, c1, c2, sg, eg, rec["score"], p, int(rec["cells"]),
+                                                              (win_ge[k], run.params.sampleN) if win_ge is not None else None))
+                if run.summary is not None:
+                    run.summary.add(w.id, rec["score"], win_null[k])
+                w.matched = True
 
 
 def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
     try:
-        params, regions, species = _intake(a)
+        params, regions, species, wins = _intake(a)
     except _Refused as e:
         print(f"ERROR: {e}", file=sys.stderr)
         return 1
@@ -455,10 +517,12 @@ def main(argv=None) -> int:
         for name, header in SIDE_FILES:
             if getattr(a, name):
                 side[name] = files.enter_context(open(getattr(a, name), "w"))
-                side[name].write(header(null=a.regions_null, shuffle=a.regions_shuffle_null is not None) if name in ("regions_out", "regions_support") else header())
+                side[name].write(header(null=a.regions_null, shuffle=a.regions_shuffle_null is not None) if name in ("regions_out", "regions_support") else
+                                 header(null=a.windows_null) if name == "windows_out" else header())
         code = params.genetic_code.decode()
         run = _Run(a, params, code, api.code_tables(a.blosum, code) if a.details else None, blocks, read_index, refused,
-                   segments.by_name(regions) if regions is not None else {}, out, fmt, side)
+                   segments.by_name(regions) if regions is not None else {}, out, fmt, side,
+                   segments.by_name(wins) if wins is not None else {}, windows.Summary(params.sampleN) if a.windows_summary else None)
         # the blocks go through the GPU as a stream of sub-batches (rc_stream_*): while one is being scored the next is prepared
         # on the host threads, and the listing of a finished one is written meanwhile (the reference's loop, RNAcode.c:115-221).
         # Sub-batch sizes: --sub-blocks, or the library's schedule (rc_stream_plan: a small first sub-batch, then doubling, whole rounds
@@ -468,8 +532,12 @@ def main(argv=None) -> int:
             _list_batch(run, batch, base)
             base += batch.n
             batch.close()
+        if run.summary is not None:
+            side["windows_summary"].writelines(run.summary.lines())
     if regions is not None:   # what matched nothing: one line each, the exit status stays 0
         sys.stderr.write("".join(segments.skipped_lines(regions)))
+    if wins is not None:
+        sys.stderr.write("".join(windows.skipped_lines(wins)))
     if fmt == 0:
         report.print_footer(out, n_read, time.perf_counter() - t0, params.sampleN, params.Delta, params.Omega,
                             params.omega, params.stopPenalty_k)

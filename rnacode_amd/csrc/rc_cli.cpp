@@ -39,6 +39,10 @@
 // --regions-support FILE (with --regions): the --support table for named segments, one line per region, scored block that contains it and
 // non-reference row (rc_eps.h, region_support_lines); with --regions-null / --regions-shuffle-null each line ends in that null's count for the
 // row and p_pair = (count + 1) / (n + 1), from rc_batch_segment_null_pairs / rc_batch_segment_shuffle_null_pairs in the plain calls' place.
+// --windows FILE with --windows-out FILE: the best segment inside intervals named in advance (the --regions format, any length, any frame), cut to
+// every scored block that overlaps them -- ONE rc_batch_window_best call per sub-batch; --windows-null: null_ge and p_window behind every line, ONE
+// rc_batch_window_null call in its place (in the sample split one per slice, the counts added); --windows-summary FILE: one line per window id over
+// all its pieces in the run, the null vectors of the pieces joined by sample index (rc_eps.h, win_clip / window_line / WinSummary; windows.py).
 // --regions-shuffle-null N (with --regions): every --regions-out line ends in shuffle_ge, p_segment_shuffled = (shuffle_ge + 1) / (N + 1) and movable,
 // the same test against a null made from the block itself -- the regions' ranges of a sub-batch in N gap-class column shuffles of their blocks,
 // seeds seed_base + n .. (the shuffles of --shuffle-null), in ONE rc_batch_segment_shuffle_null call (in the sample split one slice's batch
@@ -314,7 +318,7 @@ struct SideFile {
   std::string path;
   FILE *f;
 };
-enum { kDetails, kTrack, kSupport, kRegions, kDecoys, kShuffleNull, kRegionSupport, kSides };
+enum { kDetails, kTrack, kSupport, kRegions, kDecoys, kShuffleNull, kRegionSupport, kWindows, kWindowSummary, kSides };
 const char *decoys_header() { return "block\tdecoy\tstrand\tframe\tlength\tfrom\tto\tname\tstart\tend\tscore\tp\n"; }
 const char *shuffle_null_header() { return "hss\tname\tstrand\tframe\tstart\tend\tscore\tp\tp_shuffled\tge\tn\tmovable\n"; }
 
@@ -337,7 +341,8 @@ struct Listing {
   std::string epsDir = "eps";
   SideFile side[kSides] = {{rceps::details_header, "", nullptr}, {rceps::track_header, "", nullptr}, {rceps::support_header, "", nullptr},
                            {rceps::regions_header, "", nullptr}, {decoys_header, "", nullptr}, {shuffle_null_header, "", nullptr},
-                           {rceps::region_support_header, "", nullptr}};
+                           {rceps::region_support_header, "", nullptr}, {rceps::windows_header, "", nullptr},
+                           {rceps::windows_summary_header, "", nullptr}};
   bool on(int s) const { return !side[s].path.empty(); }
   int hitCounter = 0;
 
@@ -439,6 +444,7 @@ void usage() {
   std::fprintf(stderr, "usage: rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]\n"
                        "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null]\n"
                        "                   [--regions-shuffle-null N] [--regions-support FILE]]\n"
+                       "                   [--windows FILE --windows-out FILE [--windows-null [--windows-summary FILE]]]\n"
                        "                   [--decoys K --decoys-out FILE [--decoy-kind simulated|shuffled]] [--shuffle-null N --shuffle-null-out FILE]\n"
                        "                   [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]\n"
                        "                   [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]\n"
@@ -472,6 +478,15 @@ void usage() {
                        "                             without it; with --regions-null also pair_null_ge = how many of the -n null alignments have a\n"
                        "                             pair score at least as high for that sequence, p_pair = (pair_null_ge + 1) / (n + 1); with\n"
                        "                             --regions-shuffle-null N also pair_shuffle_ge and p_pair_shuffled, the same under the N shuffles\n"
+                       "  --windows FILE             find the best segment inside given windows: the --regions format, any length, any frame; a window\n"
+                       "                             is cut to every scored block that overlaps it\n"
+                       "  --windows-out FILE         one line per window and block: id name strand lo hi frame from to start end score p cells -- the cut\n"
+                       "                             window, its best segment of whole codons, the block-wide p, the segments the window holds\n"
+                       "  --windows-null             with --windows: two more columns, null_ge = how many of the -n null alignments hold a segment inside\n"
+                       "                             the same window that scores at least as high, p_window = (null_ge + 1) / (n + 1): the test for a\n"
+                       "                             window named in advance (not for an interval picked around a listed HSS)\n"
+                       "  --windows-summary FILE     with --windows-null: one line per window id over all its pieces in the run (the exons of a\n"
+                       "                             transcript, in whatever blocks they lie): id pieces score null_ge p_window\n"
                        "  --decoys K                 with --decoys-out: list the HSS of K (1..64) null alignments per scored block, simulated as the\n"
                        "                             samples behind the p-values are and selected by -p, -b and -r as the block's own\n"
                        "  --decoys-out FILE          the decoy listing, one line per decoy HSS: block decoy strand frame length from to name start\n"
@@ -495,6 +510,9 @@ struct BlockOut {
   std::vector<Line> lines;     // the HSS that get a line, what goes out beside each attached
   std::string track, regions, decoys;  // its --track / --regions-out / --decoys-out lines
   std::string regionSupport;           // its --regions-support lines
+  std::string windows;                 // its --windows-out lines
+  struct Piece { int window; float score; std::vector<float> null; };
+  std::vector<Piece> pieces;           // --windows-summary: its windows' scores and null vectors, in line order
 };
 
 // results of one sub-batch on their way to the writer
@@ -504,6 +522,8 @@ struct Job {
   std::vector<rc_hss> hss;           // as fetched: block i's are [offs[i], offs[i + 1]); the writer reads the blocks' lines, not these
   std::vector<int64_t> offs;
   std::vector<int> matched;          // the regions (positions in Run::regions) its --regions-out lines belong to
+  std::vector<int> matchedWindows;   // the windows (positions in Run::windows) its --windows-out lines belong to
+  std::vector<int> noCodon;          // ... and those a block overlaps without a whole codon inside
 };
 
 // everything the threads share
@@ -526,6 +546,12 @@ struct Run {
   bool decoysShuffled = false;                            // --decoy-kind shuffled: the block's own columns, permuted within their gap classes, instead
   int regionsShuffleNull = 0;                             // --regions-shuffle-null: shuffles scored per region's block (0: off)
   int shuffleNull = 0;                                    // --shuffle-null: shuffles scored per listed block
+  std::vector<rceps::Region> windows;                     // --windows, in file order
+  std::map<std::string, std::vector<int>> windowsOf;      // reference row name -> the windows that can match a block, in file order
+  std::vector<char> windowMatched;                        // set by the writer
+  bool windowsNull = false;                               // --windows-null: null_ge and p_window behind every --windows-out line
+  rceps::WinSummary winSummary;                           // --windows-summary: what the ids have so far (the writer's)
+  std::vector<std::pair<int, int>> sliceRange;            // the sample split: (first sample, samples) of every slice's batch
   // the writer: one thread, jobs in input order
   std::mutex jm;
   std::condition_variable jcv;
@@ -575,8 +601,12 @@ void writer_thread(Run &R) {
       if (!o.regions.empty()) std::fwrite(o.regions.data(), 1, o.regions.size(), R.list.side[kRegions].f);
       if (!o.regionSupport.empty()) std::fwrite(o.regionSupport.data(), 1, o.regionSupport.size(), R.list.side[kRegionSupport].f);
       if (!o.decoys.empty()) std::fwrite(o.decoys.data(), 1, o.decoys.size(), R.list.side[kDecoys].f);
+      if (!o.windows.empty()) std::fwrite(o.windows.data(), 1, o.windows.size(), R.list.side[kWindows].f);
+      for (const BlockOut::Piece &pc : o.pieces) R.winSummary.add(R.windows[pc.window].id, pc.score, pc.null.data(), static_cast<int>(pc.null.size()));
     }
     for (int r : j->matched) R.regionMatched[r] = 1;
+    for (int r : j->noCodon) if (!R.windowMatched[r]) R.windows[r].reason = rceps::kSegNoCodon;
+    for (int r : j->matchedWindows) R.windowMatched[r] = 1;
     R.tList += now() - t;
   }
 }
@@ -819,6 +849,71 @@ bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std
   return true;
 }
 
+// --windows for every block the listing covers, while the batch is alive: the windows that overlap a block, cut to it (rc_eps.h, win_clip), in
+// ONE rc_batch_window_best call, or with --windows-null ONE rc_batch_window_null call; where the samples were split over several batches, one
+// call per batch, the counts added and -- for --windows-summary -- the null vectors joined by sample index.
+bool add_windows(const Run &R, rc_batch *b, Job &j, std::string &err, const std::vector<EvdFit> *fits, const std::vector<rc_batch *> *slices) {
+  struct Found { int blk, window; rceps::WinClip at; };
+  std::vector<Found> found;
+  std::vector<rc_bt_range> wins;
+  for (int i = 0; i < static_cast<int>(j.blocks.size()); i++) {
+    const Block &blk = R.blocks[j.blocks[i].index];
+    if (!scored(R, j.blocks[i])) continue;
+    const auto it = R.windowsOf.find(std::string(blk.rows[0].name));
+    if (it == R.windowsOf.end()) continue;
+    long long L = 0;
+    for (char c : blk.rows[0].seq) L += c != '-';
+    for (int r : it->second) {
+      const rceps::Region &g = R.windows[r];
+      rceps::WinClip at;
+      const rceps::SegReason why = rceps::win_clip(g.strand, g.start, g.end, blk.rows[0].start, blk.rows[0].length, L, at);
+      if (why == rceps::kSegNoCodon) j.noCodon.push_back(r);
+      if (why != rceps::kSegOk) continue;
+      found.push_back(Found{i, r, at});
+      wins.push_back(rc_bt_range{i, g.strand == '+' ? 0 : 1, at.lo, at.hi});
+    }
+  }
+  const int nw = static_cast<int>(wins.size()), n = R.par.sampleN;
+  if (!nw) return true;
+  std::vector<float> score(nw);
+  std::vector<int32_t> frame(nw), optB(nw), optI(nw), ge(nw, 0);
+  std::vector<int64_t> cells(nw);
+  const bool keep = R.list.on(kWindowSummary);
+  std::vector<float> nullAll(keep ? static_cast<size_t>(nw) * n : 0);
+  if (!R.windowsNull) {
+    if (rc_batch_window_best(b, wins.data(), nw, score.data(), frame.data(), optB.data(), optI.data(), cells.data()) != RC_OK) { err = rc_last_error(); return false; }
+  } else if (!slices) {
+    if (rc_batch_window_null(b, wins.data(), nw, score.data(), frame.data(), optB.data(), optI.data(), cells.data(), ge.data(), keep ? nullAll.data() : nullptr,
+                             static_cast<int64_t>(nullAll.size())) != RC_OK) { err = rc_last_error(); return false; }
+  } else {
+    for (size_t g = 0; g < slices->size(); g++) {
+      rc_batch *sb = (*slices)[g];
+      if (!sb) continue;
+      const int lo = R.sliceRange[g].first, w = R.sliceRange[g].second;
+      std::vector<int32_t> part(nw);
+      std::vector<float> mat(keep ? static_cast<size_t>(nw) * w : 0);
+      if (rc_batch_window_null(sb, wins.data(), nw, score.data(), frame.data(), optB.data(), optI.data(), cells.data(), part.data(), keep ? mat.data() : nullptr,
+                               static_cast<int64_t>(mat.size())) != RC_OK) { err = rc_last_error(); return false; }
+      for (int k = 0; k < nw; k++) ge[k] += part[k];
+      if (keep)
+        for (int k = 0; k < nw; k++)
+          for (int s = 0; s < w && lo + s < n; s++) nullAll[static_cast<size_t>(k) * n + lo + s] = mat[static_cast<size_t>(k) * w + s];
+    }
+  }
+  for (int k = 0; k < nw; k++) {
+    const Found &f = found[k];
+    EvdFit fit;
+    if (!fit_of(b, fits, f.blk, fit, err)) return false;
+    const float p = fit.rc == 1 ? rc_pvalue(score[k], fit.mu, fit.lambda) : 99.0f;
+    const Block &blk = R.blocks[j.blocks[f.blk].index];
+    j.blocks[f.blk].windows += rceps::window_line(R.windows[f.window], f.at, frame[k], optB[k], optI[k], blk.rows[0].start, blk.rows[0].length, score[k], p, cells[k],
+                                                  R.windowsNull ? ge[k] : -1, n);
+    if (keep) j.blocks[f.blk].pieces.push_back(BlockOut::Piece{f.window, score[k], std::vector<float>(nullAll.begin() + static_cast<size_t>(k) * n, nullAll.begin() + static_cast<size_t>(k + 1) * n)});
+    j.matchedWindows.push_back(f.window);
+  }
+  return true;
+}
+
 // --decoys for every block the listing covers, while the batch is alive: ONE rc_batch_decoys (--decoy-kind shuffled: rc_batch_decoys_shuffled) call (a second one only where the lists are longer
 // than the first one's room), seeds seed_base + n ..: the first the fit did not see, n the run's whole sample count.  Each decoy's HSS are
 // arranged as the block's own are; where the caller made the fits itself (the sample split) the p-values are theirs.
@@ -934,6 +1029,7 @@ bool deliver(Run &R, rc_batch *b, std::unique_ptr<Job> j, std::string &err, cons
   if ((R.list.eps || R.list.on(kDetails)) && !annotate(R, b, *j, err)) return false;
   if (R.list.on(kTrack) && !add_track(R, b, *j, err, fits)) return false;
   if ((R.list.on(kSupport) || R.list.on(kRegions)) && !add_segments(R, b, *j, err, fits, slices)) return false;
+  if (R.list.on(kWindows) && !add_windows(R, b, *j, err, fits, slices)) return false;
   if (R.list.on(kDecoys) && !add_decoys(R, b, *j, err, fits)) return false;
   if (R.list.on(kShuffleNull) && !add_shuffle_null(R, b, *j, err)) return false;
   post(R, std::move(j));
@@ -1107,6 +1203,8 @@ bool run_sample_split(Run &R, std::vector<Worker> &W, std::string &err) {
   }
   for (auto &t : th) t.join();
   for (int g = 0; g < G; g++) if (!werr[g].empty()) { err = werr[g]; return false; }
+  R.sliceRange.clear();
+  for (int g = 0; g < G; g++) R.sliceRange.emplace_back(lo[g], std::max(1, hi[g] - lo[g]));
   // the native HSS lists are the same on every GPU: the first one's, with p-values from the fit of the gathered row
   std::unique_ptr<Job> j = fetch(batch[0], 0, all.data(), err);
   if (!j) return false;
@@ -1153,7 +1251,7 @@ int main(int argc, char **argv) {
   rc_default_params(&R.par);
   rc_params &par = R.par;
   Listing &list = R.list;
-  std::string file, outfile, trees, limit, devicesArg, speciesFile, writeTrees, regionsFile;
+  std::string file, outfile, trees, limit, devicesArg, speciesFile, writeTrees, regionsFile, windowsFile;
   int device = 0, subBlocks = 0, gpus = 1;   // subBlocks 0: the library's schedule
   bool dumpBlocks = false, decoysGiven = false, decoyKindGiven = false, shuffleNullGiven = false, regionsShuffleGiven = false;
   std::string decoyKind;
@@ -1209,6 +1307,10 @@ int main(int argc, char **argv) {
     else if (o == "--regions-out") list.side[kRegions].path = val();
     else if (o == "--regions-support") list.side[kRegionSupport].path = val();
     else if (o == "--regions-null") R.regionsNull = true;
+    else if (o == "--windows") windowsFile = val();
+    else if (o == "--windows-out") list.side[kWindows].path = val();
+    else if (o == "--windows-null") R.windowsNull = true;
+    else if (o == "--windows-summary") list.side[kWindowSummary].path = val();
     else if (o == "--regions-shuffle-null") { regionsShuffleGiven = true; R.regionsShuffleNull = std::atoi(val()); }
     else if (o == "--decoys") { decoysGiven = true; R.decoys = std::atoi(val()); }
     else if (o == "--decoys-out") list.side[kDecoys].path = val();
@@ -1224,6 +1326,10 @@ int main(int argc, char **argv) {
     if (rc_code_tables_for(&par, pep, matrix) != RC_OK) die("--genetic-code: " + std::string(rc_last_error()));
   }
   if (!regionsFile.empty() != list.on(kRegions)) die("--regions and --regions-out go together");   // before any context exists
+  if (!windowsFile.empty() != list.on(kWindows)) die("--windows and --windows-out go together");
+  if (R.windowsNull && windowsFile.empty()) die("--windows-null needs --windows");
+  if (list.on(kWindowSummary) && !R.windowsNull) die("--windows-summary needs --windows-null");
+  if (R.windowsNull) list.side[kWindows].header = rceps::windows_header_null;
   if (R.regionsNull && regionsFile.empty()) die("--regions-null needs --regions");
   if (regionsShuffleGiven && regionsFile.empty()) die("--regions-shuffle-null needs --regions");
   if (list.on(kRegionSupport) && regionsFile.empty()) die("--regions-support needs --regions");
@@ -1239,6 +1345,15 @@ int main(int argc, char **argv) {
   R.decoysShuffled = decoyKind == "shuffled";
   if (shuffleNullGiven != list.on(kShuffleNull)) die("--shuffle-null and --shuffle-null-out go together");
   if (shuffleNullGiven && (R.shuffleNull < 1 || R.shuffleNull > 65536)) die("--shuffle-null takes a number of shuffles from 1 to 65536");
+  if (!windowsFile.empty()) {
+    std::ifstream in(windowsFile, std::ios::binary);
+    if (!in) die("--windows: could not open " + windowsFile);
+    std::stringstream ss;
+    ss << in.rdbuf();
+    R.windows = rceps::regions_read(ss.str(), true);
+    R.windowMatched.assign(R.windows.size(), 0);
+    for (size_t r = 0; r < R.windows.size(); r++) if (R.windows[r].reason == rceps::kSegOk) R.windowsOf[R.windows[r].name].push_back(static_cast<int>(r));
+  }
   if (!regionsFile.empty()) {
     std::ifstream in(regionsFile, std::ios::binary);
     if (!in) die("--regions: could not open " + regionsFile);
@@ -1462,9 +1577,15 @@ int main(int argc, char **argv) {
   // context) takes longer than the operating system needs to reclaim the process, so a driver that is done leaves at once
   // (RC_CLI_TEARDOWN=1: the orderly way, for leak checkers).
   if (list.out != stdout) std::fclose(list.out);
+  if (list.on(kWindowSummary)) {   // one line per id over all its pieces in the run
+    const std::string text = R.winSummary.lines(par.sampleN);
+    std::fwrite(text.data(), 1, text.size(), list.side[kWindowSummary].f);
+  }
   for (SideFile &sf : list.side) if (sf.f && std::fclose(sf.f) != 0) die("Could not write " + sf.path);
   for (size_t r = 0; r < R.regions.size(); r++)   // what matched nothing: one line each, the exit status stays 0
     if (!R.regionMatched[r]) std::fputs(rceps::region_skipped(R.regions[r]).c_str(), stderr);
+  for (size_t r = 0; r < R.windows.size(); r++)
+    if (!R.windowMatched[r]) std::fputs(rceps::region_skipped(R.windows[r]).c_str(), stderr);
   std::fflush(stdout);
   std::fflush(stderr);
   if (!std::getenv("RC_CLI_TEARDOWN")) {

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <algorithm>
 #include <functional>
+#include <map>
 #include <set>
 #include <string>
 #include <tuple>
@@ -331,7 +332,7 @@ inline void track_block(std::string &out, const std::string &refName, int refSta
 
 // --support / --regions: scores of given segments with their per-row pair scores (rc_batch_segment_scores).  Same rules and bytes as
 // rnacode_amd/segments.py, which documents them.
-enum SegReason { kSegOk = 0, kSegMalformed, kSegBadLength, kSegOutside, kSegPastLastCodon };
+enum SegReason { kSegOk = 0, kSegMalformed, kSegBadLength, kSegOutside, kSegPastLastCodon, kSegNoCodon };
 struct SegLoc { int frame, c1, c2; };
 // the inverse of an HSS's coordinates (rc_results.cpp, score.c:921-936): the frame and codons whose segment the listing prints as start..end
 inline SegReason seg_locate(char strand, long long start, long long end, long long refStart, long long refLength, long long L, SegLoc &out) {
@@ -356,7 +357,8 @@ inline bool seg_int(const std::string &s, long long &v) {
   return true;
 }
 // the regions of a --regions file's text, in file order; a malformed line and a length that is no multiple of three keep their reason
-inline std::vector<Region> regions_read(const std::string &text) {
+// (windows: the text of a --windows file -- the same lines, any length, ids `window<line number>`)
+inline std::vector<Region> regions_read(const std::string &text, bool windows = false) {
   std::vector<Region> out;
   int n = 0;
   for (size_t at = 0; at < text.size();) {
@@ -377,14 +379,14 @@ inline std::vector<Region> regions_read(const std::string &text) {
     if (n == 1 && f[0] == "name") continue;
     Region r;
     r.line = n;
-    r.id = (f.size() > 4 && !f[4].empty()) ? f[4] : "region" + std::to_string(n);
+    r.id = (f.size() > 4 && !f[4].empty()) ? f[4] : (windows ? "window" : "region") + std::to_string(n);
     if (f.size() < 4 || f[0].empty() || (f[1] != "+" && f[1] != "-") || !seg_int(f[2], r.start) || !seg_int(f[3], r.end) || r.end < r.start) {
       r.reason = kSegMalformed;
       out.push_back(r);
       continue;
     }
     r.name = f[0]; r.strand = f[1][0];
-    if ((r.end - r.start + 1) % 3 != 0) r.reason = kSegBadLength;
+    if (!windows && (r.end - r.start + 1) % 3 != 0) r.reason = kSegBadLength;
     out.push_back(r);
   }
   return out;
@@ -392,7 +394,8 @@ inline std::vector<Region> regions_read(const std::string &text) {
 inline std::string region_skipped(const Region &r) {
   std::string out;
   put(out, "Skipping region %s (line %i): %s\n", r.id.c_str(), r.line,
-      r.reason == kSegMalformed ? "malformed line" : r.reason == kSegBadLength ? "length not a multiple of three" : "no scored alignment block contains it");
+      r.reason == kSegMalformed ? "malformed line" : r.reason == kSegBadLength ? "length not a multiple of three" :
+      r.reason == kSegNoCodon ? "no whole codon inside" : "no scored alignment block contains it");
   return out;
 }
 // %.3f; a NaN is `nan` whatever its sign (printf may write -nan)
@@ -454,6 +457,88 @@ inline std::string region_line(const Region &r, const SegLoc &at, float score, f
   out += "\n";
   return out;
 }
+
+// --windows: the best segment inside named windows and its own null (rc_batch_window_best / rc_batch_window_null).  Same rules and bytes as
+// rnacode_amd/windows.py, which documents them.
+struct WinClip { int lo, hi; long long cutStart, cutEnd; };
+// the cells of the window lo..hi (1-based positions of a row of L): per frame the segments with 3 a + f + 1 >= lo and 3 j + f + 3 <= min(hi, L)
+inline long long win_cells(long long L, long long lo, long long hi) {
+  const long long top = hi < L ? hi : L;
+  long long cells = 0;
+  for (int f = 0; f < 3; f++) {
+    const long long a = lo - f - 1 <= 0 ? 0 : (lo - f - 1 + 2) / 3, j = top - f - 3 < 0 ? -1 : (top - f - 3) / 3;
+    if (j >= a) cells += (j - a + 1) * (j - a + 2) / 2;
+  }
+  return cells;
+}
+// seg_locate's arithmetic without the codon rule: the window in the strand's own row, cut to the block, and the cut window in the coordinates
+// start / end came in; kSegOutside: no overlap, kSegNoCodon: no whole codon inside what is left
+inline SegReason win_clip(char strand, long long start, long long end, long long refStart, long long refLength, long long L, WinClip &out) {
+  long long first, last, size, top = 0;
+  const bool plain = refStart == 0 && refLength == 0;
+  if (plain) { first = start - 1; last = end - 1; size = L; }
+  else if (strand == '+') { first = start - refStart; last = end - refStart; size = refLength; }
+  else { top = refStart + refLength - 1; first = top - end; last = top - start; size = refLength; }
+  if (size > L) size = L;
+  if (last < 0 || first >= size || last < first) return kSegOutside;
+  if (first < 0) first = 0;
+  if (last > size - 1) last = size - 1;
+  if (win_cells(L, first + 1, last + 1) == 0) return kSegNoCodon;
+  out.lo = static_cast<int>(first + 1); out.hi = static_cast<int>(last + 1);
+  if (plain) { out.cutStart = first + 1; out.cutEnd = last + 1; }
+  else if (strand == '+') { out.cutStart = refStart + first; out.cutEnd = refStart + last; }
+  else { out.cutStart = top - last; out.cutEnd = top - first; }
+  return kSegOk;
+}
+inline const char *windows_header() { return "id\tname\tstrand\tlo\thi\tframe\tfrom\tto\tstart\tend\tscore\tp\tcells\n"; }
+inline const char *windows_header_null() { return "id\tname\tstrand\tlo\thi\tframe\tfrom\tto\tstart\tend\tscore\tp\tcells\tnull_ge\tp_window\n"; }   // --windows-null
+inline const char *windows_summary_header() { return "id\tpieces\tscore\tnull_ge\tp_window\n"; }
+// frame, optB, optI: the best segment (rc_batch_window_best); ge >= 0 (--windows-null): null_ge and (ge + 1) / (n + 1) behind the line
+inline std::string window_line(const Region &w, const WinClip &at, int frame, int optB, int optI, int refStart, int refLength, float score, float p,
+                               long long cells, int ge = -1, int n = 0) {
+  const int c1 = (optB - 1) / 3, c2 = (optI - 3) / 3;
+  long long sg = optB, eg = optI;   // what ClustalW input (no coordinates) lists
+  if (!(refStart == 0 && refLength == 0)) {
+    if (w.strand == '+') { sg = refStart + c1 * 3 + frame; eg = refStart + c2 * 3 + frame + 2; }
+    else { eg = (refStart + refLength - 1) - c1 * 3 - frame; sg = (refStart + refLength - 1) - c2 * 3 - frame - 2; }
+  }
+  std::string out;
+  char pe[64];
+  if (p != p) std::snprintf(pe, sizeof pe, "nan"); else std::snprintf(pe, sizeof pe, "%.3e", static_cast<double>(p));
+  put(out, "%s\t%s\t%c\t%lld\t%lld\t%i\t%i\t%i\t%lld\t%lld\t%s\t%s\t%lld", w.id.c_str(), w.name.c_str(), w.strand, at.cutStart, at.cutEnd, frame + 1, c1 + 1, c2 + 1,
+      sg, eg, fmt3(score).c_str(), pe, cells);
+  if (ge >= 0) {
+    if (score != score) put(out, "\t%i\tnan", ge);
+    else put(out, "\t%i\t%.3e", ge, (ge + 1.0) / (n + 1.0));
+  }
+  out += "\n";
+  return out;
+}
+// --windows-summary: per id the pieces met so far, the fmax of their scores and the element-wise fmax of their null vectors (windows.Summary)
+struct WinSummary {
+  struct Rec { std::string id; int pieces; float score; std::vector<float> vec; };
+  std::vector<Rec> recs;   // in order of first appearance
+  std::map<std::string, size_t> at;
+  void add(const std::string &id, float score, const float *null, int n) {
+    const auto it = at.find(id);
+    if (it == at.end()) { at[id] = recs.size(); recs.push_back(Rec{id, 1, score, std::vector<float>(null, null + n)}); return; }
+    Rec &r = recs[it->second];
+    r.pieces++;
+    r.score = std::fmax(r.score, score);
+    for (int s = 0; s < n; s++) r.vec[static_cast<size_t>(s)] = std::fmax(r.vec[static_cast<size_t>(s)], null[s]);
+  }
+  std::string lines(int n) const {
+    std::string out;
+    for (const Rec &r : recs) {
+      int ge = 0;
+      for (float v : r.vec) ge += v >= r.score;
+      put(out, "%s\t%i\t%s", r.id.c_str(), r.pieces, fmt3(r.score).c_str());
+      if (r.score != r.score) put(out, "\t%i\tnan\n", ge);
+      else put(out, "\t%i\t%.3e\n", ge, (ge + 1.0) / (n + 1.0));
+    }
+    return out;
+  }
+};
 
 // --regions-support: the --support table for named segments, one line per region, scored block that contains it and non-reference row;
 // behind it --regions-null's pair of columns, then --regions-shuffle-null's (segments.py, region_support_lines)

@@ -293,6 +293,48 @@ struct SegPairArgs {
   float *pairNull;            // [nItems][n], or null
 };
 void launch_segment_null_pairs(const SegNullArgs &a, const SegPairArgs &pa, hipStream_t stream);   // k_segment_null_pairs, the same grid
+// rc_batch_window_best / rc_batch_window_null (rc_window_null.hip).  A window's cells per frame f are the triangle aLo[f] <= a <= j <= jHi[f]
+// of that strand's S (rc_window_plan.h; jHi < aLo: none).
+struct WinBox { int32_t blk, strand, aLo[3], jHi[3]; };
+// k_window_best: one wavefront per window; score[w] the fmaxf of the window's cells in the block itself (NaN where every cell is NaN),
+// pos[3 w ..] = (frame, a, j) of the first cell, in the order frame, a, j ascending, with that value (the window's first cell where NaN).
+struct WinBestArgs {
+  const uint8_t *blob;
+  const DevBlock *dblocks;
+  const uint32_t *flags;      // per batch index: kFlagNan picks the reference's MAX macro
+  const WinBox *boxes;        // [nWindows]
+  float *score;               // [nWindows]
+  int32_t *pos;               // [nWindows][3]
+  int nWindows;
+};
+void launch_window_best(const WinBestArgs &a, hipStream_t stream);
+// k_window_null's unit of work: the rows [aBeg, aEnd) of one frame of one window, each walked to jHi, in the codes of position `pos` of the
+// round's blocks; with the sample group g it owns the 64 floats at partial + (slot * groups + g) * 64, the maximum of its cells per sample.
+struct WinItem { int32_t pos, strand, frame, aBeg, aEnd, jHi, slot, pad; };
+// k_window_fold's: window w's value is the fmaxf of the slots [slotBeg, slotEnd)
+struct WinFold { int32_t w, slotBeg, slotEnd, pad; };
+constexpr int kWinTile = 8;         // end codons of a tile: two code words, aligned to them
+constexpr int kWinLdsMaxNK = 21;    // rounds whose blocks have up to this many rows besides the reference park the states in LDS (16 KB a workgroup)
+constexpr size_t win_park_floats(int NK) { return static_cast<size_t>(3) * NK * kWave; }   // [3 k + state][lane]
+struct WinNullArgs {
+  const uint8_t *blob;
+  const DevBlock *dblocks;
+  const uint32_t *flags;      // per batch index: kFlagNan picks the reference's MAX macro
+  const int *blocks;          // [nBlocks] batch indices of the round
+  const WinItem *items;       // [nItems] of the round
+  const WinFold *folds;       // [nFolds] of the round
+  const float *scores;        // [nWindows] k_window_best's
+  int *ge;                    // [nWindows] += samples whose value is >= scores[w]
+  float *nullOut;             // [nWindows][sampleN], or null
+  float *partial;             // [slots of the round][groups][64]
+  float *scratch;             // null: the states are parked in LDS; else workgroup x parkStride floats
+  size_t parkStride;
+  const uint8_t *codesAll;
+  size_t codesStride;
+  int nItems, nFolds, groups, sampleN;
+};
+// k_window_null on `grid` workgroups of one wavefront, which stride over the nItems x groups units, then k_window_fold on nFolds x groups
+void launch_window_null(const WinNullArgs &a, int grid, size_t ldsBytes, hipStream_t stream);
 // rc_batch_decoys (rc_decoys.hip): the codes k_generic_sim<false> has left at codesAll for a round of blocks (position p of `blocks`: one item
 // of one sample group, lane = decoy, at p * codesStride) expanded into native-format sigma tables f32 [2][NK][L + 1], decoy d of position p at
 // sigmaAll + (p * nDecoys + d) * sigmaStride.  vblocks / vflags [p * nDecoys + d]: the block's header with off_sigma aimed at that table, and

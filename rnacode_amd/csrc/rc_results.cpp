@@ -1,9 +1,10 @@
-// rc_results.cpp -- what a finished batch holds: statuses, models, maxima, fits, HSS tables, native S matrices, backtrack paths, per-codon tracks, segment scores and their null distributions.
+// rc_results.cpp -- what a finished batch holds: statuses, models, maxima, fits, HSS tables, native S matrices, backtrack paths, per-codon tracks, segment scores and their null distributions, named windows.
 #include "rc_runtime.h"
 #include "rc_decoy_plan.h"
 #include "rc_segnull_plan.h"
 #include "rc_shuffle_plan.h"
 #include "rc_shuffle_null_plan.h"
+#include "rc_window_plan.h"
 
 extern "C" {
 
@@ -703,6 +704,186 @@ int rc_batch_segment_null_pairs(const rc_batch *b, const rc_bt_range *ranges, in
                                 int32_t *pair_ge_out, int64_t cap, int64_t *offsets, float *pair_null_out, int64_t null_cap) {
   const SegPairsOut po{pair_out, pair_ge_out, cap, offsets, pair_null_out, null_cap};
   return segment_null_call(b, ranges, n_ranges, score_out, ge_out, nullptr, 0, &po);
+}
+
+// The best segment inside named windows and its own null (rc_window_null.hip).  A window's cells are the triangles of rc_window_plan.h; the
+// block's own value and position come from k_window_best on the native sigma tables.  The null side is rc_batch_segment_null's call with
+// k_window_null / k_window_fold in k_segment_null's place: the windows grouped by block, the distinct blocks in rounds under the same budget
+// (rc_segnull_plan.h), per round k_generic_sim<false> then the window kernels; a window is cut into chunks of rows (rc_window_plan.h), the
+// round's chunks x sample groups are the units the grid strides over.  Nothing of the batch is written.
+struct WinOuts {
+  float *score;
+  int32_t *frame, *opt_b, *opt_i;
+  int64_t *cells;
+  int32_t *ge;      // the null side: rc_batch_window_null only
+  float *null;
+  int64_t cap;
+};
+static_assert(sizeof(WinItem) == 8 * sizeof(int32_t) && sizeof(WinFold) == 4 * sizeof(int32_t) && sizeof(WinBox) == 8 * sizeof(int32_t), "packed as int32 words");
+
+static int window_call(const rc_batch *bc, const rc_bt_range *windows, int32_t n_windows, const WinOuts &o, bool withNull) {
+  rc_batch *b = const_cast<rc_batch *>(bc);
+  if (!b || n_windows < 0 || (n_windows > 0 && (!windows || !o.score || (withNull && !o.ge)))) return fail(RC_ERR_ARG, "bad argument");
+  if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
+  const int sampleN = b->par.sampleN, groups = (sampleN + kWave - 1) / kWave, Spad = groups * kWave;
+  if (withNull && o.null && o.cap < static_cast<int64_t>(n_windows) * sampleN)
+    return fail(RC_ERR_ARG, "null_out too small: " + std::to_string(static_cast<int64_t>(n_windows) * sampleN) + " values");
+  // every window is checked, and the plan made, before anything touches the device (or the caller's arrays)
+  const size_t nw = static_cast<size_t>(n_windows);
+  std::vector<WinBox> boxes(nw);
+  std::vector<WinGeom> geom(nw);
+  for (int w = 0; w < n_windows; w++) {
+    const rc_bt_range &g = windows[w];
+    const std::string who = "window " + std::to_string(w);
+    if (g.blk < 0 || g.blk >= b->n) return fail(RC_ERR_ARG, who + ": block index out of range");
+    const BlockMeta &h = b->meta[g.blk];
+    if (h.status != RC_OK) { g_err = who + ": the block was not scored"; return h.status; }
+    if (g.strand < 0 || g.strand > 1 || g.opt_b < 1 || g.opt_i < g.opt_b || g.opt_i - g.opt_b < 2) return fail(RC_ERR_ARG, who + ": bad window");
+    geom[w] = window_geom(h.L, g.opt_b, g.opt_i);
+    if (geom[w].cells == 0) return fail(RC_ERR_ARG, who + ": no whole codon inside");
+    if (geom[w].cells > static_cast<long long>(UINT32_MAX) - 1) return fail(RC_ERR_ARG, who + ": more than 2^32 - 2 cells");
+    boxes[w].blk = g.blk; boxes[w].strand = g.strand;
+    for (int f = 0; f < 3; f++) { boxes[w].aLo[f] = geom[w].aLo[f]; boxes[w].jHi[f] = geom[w].jHi[f]; }
+  }
+  if (n_windows == 0) return RC_OK;
+  rc_ctx *c = b->ctx;
+  // the null side's plan: the windows by block, the blocks in rounds, per round the items (chunks of rows) and the folds (windows)
+  struct Round { size_t item0, nItems, fold0, nFolds, slots; int maxNK, maxN, maxNodes, grid; bool lds; };
+  SegNullPlan pl;
+  std::vector<WinItem> items;
+  std::vector<WinFold> folds;
+  std::vector<Round> rounds;
+  size_t codesNeed = 0, partialNeed = 0, scratchNeed = 0;
+  if (withNull) {
+    size_t budget = kSegNullMaxBytes;
+    if (const char *e = std::getenv("RC_SEGNULL_MAX_BYTES")) budget = static_cast<size_t>(std::max(1ll, std::atoll(e)));
+    const auto codes_bytes = [&](int blk) { return null_generic_codes_bytes(b->meta[blk].N, b->meta[blk].L, b->db[blk].nnodes); };
+    pl = seg_null_plan(n_windows, [&](int r) { return windows[r].blk; }, codes_bytes, groups, budget);
+    for (int blk : pl.blocks) RC_TRY(check_codes_layout(b, blk));
+    for (const SegNullRound &rd : pl.rounds) {
+      if (static_cast<size_t>(rd.count) * groups > static_cast<size_t>(INT32_MAX)) return fail(RC_ERR_ARG, "more than 2^31 - 1 (block, sample group) items in one round");
+      Round R{items.size(), 0, folds.size(), 0, 0, 0, 0, 0, 0, false};
+      for (int p = rd.first; p < rd.first + rd.count; p++) {
+        const int blk = pl.blocks[p];
+        R.maxNK = std::max(R.maxNK, b->meta[blk].NK); R.maxN = std::max(R.maxN, b->meta[blk].N); R.maxNodes = std::max(R.maxNodes, b->db[blk].nnodes);
+        for (int q = pl.blkStart[p]; q < pl.blkStart[p + 1]; q++) {
+          const int w = pl.rangeIdx[q];
+          const size_t slot0 = R.slots;
+          window_chunks(geom[w], kWindowChunkCells, [&](int f, int aBeg, int aEnd, int jHi) {
+            items.push_back(WinItem{p - rd.first, windows[w].strand, f, aBeg, aEnd, jHi, static_cast<int32_t>(R.slots++), 0});
+          });
+          folds.push_back(WinFold{w, static_cast<int32_t>(slot0), static_cast<int32_t>(R.slots), 0});
+        }
+      }
+      R.nItems = items.size() - R.item0; R.nFolds = folds.size() - R.fold0;
+      if (R.slots * groups > static_cast<size_t>(INT32_MAX)) return fail(RC_ERR_ARG, "more than 2^31 - 1 (chunk of a window, sample group) units in one round");
+      R.lds = R.maxNK <= kWinLdsMaxNK;
+      R.grid = static_cast<int>(std::min<size_t>(R.nItems * groups, R.lds ? 16384 : 2048));
+      codesNeed = std::max(codesNeed, static_cast<size_t>(rd.count) * groups * rd.stride);
+      partialNeed = std::max(partialNeed, R.slots * groups * kWave * sizeof(float));
+      if (!R.lds) scratchNeed = std::max(scratchNeed, static_cast<size_t>(R.grid) * win_park_floats(R.maxNK) * sizeof(float));
+      rounds.push_back(R);
+    }
+  }
+  // one upload: the boxes, then (the null side) the distinct blocks, the items, the folds
+  const size_t nb = pl.blocks.size();
+  const size_t oBoxes = 0, oBlocks = oBoxes + 8 * nw, oItems = oBlocks + nb, oFolds = oItems + 8 * items.size(), upWords = oFolds + 4 * folds.size();
+  std::vector<int32_t> up(upWords);
+  std::memcpy(up.data() + oBoxes, boxes.data(), nw * sizeof(WinBox));
+  if (nb) std::memcpy(up.data() + oBlocks, pl.blocks.data(), nb * sizeof(int32_t));
+  if (!items.empty()) std::memcpy(up.data() + oItems, items.data(), items.size() * sizeof(WinItem));
+  if (!folds.empty()) std::memcpy(up.data() + oFolds, folds.data(), folds.size() * sizeof(WinFold));
+  std::vector<float> score(nw);
+  std::vector<int32_t> pos(3 * nw), ge(nw);
+  HIP_TRY(hipSetDevice(c->device));
+  RC_STREAM_TRY(st, stream_aux(c));
+  HIP_TRY(hipEventSynchronize(b->evPrep));   // the tables of the blob are made on the device
+  DevBuf d_up, d_best, d_ge, d_cnt, d_codes, d_null, d_partial, d_scratch;
+  adopt_bufs(c, {&d_up, &d_best, &d_ge, &d_cnt, &d_codes, &d_null, &d_partial, &d_scratch});
+  const uint8_t *blob = b->dblob.as<uint8_t>();
+  constexpr size_t kCntWords = 16;   // the simulation's eight work queues, then (8-aligned) its clamp count: this call's own, read by nobody
+  bool launched = false;
+  // (a lambda: whatever fails in it, nothing returns to the caller -- who owns the outputs, while the vectors and the buffers die with this
+  // frame -- before the work already queued on the stream has drained)
+  const int rc = [&]() -> int {
+    HIP_TRY(d_up.ensure(up.size() * sizeof(int32_t)));
+    HIP_TRY(d_best.ensure(4 * nw * sizeof(float)));   // the scores, then the positions
+    if (withNull) {
+      HIP_TRY(d_ge.ensure(nw * sizeof(int32_t)));
+      HIP_TRY(d_cnt.ensure(kCntWords * sizeof(uint32_t)));
+      HIP_TRY(d_codes.ensure(codesNeed));
+      HIP_TRY(d_partial.ensure(std::max<size_t>(partialNeed, 4)));
+      if (scratchNeed) HIP_TRY(d_scratch.ensure(scratchNeed));
+      if (o.null) HIP_TRY(d_null.ensure(nw * static_cast<size_t>(sampleN) * sizeof(float)));
+    }
+    launched = true;   // from here on something may be in flight
+    if (withNull) {
+      // the MT19937 streams of the batch's seeds: the context's cache, or regenerated as a run does (the batch's own record of it stays)
+      const bool mtLaunched = b->mtLaunched;
+      const int mt = ensure_mt_stream(c, b, st, b->par.seed_base, Spad, b->maxDraws);
+      b->mtLaunched = mtLaunched;
+      RC_TRY(mt);
+    }
+    HIP_TRY(hipMemcpyAsync(d_up.p, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    WinBestArgs wb{};
+    wb.blob = blob; wb.dblocks = reinterpret_cast<const DevBlock *>(blob + b->oDblocks); wb.flags = b->dflags.as<uint32_t>();
+    wb.boxes = reinterpret_cast<const WinBox *>(d_up.as<int>() + oBoxes);
+    wb.score = d_best.as<float>(); wb.pos = reinterpret_cast<int32_t *>(d_best.as<float>() + nw); wb.nWindows = n_windows;
+    launch_window_best(wb, st);
+    HIP_TRY(hipGetLastError());
+    if (withNull) {
+      HIP_TRY(hipMemsetAsync(d_ge.p, 0, nw * sizeof(int32_t), st));
+      NullArgs sim{};
+      sim.blob = blob; sim.dblocks = wb.dblocks; sim.flags = wb.flags;
+      sim.gLo = 0; sim.gHi = groups; sim.sampleN = sampleN; sim.Spad = Spad;   // every sample, whatever --stop-early cut from the run (skipMask 0)
+      sim.U = c->d_U; sim.pair = b->tables->ptrs.pair; sim.tieThr = c->tieThr;
+      sim.workCounter = d_cnt.as<unsigned int>(); sim.clampCount = reinterpret_cast<unsigned long long *>(d_cnt.as<uint32_t>() + 8);
+      sim.codesAll = d_codes.as<uint8_t>();
+      WinNullArgs wn{};
+      wn.blob = blob; wn.dblocks = wb.dblocks; wn.flags = wb.flags;
+      wn.scores = wb.score; wn.ge = d_ge.as<int>(); wn.nullOut = o.null ? d_null.as<float>() : nullptr;
+      wn.partial = d_partial.as<float>(); wn.codesAll = d_codes.as<uint8_t>(); wn.groups = groups; wn.sampleN = sampleN;
+      for (size_t r = 0; r < rounds.size(); r++) {
+        const SegNullRound &rd = pl.rounds[r];
+        const Round &R = rounds[r];
+        sim.classBlocks = d_up.as<int>() + oBlocks + rd.first; sim.nClassBlocks = rd.count; sim.codesStride = rd.stride;
+        RC_TRY(launch_sim_side(c, sim, static_cast<long long>(rd.count) * groups, R.maxN, R.maxNodes, kCntWords, st));
+        wn.blocks = sim.classBlocks; wn.codesStride = rd.stride;
+        wn.items = reinterpret_cast<const WinItem *>(d_up.as<int>() + oItems) + R.item0; wn.nItems = static_cast<int>(R.nItems);
+        wn.folds = reinterpret_cast<const WinFold *>(d_up.as<int>() + oFolds) + R.fold0; wn.nFolds = static_cast<int>(R.nFolds);
+        wn.scratch = R.lds ? nullptr : d_scratch.as<float>(); wn.parkStride = win_park_floats(R.maxNK);
+        launch_window_null(wn, R.grid, R.lds ? win_park_floats(R.maxNK) * sizeof(float) : 0, st);
+        HIP_TRY(hipGetLastError());
+      }
+      HIP_TRY(hipMemcpyAsync(ge.data(), d_ge.p, nw * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      if (o.null) HIP_TRY(hipMemcpyAsync(o.null, d_null.p, nw * static_cast<size_t>(sampleN) * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(score.data(), d_best.p, nw * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(pos.data(), d_best.as<float>() + nw, 3 * nw * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // (the streams are non-blocking: nothing else would wait for the copies)
+    return RC_OK;
+  }();
+  if (rc != RC_OK) { if (launched) (void)hipStreamSynchronize(st); return rc; }
+  for (size_t w = 0; w < nw; w++) {
+    const int f = pos[3 * w], a = pos[3 * w + 1], j = pos[3 * w + 2];
+    o.score[w] = score[w];
+    if (o.frame) o.frame[w] = f;
+    if (o.opt_b) o.opt_b[w] = 3 * a + f + 1;
+    if (o.opt_i) o.opt_i[w] = 3 * j + f + 3;
+    if (o.cells) o.cells[w] = geom[w].cells;
+  }
+  if (withNull) std::memcpy(o.ge, ge.data(), nw * sizeof(int32_t));
+  return RC_OK;
+}
+
+int rc_batch_window_best(const rc_batch *b, const rc_bt_range *windows, int32_t n_windows, float *score_out, int32_t *frame_out, int32_t *opt_b_out,
+                         int32_t *opt_i_out, int64_t *cells_out) {
+  return window_call(b, windows, n_windows, WinOuts{score_out, frame_out, opt_b_out, opt_i_out, cells_out, nullptr, nullptr, 0}, false);
+}
+
+int rc_batch_window_null(const rc_batch *b, const rc_bt_range *windows, int32_t n_windows, float *score_out, int32_t *frame_out, int32_t *opt_b_out,
+                         int32_t *opt_i_out, int64_t *cells_out, int32_t *ge_out, float *null_out, int64_t cap) {
+  return window_call(b, windows, n_windows, WinOuts{score_out, frame_out, opt_b_out, opt_i_out, cells_out, ge_out, null_out, cap}, true);
 }
 
 }  // extern "C"
