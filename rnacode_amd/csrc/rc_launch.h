@@ -51,7 +51,7 @@ struct NullArgs {
   int rowParts;               // > 1: a strand x frame part's rows are split into this many ranges, each a work item (k_null<.., ROWS>); needs comboSplit
   float *sbuf;                // ... whose S values go here, [item][6][sbufStride]: getHSS's entry order, [entry][64 lanes]; k_null_rowscan folds them
   size_t sbufStride;          // floats per (item, strand x frame): 64 x (largest sites (sites + 1) / 2 of the launch)
-  int debugSkip;              // RC_PROFILING builds only: bit0 skip the DP/scan phase, bit1 skip simulation
+  int debugSkip;              // RC_PROFILING builds only: bit0 skip the DP/scan phase, bit1 skip simulation, bit2 frame-shift cells as cells between events
   unsigned long long *cellStats;   // RC_PROFILING builds only: [0] wavefront-cells, [1] of those with no lane's sum > 0, [2] lanes with sum > 0, [3..5] cells before the row's first event / at events / after its last, [6..7] chunks of the buffered row tested against the scan's gate / passed over, [8..9] row a's groups of four cells tested / passed over
 };
 

@@ -3,11 +3,12 @@
 // instantiates k_null for a range of N-1 so that the ranges compile in parallel.
 //
 // In the order of the file:
-//   shared device pieces     ref_max / pair_step (the recurrence), scan_step and native_scan_rows (getHSS for the native block), KRegs and
+//   shared device pieces     ref_max / pair_step (the recurrence) and shift_step (its shifting arms as the fast kernels' frame-shift cells make them), scan_step and native_scan_rows (getHSS for the native block), KRegs and
 //                            static_for (per-sequence registers), div_by_nk (SampleScan, getHSS per null sample: rc_scan_core.h)
 //   null_body                the work queues and the sharing of a launch's last items; phase A (simulation -> sigma codes in the staging
 //                            scratch); phase B per strand x frame: staging of the codes, the fetch_* lambdas and load_words, lookup, finish,
-//                            the cell kinds (fast, pristine, tail, event -- with the reference's maximum for NaN tables), next_event,
+//                            the cell kinds (fast, pristine, tail, event -- with the reference's maximum for NaN tables), next_event and request_z
+//                            (the event mask on a register: rc_event_plan.h; an event's z words asked for a span ahead),
 //                            then the rows: two per pass (DUAL: the ...2 cells, a pair's walk with dspan, the row left over) or one per
 //                            pass (take / one / span), and the result
 //   null_min_waves, k_null, k_null_occ, null_occupancy_one, launch_null_one, RC_DEFINE_NULL_RANGE
@@ -18,6 +19,7 @@
 #include <utility>
 
 #include "rc_device.h"
+#include "rc_event_plan.h"
 #include "rc_launch.h"
 #include "rc_scan_core.h"
 #include "rc_sim_core.h"
@@ -60,6 +62,24 @@ __device__ __forceinline__ void pair_step(int zc, float sig, float Delta, float 
     const float n2 = ref_max<SEM>(s2 + Delta, s0 + Omega);
     s0 = n0; s1 = n1; s2 = n2;
   }
+}
+
+// pair_step's two shifting arms (zc != 0) for one row of one sequence, for the frame-shift cells of the fast instantiations (no NaN
+// states: the one-instruction maximum).  The caller has tested zc != 0 (wave-uniform) and keeps the zc == 0 update as its fall-through.
+// The choice of z = +1 or z = -1 is made by selects on the wave-uniform zc, not by a branch (a branch inside the arm comes back from the
+// compiler as four branch instructions): which STATE each addition takes is selected in front of it, and which of Delta and Omega in
+// scalar registers -- six additions, four selects, three maxima, and no more than two temporaries alive at a time (all six sums first
+// cost k_null<2, true, false, true> a register).  The selected state is the state bit for bit, so each result is the operation
+// pair_step<false> makes, on its operands, in its order.  scan_max: the plain v_max_f32 (fmaxf canonicalises operands it cannot see
+// the arithmetic of).
+__device__ __forceinline__ void shift_step(int zc, float Delta, float Omega, float &s0, float &s1, float &s2) {
+  const bool up = zc == 1;
+  const float cA = up ? Omega : Delta, cB = up ? Delta : Omega;
+  const float t12 = up ? s1 : s2;
+  const float n0 = scan_max(s0 + Delta, (up ? s2 : s1) + Omega);   // z = +1: max(s0 + Delta, s2 + Omega)   z = -1: max(s0 + Delta, s1 + Omega)
+  const float n1 = scan_max((up ? s0 : s1) + cA, t12 + cB);        //         max(s0 + Omega, s1 + Delta)           max(s1 + Delta, s2 + Omega)
+  const float n2 = scan_max(t12 + cA, (up ? s2 : s0) + cB);        //         max(s1 + Omega, s2 + Delta)           max(s2 + Delta, s0 + Omega)
+  s0 = n0; s1 = n1; s2 = n2;
 }
 
 // getHSS's serial state machine for one entry (score.c:892-959), emission reduced to a callback.
@@ -183,6 +203,8 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
   constexpr int PSW = code_pos_words(NK);                  // dwords per (strand, position)
   using TailT = std::conditional_t<LB == 1, uint8_t, std::conditional_t<LB == 2, uint16_t, uint32_t>>;
   constexpr int ZW = (NK + 31) / 32;      // 64-bit words per z entry (2 bits per sequence)
+  // a z word as the walks hold it from one event to the next (request_z): up to sixteen sequences live in its low half (little-endian), one scalar register
+  using ZT = std::conditional_t<(NK <= 16), uint32_t, unsigned long long>;
   using Regs = KRegs<std::make_integer_sequence<int, NK>>;
   // DUAL: two rows of S per pass (see "rows a and a + 1 together" below): for instantiations whose codes are staged in LDS and whose
   // register budget has room for a second row's states and a 32-entry row buffer at four wavefronts per SIMD.  The host picks it per
@@ -833,8 +855,11 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
           auto wait_lookups = [&](auto leave) {
             constexpr int k0 = (NCW - 1) * CPW;
             constexpr int cnt = NK - k0;   // look-ups of the last code word: 1..5, each one an operand of the wait (no padding copies)
-            // (scalar loads share the counter and may complete out of order: where the compiler could have one
-            // in flight -- the event cell reads z -- wait for everything)
+            // (Scalar loads share the counter and may complete out of order.  scalarLoadsNearby: the cell is an event's, which stands
+            // between the scalar work of the walk -- where the span behind it ends, the request for the next event's z words -- and whose
+            // own z words, asked for a span ahead, must have arrived: it waits for everything.  A span's cells pass false and keep
+            // their partial wait although the request made in front of the span (request_z) may still be outstanding: "at most n
+            // outstanding" then still means that every look-up has returned -- the argument stands at request_z.)
             constexpr int left = (decltype(leave)::value > 0 && !decltype(scalarLoadsNearby)::value) ? decltype(leave)::value : 0;
             if constexpr (cnt == 1) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(sig[k0]) : "n"(left));
             else if constexpr (cnt == 2) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(sig[k0]), "+v"(sig[k0 + 1]) : "n"(left));
@@ -956,31 +981,56 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
         };
         // codon where some sequence has z != 0 (score.c:512-533), wave-uniform branch per sequence
         // sem = true: every codon of a block with NaN score tables: the recurrence as the reference writes it, its MAX macro and operand order (ref_max)
-        auto event_cell = [&](uint32_t (&w)[NCW], int j, int jn, auto kind, auto sem) -> float {
+        // z: the codon's z words, which the caller asked for a span ahead (request_z below): the cell waits for no scalar load of its own
+        auto event_cell = [&](uint32_t (&w)[NCW], const ZT (&z)[ZW], int jn, auto kind, auto sem) -> float {
           constexpr bool SEM = decltype(sem)::value;
+          if constexpr (kProfiling && !SEM) {   // debugSkip bit 2: every event codon as if no sequence shifted, at the price of a cell between events (wrong results)
+            if (A.debugSkip & 4) return fast_cell(w, jn, kind);
+          }
           float sig[NK];
           lookup(w, sig, jn, std::true_type{}, kind);
-          unsigned long long z[ZW];
-#pragma unroll
-          for (int x = 0; x < ZW; x++) z[x] = zbase[static_cast<size_t>(3 * j) * ZW + x];
           float sum = 0.0f;
           static_for<NK>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
             auto &r = R.template at<k>();
-            pair_step<SEM>(static_cast<int>((z[k >> 5] >> (2 * (k & 31))) & 3ull), sig[k], Delta, Omega, omega, r.s0, r.s1, r.s2);
+            const int zc = static_cast<int>((z[k >> 5] >> (2 * (k & 31))) & 3u);
+            if constexpr (SEM) {
+              pair_step<SEM>(zc, sig[k], Delta, Omega, omega, r.s0, r.s1, r.s2);
+            } else if (__builtin_expect(zc != 0, 0)) {   // one wave-uniform test per sequence; most sequences of an event codon do not shift:
+              shift_step(zc, Delta, Omega, r.s0, r.s1, r.s2);
+            } else {                                     // their update is the fall-through, and it is fast_cell's (omega from its vector register)
+              r.s0 = r.s0 + sig[k];
+              r.s1 = r.s1 + omega_v;
+              r.s2 = r.s2 + omega_v;
+            }
             const float m = ref_max3<SEM>(r.s0, r.s1, r.s2);
             sum = (k == 0) ? m : sum + m;
           });
           return finish(sum);
         };
+        // Where the walk meets its next event (rc_event_plan.h): the mask's word of sites 0..63 is loaded here, once per strand x frame, into a
+        // register pair; a frame of up to 64 sites never loads another, so no walk waits for a scalar load to find its next event.
+        EventMask zmaskReg = event_mask_begin(zany);
         // first site >= j (and < end) with an event, or end
-        auto next_event = [&](int j, int end) -> int {
-          while (j < end) {
-            const unsigned long long mword = zany[j >> 6] >> (j & 63);
-            if (mword) { const int e = j + __builtin_ctzll(mword); return e < end ? e : end; }
-            j = (j | 63) + 1;
-          }
-          return end;
+        auto next_event = [&](int j, int end) -> int { return event_next(zmaskReg, j, end); };
+        // The z words of site j: wave-uniform, scalar loads.  request_z: those of the event e that ends the span [j, e), asked for when the
+        // span STARTS, so that they arrive while its cells run and the event cell waits for nothing (e == end: no event follows and the
+        // words are never looked at; site 0 exists in every frame that is walked).
+        // The counter: scalar loads and LDS operations share lgkmcnt and scalar loads return out of order.  A cell's own waits are asm the
+        // compiler does not see, and with a request outstanding they stay correct: every wait for the fetched words is lgkmcnt(0), and the
+        // partial wait behind the look-ups (wait_lookups, leave = n > 0) asks for "at most n outstanding" -- LDS operations return in
+        // order, so with a scalar load among the outstanding ones at most n of them are LDS operations, and those are the youngest n, the
+        // fetches: every look-up has returned.  The request can only make such a wait longer (until the words have arrived), never shorter.
+        // The compiler knows the request (a plain load) and puts its own lgkmcnt(0) in front of the first use, in the event cell.
+        auto load_z = [&](int j, ZT (&z)[ZW]) {
+#pragma unroll
+          for (int x = 0; x < ZW; x++) z[x] = *reinterpret_cast<const ZT *>(zbase + static_cast<size_t>(3 * j) * ZW + x);
+        };
+        // (The EXACT instantiation keeps its walk as it was, the test of the mask's bit at the head of every turn and the load at the
+        // event's cell: restated, the walk cost k_null<9, false, true> and k_null<36, false, true> two registers and with them a
+        // wavefront per SIMD.)
+        auto request_z = [&](int e, int end, ZT (&z)[ZW]) {
+          if constexpr (!EXACT) load_z(e < end ? e : 0, z);
         };
         SampleScan st{0.0f, 0.0f, 0u, 0u};
         float negTwo_v;   // what the scan's X moves by from entry to entry, in a register (sample_scan_step)
@@ -1099,22 +1149,33 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
             vB = sumB;
             return sumA;
           };
-          auto event2 = [&](uint32_t (&w)[NCW], int j, int jn, float &vB) -> float {
+          auto event2 = [&](uint32_t (&w)[NCW], const ZT (&z)[ZW], int jn, float &vB) -> float {
+            if constexpr (kProfiling) {   // debugSkip bit 2: what the frame-shift cells cost beyond a cell between events (wrong results)
+              if (A.debugSkip & 4) return fast2(w, jn, vB, std::true_type{});
+            }
             float sig[NK];
             lookup(w, sig, jn, std::true_type{}, std::true_type{});
-            unsigned long long z[ZW];
-#pragma unroll
-            for (int x = 0; x < ZW; x++) z[x] = zbase[static_cast<size_t>(3 * j) * ZW + x];
             float sumA = 0.0f, sumB = 0.0f;
             static_for<NK>([&](auto kc) {
               constexpr int k = decltype(kc)::value;
               auto &ra = R.template at<k>();
               auto &rb = RB.template at<k>();
-              const int zc = static_cast<int>((z[k >> 5] >> (2 * (k & 31))) & 3ull);
-              pair_step(zc, sig[k], Delta, Omega, omega, ra.s0, ra.s1, ra.s2);
+              // both rows see the same zc: one wave-uniform test per sequence decides for both.  The fall-through is the update of a
+              // sequence that does not shift (fast2's six additions); the arm holds both rows' shifting steps and the choice of +1 / -1.
+              const int zc = static_cast<int>((z[k >> 5] >> (2 * (k & 31))) & 3u);
+              if (__builtin_expect(zc != 0, 0)) {
+                shift_step(zc, Delta, Omega, ra.s0, ra.s1, ra.s2);
+                shift_step(zc, Delta, Omega, rb.s0, rb.s1, rb.s2);
+              } else {
+                ra.s0 = ra.s0 + sig[k];
+                ra.s1 = ra.s1 + omega_v;
+                ra.s2 = ra.s2 + omega_v;
+                rb.s0 = rb.s0 + sig[k];
+                rb.s1 = rb.s1 + omega_v;
+                rb.s2 = rb.s2 + omega_v;
+              }
               const float ma = fmaxf(fmaxf(ra.s0, ra.s1), ra.s2);
               sumA = (k == 0) ? ma : sumA + ma;
-              pair_step(zc, sig[k], Delta, Omega, omega, rb.s0, rb.s1, rb.s2);
               const float mb = fmaxf(fmaxf(rb.s0, rb.s1), rb.s2);
               sumB = (k == 0) ? mb : sumB + mb;
             });
@@ -1126,7 +1187,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
           int a = 0;
           int pendRow = -1, pendExtra = 0, pendN = 0;   // row a + 1 of the last pair: its first pendExtra cells are still to be made, then pendN buffered values to scan
           while (a < sites || pendRow >= 0) {
-            if (pendRow < 0 && a + 2 < sites && !((zany[a >> 6] >> (a & 63)) & 1ull)) {
+            if (pendRow < 0 && a + 2 < sites && !event_at(zmaskReg, a)) {
               // ---- rows a and a + 1 together
               sample_scan_row_begin(st, best, static_cast<uint32_t>(a));
               static_for<NK>([&](auto kc) {
@@ -1233,9 +1294,15 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                 }
                 for (; j < e; j++) pair_cell(wcur, j, j + 1 < sites ? j + 1 : j, std::true_type{}, fn);
               };
+              // Every span ends at the next event e or at the frame's end, so behind a span j == e < sites IS an event codon: the walk tests
+              // no bit of the event mask there.  Where the span behind an event ends is found in front of its cell, on the mask's register
+              // (next_event), and the z words of the event at e were asked for when the span in front of it started (request_z).
+              int e = next_event(j, sites);
+              ZT zev[ZW];
+              request_z(e, sites, zev);
               {
-                if constexpr (kProfiling) statPristine += 1 + 2 * (next_event(j, sites) - j);   // (row a's first cell; a pair is two cells)
-                dspan(next_event(j, sites), [&](uint32_t (&w)[NCW], auto jn, float &vB, auto kd) { return pristine2(w, wvA, wvB, jn, vB, kd); });
+                if constexpr (kProfiling) statPristine += 1 + 2 * (e - j);   // (row a's first cell; a pair is two cells)
+                dspan(e, [&](uint32_t (&w)[NCW], auto jn, float &vB, auto kd) { return pristine2(w, wvA, wvB, jn, vB, kd); });
                 static_for<NK>([&](auto kc) {
                   constexpr int k = decltype(kc)::value;
                   auto &r = R.template at<k>();
@@ -1244,21 +1311,21 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                   rb.s1 = rb.s2 = wvB;
                 });
               }
-              while (j < sites) {
-                if ((zany[j >> 6] >> (j & 63)) & 1ull) {
-                  const int jev = j;
+              while (j < sites) {   // j == e: an event codon, its z words in zev
+                {
+                  e = next_event(j + 1, sites);   // (in front of the cell: behind it the compiler sets this loop between the cell's sums and its scan step)
                   if constexpr (kProfiling) statEvent += 2;
-                  pair_cell(wcur, j, j + 1 < sites ? j + 1 : j, std::true_type{}, [&](uint32_t (&w)[NCW], int jn, float &vB, auto) { return event2(w, jev, jn, vB); });
+                  pair_cell(wcur, j, j + 1 < sites ? j + 1 : j, std::true_type{}, [&](uint32_t (&w)[NCW], int jn, float &vB, auto) { return event2(w, zev, jn, vB); });
                   j++;
+                  request_z(e, sites, zev);
                 }
-                const int e = next_event(j, sites);
                 if (e == sites) {
                   static_for<NK>([&](auto kc) {
                     constexpr int k = decltype(kc)::value;
                     auto &r = R.template at<k>();
-                    r.s1 = fmaxf(r.s1, r.s2);
+                    r.s1 = scan_max(r.s1, r.s2);   // (one v_max: states are results of arithmetic, never signalling -- fmaxf canonicalises both operands first)
                     auto &rb = RB.template at<k>();
-                    rb.s1 = fmaxf(rb.s1, rb.s2);
+                    rb.s1 = scan_max(rb.s1, rb.s2);
                   });
                   if constexpr (kProfiling) statTail += 2 * (e - j);
                   dspan(e, [&](uint32_t (&w)[NCW], auto jn, float &vB, auto kd) { return tail2(w, jn, vB, kd); });
@@ -1292,8 +1359,10 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                 const int jn = j + 1 < sites ? j + 1 : j;
                 take(cell(wcur, jn, std::true_type{}));
               };
+              int e = next_event(j, jend);   // (as in the pair's walk: behind a span j == e < jend is an event codon, its z words asked for a span ahead)
+              ZT zev[ZW];
+              request_z(e, jend, zev);
               {   // pristine segment: up to the row's first event
-                const int e = next_event(j, jend);
                 float wv = 0.0f;
                 asm volatile("v_mov_b32 %0, 0" : "=v"(wv));   // keep w a per-lane register (full-rate v_add/v_max operands)
                 for (; j < e; j++) one([&](uint32_t (&w)[NCW], int jn, auto kd) {
@@ -1306,19 +1375,19 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                   r.s1 = r.s2 = wv;
                 });
               }
-              while (j < jend) {
-                if ((zany[j >> 6] >> (j & 63)) & 1ull) {               // event codon
+              while (j < jend) {   // j == e: an event codon
+                {
+                  e = next_event(j + 1, jend);
                   if constexpr (kProfiling) statEvent++;
-                  const int jj = j;
-                  one([&](uint32_t (&w)[NCW], int jn, auto kd) { return event_cell(w, jj, jn, kd, std::false_type{}); });
+                  one([&](uint32_t (&w)[NCW], int jn, auto kd) { return event_cell(w, zev, jn, kd, std::false_type{}); });
                   j++;
+                  request_z(e, jend, zev);
                 }
-                const int e = next_event(j, jend);
                 if (e == jend) {                                       // no further event in this row: the tail
                   static_for<NK>([&](auto kc) {
                     constexpr int k = decltype(kc)::value;
                     auto &r = R.template at<k>();
-                    r.s1 = fmaxf(r.s1, r.s2);
+                    r.s1 = scan_max(r.s1, r.s2);
                   });
                   for (; j < e; j++) one([&](uint32_t (&w)[NCW], int jn, auto kd) {
                     if constexpr (kProfiling) statTail++;
@@ -1447,12 +1516,15 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
             if constexpr (EXACT) {
               if (nanSem)   // (the whole row: none of the shortcuts below holds with NaN states)
                 for (; j < jend; j++) {
-                  const int jj = j;
-                  one([&](uint32_t (&w)[NCW], int jn, auto kd) { return event_cell(w, jj, jn, kd, std::true_type{}); });
+                  ZT zj[ZW];
+                  load_z(j, zj);
+                  one([&](uint32_t (&w)[NCW], int jn, auto kd) { return event_cell(w, zj, jn, kd, std::true_type{}); });
                 }
             }
+            int e = next_event(j, jend);   // (behind a span j == e < jend is an event codon, its z words asked for when the span started: request_z)
+            ZT zev[ZW] = {};
+            request_z(e, jend, zev);
             {   // pristine segment: up to the row's first event
-              const int e = next_event(j, jend);
               float wv = 0.0f;
               asm volatile("v_mov_b32 %0, 0" : "=v"(wv));   // keep w a per-lane register (full-rate v_add/v_max operands)
               span(e, [&](uint32_t (&w)[NCW], int jn, auto kd) {
@@ -1465,19 +1537,27 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                 r.s1 = r.s2 = wv;
               });
             }
-            while (j < jend) {
-              if ((zany[j >> 6] >> (j & 63)) & 1ull) {               // event codon
+            while (j < jend) {   // (not EXACT: j == e, an event codon)
+              if constexpr (EXACT) {   // (the walk as it was, its test of the mask and the z words loaded at the cell: see request_z)
+                if (event_at(zmaskReg, j)) {
+                  if constexpr (kProfiling) statEvent++;
+                  load_z(j, zev);
+                  one([&](uint32_t (&w)[NCW], int jn, auto kd) { return event_cell(w, zev, jn, kd, std::false_type{}); });
+                  j++;
+                }
+                e = next_event(j, jend);
+              } else {
+                e = next_event(j + 1, jend);
                 if constexpr (kProfiling) statEvent++;
-                const int jj = j;
-                one([&](uint32_t (&w)[NCW], int jn, auto kd) { return event_cell(w, jj, jn, kd, std::false_type{}); });
+                one([&](uint32_t (&w)[NCW], int jn, auto kd) { return event_cell(w, zev, jn, kd, std::false_type{}); });
                 j++;
+                request_z(e, jend, zev);
               }
-              const int e = next_event(j, jend);
               if (e == jend) {                                       // no further event in this row: the tail
                 static_for<NK>([&](auto kc) {
                   constexpr int k = decltype(kc)::value;
                   auto &r = R.template at<k>();
-                  r.s1 = fmaxf(r.s1, r.s2);
+                  r.s1 = scan_max(r.s1, r.s2);
                 });
                 span(e, [&](uint32_t (&w)[NCW], int jn, auto kd) {
                   if constexpr (kProfiling) statTail++;
