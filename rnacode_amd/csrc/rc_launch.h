@@ -7,6 +7,7 @@
 #include <string>
 
 #include "rc_device.h"
+#include "rc_spill_plan.h"
 
 namespace rc {
 
@@ -44,14 +45,15 @@ struct NullArgs {
   uint8_t *codesAll;          // k_generic_sim / k_generic_dp: the codes of every item of the launch pair, item u at u * codesStride
   size_t codesStride;
   int cacheSites;             // codes from L2: the words of the last cacheSites sites of a strand x frame are kept in LDS (0: none)
-  int reserved[3];            // unused, zero: keeps the offsets of the fields below (the launch's instantiation is a NullKind, below)
+  uint32_t spillOff;          // two rows per pass: uint32 from a workgroup's scratch to its spill area, the end of its stride (rc_spill_plan.h)
+  int reserved[2];            // unused, zero: keeps the offsets of the fields below (the launch's instantiation is a NullKind, below)
   int stealWait;              // 1: a workgroup without work waits for owners that are still simulating a late item; 0: it leaves at once (a stream: the next sub-batch's workgroups want its place)
   int simParts, simGrid;      // rows split over workgroups: an item's simulation is cut into simParts site ranges, simGrid workgroups take them (k_null<.., 2>)
   unsigned int *simCounter;   // ... from queues of their own [8]
   int rowParts;               // > 1: a strand x frame part's rows are split into this many ranges, each a work item (k_null<.., ROWS>); needs comboSplit
   float *sbuf;                // ... whose S values go here, [item][6][sbufStride]: getHSS's entry order, [entry][64 lanes]; k_null_rowscan folds them
   size_t sbufStride;          // floats per (item, strand x frame): 64 x (largest sites (sites + 1) / 2 of the launch)
-  int debugSkip;              // RC_PROFILING builds only: bit0 skip the DP/scan phase, bit1 skip simulation, bit2 frame-shift cells as cells between events
+  int debugSkip;              // RC_PROFILING builds only: bit0 skip the DP/scan phase, bit1 skip simulation, bit2 frame-shift cells as cells between events, bit3 the row left over from a pair skips the cells in front of its buffer
   unsigned long long *cellStats;   // RC_PROFILING builds only: [0] wavefront-cells, [1] of those with no lane's sum > 0, [2] lanes with sum > 0, [3..5] cells before the row's first event / at events / after its last, [6..7] chunks of the buffered row tested against the scan's gate / passed over, [8..9] row a's groups of four cells tested / passed over
 };
 

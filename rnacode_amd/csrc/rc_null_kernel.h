@@ -1060,13 +1060,35 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
           // ds_bpermute per sequence -- is what the cell loop waits for most (tools/ab_lookup.sh: four of the five look-ups left out,
           // 49.1 -> 43.7 ms).  Rows a and a + 1 therefore walk their common sites together on one set of look-ups.  getHSS reads the
           // entries row by row, so row a's entries go through the scan as they are made and row a + 1's S values wait in a register
-          // buffer (32 floats, indexed with the wave-uniform site number: s_set_gpr_idx) until row a is done; a row longer than the
-          // buffer has its first cells made twice -- states only beside row a, then again with their scan when its turn comes.
+          // buffer (32 floats, indexed with the wave-uniform site number: s_set_gpr_idx) until row a is done; of a row longer than the
+          // buffer the first sums wait in global memory (kSpill below: codes staged in LDS) or, with the codes from L2, its first cells are
+          // made twice -- states only beside row a, then again with their scan when its turn comes.
           // Every row's additions and maxima are the ones of the one-row loop in the same order: results are bit-identical.
           // A pair needs a site a without a frame-shift event (both rows then change their cell kind at the same sites) and two more
           // rows below it; other rows go alone.
           typedef float RowBuf __attribute__((ext_vector_type(32)));
-          constexpr int kBuf = 32;
+          constexpr int kBuf = kSpillBuf;
+          static_assert(kBuf == 32, "RowBuf");
+          // kSpill (codes staged in LDS): a row longer than the buffer makes no cell twice.  The pair's walk stores row a + 1's undivided
+          // sums of the cells in front of the buffer to the workgroup's spill area (rc_spill_plan.h: global memory, [entry][64 lanes], entry
+          // = site - (a + 1)), and the row's turn -- right behind the pair, no walk of its own -- reads them back in order and puts them
+          // through the gate on sums and the scan like the buffer's.  Same sums, same division, same steps in the row's order.  A lane
+          // reads only what it wrote (plain stores and loads, which the compiler waits for itself); the staged row loops issue no other
+          // vector memory operation.  The kernel that reads its codes from L2 keeps the second walk: its fetches are asm loads waited
+          // for by COUNT (vmcnt(n): loads return in order), and a store among them may return out of order with the loads.
+#ifndef RC_SPILL_ROWS
+#define RC_SPILL_ROWS 1
+#endif
+          constexpr bool kSpill = LDSC && RC_SPILL_ROWS != 0;
+          // this lane's float of entry x: formed where it is used, from the kernel's arguments and the workgroup's number (nothing of it
+          // lives in a register across the pair's walk: x is opaque where it enters)
+          auto spill_at = [&](int x) -> float * {
+            uint32_t wg = blockIdx.x;
+            int ln = lane;
+            asm volatile("" : "+s"(x), "+v"(ln));   // (or the compiler keeps the workgroup's base plus the lane's offset in a register pair of its own for the whole kernel)
+            const size_t word = static_cast<size_t>(wg) * A.scratchStride + A.spillOff + static_cast<size_t>(x) * kSpillLanes;
+            return reinterpret_cast<float *>(scratch + word) + ln;
+          };
           constexpr int kGroup = 4;   // cells per group in the span loops (codes staged in LDS)
           // entries of the buffered row per test of the scan's gate (rc_scan_core.h).  Measured at 2, 4 and 8 (profiles/r10): chunks of two are
           // passed over more often (76 % against 65 and 50, tools/scan_gate_stats.py) and pay a test and a branch per two entries -- no gain at
@@ -1235,6 +1257,7 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                     float sB;
                     const float v = divide(fn(wcur, j + 1, sB, std::true_type{}));
                     sample_scan_step(st, v, negTie, negTwo_v);
+                    if constexpr (kSpill) *spill_at(spill_entry(a, j)) = sB;
                   }
                   // Row a's four entries of a group are a chunk of the gate on sums: the cells hand out row a's sums undivided, the group takes
                   // their maximum, Gs from the state as it stands (no step has touched it since the last group that was taken, or since the
@@ -1318,6 +1341,10 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
                   pair_cell(wcur, j, j + 1 < sites ? j + 1 : j, std::true_type{}, [&](uint32_t (&w)[NCW], int jn, float &vB, auto) { return event2(w, zev, jn, vB); });
                   j++;
                   request_z(e, sites, zev);
+                  // (an event codon in front of b0 has left row a + 1's sum in entry 0 of the buffer: to the spill area from there, in a block of its own behind the cell)
+                  if constexpr (kSpill) {
+                    if (j <= b0) *spill_at(spill_entry(a, j - 1)) = buf[0];
+                  }
                 }
                 if (e == sites) {
                   static_for<NK>([&](auto kc) {
@@ -1335,7 +1362,71 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
 #pragma unroll
               for (int x = 0; x < NCW; x++) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wcur[x]));
               sample_scan_row_end(st, static_cast<uint32_t>(a), static_cast<uint32_t>(sites));
-              pendRow = a + 1; pendExtra = extra; pendN = sites - b0;
+              if constexpr (kSpill) {
+                // ---- row a + 1's turn: its spilled sums, entries 0 .. extra - 1, then the buffer.  No cell, no code word, no event.  The
+                // spilled entries go through the gate on sums in chunks of kGateChunk like the buffer's (four loads at constant offsets
+                // from one base), the ones behind the last whole chunk one at a time; Gs is taken behind the row's begin.
+                sample_scan_row_begin(st, best, static_cast<uint32_t>(a + 1));
+                int x = 0;
+                if (extra >= kGateChunk) {
+                  float Gs = sample_scan_gate_sum(st, best, negTie, kNkF);
+                  for (; x + kGateChunk <= extra; x += kGateChunk) {
+                    const float *p = spill_at(x);
+                    float sp[kGateChunk];
+#pragma unroll
+                    for (int u = 0; u < kGateChunk; u++) sp[u] = p[u * kSpillLanes];
+                    float m = sp[0];
+#pragma unroll
+                    for (int u = 1; u + 1 < kGateChunk; u += 2) m = scan_max3(m, sp[u], sp[u + 1]);
+                    if constexpr (kGateChunk % 2 == 0) m = scan_max(m, sp[kGateChunk - 1]);
+                    if constexpr (kProfiling) statGateTested++;
+                    if (__builtin_amdgcn_ballot_w64(sample_scan_gate_pass(m, Gs)) != 0ull) {
+#pragma unroll
+                      for (int u = 0; u < kGateChunk; u++) sample_scan_step(st, divide(sp[u]), negTie, negTwo_v);
+                      Gs = sample_scan_gate_sum(st, best, negTie, kNkF);
+                    } else {
+                      if constexpr (kProfiling) statGateSkipped++;
+                      sample_scan_skip(st, kGateChunk);
+                    }
+                  }
+                }
+                for (; x < extra; x++) sample_scan_step(st, divide(*spill_at(x)), negTie, negTwo_v);
+                {
+                  // ... then the buffered values, as the walk that keeps its second pass scans them below (the text stands twice: as one
+                  // lambda called from both places k_null<5, true, false, true> took a register more, 124 for 123)
+                  const int pendN = sites - b0;
+                  float G = sample_scan_gate_sum(st, best, negTie, kNkF);
+                  [&]() {
+#pragma unroll
+                    for (int c0 = 0; c0 < kBuf; c0 += kGateChunk) {
+                      if (c0 + kGateChunk > pendN) {
+#pragma unroll
+                        for (int u = 0; u < kGateChunk - 1; u++) {
+                          if (c0 + u >= pendN) return;
+                          sample_scan_step(st, divide(buf[c0 + u]), negTie, negTwo_v);
+                        }
+                        return;
+                      }
+                      float m = buf[c0];
+#pragma unroll
+                      for (int u = 1; u + 1 < kGateChunk; u += 2) m = scan_max3(m, buf[c0 + u], buf[c0 + u + 1]);
+                      if constexpr (kGateChunk % 2 == 0) m = scan_max(m, buf[c0 + kGateChunk - 1]);
+                      if constexpr (kProfiling) statGateTested++;
+                      if (__builtin_amdgcn_ballot_w64(sample_scan_gate_pass(m, G)) != 0ull) {
+#pragma unroll
+                        for (int u = 0; u < kGateChunk; u++) sample_scan_step(st, divide(buf[c0 + u]), negTie, negTwo_v);
+                        G = sample_scan_gate_sum(st, best, negTie, kNkF);
+                      } else {
+                        if constexpr (kProfiling) statGateSkipped++;
+                        sample_scan_skip(st, kGateChunk);
+                      }
+                    }
+                  }();
+                }
+                sample_scan_row_end(st, static_cast<uint32_t>(a + 1), static_cast<uint32_t>(sites));
+              } else {
+                pendRow = a + 1; pendExtra = extra; pendN = sites - b0;
+              }
               a += 2;
             } else {
               // ---- one row: row `a`, or the row left over from a pair (its first pendExtra cells, then its buffered values).  The walk of
@@ -1344,7 +1435,8 @@ __device__ __forceinline__ void null_body(const NullArgs &A, const uint8_t *__re
               // register figures moved, speed not measured; profiles/r07/refactor_isa_identity.txt.)
               const bool pend = pendRow >= 0;
               const int row = pend ? pendRow : a;
-              const int jend = pend ? row + pendExtra : ((row == sites - 1) ? sites - 1 : sites);
+              // (debugSkip bit 3: the row left over from a pair does not walk its first pendExtra cells -- what making them a second time costs; wrong results)
+              const int jend = pend ? row + ((kProfiling && (A.debugSkip & 8)) ? 0 : pendExtra) : ((row == sites - 1) ? sites - 1 : sites);
               sample_scan_row_begin(st, best, static_cast<uint32_t>(row));
               static_for<NK>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;

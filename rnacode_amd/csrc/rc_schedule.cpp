@@ -132,6 +132,7 @@ struct ClassPlan {
   NullKind simKind = NullKind::GenericSim; int simGrid = 0; size_t simLds = 0;   // the simulation launch (rows split over workgroups: k_null<.., 2>'s grid)
   int comboSplit = 0, rowParts = 0, simParts = 0, cacheSites = 0;   // (NullArgs)
   size_t stride = 0, sbufStride = 0, sbufFloats = 0;   // k_null: uint32 of code staging per workgroup; rows split: k_null<.., ROWS>'s S buffer
+  size_t spillOff = 0; int spillMaxL = 0;               // two rows per pass: where in the stride the spill area starts, sized for blocks of up to spillMaxL residues (rc_spill_plan.h)
   size_t codesBytes = 0, stateBytes = 0; int roundBlocks = 0;   // the wide classes: an item's codes, a DP workgroup's states; blocks per round
   double itemCost = 0.0; size_t need = 0;   // (cell, sequence) steps of the class's longest item, up to a factor; uint32 of staging scratch
   bool tailShare = false;               // k_null: tail sharing (where the steal area has room)
@@ -202,6 +203,9 @@ static ClassPlan plan_rows(const RoundIn &in, int NK, const std::vector<int> &me
   // staging leaves twelve or fewer (blocks of more than ~135 columns), the same kernel reading its codes from L2 behind a suffix
   // cache runs sixteen and is faster: 6 rows x 150 columns 77.3 -> 71.7 ms; at 120 columns (fifteen staged) it is slower, 42.6 -> 47.0.
   const bool twoRows = R.two_rows(NK);
+  // two rows per pass: the spill area of row a + 1's sums in front of its register buffer, at the end of each workgroup's stride
+  // (rc_spill_plan.h; a multiple of 64 words: the stride keeps its alignment)
+  if (twoRows && !exactOnly) { p.spillOff = p.stride; p.spillMaxL = x.maxL; p.stride += spill_words(x.maxL); }
   const size_t staged = static_cast<size_t>(x.maxL / 3) * ((NK + 4) / 5) * kWave * sizeof(uint32_t);   // 5 six-bit sigma codes per word
   const bool dualL2 = p.rowParts == 1 && !exactOnly && NK >= 3 && twoRows && staged <= c->ldsMaxBytes &&
                       c->ldsPerCU / std::max<size_t>(staged, kPhaseALds) <= 12;
@@ -471,6 +475,9 @@ int launch_null_groups(const RunEnv &R, int gLo, int gHi, int phase, uint32_t ex
     a.flags = b->dflags.as<uint32_t>();
     a.gLo = gLo; a.gHi = gHi; a.sampleN = R.sampleN; a.Spad = R.Spad;
     a.U = c->d_U; a.pair = R.tp.pair; a.scratch = b->dscratch.as<uint32_t>() + p.scratchOff; a.scratchStride = p.stride;
+    a.spillOff = static_cast<uint32_t>(p.spillOff);
+    if (p.kind == NullKind::StagedTwoRow && (p.spillOff + spill_words(p.spillMaxL) > p.stride || p.spillOff > 0xFFFFFFFFull || p.spillMaxL <= 0))
+      return fail(RC_ERR_ARG, "internal: the two-row walk's spill area does not fit the workgroup's scratch");
     a.maxima = b->maxPtr; a.clampCount = reinterpret_cast<unsigned long long *>(b->dcounters.as<uint32_t>() + kCntClamp);
     a.tieThr = c->tieThr; a.debugSkip = c->debugSkip; a.comboSplit = p.comboSplit;
     a.cellStats = c->d_cellStats.as<unsigned long long>();
