@@ -535,6 +535,40 @@ int rc_batch_segment_shuffle_null_pairs(const rc_batch *b, const rc_bt_range *ra
                                         int64_t cap /* entries in each */, int64_t *offsets /* n_ranges + 1 */,
                                         float *pair_null_out /* may be NULL: [offsets[n_ranges]][n_shuffles] */, int64_t null_cap /* floats in pair_null_out */);
 
+/* Named windows under the shuffle null: the test for an interval NAMED IN ADVANCE against a null made from its own block's columns --
+ * rc_batch_window_null's question asked of rc_batch_shuffle_null's alignments.  Windows, their cells and validity rules and the five outputs
+ * of the block itself (score_out, frame_out, opt_b_out, opt_i_out, cells_out) are rc_batch_window_best's, with that call's bits.  For every
+ * window and d = 0 .. n_shuffles - 1 (1 <= n_shuffles <= 65536)
+ *     null[w][d] = the window's value -- the fmaxf of its cells -- in the gap-class column shuffle of seed seed + d of the window's block
+ * (rc_batch_decoys_shuffled's definition, key function and seeds: shuffle d of this call IS shuffled decoy d and shuffle d of
+ * rc_batch_shuffle_null and rc_batch_segment_shuffle_null), scored with the block's own models, gap tables and parameters; every cell has the
+ * bits rc_batch_segment_shuffle_null gives that segment.  ge_out[w] is the number of shuffles with null[w][d] >= score_out[w] (binary32
+ * compare: a NaN on either side does not count); if null_out is not NULL the values come back at null_out[w * n_shuffles + d], and
+ * cap < n_windows * n_shuffles is RC_ERR_ARG.  Shuffle d depends on seed + d and the block only: not on n_shuffles, on which windows are
+ * listed, on the budget or on RC_SHUFFLE_LDS_COLS.  A block where no gap class has two columns has only the identity shuffle: every value is
+ * the window's own score, and ge_out[w] = n_shuffles.
+ * The empirical p is the caller's: p_window_shuffled = (ge + 1) / (n_shuffles + 1), valid for a window chosen WITHOUT looking at the scores.
+ * Shuffle d of one block and shuffle d of another share a seed, not columns: for windows in several blocks (the exons of one transcript) the
+ * element-wise fmaxf of their rows is the null of the fmaxf of their scores under the joint shuffle d of all those blocks.
+ * n_shuffles outside 1..65536 returns RC_ERR_ARG; the other errors are rc_batch_window_null's: every window is checked before the device is
+ * touched, rc_last_error names the window's index, a window on a block that was not scored returns that block's status, a batch that has not
+ * completed a run RC_ERR_ARG, and on any error nothing is launched and the outputs are left alone.  n_windows = 0 is RC_OK; a window may
+ * repeat.  Works on a batch rc_stream_next handed out until it is recycled, and leaves the batch's maxima, fit, HSS, timings and
+ * rc_batch_clamped as they are; no MT19937 stream is touched.
+ * Cost: the block's own side as for rc_batch_window_best; the class ids of every distinct block that has a window once per call on the host;
+ * per (block, shuffle) one sort as for a shuffled decoy; per (block, group of 64 shuffles) the sigma codes of the code words the block's
+ * windows read and of nothing else -- per strand that has a window the words 2 (aMin / 8) .. 2 (jMax / 8) + 1 of four codons each, aMin and
+ * jMax the first and last codon of any of its windows: 3 (N - 1) x 256 bytes a word --, then the walk of rc_batch_window_null on them, lane
+ * = shuffle.  The distinct blocks go in rounds whose codes and permutations fit a budget of device memory, 2 GB by default
+ * (RC_WINSHUFFLE_MAX_BYTES overrides, read per call; a single block may exceed it; the result does not depend on it).  Device memory beside
+ * the budget: 48 bytes per window, 16 bytes per block, 32 bytes and 256 x ceil(n_shuffles / 64) bytes per chunk of the largest round, 4 bytes
+ * x n_shuffles per window when null_out is asked for, and up to 110 MB of scratch for rounds with blocks of more than 22 rows.  One
+ * synchronisation, and one copy back per output array.  RC_WINSHUFFLE_TIMING=1 prints the phases' event times on stderr. */
+int rc_batch_window_shuffle_null(const rc_batch *b, const rc_bt_range *windows, int32_t n_windows, uint32_t seed, int32_t n_shuffles,
+                                 float *score_out /* n_windows */, int32_t *frame_out, int32_t *opt_b_out, int32_t *opt_i_out, int64_t *cells_out,
+                                 int32_t *ge_out /* n_windows */, float *null_out /* may be NULL: [n_windows][n_shuffles] */,
+                                 int64_t cap /* floats in null_out */);
+
 /* The substitution matrix and genetic code the scorer uses, for callers that render results
  * (getScoringMatrix() score.c:50-76 and transcode[4][4][4] code.c:28-39, which src/postscript.c:362,412
  * read): pep_out[16a+4b+c] = amino-acid index 0..19 of codon (a,b,c) in A,C,G,T order or -1 for a stop;

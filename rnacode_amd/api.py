@@ -175,6 +175,8 @@ def lib():
         l.rc_batch_window_best.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.rc_batch_window_null.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_int64]
+        l.rc_batch_window_shuffle_null.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
         l.rc_batch_decoys.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(RcHss), C.c_int64,
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         l.rc_batch_decoys_shuffled.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(RcHss), C.c_int64,
@@ -223,7 +225,7 @@ EXPORTED_SYMBOLS = [
     "rc_batch_prep_timing", "rc_host_cpus", "rc_ctx_set_host_threads", "rc_ctx_host_threads", "rc_ctx_fit_exp_mode", "rc_stream_create_v2", "rc_stream_submit", "rc_stream_submit_bound",
     "rc_stream_next", "rc_stream_recycle", "rc_stream_pending", "rc_stream_plan", "rc_stream_destroy", "rc_set_stream_cache", "rc_batch_work", "rc_batch_timing", "rc_batch_null_kernel", "rc_batch_status",
     "rc_batch_models", "rc_batch_maxima", "rc_batch_maxima_all", "rc_batch_fit", "rc_batch_fit_all", "rc_batch_hss", "rc_batch_hss_all", "rc_batch_clamped",
-    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_batch_segment_scores", "rc_batch_segment_null", "rc_batch_decoys", "rc_batch_decoys_shuffled", "rc_batch_shuffle_null", "rc_batch_segment_shuffle_null", "rc_batch_segment_null_pairs", "rc_batch_segment_shuffle_null_pairs", "rc_batch_window_best", "rc_batch_window_null", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
+    "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_batch_segment_scores", "rc_batch_segment_null", "rc_batch_decoys", "rc_batch_decoys_shuffled", "rc_batch_shuffle_null", "rc_batch_segment_shuffle_null", "rc_batch_segment_null_pairs", "rc_batch_segment_shuffle_null_pairs", "rc_batch_window_best", "rc_batch_window_null", "rc_batch_window_shuffle_null", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
     "rc_code_tables_for", "rc_genetic_code", "rc_species_tree_create", "rc_species_tree_destroy", "rc_species_tree_tips", "rc_species_tree_prune",
     "rc_fit_species_trees", "rc_fit_species_trees_device",
 ]
@@ -794,14 +796,20 @@ class Batch:
                                            null.ctypes.data if matrix else None, n * sample_n if matrix else 0))
         return scores, ge, null
 
-    def _window_call(self, windows, null: bool, matrix: bool):
+    def _window_call(self, windows, null: bool, matrix: bool, shuffles: Optional[Tuple[int, int]] = None):
         arr = np.ascontiguousarray(np.asarray(list(windows), dtype=np.int32).reshape(-1, 4))
         n, sample_n = arr.shape[0], int(self.params.sampleN)
         best = np.zeros(n, dtype=WINDOW_BEST_DTYPE)
         cols = {k: np.zeros(n, dtype=best.dtype[k]) for k in best.dtype.names}   # (the C arrays are contiguous, the record's fields are not)
         head = (self._h, arr.ctypes.data, n, *(cols[k].ctypes.data for k in best.dtype.names))
         ge = mat = None
-        if null:
+        if shuffles is not None:   # (seed, n_shuffles): rc_batch_window_shuffle_null
+            seed, k = shuffles
+            ge = np.zeros(n, dtype=np.int32)
+            mat = np.zeros((n, max(k, 0)), dtype=np.float32) if matrix else None
+            _check(lib().rc_batch_window_shuffle_null(*head[:3], C.c_uint32(seed & 0xFFFFFFFF), k, *head[3:], ge.ctypes.data,
+                                                      mat.ctypes.data if matrix else None, n * max(k, 0) if matrix else 0))
+        elif null:
             ge = np.zeros(n, dtype=np.int32)
             mat = np.zeros((n, sample_n), dtype=np.float32) if matrix else None
             _check(lib().rc_batch_window_null(*head, ge.ctypes.data, mat.ctypes.data if matrix else None, n * sample_n if matrix else 0))
@@ -824,6 +832,18 @@ class Batch:
         samples with null[w][s] >= best["score"][w], int32.  segments.empirical_p(ge, sampleN) is the p of a window named in advance --
         not of an interval picked around a listed HSS.  windows.group_p combines the windows of one transcript in several blocks."""
         return self._window_call(windows, True, matrix)
+
+    def window_shuffle_null(self, windows, n_shuffles: int, seed: Optional[int] = None,
+                            matrix: bool = False) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """rc_batch_window_shuffle_null: (best, ge, null) of all `windows` -- best as window_best gives it; null[w][d] (matrix, else None)
+        the window's value in the gap-class column shuffle of seed seed + d of its block (decoys.shuffle_columns: shuffle d is shuffled
+        decoy d and shuffle d of shuffle_null and segment_shuffle_null), float32 [n][n_shuffles], every cell with segment_shuffle_null's
+        bits; ge[w] the number of shuffles with null[w][d] >= best["score"][w], int32.  segments.empirical_p(ge, n_shuffles) is the p of a
+        window named in advance against its block's own columns.  windows.group_p combines the windows of one transcript in several
+        blocks: shuffle d of the transcript is shuffle d of each of its blocks.  The default seed is seed_base + sampleN."""
+        if seed is None:
+            seed = int(self.params.seed_base) + int(self.params.sampleN)
+        return self._window_call(windows, True, matrix, (int(seed), int(n_shuffles)))
 
     def segment_shuffle_null(self, ranges, n_shuffles: int, seed: Optional[int] = None,
                              matrix: bool = False) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:

@@ -36,8 +36,10 @@ call per null becomes rc_batch_segment_null_pairs / rc_batch_segment_shuffle_nul
 format, any length, any frame; a window is cut to every scored block that overlaps it -- and writes the cut window, that segment, its
 score, the block-wide p and the number of segments the window holds (windows.py; one rc_batch_window_best call per sub-batch).
 --windows-null adds null_ge and p_window = (null_ge + 1) / (n + 1): how many of the -n null alignments hold a segment inside the same window
-that scores at least as high (rc_batch_window_null in that call's place); --windows-summary FILE (with --windows-null) writes one line per
-window id over all its pieces in the run, the exons of a transcript in whatever blocks they lie (windows.group_p's rule).
+that scores at least as high (rc_batch_window_null in that call's place); --windows-shuffle-null N adds shuffle_ge, p_window_shuffled =
+(shuffle_ge + 1) / (N + 1) and movable, the same test against N gap-class column shuffles of the window's block (seeds seed_base + n .., one
+rc_batch_window_shuffle_null call per sub-batch); --windows-summary FILE (with either null) writes one line per window id over all its
+pieces in the run, the exons of a transcript in whatever blocks they lie (windows.group_p's rule).
 --decoys K with --decoys-out FILE (not in the reference) writes the complete listing of K null alignments per scored block, selected by
 --cutoff, -b and -r as the block's own HSS are (decoys.py; one rc_batch_decoys call per sub-batch, seeds seed_base + n ..: the first the
 fit did not see): what `python -m rnacode_amd.decoys` turns into a false discovery rate of the listing.  --decoy-kind shuffled lists, in
@@ -179,8 +181,13 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --windows: two more columns in --windows-out, null_ge = how many of the -n null alignments hold a segment "
                          "inside the same window that scores at least as high, and p_window = (null_ge + 1) / (n + 1), the test for a "
                          "window named in advance (not for an interval picked around a listed HSS)")
+    ap.add_argument("--windows-shuffle-null", type=int, metavar="N",
+                    help="with --windows: three more columns in --windows-out, shuffle_ge = how many of N (1..65536) shuffles of the block "
+                         "-- its own columns, permuted among the columns with the same gap mask -- hold a segment inside the same window "
+                         "that scores at least as high, p_window_shuffled = (shuffle_ge + 1) / (N + 1), and movable = the columns a "
+                         "shuffle can move")
     ap.add_argument("--windows-summary", metavar="FILE",
-                    help="with --windows-null: one line per window id over all its pieces in the run (the exons of a transcript, in "
+                    help="with --windows-null or --windows-shuffle-null: one line per window id over all its pieces in the run (the exons of a transcript, in "
                          "whatever blocks they lie): the best score, null_ge and p_window of the pieces taken together")
     ap.add_argument("--decoys", type=int, metavar="K",
                     help="with --decoys-out: list the HSS of K (1..64) null alignments per scored block, simulated as the samples behind the "
@@ -224,8 +231,12 @@ def _intake(a):
         raise _Refused("--windows and --windows-out go together")
     if a.windows_null and not a.windows:
         raise _Refused("--windows-null needs --windows")
-    if a.windows_summary and not a.windows_null:
-        raise _Refused("--windows-summary needs --windows-null")
+    if a.windows_shuffle_null is not None and not a.windows:
+        raise _Refused("--windows-shuffle-null needs --windows")
+    if a.windows_shuffle_null is not None and not 1 <= a.windows_shuffle_null <= 65536:
+        raise _Refused("--windows-shuffle-null takes a number of shuffles from 1 to 65536")
+    if a.windows_summary and not a.windows_null and a.windows_shuffle_null is None:
+        raise _Refused("--windows-summary needs --windows-null or --windows-shuffle-null")
     if bool(a.regions) != bool(a.regions_out):
         raise _Refused("--regions and --regions-out go together")
     if a.regions_null and not a.regions:
@@ -401,11 +412,16 @@ def _list_batch(run: _Run, batch, base: int) -> None:
                     win_ranges.append((i, 0 if w.strand == "+" else 1, at[0], at[1]))
                 elif at == windows.NO_CODON:
                     w.reason = at   # (what the window's stderr line says if no block has a whole codon for it)
-    win_best = win_ge = win_null = None
+    win_best = win_ge = win_null = win_shuffle_ge = win_shuffle = None
     if win_ranges:
         if a.windows_null:
             win_best, win_ge, win_null = batch.window_null(win_ranges, matrix=run.summary is not None)
-        else:
+        # --windows-shuffle-null: the same windows in the block's own column shuffles with ONE call (rc_batch_window_shuffle_null)
+        if a.windows_shuffle_null is not None:
+            best, win_shuffle_ge, win_shuffle = batch.window_shuffle_null(win_ranges, a.windows_shuffle_null, run.params.seed_base + run.params.sampleN,
+                                                                          matrix=run.summary is not None)
+            win_best = best if win_best is None else win_best
+        if win_best is None:
             win_best = batch.window_best(win_ranges)
     paths = batch.backtrack_many(bt.ranges) if bt.ranges else []
     # --track: the tracks of the blocks the listing covers with ONE call (rc_batch_track)
@@ -461,15 +477,17 @@ def _list_batch(run: _Run, batch, base: int) -> None:
                         (pair_null_ge[rn], run.params.sampleN) if rn >= 0 else None,
                         (pair_shuffle_ge[rs], a.regions_shuffle_null) if rs >= 0 else None))
                 reg.matched = True
+            win_movable = shuffle_null.movable([r.seq for r in b.rows]) if i in win_found and a.windows_shuffle_null is not None else 0
             for w, (_, _, cut_start, cut_end), k in win_found.get(i, ()):
                 rec = win_best[k]
                 frame, c1, c2 = int(rec["frame"]), (int(rec["opt_b"]) - 1) // 3, (int(rec["opt_i"]) - 3) // 3
                 _, _, sg, eg = track.run_coords(w.strand, frame, c1, c2, b.rows[0].start, b.rows[0].length)
                 p = api.pvalue(float(rec["score"]), mu, lam) if rc == 1 else 99.0
                 side["windows_out"].write(windows.window_line(w, cut_start, cut_end, frame, c1, c2, sg, eg, rec["score"], p, int(rec["cells"]),
-                                                              (win_ge[k], run.params.sampleN) if win_ge is not None else None))
+                                                              (win_ge[k], run.params.sampleN) if win_ge is not None else None,
+                                                              (win_shuffle_ge[k], a.windows_shuffle_null, win_movable) if win_shuffle_ge is not None else None))
                 if run.summary is not None:
-                    run.summary.add(w.id, rec["score"], win_null[k])
+                    run.summary.add(w.id, rec["score"], win_null[k] if win_null is not None else None, win_shuffle[k] if win_shuffle is not None else None)
                 w.matched = True
 
 
@@ -518,11 +536,12 @@ def main(argv=None) -> int:
             if getattr(a, name):
                 side[name] = files.enter_context(open(getattr(a, name), "w"))
                 side[name].write(header(null=a.regions_null, shuffle=a.regions_shuffle_null is not None) if name in ("regions_out", "regions_support") else
-                                 header(null=a.windows_null) if name == "windows_out" else header())
+                                 header(null=a.windows_null, shuffle=a.windows_shuffle_null is not None) if name == "windows_out" else
+                                 header(null=a.windows_null, shuffle=a.windows_shuffle_null is not None) if name == "windows_summary" else header())
         code = params.genetic_code.decode()
         run = _Run(a, params, code, api.code_tables(a.blosum, code) if a.details else None, blocks, read_index, refused,
                    segments.by_name(regions) if regions is not None else {}, out, fmt, side,
-                   segments.by_name(wins) if wins is not None else {}, windows.Summary(params.sampleN) if a.windows_summary else None)
+                   segments.by_name(wins) if wins is not None else {}, windows.Summary(params.sampleN if a.windows_null else None, a.windows_shuffle_null) if a.windows_summary else None)
         # the blocks go through the GPU as a stream of sub-batches (rc_stream_*): while one is being scored the next is prepared
         # on the host threads, and the listing of a finished one is written meanwhile (the reference's loop, RNAcode.c:115-221).
         # Sub-batch sizes: --sub-blocks, or the library's schedule (rc_stream_plan: a small first sub-batch, then doubling, whole rounds

@@ -43,6 +43,10 @@
 // every scored block that overlaps them -- ONE rc_batch_window_best call per sub-batch; --windows-null: null_ge and p_window behind every line, ONE
 // rc_batch_window_null call in its place (in the sample split one per slice, the counts added); --windows-summary FILE: one line per window id over
 // all its pieces in the run, the null vectors of the pieces joined by sample index (rc_eps.h, win_clip / window_line / WinSummary; windows.py).
+// --windows-shuffle-null N (with --windows): every --windows-out line ends in shuffle_ge, p_window_shuffled = (shuffle_ge + 1) / (N + 1) and movable,
+// the same test against a null made from the block itself -- the windows of a sub-batch in N gap-class column shuffles of their blocks, seeds
+// seed_base + n .. (the shuffles of --shuffle-null), in ONE rc_batch_window_shuffle_null call (in the sample split one slice's batch gets it with
+// all N shuffles: nothing is added over slices); --windows-summary takes either null, the shuffle vectors joined by shuffle index.
 // --regions-shuffle-null N (with --regions): every --regions-out line ends in shuffle_ge, p_segment_shuffled = (shuffle_ge + 1) / (N + 1) and movable,
 // the same test against a null made from the block itself -- the regions' ranges of a sub-batch in N gap-class column shuffles of their blocks,
 // seeds seed_base + n .. (the shuffles of --shuffle-null), in ONE rc_batch_segment_shuffle_null call (in the sample split one slice's batch
@@ -444,7 +448,8 @@ void usage() {
   std::fprintf(stderr, "usage: rnacode_hip [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S] [-o OUT] [-l SPECIES,...] [--trees SIDECAR]\n"
                        "                   [-e [-i EPS_CUTOFF] [-d EPS_DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null]\n"
                        "                   [--regions-shuffle-null N] [--regions-support FILE]]\n"
-                       "                   [--windows FILE --windows-out FILE [--windows-null [--windows-summary FILE]]]\n"
+                       "                   [--windows FILE --windows-out FILE [--windows-null] [--windows-shuffle-null N]\n"
+                       "                    [--windows-summary FILE]]\n"
                        "                   [--decoys K --decoys-out FILE [--decoy-kind simulated|shuffled]] [--shuffle-null N --shuffle-null-out FILE]\n"
                        "                   [--seed-base S] [--device D | --gpus N [--devices D0,D1,...]] [--sub-blocks B]\n"
                        "                   [--genetic-code ID|LETTERS] [--species-tree NEWICK_FILE [--species-tree-fit fixed|scale|branches]]\n"
@@ -485,8 +490,13 @@ void usage() {
                        "  --windows-null             with --windows: two more columns, null_ge = how many of the -n null alignments hold a segment inside\n"
                        "                             the same window that scores at least as high, p_window = (null_ge + 1) / (n + 1): the test for a\n"
                        "                             window named in advance (not for an interval picked around a listed HSS)\n"
-                       "  --windows-summary FILE     with --windows-null: one line per window id over all its pieces in the run (the exons of a\n"
-                       "                             transcript, in whatever blocks they lie): id pieces score null_ge p_window\n"
+                       "  --windows-shuffle-null N   with --windows: three more columns, shuffle_ge = how many of N (1..65536) shuffles of the block -- its\n"
+                       "                             own columns, permuted among the columns with the same gap mask -- hold a segment inside the same\n"
+                       "                             window that scores at least as high, p_window_shuffled = (shuffle_ge + 1) / (N + 1), movable = the\n"
+                       "                             columns a shuffle can move\n"
+                       "  --windows-summary FILE     with --windows-null or --windows-shuffle-null: one line per window id over all its pieces in the run\n"
+                       "                             (the exons of a transcript, in whatever blocks they lie): id pieces score, then null_ge p_window\n"
+                       "                             and / or shuffle_ge p_window_shuffled\n"
                        "  --decoys K                 with --decoys-out: list the HSS of K (1..64) null alignments per scored block, simulated as the\n"
                        "                             samples behind the p-values are and selected by -p, -b and -r as the block's own\n"
                        "  --decoys-out FILE          the decoy listing, one line per decoy HSS: block decoy strand frame length from to name start\n"
@@ -511,7 +521,7 @@ struct BlockOut {
   std::string track, regions, decoys;  // its --track / --regions-out / --decoys-out lines
   std::string regionSupport;           // its --regions-support lines
   std::string windows;                 // its --windows-out lines
-  struct Piece { int window; float score; std::vector<float> null; };
+  struct Piece { int window; float score; std::vector<float> null, shuffle; };
   std::vector<Piece> pieces;           // --windows-summary: its windows' scores and null vectors, in line order
 };
 
@@ -550,6 +560,7 @@ struct Run {
   std::map<std::string, std::vector<int>> windowsOf;      // reference row name -> the windows that can match a block, in file order
   std::vector<char> windowMatched;                        // set by the writer
   bool windowsNull = false;                               // --windows-null: null_ge and p_window behind every --windows-out line
+  int windowsShuffleNull = 0;                             // --windows-shuffle-null: shuffles scored per window's block (0: off)
   rceps::WinSummary winSummary;                           // --windows-summary: what the ids have so far (the writer's)
   std::vector<std::pair<int, int>> sliceRange;            // the sample split: (first sample, samples) of every slice's batch
   // the writer: one thread, jobs in input order
@@ -602,7 +613,8 @@ void writer_thread(Run &R) {
       if (!o.regionSupport.empty()) std::fwrite(o.regionSupport.data(), 1, o.regionSupport.size(), R.list.side[kRegionSupport].f);
       if (!o.decoys.empty()) std::fwrite(o.decoys.data(), 1, o.decoys.size(), R.list.side[kDecoys].f);
       if (!o.windows.empty()) std::fwrite(o.windows.data(), 1, o.windows.size(), R.list.side[kWindows].f);
-      for (const BlockOut::Piece &pc : o.pieces) R.winSummary.add(R.windows[pc.window].id, pc.score, pc.null.data(), static_cast<int>(pc.null.size()));
+      for (const BlockOut::Piece &pc : o.pieces) R.winSummary.add(R.windows[pc.window].id, pc.score, pc.null.data(), static_cast<int>(pc.null.size()),
+                                                               pc.shuffle.empty() ? nullptr : pc.shuffle.data(), static_cast<int>(pc.shuffle.size()));
     }
     for (int r : j->matched) R.regionMatched[r] = 1;
     for (int r : j->noCodon) if (!R.windowMatched[r]) R.windows[r].reason = rceps::kSegNoCodon;
@@ -851,7 +863,8 @@ bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std
 
 // --windows for every block the listing covers, while the batch is alive: the windows that overlap a block, cut to it (rc_eps.h, win_clip), in
 // ONE rc_batch_window_best call, or with --windows-null ONE rc_batch_window_null call; where the samples were split over several batches, one
-// call per batch, the counts added and -- for --windows-summary -- the null vectors joined by sample index.
+// call per batch, the counts added and -- for --windows-summary -- the null vectors joined by sample index.  --windows-shuffle-null: the same
+// windows in ONE rc_batch_window_shuffle_null call on `b` -- every shuffle is made from the block, not from the samples: nothing to add over slices.
 bool add_windows(const Run &R, rc_batch *b, Job &j, std::string &err, const std::vector<EvdFit> *fits, const std::vector<rc_batch *> *slices) {
   struct Found { int blk, window; rceps::WinClip at; };
   std::vector<Found> found;
@@ -879,9 +892,9 @@ bool add_windows(const Run &R, rc_batch *b, Job &j, std::string &err, const std:
   std::vector<int32_t> frame(nw), optB(nw), optI(nw), ge(nw, 0);
   std::vector<int64_t> cells(nw);
   const bool keep = R.list.on(kWindowSummary);
-  std::vector<float> nullAll(keep ? static_cast<size_t>(nw) * n : 0);
+  std::vector<float> nullAll(keep && R.windowsNull ? static_cast<size_t>(nw) * n : 0);
   if (!R.windowsNull) {
-    if (rc_batch_window_best(b, wins.data(), nw, score.data(), frame.data(), optB.data(), optI.data(), cells.data()) != RC_OK) { err = rc_last_error(); return false; }
+    if (R.windowsShuffleNull == 0 && rc_batch_window_best(b, wins.data(), nw, score.data(), frame.data(), optB.data(), optI.data(), cells.data()) != RC_OK) { err = rc_last_error(); return false; }
   } else if (!slices) {
     if (rc_batch_window_null(b, wins.data(), nw, score.data(), frame.data(), optB.data(), optI.data(), cells.data(), ge.data(), keep ? nullAll.data() : nullptr,
                              static_cast<int64_t>(nullAll.size())) != RC_OK) { err = rc_last_error(); return false; }
@@ -900,6 +913,17 @@ bool add_windows(const Run &R, rc_batch *b, Job &j, std::string &err, const std:
           for (int s = 0; s < w && lo + s < n; s++) nullAll[static_cast<size_t>(k) * n + lo + s] = mat[static_cast<size_t>(k) * w + s];
     }
   }
+  const int N = R.windowsShuffleNull;
+  std::vector<int32_t> shuffleGe(N > 0 ? nw : 0, 0);
+  std::vector<float> shuffleAll(N > 0 && keep ? static_cast<size_t>(nw) * N : 0);
+  std::map<int, int> movableOf;   // block of the batch -> the columns a shuffle can move
+  if (N > 0) {
+    const uint32_t seed = R.par.seed_base + static_cast<uint32_t>(R.par.sampleN);
+    if (rc_batch_window_shuffle_null(b, wins.data(), nw, seed, N, score.data(), frame.data(), optB.data(), optI.data(), cells.data(), shuffleGe.data(),
+                                     keep ? shuffleAll.data() : nullptr, static_cast<int64_t>(shuffleAll.size())) != RC_OK) { err = rc_last_error(); return false; }
+    for (const Found &f : found)
+      if (!movableOf.count(f.blk)) movableOf[f.blk] = movable_columns(R.blocks[j.blocks[f.blk].index]);
+  }
   for (int k = 0; k < nw; k++) {
     const Found &f = found[k];
     EvdFit fit;
@@ -907,8 +931,12 @@ bool add_windows(const Run &R, rc_batch *b, Job &j, std::string &err, const std:
     const float p = fit.rc == 1 ? rc_pvalue(score[k], fit.mu, fit.lambda) : 99.0f;
     const Block &blk = R.blocks[j.blocks[f.blk].index];
     j.blocks[f.blk].windows += rceps::window_line(R.windows[f.window], f.at, frame[k], optB[k], optI[k], blk.rows[0].start, blk.rows[0].length, score[k], p, cells[k],
-                                                  R.windowsNull ? ge[k] : -1, n);
-    if (keep) j.blocks[f.blk].pieces.push_back(BlockOut::Piece{f.window, score[k], std::vector<float>(nullAll.begin() + static_cast<size_t>(k) * n, nullAll.begin() + static_cast<size_t>(k + 1) * n)});
+                                                  R.windowsNull ? ge[k] : -1, n, N > 0 ? shuffleGe[k] : -1, N, N > 0 ? movableOf[f.blk] : 0);
+    if (keep)
+      j.blocks[f.blk].pieces.push_back(BlockOut::Piece{
+          f.window, score[k],
+          R.windowsNull ? std::vector<float>(nullAll.begin() + static_cast<size_t>(k) * n, nullAll.begin() + static_cast<size_t>(k + 1) * n) : std::vector<float>(),
+          N > 0 ? std::vector<float>(shuffleAll.begin() + static_cast<size_t>(k) * N, shuffleAll.begin() + static_cast<size_t>(k + 1) * N) : std::vector<float>()});
     j.matchedWindows.push_back(f.window);
   }
   return true;
@@ -1253,7 +1281,7 @@ int main(int argc, char **argv) {
   Listing &list = R.list;
   std::string file, outfile, trees, limit, devicesArg, speciesFile, writeTrees, regionsFile, windowsFile;
   int device = 0, subBlocks = 0, gpus = 1;   // subBlocks 0: the library's schedule
-  bool dumpBlocks = false, decoysGiven = false, decoyKindGiven = false, shuffleNullGiven = false, regionsShuffleGiven = false;
+  bool dumpBlocks = false, decoysGiven = false, decoyKindGiven = false, shuffleNullGiven = false, regionsShuffleGiven = false, windowsShuffleGiven = false;
   std::string decoyKind;
   for (int a = 1; a < argc; a++) {
     const std::string o = argv[a];
@@ -1310,6 +1338,7 @@ int main(int argc, char **argv) {
     else if (o == "--windows") windowsFile = val();
     else if (o == "--windows-out") list.side[kWindows].path = val();
     else if (o == "--windows-null") R.windowsNull = true;
+    else if (o == "--windows-shuffle-null") { windowsShuffleGiven = true; R.windowsShuffleNull = std::atoi(val()); }
     else if (o == "--windows-summary") list.side[kWindowSummary].path = val();
     else if (o == "--regions-shuffle-null") { regionsShuffleGiven = true; R.regionsShuffleNull = std::atoi(val()); }
     else if (o == "--decoys") { decoysGiven = true; R.decoys = std::atoi(val()); }
@@ -1328,8 +1357,12 @@ int main(int argc, char **argv) {
   if (!regionsFile.empty() != list.on(kRegions)) die("--regions and --regions-out go together");   // before any context exists
   if (!windowsFile.empty() != list.on(kWindows)) die("--windows and --windows-out go together");
   if (R.windowsNull && windowsFile.empty()) die("--windows-null needs --windows");
-  if (list.on(kWindowSummary) && !R.windowsNull) die("--windows-summary needs --windows-null");
-  if (R.windowsNull) list.side[kWindows].header = rceps::windows_header_null;
+  if (windowsShuffleGiven && windowsFile.empty()) die("--windows-shuffle-null needs --windows");
+  if (windowsShuffleGiven && (R.windowsShuffleNull < 1 || R.windowsShuffleNull > 65536)) die("--windows-shuffle-null takes a number of shuffles from 1 to 65536");
+  if (list.on(kWindowSummary) && !R.windowsNull && !windowsShuffleGiven) die("--windows-summary needs --windows-null or --windows-shuffle-null");
+  if (R.windowsNull) list.side[kWindows].header = windowsShuffleGiven ? rceps::windows_header_null_shuffle : rceps::windows_header_null;
+  else if (windowsShuffleGiven) list.side[kWindows].header = rceps::windows_header_shuffle;
+  if (windowsShuffleGiven) list.side[kWindowSummary].header = R.windowsNull ? rceps::windows_summary_header_null_shuffle : rceps::windows_summary_header_shuffle;
   if (R.regionsNull && regionsFile.empty()) die("--regions-null needs --regions");
   if (regionsShuffleGiven && regionsFile.empty()) die("--regions-shuffle-null needs --regions");
   if (list.on(kRegionSupport) && regionsFile.empty()) die("--regions-support needs --regions");
@@ -1578,7 +1611,7 @@ int main(int argc, char **argv) {
   // (RC_CLI_TEARDOWN=1: the orderly way, for leak checkers).
   if (list.out != stdout) std::fclose(list.out);
   if (list.on(kWindowSummary)) {   // one line per id over all its pieces in the run
-    const std::string text = R.winSummary.lines(par.sampleN);
+    const std::string text = R.winSummary.lines(par.sampleN, R.windowsNull, R.windowsShuffleNull);
     std::fwrite(text.data(), 1, text.size(), list.side[kWindowSummary].f);
   }
   for (SideFile &sf : list.side) if (sf.f && std::fclose(sf.f) != 0) die("Could not write " + sf.path);

@@ -458,7 +458,7 @@ inline std::string region_line(const Region &r, const SegLoc &at, float score, f
   return out;
 }
 
-// --windows: the best segment inside named windows and its own null (rc_batch_window_best / rc_batch_window_null).  Same rules and bytes as
+// --windows: the best segment inside named windows and its own nulls (rc_batch_window_best / rc_batch_window_null / rc_batch_window_shuffle_null).  Same rules and bytes as
 // rnacode_amd/windows.py, which documents them.
 struct WinClip { int lo, hi; long long cutStart, cutEnd; };
 // the cells of the window lo..hi (1-based positions of a row of L): per frame the segments with 3 a + f + 1 >= lo and 3 j + f + 3 <= min(hi, L)
@@ -492,10 +492,17 @@ inline SegReason win_clip(char strand, long long start, long long end, long long
 }
 inline const char *windows_header() { return "id\tname\tstrand\tlo\thi\tframe\tfrom\tto\tstart\tend\tscore\tp\tcells\n"; }
 inline const char *windows_header_null() { return "id\tname\tstrand\tlo\thi\tframe\tfrom\tto\tstart\tend\tscore\tp\tcells\tnull_ge\tp_window\n"; }   // --windows-null
+inline const char *windows_header_shuffle() { return "id\tname\tstrand\tlo\thi\tframe\tfrom\tto\tstart\tend\tscore\tp\tcells\tshuffle_ge\tp_window_shuffled\tmovable\n"; }   // --windows-shuffle-null
+inline const char *windows_header_null_shuffle() {
+  return "id\tname\tstrand\tlo\thi\tframe\tfrom\tto\tstart\tend\tscore\tp\tcells\tnull_ge\tp_window\tshuffle_ge\tp_window_shuffled\tmovable\n";
+}
 inline const char *windows_summary_header() { return "id\tpieces\tscore\tnull_ge\tp_window\n"; }
-// frame, optB, optI: the best segment (rc_batch_window_best); ge >= 0 (--windows-null): null_ge and (ge + 1) / (n + 1) behind the line
+inline const char *windows_summary_header_shuffle() { return "id\tpieces\tscore\tshuffle_ge\tp_window_shuffled\n"; }
+inline const char *windows_summary_header_null_shuffle() { return "id\tpieces\tscore\tnull_ge\tp_window\tshuffle_ge\tp_window_shuffled\n"; }
+// frame, optB, optI: the best segment (rc_batch_window_best); ge >= 0 (--windows-null): null_ge and (ge + 1) / (n + 1) behind the line; sge >= 0
+// (--windows-shuffle-null): shuffle_ge, (sge + 1) / (sn + 1) and movable behind that
 inline std::string window_line(const Region &w, const WinClip &at, int frame, int optB, int optI, int refStart, int refLength, float score, float p,
-                               long long cells, int ge = -1, int n = 0) {
+                               long long cells, int ge = -1, int n = 0, int sge = -1, int sn = 0, int movable = 0) {
   const int c1 = (optB - 1) / 3, c2 = (optI - 3) / 3;
   long long sg = optB, eg = optI;   // what ClustalW input (no coordinates) lists
   if (!(refStart == 0 && refLength == 0)) {
@@ -511,30 +518,46 @@ inline std::string window_line(const Region &w, const WinClip &at, int frame, in
     if (score != score) put(out, "\t%i\tnan", ge);
     else put(out, "\t%i\t%.3e", ge, (ge + 1.0) / (n + 1.0));
   }
+  if (sge >= 0) {
+    if (score != score) put(out, "\t%i\tnan", sge);
+    else put(out, "\t%i\t%.3e", sge, (sge + 1.0) / (sn + 1.0));
+    put(out, "\t%i", movable);
+  }
   out += "\n";
   return out;
 }
 // --windows-summary: per id the pieces met so far, the fmax of their scores and the element-wise fmax of their null vectors (windows.Summary)
 struct WinSummary {
-  struct Rec { std::string id; int pieces; float score; std::vector<float> vec; };
+  struct Rec { std::string id; int pieces; float score; std::vector<float> vec, shf; };   // vec: --windows-null's vector, shf: --windows-shuffle-null's
   std::vector<Rec> recs;   // in order of first appearance
   std::map<std::string, size_t> at;
-  void add(const std::string &id, float score, const float *null, int n) {
+  void add(const std::string &id, float score, const float *null, int n, const float *shuffle = nullptr, int sn = 0) {
     const auto it = at.find(id);
-    if (it == at.end()) { at[id] = recs.size(); recs.push_back(Rec{id, 1, score, std::vector<float>(null, null + n)}); return; }
+    if (it == at.end()) {
+      at[id] = recs.size();
+      recs.push_back(Rec{id, 1, score, std::vector<float>(null, null + n), shuffle ? std::vector<float>(shuffle, shuffle + sn) : std::vector<float>()});
+      return;
+    }
     Rec &r = recs[it->second];
     r.pieces++;
     r.score = std::fmax(r.score, score);
     for (int s = 0; s < n; s++) r.vec[static_cast<size_t>(s)] = std::fmax(r.vec[static_cast<size_t>(s)], null[s]);
+    for (int s = 0; shuffle && s < sn; s++) r.shf[static_cast<size_t>(s)] = std::fmax(r.shf[static_cast<size_t>(s)], shuffle[s]);
   }
-  std::string lines(int n) const {
+  // withNull: null_ge and p_window over n; sn > 0: shuffle_ge and p_window_shuffled over the sn shuffles behind them
+  std::string lines(int n, bool withNull = true, int sn = 0) const {
     std::string out;
-    for (const Rec &r : recs) {
+    const auto cols = [&](const Rec &r, const std::vector<float> &v, int m) {
       int ge = 0;
-      for (float v : r.vec) ge += v >= r.score;
+      for (float x : v) ge += x >= r.score;
+      if (r.score != r.score) put(out, "\t%i\tnan", ge);
+      else put(out, "\t%i\t%.3e", ge, (ge + 1.0) / (m + 1.0));
+    };
+    for (const Rec &r : recs) {
       put(out, "%s\t%i\t%s", r.id.c_str(), r.pieces, fmt3(r.score).c_str());
-      if (r.score != r.score) put(out, "\t%i\tnan\n", ge);
-      else put(out, "\t%i\t%.3e\n", ge, (ge + 1.0) / (n + 1.0));
+      if (withNull) cols(r, r.vec, n);
+      if (sn > 0) cols(r, r.shf, sn);
+      out += "\n";
     }
     return out;
   }

@@ -337,6 +337,26 @@ struct WinNullArgs {
 };
 // k_window_null on `grid` workgroups of one wavefront, which stride over the nItems x groups units, then k_window_fold on nFolds x groups
 void launch_window_null(const WinNullArgs &a, int grid, size_t ldsBytes, hipStream_t stream);
+void launch_window_fold(const WinNullArgs &a, hipStream_t stream);   // k_window_fold alone
+// rc_batch_window_shuffle_null (rc_window_shuffle.hip): the windows' values in every column shuffle.  k_window_shuffle_codes writes, from the
+// permutations k_shuffle_perm has left (slots as for ShuffleNullArgs), the sigma codes of item u = (position p of `blocks`) x groups + g at
+// codesAll + u * codesStride -- only the words spans[p] names, in the compact layout of rc_window_shuffle_plan.h; k_window_shuffle is
+// k_window_null on those items (WinNullArgs as above, sampleN = the number of shuffles), then k_window_fold.
+struct WinSpan;
+struct WinShuffleCodesArgs {
+  const uint8_t *blob;
+  const DevBlock *dblocks;
+  const int *blocks;          // [nBlocks] batch indices of the round
+  const WinSpan *spans;       // [nBlocks] the words each block's windows read, per strand
+  const uint8_t *pair;        // [64][64] codon pair -> sigma code
+  const uint8_t *permAll;
+  size_t permStride;
+  uint8_t *codesAll;
+  size_t codesStride;
+  int nBlocks, groups, nShuffles;
+};
+void launch_window_shuffle_codes(const WinShuffleCodesArgs &a, int seqParts, hipStream_t stream);   // nBlocks x groups workgroups of one wavefront, times seqParts shares of the sequences
+void launch_window_shuffle(const WinNullArgs &a, const WinSpan *spans, int grid, size_t ldsBytes, hipStream_t stream);
 // rc_batch_decoys (rc_decoys.hip): the codes k_generic_sim<false> has left at codesAll for a round of blocks (position p of `blocks`: one item
 // of one sample group, lane = decoy, at p * codesStride) expanded into native-format sigma tables f32 [2][NK][L + 1], decoy d of position p at
 // sigmaAll + (p * nDecoys + d) * sigmaStride.  vblocks / vflags [p * nDecoys + d]: the block's header with off_sigma aimed at that table, and

@@ -5,6 +5,7 @@
 #include "rc_shuffle_plan.h"
 #include "rc_shuffle_null_plan.h"
 #include "rc_window_plan.h"
+#include "rc_window_shuffle_plan.h"
 
 extern "C" {
 
@@ -721,17 +722,8 @@ struct WinOuts {
 };
 static_assert(sizeof(WinItem) == 8 * sizeof(int32_t) && sizeof(WinFold) == 4 * sizeof(int32_t) && sizeof(WinBox) == 8 * sizeof(int32_t), "packed as int32 words");
 
-static int window_call(const rc_batch *bc, const rc_bt_range *windows, int32_t n_windows, const WinOuts &o, bool withNull) {
-  rc_batch *b = const_cast<rc_batch *>(bc);
-  if (!b || n_windows < 0 || (n_windows > 0 && (!windows || !o.score || (withNull && !o.ge)))) return fail(RC_ERR_ARG, "bad argument");
-  if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
-  const int sampleN = b->par.sampleN, groups = (sampleN + kWave - 1) / kWave, Spad = groups * kWave;
-  if (withNull && o.null && o.cap < static_cast<int64_t>(n_windows) * sampleN)
-    return fail(RC_ERR_ARG, "null_out too small: " + std::to_string(static_cast<int64_t>(n_windows) * sampleN) + " values");
-  // every window is checked, and the plan made, before anything touches the device (or the caller's arrays)
-  const size_t nw = static_cast<size_t>(n_windows);
-  std::vector<WinBox> boxes(nw);
-  std::vector<WinGeom> geom(nw);
+// every window of a call checked, its cells and its box for k_window_best: rc_batch_window_best / _null / _shuffle_null's rules and messages
+static int window_boxes(const rc_batch *b, const rc_bt_range *windows, int32_t n_windows, std::vector<WinBox> &boxes, std::vector<WinGeom> &geom) {
   for (int w = 0; w < n_windows; w++) {
     const rc_bt_range &g = windows[w];
     const std::string who = "window " + std::to_string(w);
@@ -745,6 +737,21 @@ static int window_call(const rc_batch *bc, const rc_bt_range *windows, int32_t n
     boxes[w].blk = g.blk; boxes[w].strand = g.strand;
     for (int f = 0; f < 3; f++) { boxes[w].aLo[f] = geom[w].aLo[f]; boxes[w].jHi[f] = geom[w].jHi[f]; }
   }
+  return RC_OK;
+}
+
+static int window_call(const rc_batch *bc, const rc_bt_range *windows, int32_t n_windows, const WinOuts &o, bool withNull) {
+  rc_batch *b = const_cast<rc_batch *>(bc);
+  if (!b || n_windows < 0 || (n_windows > 0 && (!windows || !o.score || (withNull && !o.ge)))) return fail(RC_ERR_ARG, "bad argument");
+  if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
+  const int sampleN = b->par.sampleN, groups = (sampleN + kWave - 1) / kWave, Spad = groups * kWave;
+  if (withNull && o.null && o.cap < static_cast<int64_t>(n_windows) * sampleN)
+    return fail(RC_ERR_ARG, "null_out too small: " + std::to_string(static_cast<int64_t>(n_windows) * sampleN) + " values");
+  // every window is checked, and the plan made, before anything touches the device (or the caller's arrays)
+  const size_t nw = static_cast<size_t>(n_windows);
+  std::vector<WinBox> boxes(nw);
+  std::vector<WinGeom> geom(nw);
+  RC_TRY(window_boxes(b, windows, n_windows, boxes, geom));
   if (n_windows == 0) return RC_OK;
   rc_ctx *c = b->ctx;
   // the null side's plan: the windows by block, the blocks in rounds, per round the items (chunks of rows) and the folds (windows)
@@ -1594,6 +1601,196 @@ int rc_batch_segment_shuffle_null_pairs(const rc_batch *b, const rc_bt_range *ra
                                         float *pair_null_out, int64_t null_cap) {
   const SegPairsOut po{pair_out, pair_ge_out, cap, offsets, pair_null_out, null_cap};
   return segment_shuffle_call(b, ranges, n_ranges, seed, n_shuffles, score_out, ge_out, nullptr, 0, &po);
+}
+
+// Named windows under the shuffle null (rc_window_shuffle.hip): the value of every window -- the fmaxf of its cells -- in n_shuffles gap-class
+// column shuffles of its block, and how many of them reach the window's own value.  The checks and the block's own side are
+// rc_batch_window_best's (k_window_best, once); the windows are grouped by block and cut into chunks as for rc_batch_window_null, the distinct
+// blocks walked in rounds under a budget (rc_window_shuffle_plan.h): per round k_shuffle_perm leaves every (block, shuffle)'s permutation --
+// the classes from the host, the sort in pieces, the slots where rc_batch_shuffle_null has them --, k_window_shuffle_codes the sigma codes of
+// the words the block's windows read, in the compact item, and k_window_shuffle / k_window_fold the values and the counts.  No MT19937 stream is
+// touched and nothing of the batch written.
+int rc_batch_window_shuffle_null(const rc_batch *bc, const rc_bt_range *windows, int32_t n_windows, uint32_t seed, int32_t n_shuffles,
+                                 float *score_out, int32_t *frame_out, int32_t *opt_b_out, int32_t *opt_i_out, int64_t *cells_out, int32_t *ge_out,
+                                 float *null_out, int64_t cap) {
+  rc_batch *b = const_cast<rc_batch *>(bc);
+  if (!b || n_windows < 0 || (n_windows > 0 && (!windows || !score_out || !ge_out))) return fail(RC_ERR_ARG, "bad argument");
+  if (n_shuffles < 1 || n_shuffles > kShuffleNullMax) return fail(RC_ERR_ARG, "the number of shuffles must be 1..65536");
+  if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
+  const int n = n_shuffles, groups = (n + kWave - 1) / kWave;
+  if (null_out && cap < static_cast<int64_t>(n_windows) * n)
+    return fail(RC_ERR_ARG, "null_out too small: " + std::to_string(static_cast<int64_t>(n_windows) * n) + " values");
+  // every window is checked, and the plan made, before anything touches the device (or the caller's arrays)
+  const size_t nw = static_cast<size_t>(n_windows);
+  std::vector<WinBox> boxes(nw);
+  std::vector<WinGeom> geom(nw);
+  RC_TRY(window_boxes(b, windows, n_windows, boxes, geom));
+  if (n_windows == 0) return RC_OK;
+  rc_ctx *c = b->ctx;
+  size_t budget = kShuffleNullMaxBytes;
+  if (const char *e = std::getenv("RC_WINSHUFFLE_MAX_BYTES")) budget = static_cast<size_t>(std::max(1ll, std::atoll(e)));
+  ShuffleFill fill(b, seed, 1);
+  // the windows by block (the grouping of rc_segnull_plan.h; its rounds are not used), then each block's span and the rounds
+  const SegNullPlan pl = seg_null_plan(n_windows, [&](int r) { return windows[r].blk; }, [](int) { return static_cast<size_t>(0); }, groups, 0);
+  const size_t nb = pl.blocks.size();
+  RC_TRY(fill.plan(pl.blocks));   // the classes of every distinct block, on the host
+  std::vector<WinSpan> spans(nb, win_span_none());
+  for (size_t p = 0; p < nb; p++)
+    for (int q = pl.blkStart[p]; q < pl.blkStart[p + 1]; q++) {
+      const int w = pl.rangeIdx[static_cast<size_t>(q)];
+      win_span_add(spans[p], windows[w].strand, geom[static_cast<size_t>(w)]);
+    }
+  const std::vector<ShuffleNullRound> plan = window_shuffle_plan(static_cast<int>(nb), [&](int p) {
+    const int blk = pl.blocks[static_cast<size_t>(p)];
+    return ShuffleNullCost{win_span_bytes(spans[static_cast<size_t>(p)], b->meta[blk].NK), fill.slot_bytes(b->meta[blk].cols)};
+  }, n, budget);
+  struct Round { size_t item0, nItems, fold0, nFolds, slots, sortLds; int maxNK, grid, sortThreads, seqParts; bool lds; };
+  std::vector<WinItem> items;
+  std::vector<WinFold> folds;
+  std::vector<Round> rounds;
+  size_t codesNeed = 0, permNeed = 0, partialNeed = 0, scratchNeed = 0;
+  for (const ShuffleNullRound &rd : plan) {
+    Round R{items.size(), 0, folds.size(), 0, 0, 0, 0, 0, 0, 0, false};
+    for (int p = rd.first; p < rd.first + rd.count; p++) {
+      R.maxNK = std::max(R.maxNK, b->meta[pl.blocks[static_cast<size_t>(p)]].NK);
+      for (int q = pl.blkStart[static_cast<size_t>(p)]; q < pl.blkStart[static_cast<size_t>(p) + 1]; q++) {
+        const int w = pl.rangeIdx[static_cast<size_t>(q)];
+        const size_t slot0 = R.slots;
+        window_chunks(geom[static_cast<size_t>(w)], kWindowChunkCells, [&](int f, int aBeg, int aEnd, int jHi) {
+          items.push_back(WinItem{p - rd.first, windows[w].strand, f, aBeg, aEnd, jHi, static_cast<int32_t>(R.slots++), 0});
+        });
+        folds.push_back(WinFold{w, static_cast<int32_t>(slot0), static_cast<int32_t>(R.slots), 0});
+      }
+    }
+    R.nItems = items.size() - R.item0; R.nFolds = folds.size() - R.fold0;
+    if (R.slots * groups > static_cast<size_t>(INT32_MAX)) return fail(RC_ERR_ARG, "more than 2^31 - 1 (chunk of a window, shuffle group) units in one round");
+    fill.sort_launch(rd.first, rd.count, R.sortLds, R.sortThreads);
+    const long long citems = static_cast<long long>(rd.count) * groups;
+    // few items: the sequences of an item over several workgroups of k_window_shuffle_codes (as rc_batch_shuffle_null sizes k_shuffle_codes)
+    R.seqParts = static_cast<int>(std::max<long long>(1, std::min<long long>({static_cast<long long>(R.maxNK), 64, static_cast<long long>(c->numCU) * 8 / citems})));
+    R.lds = R.maxNK <= kWinLdsMaxNK;
+    R.grid = static_cast<int>(std::min<size_t>(R.nItems * groups, R.lds ? 16384 : 2048));
+    codesNeed = std::max(codesNeed, static_cast<size_t>(citems) * rd.codesStride);
+    permNeed = std::max(permNeed, static_cast<size_t>(rd.count) * n * rd.permStride);
+    partialNeed = std::max(partialNeed, R.slots * groups * kWave * sizeof(float));
+    if (!R.lds) scratchNeed = std::max(scratchNeed, static_cast<size_t>(R.grid) * win_park_floats(R.maxNK) * sizeof(float));
+    rounds.push_back(R);
+  }
+  // one upload: the boxes, the distinct blocks, their spans, the items, the folds
+  static_assert(sizeof(WinSpan) == 4 * sizeof(int32_t), "packed as int32 words");
+  const size_t oBoxes = 0, oBlocks = oBoxes + 8 * nw, oSpans = oBlocks + nb, oItems = oSpans + 4 * nb, oFolds = oItems + 8 * items.size(),
+               upWords = oFolds + 4 * folds.size();
+  std::vector<int32_t> up(upWords);
+  std::memcpy(up.data() + oBoxes, boxes.data(), nw * sizeof(WinBox));
+  std::memcpy(up.data() + oBlocks, pl.blocks.data(), nb * sizeof(int32_t));
+  std::memcpy(up.data() + oSpans, spans.data(), nb * sizeof(WinSpan));
+  std::memcpy(up.data() + oItems, items.data(), items.size() * sizeof(WinItem));
+  std::memcpy(up.data() + oFolds, folds.data(), folds.size() * sizeof(WinFold));
+  std::vector<float> score(nw);
+  std::vector<int32_t> pos(3 * nw), ge(nw);
+  HIP_TRY(hipSetDevice(c->device));
+  RC_STREAM_TRY(st, stream_aux(c));
+  HIP_TRY(hipEventSynchronize(b->evPrep));   // the tables of the blob are made on the device
+  DevBuf d_up, d_best, d_ge, d_codes, d_null, d_partial, d_scratch;
+  adopt_bufs(c, {&d_up, &d_best, &d_ge, &d_codes, &d_null, &d_partial, &d_scratch});
+  const uint8_t *blob = b->dblob.as<uint8_t>();
+  bool launched = false;
+  // RC_WINSHUFFLE_TIMING=1 (tools/time_window_shuffle.py): events between the phases of every round, their sums on stderr
+  const bool timing = std::getenv("RC_WINSHUFFLE_TIMING") != nullptr;
+  std::vector<hipEvent_t> marks;   // per round: in front of the sort, behind it, behind the codes, behind the walk and the fold
+  const auto mark = [&]() -> int {
+    if (!timing) return RC_OK;
+    hipEvent_t e = nullptr;
+    HIP_TRY(hipEventCreate(&e));
+    marks.push_back(e);
+    HIP_TRY(hipEventRecord(e, st));
+    return RC_OK;
+  };
+  // (a lambda: whatever fails in it, nothing returns to the caller -- who owns the outputs, while the vectors and the buffers die with this
+  // frame -- before the work already queued on the stream has drained)
+  const int rc = [&]() -> int {
+    HIP_TRY(d_up.ensure(up.size() * sizeof(int32_t)));
+    HIP_TRY(d_best.ensure(4 * nw * sizeof(float)));   // the scores, then the positions
+    HIP_TRY(d_ge.ensure(nw * sizeof(int32_t)));
+    RC_TRY(fill.ensure(permNeed));
+    HIP_TRY(d_codes.ensure(std::max<size_t>(codesNeed, 4)));
+    HIP_TRY(d_partial.ensure(std::max<size_t>(partialNeed, 4)));
+    if (scratchNeed) HIP_TRY(d_scratch.ensure(scratchNeed));
+    if (null_out) HIP_TRY(d_null.ensure(nw * static_cast<size_t>(n) * sizeof(float)));
+    launched = true;   // from here on something may be in flight
+    RC_TRY(fill.begin(st, nullptr));   // the class arrays go up
+    HIP_TRY(hipMemcpyAsync(d_up.p, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_ge.p, 0, nw * sizeof(int32_t), st));
+    WinBestArgs wb{};
+    wb.blob = blob; wb.dblocks = reinterpret_cast<const DevBlock *>(blob + b->oDblocks); wb.flags = b->dflags.as<uint32_t>();
+    wb.boxes = reinterpret_cast<const WinBox *>(d_up.as<int>() + oBoxes);
+    wb.score = d_best.as<float>(); wb.pos = reinterpret_cast<int32_t *>(d_best.as<float>() + nw); wb.nWindows = n_windows;
+    launch_window_best(wb, st);
+    HIP_TRY(hipGetLastError());
+    ShuffleArgs sa = fill.sa;
+    WinShuffleCodesArgs ca{};
+    ca.blob = blob; ca.dblocks = wb.dblocks; ca.pair = sa.pair; ca.permAll = fill.d_perm.as<uint8_t>(); ca.codesAll = d_codes.as<uint8_t>();
+    ca.groups = groups; ca.nShuffles = n;
+    WinNullArgs wn{};
+    wn.blob = blob; wn.dblocks = wb.dblocks; wn.flags = wb.flags;
+    wn.scores = wb.score; wn.ge = d_ge.as<int>(); wn.nullOut = null_out ? d_null.as<float>() : nullptr;
+    wn.partial = d_partial.as<float>(); wn.codesAll = d_codes.as<uint8_t>(); wn.groups = groups; wn.sampleN = n;
+    for (size_t r = 0; r < rounds.size(); r++) {
+      const ShuffleNullRound &rd = plan[r];
+      const Round &R = rounds[r];
+      sa.blocks = d_up.as<int>() + oBlocks + rd.first; sa.clsAt = fill.d_cls.as<long long>() + rd.first; sa.permStride = rd.permStride;
+      RC_TRY(mark());
+      for (int piece = 0; piece * kShuffleNullPiece < n; piece++) {
+        sa.permAll = fill.d_perm.as<uint8_t>() + shuffle_null_piece_at(rd.count, piece) * rd.permStride;
+        sa.nDecoys = shuffle_null_piece_count(n, piece);
+        sa.seed = seed + static_cast<uint32_t>(piece) * kShuffleNullPiece;
+        launch_shuffle_perm(sa, rd.count, R.sortLds, R.sortThreads, st);
+        HIP_TRY(hipGetLastError());
+      }
+      RC_TRY(mark());
+      const WinSpan *dspans = reinterpret_cast<const WinSpan *>(d_up.as<int>() + oSpans) + rd.first;
+      ca.blocks = sa.blocks; ca.spans = dspans; ca.nBlocks = rd.count; ca.permStride = rd.permStride; ca.codesStride = rd.codesStride;
+      launch_window_shuffle_codes(ca, R.seqParts, st);
+      HIP_TRY(hipGetLastError());
+      RC_TRY(mark());
+      wn.blocks = sa.blocks; wn.codesStride = rd.codesStride;
+      wn.items = reinterpret_cast<const WinItem *>(d_up.as<int>() + oItems) + R.item0; wn.nItems = static_cast<int>(R.nItems);
+      wn.folds = reinterpret_cast<const WinFold *>(d_up.as<int>() + oFolds) + R.fold0; wn.nFolds = static_cast<int>(R.nFolds);
+      wn.scratch = R.lds ? nullptr : d_scratch.as<float>(); wn.parkStride = win_park_floats(R.maxNK);
+      launch_window_shuffle(wn, dspans, R.grid, R.lds ? win_park_floats(R.maxNK) * sizeof(float) : 0, st);
+      HIP_TRY(hipGetLastError());
+      RC_TRY(mark());
+    }
+    HIP_TRY(hipMemcpyAsync(ge.data(), d_ge.p, nw * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (null_out) HIP_TRY(hipMemcpyAsync(null_out, d_null.p, nw * static_cast<size_t>(n) * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(score.data(), d_best.p, nw * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(pos.data(), d_best.as<float>() + nw, 3 * nw * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // (the streams are non-blocking: nothing else would wait for the copies)
+    return RC_OK;
+  }();
+  if (rc != RC_OK && launched) (void)hipStreamSynchronize(st);
+  if (rc == RC_OK && marks.size() == 4 * rounds.size()) {
+    float ms[3] = {0.0f, 0.0f, 0.0f}, t = 0.0f;
+    for (size_t r = 0; r < rounds.size(); r++)
+      for (int ph = 0; ph < 3; ph++)
+        if (hipEventElapsedTime(&t, marks[4 * r + ph], marks[4 * r + ph + 1]) == hipSuccess) ms[ph] += t;
+    size_t codeBytes = 0;
+    for (size_t r = 0; r < rounds.size(); r++) codeBytes += static_cast<size_t>(plan[r].count) * groups * plan[r].codesStride;
+    std::fprintf(stderr, "[rc] window_shuffle: windows=%d blocks=%zu shuffles=%d rounds=%zu codes_bytes=%zu k_shuffle_perm=%.3f k_window_shuffle_codes=%.3f k_window_shuffle=%.3f ms\n",
+                 n_windows, nb, n, rounds.size(), codeBytes, ms[0], ms[1], ms[2]);
+  }
+  for (hipEvent_t e : marks) (void)hipEventDestroy(e);
+  if (rc != RC_OK) return rc;
+  for (size_t w = 0; w < nw; w++) {
+    const int f = pos[3 * w], a = pos[3 * w + 1], j = pos[3 * w + 2];
+    score_out[w] = score[w];
+    if (frame_out) frame_out[w] = f;
+    if (opt_b_out) opt_b_out[w] = 3 * a + f + 1;
+    if (opt_i_out) opt_i_out[w] = 3 * j + f + 3;
+    if (cells_out) cells_out[w] = geom[w].cells;
+  }
+  std::memcpy(ge_out, ge.data(), nw * sizeof(int32_t));
+  return RC_OK;
 }
 
 int rc_code_tables(int32_t blosum, int32_t pep_out[64], int32_t matrix_out[400]) {

@@ -17,9 +17,17 @@ window_summary_line) follows the same rules and writes the same bytes.
   --windows-null      two more columns, null_ge and p_window = (null_ge + 1) / (n + 1): how many of the run's n null alignments have a
                       segment inside the same window that scores at least as high.  Valid for a window named without looking at the
                       scores; NOT for an interval picked around a listed HSS.
+  --windows-shuffle-null N   three more columns (behind --windows-null's), COLUMNS_SHUFFLE: shuffle_ge, how many of N gap-class column shuffles
+                      of the window's block (seeds seed_base + n .., the shuffles of --shuffle-null; Batch.window_shuffle_null) have a segment
+                      inside the same window that scores at least as high, p_window_shuffled = (shuffle_ge + 1) / (N + 1), and movable, the
+                      columns of the block a shuffle can move (shuffle_null.movable).  The null made from the data: valid, like p_window,
+                      for a window named without looking at the scores.
   --windows-summary   one line per id, in order of first appearance, COLUMNS_SUMMARY, over all pieces of that id in the run (group_p): the
                       test of a transcript whose exons lie in different blocks.  Sample s of different blocks comes from independent
                       simulations, so the element-wise maximum of the pieces' null vectors is the null of the maximum of their scores.
+                      With --windows-shuffle-null the line has (also, or only) shuffle_ge and p_window_shuffled by the same rule: shuffle d
+                      of a transcript is shuffle d of each of its blocks -- the joint shuffle --, so the element-wise maximum of the
+                      pieces' shuffle vectors is the transcript's value in shuffle d.
   NaN prints as `nan` whatever its sign.
 """
 from __future__ import annotations
@@ -32,17 +40,19 @@ from .segments import MALFORMED, NO_BLOCK, OUTSIDE, Region, _int, fmt3
 
 COLUMNS = ("id", "name", "strand", "lo", "hi", "frame", "from", "to", "start", "end", "score", "p", "cells")
 COLUMNS_NULL = ("null_ge", "p_window")   # --windows-null: behind COLUMNS
+COLUMNS_SHUFFLE = ("shuffle_ge", "p_window_shuffled", "movable")   # --windows-shuffle-null: behind COLUMNS and COLUMNS_NULL
 COLUMNS_SUMMARY = ("id", "pieces", "score", "null_ge", "p_window")
+COLUMNS_SUMMARY_SHUFFLE = ("shuffle_ge", "p_window_shuffled")      # --windows-summary with --windows-shuffle-null: behind the columns it has
 
 NO_CODON = "no whole codon inside"
 
 
-def header(null: bool = False) -> str:
-    return "\t".join(COLUMNS + (COLUMNS_NULL if null else ())) + "\n"
+def header(null: bool = False, shuffle: bool = False) -> str:
+    return "\t".join(COLUMNS + (COLUMNS_NULL if null else ()) + (COLUMNS_SHUFFLE if shuffle else ())) + "\n"
 
 
-def summary_header() -> str:
-    return "\t".join(COLUMNS_SUMMARY) + "\n"
+def summary_header(null: bool = True, shuffle: bool = False) -> str:
+    return "\t".join((COLUMNS_SUMMARY if null else COLUMNS_SUMMARY[:3]) + (COLUMNS_SUMMARY_SHUFFLE if shuffle else ())) + "\n"
 
 
 def read_windows(lines: Sequence[str]) -> List[Region]:
@@ -116,18 +126,23 @@ def _p_text(score, ge: int, n: int) -> str:
 
 
 def window_line(win: Region, cut_start: int, cut_end: int, frame: int, c1: int, c2: int, seg_start: int, seg_end: int, score, p, n_cells: int,
-                null: Optional[Tuple[int, int]] = None) -> str:
+                null: Optional[Tuple[int, int]] = None, shuffle: Optional[Tuple[int, int, int]] = None) -> str:
     """One --windows-out line.  frame, c1, c2: the best segment's frame and codons (0-based); seg_start / seg_end: its coordinates as the
-    listing prints them (track.run_coords); null: (ge, n) of --windows-null, or None: the line without the two columns."""
+    listing prints them (track.run_coords); null: (ge, n) of --windows-null, or None: the line without the two columns; shuffle: (ge, N,
+    movable) of --windows-shuffle-null, or None: the line without the three columns."""
     line = "%s\t%s\t%s\t%i\t%i\t%i\t%i\t%i\t%i\t%i\t%s\t%.3e\t%i" % (win.id, win.name, win.strand, cut_start, cut_end, frame + 1, c1 + 1, c2 + 1,
                                                                     seg_start, seg_end, fmt3(score), float(np.float32(p)), n_cells)
     if null is not None:
         line += _p_text(score, int(null[0]), int(null[1]))
+    if shuffle is not None:
+        line += _p_text(score, int(shuffle[0]), int(shuffle[1])) + "\t%i" % int(shuffle[2])
     return line + "\n"
 
 
 def group_null(null_rows) -> np.ndarray:
-    """The null vector of a group of windows (the pieces of one id): the element-wise np.fmax of the pieces' null vectors, float32 [n]."""
+    """The null vector of a group of windows (the pieces of one id): the element-wise np.fmax of the pieces' null vectors, float32 [n].
+    The same rule holds for the pieces' shuffle vectors (Batch.window_shuffle_null's rows): shuffle d of a transcript is shuffle d of each
+    of its blocks, the joint shuffle."""
     rows = np.ascontiguousarray(null_rows, dtype=np.float32)
     if rows.ndim != 2 or rows.shape[0] == 0:
         raise ValueError("null_rows: one row of n null values per piece")
@@ -144,31 +159,42 @@ def group_p(scores, null_rows) -> Tuple[np.float32, int, float]:
     return np.float32(score), ge, (ge + 1.0) / (g.shape[0] + 1.0)
 
 
-def summary_line(wid: str, pieces: int, score, ge: int, n: int) -> str:
-    return "%s\t%i\t%s%s\n" % (wid, pieces, fmt3(score), _p_text(score, int(ge), int(n)))
+def summary_line(wid: str, pieces: int, score, ge: Optional[int], n: int, shuffle: Optional[Tuple[int, int]] = None) -> str:
+    """One --windows-summary line: (ge, n) of --windows-null (ge None: without those two columns), shuffle = (ge, N) of
+    --windows-shuffle-null behind them."""
+    return "%s\t%i\t%s%s%s\n" % (wid, pieces, fmt3(score), _p_text(score, int(ge), int(n)) if ge is not None else "",
+                                 _p_text(score, int(shuffle[0]), int(shuffle[1])) if shuffle is not None else "")
+
+
+def _reach(vec: np.ndarray, score) -> int:
+    with np.errstate(invalid="ignore"):
+        return int((vec >= score).sum())
 
 
 class Summary:
-    """--windows-summary across the sub-batches of a run: per id the number of pieces, the fmax of their scores and one vector of n floats,
-    the element-wise fmax of their null vectors (group_p's rule, a piece at a time)."""
+    """--windows-summary across the sub-batches of a run: per id the number of pieces, the fmax of their scores and, per null, one vector of
+    floats, the element-wise fmax of the pieces' vectors (group_p's rule, a piece at a time).  n: the run's null alignments (None: no
+    --windows-null); n_shuffles: --windows-shuffle-null's N (None: without it)."""
 
-    def __init__(self, n: int):
-        self.n, self.order, self.by_id = int(n), [], {}
+    def __init__(self, n: Optional[int], n_shuffles: Optional[int] = None):
+        self.n, self.n_shuffles, self.order, self.by_id = (int(n) if n is not None else None), n_shuffles, [], {}
 
-    def add(self, wid: str, score, null_row) -> None:
-        row = np.ascontiguousarray(null_row, dtype=np.float32)
+    def add(self, wid: str, score, null_row=None, shuffle_row=None) -> None:
+        rows = [np.array(r, dtype=np.float32) if r is not None else None for r in (null_row, shuffle_row)]
         if wid not in self.by_id:
             self.order.append(wid)
-            self.by_id[wid] = [1, np.float32(score), row.copy()]
+            self.by_id[wid] = [1, np.float32(score), *rows]
         else:
             rec = self.by_id[wid]
-            rec[0], rec[1], rec[2] = rec[0] + 1, np.fmax(rec[1], np.float32(score)), np.fmax(rec[2], row)
+            rec[0], rec[1] = rec[0] + 1, np.fmax(rec[1], np.float32(score))
+            for k, row in enumerate(rows, 2):
+                if row is not None:
+                    rec[k] = np.fmax(rec[k], row)
 
     def lines(self) -> List[str]:
         out = []
         for wid in self.order:
-            pieces, score, vec = self.by_id[wid]
-            with np.errstate(invalid="ignore"):
-                ge = int((vec >= score).sum())
-            out.append(summary_line(wid, pieces, score, ge, self.n))
+            pieces, score, vec, shf = self.by_id[wid]
+            out.append(summary_line(wid, pieces, score, _reach(vec, score) if vec is not None else None, self.n or 0,
+                                    (_reach(shf, score), self.n_shuffles) if shf is not None else None))
         return out
