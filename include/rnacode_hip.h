@@ -420,6 +420,49 @@ int rc_batch_window_null(const rc_batch *b, const rc_bt_range *windows, int32_t 
                          int32_t *frame_out, int32_t *opt_b_out, int32_t *opt_i_out, int64_t *cells_out, int32_t *ge_out /* n_windows */,
                          float *null_out /* may be NULL: [n_windows][sampleN] */, int64_t cap /* floats in null_out */);
 
+/* The anchored null: named segments and windows GIVEN THE REFERENCE ROW.  A candidate open reading frame is named by looking at the reference
+ * sequence -- ATG to stop, no stop in between -- and every other null redraws that row: in a null alignment of rc_batch_segment_null a
+ * 20-codon segment's frame holds a reference stop with probability 1 - (61/64)^20 = 0.62, each costing stopPenalty_0, so most samples
+ * cannot reach the segment's score for a reason that has nothing to do with how the other species evolved, and the segment is credited
+ * for the property it was selected by.  These calls keep the reference row as it is and simulate only the other rows: HKY85 is
+ * reversible, so rooting the block's tree at the reference tip, starting from the observed base and evolving outwards is exact.
+ *   T' = the block's tree T rooted at a new node rho on the reference tip's edge, at distance 0 from the tip.  rho's children are the
+ *        reference tip on a branch of length 0, then the tip's neighbour in T on the tip's branch.  Every other node keeps its neighbours
+ *        in T's text order minus the one it is entered from: its children, or its other children and then its former parent on the
+ *        node's own former branch; the two-child root of a rooted T is dissolved, its two branches summed as doubles.  T' is rooted and
+ *        binary, 2N - 1 nodes (rc_anchor_newick writes it).
+ *   Anchored sample s = the run's own simulation on T': nodes in T''s text pre-order, node q's draw at column c the draw q * cols + c of
+ *        MT19937 seeded seed_base + s, thresholds from the block's forward frequencies and kappa -- except that where the reference row
+ *        holds A, C, G, T or U (either case) at a column, rho's state there is that base: its draw is consumed unused and counts no
+ *        clamp.  At any other letter (N, IUPAC) rho is drawn.  Gap pattern, models, score tables and scoring are the block's own.
+ * So for a block whose reference row holds no nucleotide letter, anchored sample s is the plain simulation of T'; and for a block whose
+ * reference row is what that simulation gives the reference tip in sample s, anchored sample s is that sample.
+ * rc_batch_segment_null_anchored, rc_batch_segment_null_pairs_anchored and rc_batch_window_null_anchored are rc_batch_segment_null,
+ * rc_batch_segment_null_pairs and rc_batch_window_null on these samples: signatures, range and window rules, outputs, errors, rounds,
+ * budget (RC_SEGNULL_MAX_BYTES) and "leaves the batch as it is" are theirs; score_out, pair_out and the window's own outputs have the
+ * plain calls' bits.  The empirical p, (ge + 1) / (sampleN + 1), is valid for a segment or window named from the reference sequence or
+ * an annotation, WITHOUT looking at the scores; it is NOT valid for a listed HSS.  It asks: given this reference sequence, do the
+ * substitutions in the other species look coding?  A stop codon or a frame-disrupting feature of the reference row is in every sample.
+ * Cost: the plain call's, plus one more tree node per block in the simulation ((2N - 1) / (2N - 2) of its node visits and draws: the
+ * MT19937 streams are regenerated once where the batch's own hold fewer), plus the re-rooting and the threshold tables of every distinct
+ * block on the host (the batch keeps 12 bytes per tree node in host memory for it) and their upload, 80 bytes per node. */
+int rc_batch_segment_null_anchored(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, float *score_out /* n_ranges */,
+                                   int32_t *ge_out /* n_ranges */, float *null_out /* may be NULL: [n_ranges][sampleN] */,
+                                   int64_t cap /* floats in null_out */);
+int rc_batch_segment_null_pairs_anchored(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, float *score_out /* n_ranges */,
+                                         int32_t *ge_out /* n_ranges */, float *pair_out, int32_t *pair_ge_out, int64_t cap /* entries in each */,
+                                         int64_t *offsets /* n_ranges + 1 */, float *pair_null_out /* may be NULL: [offsets[n_ranges]][sampleN] */,
+                                         int64_t null_cap /* floats in pair_null_out */);
+int rc_batch_window_null_anchored(const rc_batch *b, const rc_bt_range *windows, int32_t n_windows, float *score_out /* n_windows */,
+                                  int32_t *frame_out, int32_t *opt_b_out, int32_t *opt_i_out, int64_t *cells_out, int32_t *ge_out /* n_windows */,
+                                  float *null_out /* may be NULL: [n_windows][sampleN] */, int64_t cap /* floats in null_out */);
+/* T' of one block as Newick, "%.17g" lengths (none on the root), so that a run can be audited: the tip named blk->names[0] is the
+ * reference.  Host only; RC_ERR_ARG with the reason if blk->newick does not parse or has no such tip. */
+int rc_anchor_newick(const rc_block *blk, char *newick_out, int32_t cap);
+/* Diagnostic: the host milliseconds the last anchored call on a batch of this context spent re-rooting and making its threshold tables
+ * (0 before the first one). */
+double rc_ctx_anchor_host_ms(const rc_ctx *ctx);
+
 /* Decoy listings: the complete HSS listing of null alignments, for an empirical false discovery rate of a whole screen.  For the k-th
  * listed block (blks[k], or k where blks is NULL; a block may repeat) and decoy d = 0 .. n_decoys - 1 (1 <= n_decoys <= 64) the call
  * simulates the null alignment of MT19937 seed seed + d under the block's own tree, gap pattern and base frequencies -- the run's own

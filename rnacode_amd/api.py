@@ -172,9 +172,11 @@ def lib():
         l.rc_batch_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         l.rc_batch_segment_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         l.rc_batch_segment_null.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        l.rc_batch_segment_null_anchored.argtypes = l.rc_batch_segment_null.argtypes
         l.rc_batch_window_best.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.rc_batch_window_null.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_int64]
+        l.rc_batch_window_null_anchored.argtypes = l.rc_batch_window_null.argtypes
         l.rc_batch_window_shuffle_null.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
         l.rc_batch_decoys.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(RcHss), C.c_int64,
@@ -185,6 +187,10 @@ def lib():
         l.rc_batch_segment_shuffle_null.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
         l.rc_batch_segment_null_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                   C.c_void_p, C.c_int64]
+        l.rc_batch_segment_null_pairs_anchored.argtypes = l.rc_batch_segment_null_pairs.argtypes
+        l.rc_anchor_newick.argtypes = [C.POINTER(RcBlock), C.c_char_p, C.c_int32]
+        l.rc_ctx_anchor_host_ms.argtypes = [C.c_void_p]
+        l.rc_ctx_anchor_host_ms.restype = C.c_double
         l.rc_batch_segment_shuffle_null_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
         l.rc_evd_fit.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -228,6 +234,7 @@ EXPORTED_SYMBOLS = [
     "rc_batch_native_S", "rc_batch_backtrack", "rc_batch_backtrack_many", "rc_batch_track", "rc_batch_segment_scores", "rc_batch_segment_null", "rc_batch_decoys", "rc_batch_decoys_shuffled", "rc_batch_shuffle_null", "rc_batch_segment_shuffle_null", "rc_batch_segment_null_pairs", "rc_batch_segment_shuffle_null_pairs", "rc_batch_window_best", "rc_batch_window_null", "rc_batch_window_shuffle_null", "rc_fit_tree", "rc_fit_trees", "rc_fit_trees_device", "rc_tree_lnl", "rc_evd_fit", "rc_pvalue", "rc_mt_stream", "rc_code_tables",
     "rc_code_tables_for", "rc_genetic_code", "rc_species_tree_create", "rc_species_tree_destroy", "rc_species_tree_tips", "rc_species_tree_prune",
     "rc_fit_species_trees", "rc_fit_species_trees_device",
+    "rc_batch_segment_null_anchored", "rc_batch_segment_null_pairs_anchored", "rc_batch_window_null_anchored", "rc_anchor_newick", "rc_ctx_anchor_host_ms",
 ]
 # the entry points of the older rc_params layout (include/rnacode_hip.h, "Binary compatibility"): exported, no longer declared
 COMPAT_SYMBOLS = ["rc_default_params", "rc_batch_create", "rc_stream_create"]
@@ -246,6 +253,15 @@ def _check(code: int) -> int:
     if code < 0:
         raise RnacodeError(code, lib().rc_last_error().decode())
     return code
+
+
+def anchor_newick(block: AlnBlock) -> str:
+    """rc_anchor_newick: the block's tree rooted at a new node on its reference tip's edge, at distance 0 from the tip -- the tree the
+    anchored null (Batch.segment_null(..., anchored=True)) simulates on -- as Newick with "%.17g" lengths.  Host only."""
+    blk, _keep = _one_block(block, block.tree)
+    buf = C.create_string_buffer(max(1 << 14, 128 * block.n))
+    _check(lib().rc_anchor_newick(C.byref(blk), buf, len(buf)))
+    return buf.value.decode()
 
 
 def genetic_code(ncbi_id: int) -> str:
@@ -782,21 +798,23 @@ class Batch:
         o = offs.tolist()
         return scores, [vals[o[r]:o[r + 1]] for r in range(n)]
 
-    def segment_null(self, ranges, matrix: bool = False) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+    def segment_null(self, ranges, matrix: bool = False, anchored: bool = False) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
         """rc_batch_segment_null: (scores, ge, null) of all `ranges` -- tuples as segment_scores takes, scores with that call's bits.
         null[r][s] (matrix, else None) is the score of exactly that segment in the batch's null alignment s, float32 [n][sampleN];
         ge[r] the number of samples with null[r][s] >= scores[r], int32.  segments.empirical_p(ge, sampleN) is the p of a segment
-        named in advance -- not of a listed HSS, which was selected as a maximum."""
+        named in advance -- not of a listed HSS, which was selected as a maximum.
+        anchored: rc_batch_segment_null_anchored -- the null alignments keep the block's reference row and simulate the other rows from it
+        on the tree rooted at the reference tip (anchor_newick): the test for a segment named from the reference sequence, an ORF."""
         arr = np.ascontiguousarray(np.asarray(list(ranges), dtype=np.int32).reshape(-1, 4))
         n, sample_n = arr.shape[0], int(self.params.sampleN)
         scores = np.zeros(n, dtype=np.float32)
         ge = np.zeros(n, dtype=np.int32)
         null = np.zeros((n, sample_n), dtype=np.float32) if matrix else None
-        _check(lib().rc_batch_segment_null(self._h, arr.ctypes.data, n, scores.ctypes.data, ge.ctypes.data,
-                                           null.ctypes.data if matrix else None, n * sample_n if matrix else 0))
+        call = lib().rc_batch_segment_null_anchored if anchored else lib().rc_batch_segment_null
+        _check(call(self._h, arr.ctypes.data, n, scores.ctypes.data, ge.ctypes.data, null.ctypes.data if matrix else None, n * sample_n if matrix else 0))
         return scores, ge, null
 
-    def _window_call(self, windows, null: bool, matrix: bool, shuffles: Optional[Tuple[int, int]] = None):
+    def _window_call(self, windows, null: bool, matrix: bool, shuffles: Optional[Tuple[int, int]] = None, anchored: bool = False):
         arr = np.ascontiguousarray(np.asarray(list(windows), dtype=np.int32).reshape(-1, 4))
         n, sample_n = arr.shape[0], int(self.params.sampleN)
         best = np.zeros(n, dtype=WINDOW_BEST_DTYPE)
@@ -812,7 +830,8 @@ class Batch:
         elif null:
             ge = np.zeros(n, dtype=np.int32)
             mat = np.zeros((n, sample_n), dtype=np.float32) if matrix else None
-            _check(lib().rc_batch_window_null(*head, ge.ctypes.data, mat.ctypes.data if matrix else None, n * sample_n if matrix else 0))
+            call = lib().rc_batch_window_null_anchored if anchored else lib().rc_batch_window_null
+            _check(call(*head, ge.ctypes.data, mat.ctypes.data if matrix else None, n * sample_n if matrix else 0))
         else:
             _check(lib().rc_batch_window_best(*head))
         for k in best.dtype.names:
@@ -826,12 +845,13 @@ class Batch:
         opt_b, opt_i) the first of them, in the order frame, a, j, with that value (a range segment_scores takes), cells their number."""
         return self._window_call(windows, False, False)[0]
 
-    def window_null(self, windows, matrix: bool = False) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+    def window_null(self, windows, matrix: bool = False, anchored: bool = False) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
         """rc_batch_window_null: (best, ge, null) of all `windows` -- best as window_best gives it; null[w][s] (matrix, else None) the
         window's value in the batch's null alignment s, float32 [n][sampleN], every cell with segment_null's bits; ge[w] the number of
         samples with null[w][s] >= best["score"][w], int32.  segments.empirical_p(ge, sampleN) is the p of a window named in advance --
-        not of an interval picked around a listed HSS.  windows.group_p combines the windows of one transcript in several blocks."""
-        return self._window_call(windows, True, matrix)
+        not of an interval picked around a listed HSS.  windows.group_p combines the windows of one transcript in several blocks.
+        anchored: rc_batch_window_null_anchored -- segment_null's anchored samples: the reference row kept, the other rows simulated from it."""
+        return self._window_call(windows, True, matrix, anchored=anchored)
 
     def window_shuffle_null(self, windows, n_shuffles: int, seed: Optional[int] = None,
                             matrix: bool = False) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
@@ -889,6 +909,13 @@ class Batch:
         folds rows of it into the null of the segment restricted to those rows."""
         sample_n = int(self.params.sampleN)
         return self._segment_pairs_call(lambda *a: lib().rc_batch_segment_null_pairs(self._h, *a), ranges, sample_n, matrix)
+
+    def segment_null_pairs_anchored(self, ranges, matrix: bool = False):
+        """rc_batch_segment_null_pairs_anchored: segment_null_pairs' five outputs over segment_null(..., anchored=True)'s samples -- the
+        reference row kept, the other rows simulated from it; scores and ge with that call's bits and values.  (A method of its own:
+        segment_null_pairs' parameter list is (ranges, matrix) and stays that.)"""
+        sample_n = int(self.params.sampleN)
+        return self._segment_pairs_call(lambda *a: lib().rc_batch_segment_null_pairs_anchored(self._h, *a), ranges, sample_n, matrix)
 
     def segment_shuffle_null_pairs(self, ranges, n_shuffles: int, seed: Optional[int] = None, matrix: bool = False):
         """rc_batch_segment_shuffle_null_pairs: the same five outputs under the shuffle null -- scores and ge with segment_shuffle_null's

@@ -4,7 +4,7 @@ Mirrors the reference's command line (src/cmdline.ggo:6-20, src/RNAcode.c:236-37
 options that concern the scoring path and the listings:
 
     python -m rnacode_amd.cli [-n N] [-p CUTOFF] [-g | -t] [-b] [-r] [-s] [-m 62|90] [-c D,O,o,S]
-                              [-e [-i CUTOFF] [-d DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null] [--regions-shuffle-null N]]
+                              [-e [-i CUTOFF] [-d DIR]] [--details FILE] [--track FILE] [--support FILE] [--regions FILE --regions-out FILE [--regions-null] [--regions-shuffle-null N] [--regions-anchored-null]]
                               [--decoys K --decoys-out FILE [--decoy-kind simulated|shuffled]] [--shuffle-null N --shuffle-null-out FILE]
                               [-o OUT] [--trees SIDECAR | --species-tree NEWICK
                               [--species-tree-fit fixed|scale|branches]] [--write-trees SIDECAR] [FILE]
@@ -165,6 +165,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --regions: three more columns in --regions-out, shuffle_ge = how many of N (1..65536) shuffles of the block -- "
                          "its own columns, permuted among the columns with the same gap pattern -- score at least as high on exactly that "
                          "segment, p_segment_shuffled = (shuffle_ge + 1) / (N + 1), and movable = the columns a shuffle can move")
+    ap.add_argument("--regions-anchored-null", action="store_true",
+                    help="with --regions: two more columns in --regions-out (behind --regions-null's and --regions-shuffle-null's), anchored_ge = "
+                         "how many of -n null alignments that keep the block's reference row and simulate only the other rows from it score "
+                         "at least as high on exactly that segment, and p_segment_anchored = (anchored_ge + 1) / (n + 1): the test for a "
+                         "segment named from the reference sequence, such as an ORF; with --regions-support also pair_anchored_ge and "
+                         "p_pair_anchored")
     ap.add_argument("--regions-support", metavar="FILE",
                     help="with --regions: write a tab-separated table with one line per region, scored block that contains it and aligned "
                          "sequence: the sequence's pair score against the reference over exactly that segment, its share and the score "
@@ -186,6 +192,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "-- its own columns, permuted among the columns with the same gap mask -- hold a segment inside the same window "
                          "that scores at least as high, p_window_shuffled = (shuffle_ge + 1) / (N + 1), and movable = the columns a "
                          "shuffle can move")
+    ap.add_argument("--windows-anchored-null", action="store_true",
+                    help="with --windows: two more columns in --windows-out (behind --windows-null's and --windows-shuffle-null's), anchored_ge "
+                         "and p_window_anchored = (anchored_ge + 1) / (n + 1), --windows-null's test under null alignments that keep the "
+                         "block's reference row and simulate only the other rows from it")
     ap.add_argument("--windows-summary", metavar="FILE",
                     help="with --windows-null or --windows-shuffle-null: one line per window id over all its pieces in the run (the exons of a transcript, in "
                          "whatever blocks they lie): the best score, null_ge and p_window of the pieces taken together")
@@ -235,12 +245,16 @@ def _intake(a):
         raise _Refused("--windows-shuffle-null needs --windows")
     if a.windows_shuffle_null is not None and not 1 <= a.windows_shuffle_null <= 65536:
         raise _Refused("--windows-shuffle-null takes a number of shuffles from 1 to 65536")
-    if a.windows_summary and not a.windows_null and a.windows_shuffle_null is None:
+    if a.windows_anchored_null and not a.windows:
+        raise _Refused("--windows-anchored-null needs --windows")
+    if a.windows_summary and not a.windows_null and a.windows_shuffle_null is None and not a.windows_anchored_null:
         raise _Refused("--windows-summary needs --windows-null or --windows-shuffle-null")
     if bool(a.regions) != bool(a.regions_out):
         raise _Refused("--regions and --regions-out go together")
     if a.regions_null and not a.regions:
         raise _Refused("--regions-null needs --regions")
+    if a.regions_anchored_null and not a.regions:
+        raise _Refused("--regions-anchored-null needs --regions")
     if a.regions_shuffle_null is not None and not a.regions:
         raise _Refused("--regions-shuffle-null needs --regions")
     if a.regions_shuffle_null is not None and not 1 <= a.regions_shuffle_null <= 65536:
@@ -381,7 +395,7 @@ def _list_batch(run: _Run, batch, base: int) -> None:
     # --eps / --details: the backtracked paths with ONE call (rc_batch_backtrack_many) -- the segments themselves for the table; for the
     # plots (p below the plot cutoff) the segment and its two extensions.  --support / --regions: the scores and pair scores of every listed
     # HSS, and of every region a block contains, with ONE call (rc_batch_segment_scores)
-    bt, seg, nul, shf, found = _Ranges(), _Ranges(), _Ranges(), _Ranges(), {}
+    bt, seg, nul, shf, anc, found = _Ranges(), _Ranges(), _Ranges(), _Ranges(), _Ranges(), {}
     for i in scored:
         b = run.blocks[base + i]
         for h in listed[i]:
@@ -398,7 +412,8 @@ def _list_batch(run: _Run, batch, base: int) -> None:
                 if isinstance(at, tuple):
                     lo, hi = segments.range_of(*at)
                     found.setdefault(i, []).append((reg, at, seg.add(i, reg.strand, lo, hi), nul.add(i, reg.strand, lo, hi) if a.regions_null else -1,
-                                                    shf.add(i, reg.strand, lo, hi) if a.regions_shuffle_null is not None else -1))
+                                                    shf.add(i, reg.strand, lo, hi) if a.regions_shuffle_null is not None else -1,
+                                                    anc.add(i, reg.strand, lo, hi) if a.regions_anchored_null else -1))
     # --windows: the windows that overlap a block, cut to it, with ONE call (rc_batch_window_best, or rc_batch_window_null with --windows-null;
     # a window is no range of the other calls, and is not shared with them)
     win_found, win_ranges = {}, []
@@ -412,7 +427,7 @@ def _list_batch(run: _Run, batch, base: int) -> None:
                     win_ranges.append((i, 0 if w.strand == "+" else 1, at[0], at[1]))
                 elif at == windows.NO_CODON:
                     w.reason = at   # (what the window's stderr line says if no block has a whole codon for it)
-    win_best = win_ge = win_null = win_shuffle_ge = win_shuffle = None
+    win_best = win_ge = win_null = win_shuffle_ge = win_shuffle = win_anchored_ge = win_anchored = None
     if win_ranges:
         if a.windows_null:
             win_best, win_ge, win_null = batch.window_null(win_ranges, matrix=run.summary is not None)
@@ -420,6 +435,10 @@ def _list_batch(run: _Run, batch, base: int) -> None:
         if a.windows_shuffle_null is not None:
             best, win_shuffle_ge, win_shuffle = batch.window_shuffle_null(win_ranges, a.windows_shuffle_null, run.params.seed_base + run.params.sampleN,
                                                                           matrix=run.summary is not None)
+            win_best = best if win_best is None else win_best
+        # --windows-anchored-null: the same windows under the anchored null with ONE call (rc_batch_window_null_anchored)
+        if a.windows_anchored_null:
+            best, win_anchored_ge, win_anchored = batch.window_null(win_ranges, matrix=run.summary is not None, anchored=True)
             win_best = best if win_best is None else win_best
         if win_best is None:
             win_best = batch.window_best(win_ranges)
@@ -439,6 +458,12 @@ def _list_batch(run: _Run, batch, base: int) -> None:
         _, shuffle_ge, _, pair_shuffle_ge, _ = batch.segment_shuffle_null_pairs(shf.ranges, a.regions_shuffle_null, run.params.seed_base + run.params.sampleN)
     else:
         shuffle_ge = batch.segment_shuffle_null(shf.ranges, a.regions_shuffle_null, run.params.seed_base + run.params.sampleN)[1] if shf.ranges else None
+    # --regions-anchored-null: the same ranges under the anchored null with ONE call (rc_batch_segment_null_anchored, or its *_pairs form)
+    pair_anchored_ge = None
+    if anc.ranges and "regions_support" in side:
+        _, anchored_ge, _, pair_anchored_ge, _ = batch.segment_null_pairs_anchored(anc.ranges)
+    else:
+        anchored_ge = batch.segment_null(anc.ranges, anchored=True)[1] if anc.ranges else None
     # --decoys: the decoy listings of the blocks the listing covers with ONE call (rc_batch_decoys)
     decoyed = dict(zip(scored, batch.decoys(a.decoys, run.params.seed_base + run.params.sampleN, scored, kind=a.decoy_kind or "simulated"))) if "decoys_out" in side and scored else {}
     # --shuffle-null: the shuffle maxima and their fit for the blocks the listing covers with ONE call (rc_batch_shuffle_null)
@@ -466,16 +491,18 @@ def _list_batch(run: _Run, batch, base: int) -> None:
             if i in tracked:
                 side["track"].writelines(track.block_lines(b.rows[0].name, b.rows[0].start, b.rows[0].length, tracked[i], rc, mu, lam, a.cutoff))
             movable = shuffle_null.movable([r.seq for r in b.rows]) if i in found and a.regions_shuffle_null is not None else 0
-            for reg, (frame, c1, c2), r, rn, rs in found.get(i, ()):
+            for reg, (frame, c1, c2), r, rn, rs, ra in found.get(i, ()):
                 p = api.pvalue(float(seg_scores[r]), mu, lam) if rc == 1 else 99.0
                 side["regions_out"].write(segments.region_line(reg, frame, c1, c2, seg_scores[r], p, seg_pairs[r],
                                                                (null_ge[rn], run.params.sampleN) if rn >= 0 else None,
-                                                               (shuffle_ge[rs], a.regions_shuffle_null, movable) if rs >= 0 else None))
+                                                               (shuffle_ge[rs], a.regions_shuffle_null, movable) if rs >= 0 else None,
+                                                               (anchored_ge[ra], run.params.sampleN) if ra >= 0 else None))
                 if "regions_support" in side:
                     side["regions_support"].writelines(segments.region_support_lines(
                         reg, frame, c1, c2, seg_scores[r], [row.name for row in b.rows], seg_pairs[r], run.params.Delta,
                         (pair_null_ge[rn], run.params.sampleN) if rn >= 0 else None,
-                        (pair_shuffle_ge[rs], a.regions_shuffle_null) if rs >= 0 else None))
+                        (pair_shuffle_ge[rs], a.regions_shuffle_null) if rs >= 0 else None,
+                        (pair_anchored_ge[ra], run.params.sampleN) if ra >= 0 else None))
                 reg.matched = True
             win_movable = shuffle_null.movable([r.seq for r in b.rows]) if i in win_found and a.windows_shuffle_null is not None else 0
             for w, (_, _, cut_start, cut_end), k in win_found.get(i, ()):
@@ -485,9 +512,11 @@ def _list_batch(run: _Run, batch, base: int) -> None:
                 p = api.pvalue(float(rec["score"]), mu, lam) if rc == 1 else 99.0
                 side["windows_out"].write(windows.window_line(w, cut_start, cut_end, frame, c1, c2, sg, eg, rec["score"], p, int(rec["cells"]),
                                                               (win_ge[k], run.params.sampleN) if win_ge is not None else None,
-                                                              (win_shuffle_ge[k], a.windows_shuffle_null, win_movable) if win_shuffle_ge is not None else None))
+                                                              (win_shuffle_ge[k], a.windows_shuffle_null, win_movable) if win_shuffle_ge is not None else None,
+                                                              (win_anchored_ge[k], run.params.sampleN) if win_anchored_ge is not None else None))
                 if run.summary is not None:
-                    run.summary.add(w.id, rec["score"], win_null[k] if win_null is not None else None, win_shuffle[k] if win_shuffle is not None else None)
+                    run.summary.add(w.id, rec["score"], win_null[k] if win_null is not None else None, win_shuffle[k] if win_shuffle is not None else None,
+                                    win_anchored[k] if win_anchored is not None else None)
                 w.matched = True
 
 
@@ -535,13 +564,15 @@ def main(argv=None) -> int:
         for name, header in SIDE_FILES:
             if getattr(a, name):
                 side[name] = files.enter_context(open(getattr(a, name), "w"))
-                side[name].write(header(null=a.regions_null, shuffle=a.regions_shuffle_null is not None) if name in ("regions_out", "regions_support") else
-                                 header(null=a.windows_null, shuffle=a.windows_shuffle_null is not None) if name == "windows_out" else
-                                 header(null=a.windows_null, shuffle=a.windows_shuffle_null is not None) if name == "windows_summary" else header())
+                side[name].write(header(null=a.regions_null, shuffle=a.regions_shuffle_null is not None, anchored=a.regions_anchored_null)
+                                 if name in ("regions_out", "regions_support") else
+                                 header(null=a.windows_null, shuffle=a.windows_shuffle_null is not None, anchored=a.windows_anchored_null)
+                                 if name in ("windows_out", "windows_summary") else header())
         code = params.genetic_code.decode()
         run = _Run(a, params, code, api.code_tables(a.blosum, code) if a.details else None, blocks, read_index, refused,
                    segments.by_name(regions) if regions is not None else {}, out, fmt, side,
-                   segments.by_name(wins) if wins is not None else {}, windows.Summary(params.sampleN if a.windows_null else None, a.windows_shuffle_null) if a.windows_summary else None)
+                   segments.by_name(wins) if wins is not None else {}, windows.Summary(params.sampleN if a.windows_null else None, a.windows_shuffle_null,
+                                   params.sampleN if a.windows_anchored_null else None) if a.windows_summary else None)
         # the blocks go through the GPU as a stream of sub-batches (rc_stream_*): while one is being scored the next is prepared
         # on the host threads, and the listing of a finished one is written meanwhile (the reference's loop, RNAcode.c:115-221).
         # Sub-batch sizes: --sub-blocks, or the library's schedule (rc_stream_plan: a small first sub-batch, then doubling, whole rounds

@@ -42,11 +42,13 @@ int batch_prepare(rc_batch *b, const rc_block *blocks, int32_t n_blocks, const r
   const PairTable &pt = set->pt;
 
   // capacity of the two blob parts from the shapes alone, then one pinned buffer
-  size_t hostSum = 0, devSum = 0;
+  size_t hostSum = 0, devSum = 0, keepSum = 0;
   for (int i = 0; i < n_blocks; i++) {
     size_t h = 0, d = 0;
-    if (blocks[i].n_rows >= 3 && blocks[i].n_rows <= kMaxRows && blocks[i].n_cols >= 3 && blocks[i].n_cols <= RC_MAX_COLS)
+    if (blocks[i].n_rows >= 3 && blocks[i].n_rows <= kMaxRows && blocks[i].n_cols >= 3 && blocks[i].n_cols <= RC_MAX_COLS) {
       block_footprint(blocks[i].n_rows, blocks[i].n_cols, &h, &d);
+      keepSum += 2 * static_cast<size_t>(blocks[i].n_rows) - 1;   // (a rooted tree's nodes; an unrooted one has one fewer)
+    }
     hostSum += h; devSum += d;
   }
   const size_t nn = static_cast<size_t>(std::max(n_blocks, 1));
@@ -59,6 +61,9 @@ int batch_prepare(rc_batch *b, const rc_block *blocks, int32_t n_blocks, const r
   arena.host = b->hblob.as<uint8_t>();
   arena.hostCap = b->hostCap;          // the device-only arena starts here in the device blob
   arena.devCap = b->devCap;
+  b->treeKeep.resize(keepSum);
+  arena.keep = b->treeKeep.data();
+  arena.keepCap = keepSum;
 
   // block-constant preparation, blocks are independent -> host threads
   {

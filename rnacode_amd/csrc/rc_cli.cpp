@@ -34,6 +34,9 @@
 // file lists (name, strand, the listing's Start / End) in every scored block that contains them; a region that matches nothing gets a line on
 // stderr at the end of the run.  The ranges of a sub-batch go in ONE rc_batch_segment_scores call (rc_eps.h, support_tail / region_line; the
 // same bytes as python -m rnacode_amd.cli, whose segments.py documents the rules).  With --gpus N the one writer emits both in input order.
+// --regions-anchored-null (with --regions) / --windows-anchored-null (with --windows): --regions-null's and --windows-null's columns over again under the
+// anchored null (rc_batch_segment_null_anchored, rc_batch_window_null_anchored: the reference row kept, the other rows simulated from it), behind the other
+// nulls' columns: anchored_ge and p_segment_anchored / p_window_anchored; in --regions-support pair_anchored_ge and p_pair_anchored; in --windows-summary too.
 // --regions-null (with --regions): every --regions-out line ends in null_ge and p_segment = (null_ge + 1) / (n + 1), the test for a segment named
 // in advance -- the regions' ranges of a sub-batch in ONE rc_batch_segment_null call (in the sample split one per slice, the counts added).
 // --regions-support FILE (with --regions): the --support table for named segments, one line per region, scored block that contains it and
@@ -321,6 +324,7 @@ struct SideFile {
   const char *(*header)();
   std::string path;
   FILE *f;
+  const char *tail = nullptr;   // columns behind the header's (--regions-anchored-null, --windows-anchored-null): in front of its line end
 };
 enum { kDetails, kTrack, kSupport, kRegions, kDecoys, kShuffleNull, kRegionSupport, kWindows, kWindowSummary, kSides };
 const char *decoys_header() { return "block\tdecoy\tstrand\tframe\tlength\tfrom\tto\tname\tstart\tend\tscore\tp\n"; }
@@ -487,6 +491,12 @@ void usage() {
                        "                             is cut to every scored block that overlaps it\n"
                        "  --windows-out FILE         one line per window and block: id name strand lo hi frame from to start end score p cells -- the cut\n"
                        "                             window, its best segment of whole codons, the block-wide p, the segments the window holds\n"
+                       "  --regions-anchored-null    with --regions: two more columns (behind the other nulls'), anchored_ge = how many of -n null alignments\n"
+                       "                             that keep the reference row and simulate only the other rows from it score at least as high on exactly\n"
+                       "                             that segment, and p_segment_anchored = (anchored_ge + 1) / (n + 1), the test for a segment named from the\n"
+                       "                             reference sequence (an ORF); with --regions-support also pair_anchored_ge and p_pair_anchored\n"
+                       "  --windows-anchored-null    with --windows: two more columns, anchored_ge and p_window_anchored, --windows-null's test under those\n"
+                       "                             null alignments; in --windows-summary too\n"
                        "  --windows-null             with --windows: two more columns, null_ge = how many of the -n null alignments hold a segment inside\n"
                        "                             the same window that scores at least as high, p_window = (null_ge + 1) / (n + 1): the test for a\n"
                        "                             window named in advance (not for an interval picked around a listed HSS)\n"
@@ -521,7 +531,7 @@ struct BlockOut {
   std::string track, regions, decoys;  // its --track / --regions-out / --decoys-out lines
   std::string regionSupport;           // its --regions-support lines
   std::string windows;                 // its --windows-out lines
-  struct Piece { int window; float score; std::vector<float> null, shuffle; };
+  struct Piece { int window; float score; std::vector<float> null, shuffle, anchored; };
   std::vector<Piece> pieces;           // --windows-summary: its windows' scores and null vectors, in line order
 };
 
@@ -559,6 +569,8 @@ struct Run {
   std::vector<rceps::Region> windows;                     // --windows, in file order
   std::map<std::string, std::vector<int>> windowsOf;      // reference row name -> the windows that can match a block, in file order
   std::vector<char> windowMatched;                        // set by the writer
+  bool regionsAnchored = false;                           // --regions-anchored-null: anchored_ge and p_segment_anchored behind every --regions-out line
+  bool windowsAnchored = false;                           // --windows-anchored-null: anchored_ge and p_window_anchored behind every --windows-out line
   bool windowsNull = false;                               // --windows-null: null_ge and p_window behind every --windows-out line
   int windowsShuffleNull = 0;                             // --windows-shuffle-null: shuffles scored per window's block (0: off)
   rceps::WinSummary winSummary;                           // --windows-summary: what the ids have so far (the writer's)
@@ -613,8 +625,9 @@ void writer_thread(Run &R) {
       if (!o.regionSupport.empty()) std::fwrite(o.regionSupport.data(), 1, o.regionSupport.size(), R.list.side[kRegionSupport].f);
       if (!o.decoys.empty()) std::fwrite(o.decoys.data(), 1, o.decoys.size(), R.list.side[kDecoys].f);
       if (!o.windows.empty()) std::fwrite(o.windows.data(), 1, o.windows.size(), R.list.side[kWindows].f);
-      for (const BlockOut::Piece &pc : o.pieces) R.winSummary.add(R.windows[pc.window].id, pc.score, pc.null.data(), static_cast<int>(pc.null.size()),
-                                                               pc.shuffle.empty() ? nullptr : pc.shuffle.data(), static_cast<int>(pc.shuffle.size()));
+      for (const BlockOut::Piece &pc : o.pieces) R.winSummary.add(R.windows[pc.window].id, pc.score, pc.null.empty() ? nullptr : pc.null.data(), static_cast<int>(pc.null.size()),
+                                                               pc.shuffle.empty() ? nullptr : pc.shuffle.data(), static_cast<int>(pc.shuffle.size()),
+                                                               pc.anchored.empty() ? nullptr : pc.anchored.data(), static_cast<int>(pc.anchored.size()));
     }
     for (int r : j->matched) R.regionMatched[r] = 1;
     for (int r : j->noCodon) if (!R.windowMatched[r]) R.windows[r].reason = rceps::kSegNoCodon;
@@ -822,6 +835,26 @@ bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std
       for (size_t t = 0; t < pairNullGe.size(); t++) pairNullGe[t] += pg[t];
     }
   }
+  // --regions-anchored-null: the same ranges under the anchored null, as --regions-null's above: one call per batch, the counts added
+  std::vector<int32_t> anchoredGe, pairAnchoredGe;   // per found region; per (found region, row)
+  if (R.regionsAnchored && !found.empty()) {
+    std::vector<rc_bt_range> regs;
+    for (const Found &f : found) regs.push_back(ranges[f.range]);
+    const int nf = static_cast<int>(regs.size());
+    std::vector<float> sc(nf);
+    std::vector<int32_t> ge(nf);
+    anchoredGe.assign(nf, 0);
+    if (rowCounts) pairAnchoredGe.assign(static_cast<size_t>(pairTotal), 0);
+    const std::vector<rc_batch *> one{b};
+    for (rc_batch *sb : slices ? *slices : one) {
+      if (!sb) continue;
+      const int rc = rowCounts ? rc_batch_segment_null_pairs_anchored(sb, regs.data(), nf, sc.data(), ge.data(), pr.data(), pg.data(), pairTotal, pairOffs.data(), nullptr, 0)
+                               : rc_batch_segment_null_anchored(sb, regs.data(), nf, sc.data(), ge.data(), nullptr, 0);
+      if (rc != RC_OK) { err = rc_last_error(); return false; }
+      for (int k = 0; k < nf; k++) anchoredGe[k] += ge[k];
+      for (size_t t = 0; t < pairAnchoredGe.size(); t++) pairAnchoredGe[t] += pg[t];
+    }
+  }
   std::vector<int32_t> shuffleGe;   // per found region
   std::map<int, int> movableOf;     // block of the batch -> the columns a shuffle can move
   if (R.regionsShuffleNull > 0 && !found.empty()) {
@@ -846,7 +879,7 @@ bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std
     const float p = fit.rc == 1 ? rc_pvalue(scores[f.range], fit.mu, fit.lambda) : 99.0f;
     j.blocks[f.blk].regions += rceps::region_line(R.regions[f.region], f.at, scores[f.range], p, pairs.data() + offs[f.range], static_cast<int>(offs[f.range + 1] - offs[f.range]),
                                                   R.regionsNull ? nullGe[k] : -1, R.par.sampleN, R.regionsShuffleNull > 0 ? shuffleGe[k] : -1, R.regionsShuffleNull,
-                                                  R.regionsShuffleNull > 0 ? movableOf[f.blk] : 0);
+                                                  R.regionsShuffleNull > 0 ? movableOf[f.blk] : 0, R.regionsAnchored ? anchoredGe[k] : -1);
     if (rowCounts) {
       const Block &blk = R.blocks[j.blocks[f.blk].index];
       std::vector<std::string> names;
@@ -854,7 +887,8 @@ bool add_segments(const Run &R, rc_batch *b, Job &j, std::string &err, const std
       j.blocks[f.blk].regionSupport += rceps::region_support_lines(R.regions[f.region], f.at, scores[f.range], names, pairs.data() + offs[f.range],
                                                                   static_cast<int>(offs[f.range + 1] - offs[f.range]), R.par.Delta,
                                                                   R.regionsNull ? pairNullGe.data() + pairOffs[k] : nullptr, R.par.sampleN,
-                                                                  R.regionsShuffleNull > 0 ? pairShuffleGe.data() + pairOffs[k] : nullptr, R.regionsShuffleNull);
+                                                                  R.regionsShuffleNull > 0 ? pairShuffleGe.data() + pairOffs[k] : nullptr, R.regionsShuffleNull,
+                                                                  R.regionsAnchored ? pairAnchoredGe.data() + pairOffs[k] : nullptr);
     }
     j.matched.push_back(f.region);
   }
@@ -894,7 +928,7 @@ bool add_windows(const Run &R, rc_batch *b, Job &j, std::string &err, const std:
   const bool keep = R.list.on(kWindowSummary);
   std::vector<float> nullAll(keep && R.windowsNull ? static_cast<size_t>(nw) * n : 0);
   if (!R.windowsNull) {
-    if (R.windowsShuffleNull == 0 && rc_batch_window_best(b, wins.data(), nw, score.data(), frame.data(), optB.data(), optI.data(), cells.data()) != RC_OK) { err = rc_last_error(); return false; }
+    if (R.windowsShuffleNull == 0 && !R.windowsAnchored && rc_batch_window_best(b, wins.data(), nw, score.data(), frame.data(), optB.data(), optI.data(), cells.data()) != RC_OK) { err = rc_last_error(); return false; }
   } else if (!slices) {
     if (rc_batch_window_null(b, wins.data(), nw, score.data(), frame.data(), optB.data(), optI.data(), cells.data(), ge.data(), keep ? nullAll.data() : nullptr,
                              static_cast<int64_t>(nullAll.size())) != RC_OK) { err = rc_last_error(); return false; }
@@ -911,6 +945,28 @@ bool add_windows(const Run &R, rc_batch *b, Job &j, std::string &err, const std:
       if (keep)
         for (int k = 0; k < nw; k++)
           for (int s = 0; s < w && lo + s < n; s++) nullAll[static_cast<size_t>(k) * n + lo + s] = mat[static_cast<size_t>(k) * w + s];
+    }
+  }
+  // --windows-anchored-null: the same windows under the anchored null, by --windows-null's rule: one call per batch, the counts added and
+  // the null vectors joined by sample index
+  std::vector<int32_t> anchoredGe(R.windowsAnchored ? nw : 0, 0);
+  std::vector<float> anchoredAll(keep && R.windowsAnchored ? static_cast<size_t>(nw) * n : 0);
+  if (R.windowsAnchored && !slices) {
+    if (rc_batch_window_null_anchored(b, wins.data(), nw, score.data(), frame.data(), optB.data(), optI.data(), cells.data(), anchoredGe.data(),
+                                      keep ? anchoredAll.data() : nullptr, static_cast<int64_t>(anchoredAll.size())) != RC_OK) { err = rc_last_error(); return false; }
+  } else if (R.windowsAnchored) {
+    for (size_t g = 0; g < slices->size(); g++) {
+      rc_batch *sb = (*slices)[g];
+      if (!sb) continue;
+      const int lo = R.sliceRange[g].first, w = R.sliceRange[g].second;
+      std::vector<int32_t> part(nw);
+      std::vector<float> mat(keep ? static_cast<size_t>(nw) * w : 0);
+      if (rc_batch_window_null_anchored(sb, wins.data(), nw, score.data(), frame.data(), optB.data(), optI.data(), cells.data(), part.data(),
+                                        keep ? mat.data() : nullptr, static_cast<int64_t>(mat.size())) != RC_OK) { err = rc_last_error(); return false; }
+      for (int k = 0; k < nw; k++) anchoredGe[k] += part[k];
+      if (keep)
+        for (int k = 0; k < nw; k++)
+          for (int s = 0; s < w && lo + s < n; s++) anchoredAll[static_cast<size_t>(k) * n + lo + s] = mat[static_cast<size_t>(k) * w + s];
     }
   }
   const int N = R.windowsShuffleNull;
@@ -931,12 +987,14 @@ bool add_windows(const Run &R, rc_batch *b, Job &j, std::string &err, const std:
     const float p = fit.rc == 1 ? rc_pvalue(score[k], fit.mu, fit.lambda) : 99.0f;
     const Block &blk = R.blocks[j.blocks[f.blk].index];
     j.blocks[f.blk].windows += rceps::window_line(R.windows[f.window], f.at, frame[k], optB[k], optI[k], blk.rows[0].start, blk.rows[0].length, score[k], p, cells[k],
-                                                  R.windowsNull ? ge[k] : -1, n, N > 0 ? shuffleGe[k] : -1, N, N > 0 ? movableOf[f.blk] : 0);
+                                                  R.windowsNull ? ge[k] : -1, n, N > 0 ? shuffleGe[k] : -1, N, N > 0 ? movableOf[f.blk] : 0,
+                                                  R.windowsAnchored ? anchoredGe[k] : -1);
     if (keep)
       j.blocks[f.blk].pieces.push_back(BlockOut::Piece{
           f.window, score[k],
           R.windowsNull ? std::vector<float>(nullAll.begin() + static_cast<size_t>(k) * n, nullAll.begin() + static_cast<size_t>(k + 1) * n) : std::vector<float>(),
-          N > 0 ? std::vector<float>(shuffleAll.begin() + static_cast<size_t>(k) * N, shuffleAll.begin() + static_cast<size_t>(k + 1) * N) : std::vector<float>()});
+          N > 0 ? std::vector<float>(shuffleAll.begin() + static_cast<size_t>(k) * N, shuffleAll.begin() + static_cast<size_t>(k + 1) * N) : std::vector<float>(),
+          R.windowsAnchored ? std::vector<float>(anchoredAll.begin() + static_cast<size_t>(k) * n, anchoredAll.begin() + static_cast<size_t>(k + 1) * n) : std::vector<float>()});
     j.matchedWindows.push_back(f.window);
   }
   return true;
@@ -1338,6 +1396,8 @@ int main(int argc, char **argv) {
     else if (o == "--windows") windowsFile = val();
     else if (o == "--windows-out") list.side[kWindows].path = val();
     else if (o == "--windows-null") R.windowsNull = true;
+    else if (o == "--regions-anchored-null") R.regionsAnchored = true;
+    else if (o == "--windows-anchored-null") R.windowsAnchored = true;
     else if (o == "--windows-shuffle-null") { windowsShuffleGiven = true; R.windowsShuffleNull = std::atoi(val()); }
     else if (o == "--windows-summary") list.side[kWindowSummary].path = val();
     else if (o == "--regions-shuffle-null") { regionsShuffleGiven = true; R.regionsShuffleNull = std::atoi(val()); }
@@ -1359,11 +1419,18 @@ int main(int argc, char **argv) {
   if (R.windowsNull && windowsFile.empty()) die("--windows-null needs --windows");
   if (windowsShuffleGiven && windowsFile.empty()) die("--windows-shuffle-null needs --windows");
   if (windowsShuffleGiven && (R.windowsShuffleNull < 1 || R.windowsShuffleNull > 65536)) die("--windows-shuffle-null takes a number of shuffles from 1 to 65536");
-  if (list.on(kWindowSummary) && !R.windowsNull && !windowsShuffleGiven) die("--windows-summary needs --windows-null or --windows-shuffle-null");
+  if (R.windowsAnchored && windowsFile.empty()) die("--windows-anchored-null needs --windows");
+  if (list.on(kWindowSummary) && !R.windowsNull && !windowsShuffleGiven && !R.windowsAnchored) die("--windows-summary needs --windows-null or --windows-shuffle-null");
   if (R.windowsNull) list.side[kWindows].header = windowsShuffleGiven ? rceps::windows_header_null_shuffle : rceps::windows_header_null;
   else if (windowsShuffleGiven) list.side[kWindows].header = rceps::windows_header_shuffle;
   if (windowsShuffleGiven) list.side[kWindowSummary].header = R.windowsNull ? rceps::windows_summary_header_null_shuffle : rceps::windows_summary_header_shuffle;
+  if (R.windowsAnchored) {
+    list.side[kWindows].tail = list.side[kWindowSummary].tail = rceps::windows_anchored_columns();
+    if (!R.windowsNull && !windowsShuffleGiven) list.side[kWindowSummary].header = rceps::windows_summary_header_bare;
+  }
   if (R.regionsNull && regionsFile.empty()) die("--regions-null needs --regions");
+  if (R.regionsAnchored && regionsFile.empty()) die("--regions-anchored-null needs --regions");
+  if (R.regionsAnchored) { list.side[kRegions].tail = rceps::regions_anchored_columns(); list.side[kRegionSupport].tail = rceps::region_support_anchored_columns(); }
   if (regionsShuffleGiven && regionsFile.empty()) die("--regions-shuffle-null needs --regions");
   if (list.on(kRegionSupport) && regionsFile.empty()) die("--regions-support needs --regions");
   if (regionsShuffleGiven && (R.regionsShuffleNull < 1 || R.regionsShuffleNull > 65536)) die("--regions-shuffle-null takes a number of shuffles from 1 to 65536");
@@ -1503,7 +1570,9 @@ int main(int argc, char **argv) {
     if (sf.path.empty()) continue;
     sf.f = std::fopen(sf.path.c_str(), "w");
     if (!sf.f) die("Could not open " + sf.path);
-    std::fputs(sf.header(), sf.f);
+    std::string head = sf.header();
+    if (sf.tail) head.insert(head.size() - 1, sf.tail);
+    std::fputs(head.c_str(), sf.f);
   }
   if ((list.eps || list.on(kDetails)) && rc_code_tables_for(&par, R.tables.pep, R.tables.matrix) != RC_OK) die(rc_last_error());
   tRead = now() - tRead;
@@ -1611,7 +1680,7 @@ int main(int argc, char **argv) {
   // (RC_CLI_TEARDOWN=1: the orderly way, for leak checkers).
   if (list.out != stdout) std::fclose(list.out);
   if (list.on(kWindowSummary)) {   // one line per id over all its pieces in the run
-    const std::string text = R.winSummary.lines(par.sampleN, R.windowsNull, R.windowsShuffleNull);
+    const std::string text = R.winSummary.lines(par.sampleN, R.windowsNull, R.windowsShuffleNull, R.windowsAnchored);
     std::fwrite(text.data(), 1, text.size(), list.side[kWindowSummary].f);
   }
   for (SideFile &sf : list.side) if (sf.f && std::fclose(sf.f) != 0) die("Could not write " + sf.path);

@@ -437,8 +437,12 @@ inline std::string support_tail(const std::string &refName, const std::string &r
 // ge >= 0 (--regions-null): two more columns, how many of the n null alignments reach the score on exactly this segment, and (ge + 1) / (n + 1)
 // sge >= 0 (--regions-shuffle-null): three more, how many of the sn column shuffles of the block reach it, (sge + 1) / (sn + 1), and the columns a
 // shuffle can move
+// age >= 0 (--regions-anchored-null): two more behind those, how many of the n anchored null alignments reach it, and (age + 1) / (n + 1)
+inline const char *regions_anchored_columns() { return "\tanchored_ge\tp_segment_anchored"; }
+inline const char *region_support_anchored_columns() { return "\tpair_anchored_ge\tp_pair_anchored"; }
+inline const char *windows_anchored_columns() { return "\tanchored_ge\tp_window_anchored"; }
 inline std::string region_line(const Region &r, const SegLoc &at, float score, float p, const float *pairs, int nk, int ge = -1, int n = 0, int sge = -1,
-                               int sn = 0, int movable = 0) {
+                               int sn = 0, int movable = 0, int age = -1) {
   int support = 0;
   for (int k = 0; k < nk; k++) support += pairs[k] > 0.0f;
   std::string out;
@@ -453,6 +457,10 @@ inline std::string region_line(const Region &r, const SegLoc &at, float score, f
   if (sge >= 0) {
     if (score != score) put(out, "\t%i\tnan\t%i", sge, movable);
     else put(out, "\t%i\t%.3e\t%i", sge, (sge + 1.0) / (sn + 1.0), movable);
+  }
+  if (age >= 0) {
+    if (score != score) put(out, "\t%i\tnan", age);
+    else put(out, "\t%i\t%.3e", age, (age + 1.0) / (n + 1.0));
   }
   out += "\n";
   return out;
@@ -496,13 +504,14 @@ inline const char *windows_header_shuffle() { return "id\tname\tstrand\tlo\thi\t
 inline const char *windows_header_null_shuffle() {
   return "id\tname\tstrand\tlo\thi\tframe\tfrom\tto\tstart\tend\tscore\tp\tcells\tnull_ge\tp_window\tshuffle_ge\tp_window_shuffled\tmovable\n";
 }
+inline const char *windows_summary_header_bare() { return "id\tpieces\tscore\n"; }   // (--windows-anchored-null alone: its two columns behind these)
 inline const char *windows_summary_header() { return "id\tpieces\tscore\tnull_ge\tp_window\n"; }
 inline const char *windows_summary_header_shuffle() { return "id\tpieces\tscore\tshuffle_ge\tp_window_shuffled\n"; }
 inline const char *windows_summary_header_null_shuffle() { return "id\tpieces\tscore\tnull_ge\tp_window\tshuffle_ge\tp_window_shuffled\n"; }
 // frame, optB, optI: the best segment (rc_batch_window_best); ge >= 0 (--windows-null): null_ge and (ge + 1) / (n + 1) behind the line; sge >= 0
 // (--windows-shuffle-null): shuffle_ge, (sge + 1) / (sn + 1) and movable behind that
 inline std::string window_line(const Region &w, const WinClip &at, int frame, int optB, int optI, int refStart, int refLength, float score, float p,
-                               long long cells, int ge = -1, int n = 0, int sge = -1, int sn = 0, int movable = 0) {
+                               long long cells, int ge = -1, int n = 0, int sge = -1, int sn = 0, int movable = 0, int age = -1) {
   const int c1 = (optB - 1) / 3, c2 = (optI - 3) / 3;
   long long sg = optB, eg = optI;   // what ClustalW input (no coordinates) lists
   if (!(refStart == 0 && refLength == 0)) {
@@ -523,29 +532,37 @@ inline std::string window_line(const Region &w, const WinClip &at, int frame, in
     else put(out, "\t%i\t%.3e", sge, (sge + 1.0) / (sn + 1.0));
     put(out, "\t%i", movable);
   }
+  if (age >= 0) {   // --windows-anchored-null: anchored_ge and (age + 1) / (n + 1) behind them
+    if (score != score) put(out, "\t%i\tnan", age);
+    else put(out, "\t%i\t%.3e", age, (age + 1.0) / (n + 1.0));
+  }
   out += "\n";
   return out;
 }
 // --windows-summary: per id the pieces met so far, the fmax of their scores and the element-wise fmax of their null vectors (windows.Summary)
 struct WinSummary {
-  struct Rec { std::string id; int pieces; float score; std::vector<float> vec, shf; };   // vec: --windows-null's vector, shf: --windows-shuffle-null's
+  struct Rec { std::string id; int pieces; float score; std::vector<float> vec, shf, anc; };   // vec: --windows-null's vector, shf: --windows-shuffle-null's, anc: --windows-anchored-null's
   std::vector<Rec> recs;   // in order of first appearance
   std::map<std::string, size_t> at;
-  void add(const std::string &id, float score, const float *null, int n, const float *shuffle = nullptr, int sn = 0) {
+  void add(const std::string &id, float score, const float *null, int n, const float *shuffle = nullptr, int sn = 0, const float *anchored = nullptr, int an = 0) {
     const auto it = at.find(id);
     if (it == at.end()) {
       at[id] = recs.size();
-      recs.push_back(Rec{id, 1, score, std::vector<float>(null, null + n), shuffle ? std::vector<float>(shuffle, shuffle + sn) : std::vector<float>()});
+      recs.push_back(Rec{id, 1, score, null ? std::vector<float>(null, null + n) : std::vector<float>(),
+                         shuffle ? std::vector<float>(shuffle, shuffle + sn) : std::vector<float>(),
+                         anchored ? std::vector<float>(anchored, anchored + an) : std::vector<float>()});
       return;
     }
     Rec &r = recs[it->second];
     r.pieces++;
     r.score = std::fmax(r.score, score);
-    for (int s = 0; s < n; s++) r.vec[static_cast<size_t>(s)] = std::fmax(r.vec[static_cast<size_t>(s)], null[s]);
+    for (int s = 0; null && s < n; s++) r.vec[static_cast<size_t>(s)] = std::fmax(r.vec[static_cast<size_t>(s)], null[s]);
+    for (int s = 0; anchored && s < an; s++) r.anc[static_cast<size_t>(s)] = std::fmax(r.anc[static_cast<size_t>(s)], anchored[s]);
     for (int s = 0; shuffle && s < sn; s++) r.shf[static_cast<size_t>(s)] = std::fmax(r.shf[static_cast<size_t>(s)], shuffle[s]);
   }
   // withNull: null_ge and p_window over n; sn > 0: shuffle_ge and p_window_shuffled over the sn shuffles behind them
-  std::string lines(int n, bool withNull = true, int sn = 0) const {
+  // withAnchored: anchored_ge and p_window_anchored over n behind those
+  std::string lines(int n, bool withNull = true, int sn = 0, bool withAnchored = false) const {
     std::string out;
     const auto cols = [&](const Rec &r, const std::vector<float> &v, int m) {
       int ge = 0;
@@ -557,6 +574,7 @@ struct WinSummary {
       put(out, "%s\t%i\t%s", r.id.c_str(), r.pieces, fmt3(r.score).c_str());
       if (withNull) cols(r, r.vec, n);
       if (sn > 0) cols(r, r.shf, sn);
+      if (withAnchored) cols(r, r.anc, n);
       out += "\n";
     }
     return out;
@@ -574,7 +592,8 @@ inline const char *region_support_header_null_shuffle() { return RC_REGION_SUPPO
 // least the row's own over exactly this segment, or nullptr: the lines without those two columns.  p = (count + 1) / (n + 1), `nan` where
 // the row's pair score is NaN.
 inline std::string region_support_lines(const Region &r, const SegLoc &at, float score, const std::vector<std::string> &rowNames, const float *pairs, int nk,
-                                        float Delta, const int32_t *ge = nullptr, int n = 0, const int32_t *sge = nullptr, int sn = 0) {
+                                        float Delta, const int32_t *ge = nullptr, int n = 0, const int32_t *sge = nullptr, int sn = 0,
+                                        const int32_t *age = nullptr) {   // age: --regions-anchored-null's counts over n, behind the others
   const std::vector<float> loo = leave_one_out(pairs, nk, Delta);
   const float nkf = static_cast<float>(nk);
   std::string head, out;
@@ -583,9 +602,9 @@ inline std::string region_support_lines(const Region &r, const SegLoc &at, float
     const float pair = pairs[k - 1], share = pair / nkf;
     put(out, "%s\t%i\t%s", head.c_str(), k, rowNames[static_cast<size_t>(k)].c_str());
     out += "\t" + fmt3(pair) + "\t" + fmt3(share) + "\t" + fmt3(loo[static_cast<size_t>(k) - 1]);
-    const int32_t *counts[2] = {ge, sge};
-    const int of[2] = {n, sn};
-    for (int c = 0; c < 2; c++) {
+    const int32_t *counts[3] = {ge, sge, age};
+    const int of[3] = {n, sn, n};
+    for (int c = 0; c < 3; c++) {
       if (!counts[c]) continue;
       const int g = counts[c][k - 1];
       if (pair != pair) put(out, "\t%i\tnan", g);

@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -143,6 +144,119 @@ bool parse_newick(const char *s, Tree &t, std::string &err) {
   if (!p.subtree(-1, true, &root)) { err = p.err; return false; }
   t.length[0] = 0.0;
   return true;
+}
+
+// ---------------------------------------------------------------------------------- the tree re-rooted at a tip
+
+namespace {
+// A walk over t as an unrooted graph that writes `out` in pre-order.  Nodes are numbered in t's text pre-order, so a node's children are the
+// nodes whose parent it is, in index order.
+struct Anchorer {
+  const Tree &t;
+  Tree &out;
+  std::vector<int> kidOff, kids;   // t's children, CSR
+  explicit Anchorer(const Tree &tt, Tree &o) : t(tt), out(o) {
+    kidOff.assign(static_cast<size_t>(t.nnodes) + 1, 0);
+    for (int q = 1; q < t.nnodes; q++) kidOff[t.parent[q] + 1]++;
+    for (int q = 0; q < t.nnodes; q++) kidOff[q + 1] += kidOff[q];
+    kids.resize(kidOff[t.nnodes]);
+    std::vector<int> at(kidOff.begin(), kidOff.end() - 1);
+    for (int q = 1; q < t.nnodes; q++) kids[at[t.parent[q]]++] = q;
+  }
+  int nkids(int x) const { return kidOff[x + 1] - kidOff[x]; }
+  int emit(int parent, double len, int tipOf) {   // tipOf: the node of t whose tip this is, -1 for an internal node
+    const int q = out.nnodes++;
+    out.parent.push_back(parent < 0 ? 0 : parent);
+    out.length.push_back(len);
+    out.haslen.push_back(parent < 0 ? 0 : 1);
+    out.tip.push_back(tipOf < 0 ? -1 : t.tip[tipOf]);
+    if (tipOf >= 0) out.tipnode[t.tip[tipOf]] = q;
+    return q;
+  }
+  // node x of t, entered from its neighbour `from`, below node `parent` of `out` on a branch of `len` (recursive: a small frame per node on
+  // the path from the reference, at most kMaxNodes of them)
+  void visit(int x, int from, int parent, double len) {
+    const int q = emit(parent, len, t.tip[x] >= 0 ? x : -1);
+    for (int i = kidOff[x]; i < kidOff[x + 1]; i++)
+      if (kids[i] != from) visit(kids[i], x, q, t.length[kids[i]]);
+    if (x != 0 && from != t.parent[x]) up(x, q);
+  }
+  // what lies behind x's former parent, hung below node q of `out`: the parent itself on x's former branch, or, where the parent is the
+  // two-child root of a rooted t, that root's other child on the sum of the two root branches
+  void up(int x, int q) {
+    const int p = t.parent[x];
+    if (p == 0 && nkids(0) == 2) {
+      const int w = kids[kidOff[0]] == x ? kids[kidOff[0] + 1] : kids[kidOff[0]];
+      visit(w, 0, q, t.length[x] + t.length[w]);
+    } else {
+      visit(p, x, q, t.length[x]);
+    }
+  }
+};
+}  // namespace
+
+bool anchor_tree(const Tree &t, int refTipNode, Tree &out) {
+  out.clear();
+  if (refTipNode <= 0 || refTipNode >= t.nnodes || t.tip[refTipNode] < 0 || t.ntips() < 2) return false;
+  out.rooted = true;
+  out.namepool = t.namepool; out.nameOff = t.nameOff; out.nameLen = t.nameLen;
+  out.tipnode.assign(t.tipnode.size(), -1);
+  Anchorer a(t, out);
+  const int root = a.emit(-1, 0.0, -1);
+  a.emit(root, 0.0, refTipNode);
+  a.up(refTipNode, root);
+  return true;
+}
+
+std::string tree_text(const Tree &t) {
+  std::vector<int> kidOff(static_cast<size_t>(t.nnodes) + 1, 0), kids;
+  for (int q = 1; q < t.nnodes; q++) kidOff[t.parent[q] + 1]++;
+  for (int q = 0; q < t.nnodes; q++) kidOff[q + 1] += kidOff[q];
+  kids.resize(kidOff[t.nnodes]);
+  std::vector<int> at(kidOff.begin(), kidOff.end() - 1);
+  for (int q = 1; q < t.nnodes; q++) kids[at[t.parent[q]]++] = q;
+  std::string s;
+  struct Frame { int q, next; };
+  std::vector<Frame> st;
+  st.push_back(Frame{0, kidOff[0]});
+  if (t.tip[0] < 0) s += '(';
+  while (!st.empty()) {
+    Frame &f = st.back();
+    const int q = f.q;
+    if (t.tip[q] < 0 && f.next < kidOff[q + 1]) {
+      if (f.next > kidOff[q]) s += ',';
+      const int c = kids[f.next++];
+      if (t.tip[c] < 0) s += '(';
+      st.push_back(Frame{c, kidOff[c]});
+      continue;
+    }
+    if (t.tip[q] >= 0) s.append(t.namepool.data() + t.nameOff[t.tip[q]], static_cast<size_t>(t.nameLen[t.tip[q]]));
+    else s += ')';
+    if (q != 0) {
+      char buf[40];
+      std::snprintf(buf, sizeof buf, ":%.17g", t.length[q]);
+      s += buf;
+    }
+    st.pop_back();
+  }
+  s += ';';
+  return s;
+}
+
+void tree_of_keep(const TreeKeep *nodes, int nnodes, int N, Tree &t) {
+  t.clear();
+  t.nnodes = nnodes;
+  t.parent.resize(nnodes); t.length.resize(nnodes); t.haslen.assign(nnodes, 1); t.tip.resize(nnodes);
+  t.nameOff.assign(N, 0); t.nameLen.assign(N, 0); t.tipnode.assign(N, -1);
+  int rootKids = 0;
+  for (int q = 0; q < nnodes; q++) {
+    t.parent[q] = nodes[q].parent;
+    std::memcpy(&t.length[q], nodes[q].len, sizeof(double));
+    t.tip[q] = nodes[q].tiprow;
+    if (nodes[q].tiprow >= 0) t.tipnode[nodes[q].tiprow] = q;
+    if (q != 0 && nodes[q].parent == 0) rootKids++;
+  }
+  t.rooted = rootKids == 2;
 }
 
 // ---------------------------------------------------------------------------------- models
@@ -308,6 +422,31 @@ void pack_thresholds(const double cum[4], U4 *out, uint32_t *base) {
   out->x = thr[0]; out->y = thr[1]; out->z = thr[2]; out->w = thr[3];
 }
 }  // namespace
+
+void fill_sim_tables(const Tree &t, const int *rowtip, int N, const float freqs[4], float kappa, NodeRec *nodes, uint8_t *qtip, uint16_t *qtip16) {
+  SeqGenHky hky(freqs, kappa);
+  for (int q = 0; q < t.nnodes; q++) {
+    NodeRec &nr = nodes[q];
+    std::memset(&nr, 0, sizeof nr);
+    nr.parent = static_cast<uint16_t>(t.parent[q]);
+    nr.gctrl = node_ctrl(static_cast<uint32_t>(t.parent[q])) | ((t.parent[q] >> 3) == (q >> 3) ? 0x80000000u : 0u);
+    nr.tiprow = -1;
+    double M[4][4];
+    if (q != 0) hky.cumulative(t.length[q], M);                      // evolve.c:404 (scale 1.0), :292
+    for (int p = 0; p < 4; p++) {
+      uint32_t b = 0;
+      pack_thresholds(q == 0 ? hky.addFreq : M[p], &nr.thr[p], &b);
+      nr.basepack |= b << (2 * p);
+      if (sim_may_clamp(nr.thr[p].w)) nr.parent |= kNodeMayClamp;   // k_null compares with t3 only at such nodes
+    }
+  }
+  for (int r = 0; r < N; r++) {
+    const int q = t.tipnode[rowtip[r]];
+    if (qtip) qtip[r] = static_cast<uint8_t>(q);
+    qtip16[r] = static_cast<uint16_t>(q);
+    nodes[q].tiprow = static_cast<int16_t>(r);
+  }
+}
 
 // ---------------------------------------------------------------------------------- sigma codes
 
@@ -522,31 +661,20 @@ int prepare_block(const rc_block &in, const rc_params &par, const PairTable &pt,
     }
 
   // simulation tables: null alignments use the forward frequencies and kappa (score.c:996-998)
-  SeqGenHky hky(freqs[0], in.kappa);
-  NodeRec *nodes = reinterpret_cast<NodeRec *>(base + d.off_nodes);
-  for (int q = 0; q < t.nnodes; q++) {
-    NodeRec &nr = nodes[q];
-    std::memset(&nr, 0, sizeof nr);
-    nr.parent = static_cast<uint16_t>(t.parent[q]);
-    nr.gctrl = node_ctrl(static_cast<uint32_t>(t.parent[q])) | ((t.parent[q] >> 3) == (q >> 3) ? 0x80000000u : 0u);
-    nr.tiprow = -1;
-    double M[4][4];
-    if (q != 0) hky.cumulative(t.length[q], M);                      // evolve.c:404 (scale 1.0), :292
-    for (int p = 0; p < 4; p++) {
-      uint32_t b = 0;
-      pack_thresholds(q == 0 ? hky.addFreq : M[p], &nr.thr[p], &b);
-      nr.basepack |= b << (2 * p);
-      if (sim_may_clamp(nr.thr[p].w)) nr.parent |= kNodeMayClamp;   // k_null compares with t3 only at such nodes
+  std::memset(base + d.off_qtip, 0, sec.qtip);
+  fill_sim_tables(t, rowtip, N, freqs[0], in.kappa, reinterpret_cast<NodeRec *>(base + d.off_nodes), base + d.off_qtip,
+                  reinterpret_cast<uint16_t *>(base + d.off_qtip16));
+  if (arena.keep) {   // what re-rooting at the reference tip needs (rc_batch_segment_null_anchored)
+    const size_t at = arena.keepUsed.fetch_add(static_cast<size_t>(t.nnodes));
+    if (at + static_cast<size_t>(t.nnodes) > arena.keepCap) { err = "internal: tree arena too small"; return done(RC_ERR_ARG); }
+    meta.keepOff = at;
+    for (int q = 0; q < t.nnodes; q++) {
+      TreeKeep &k = arena.keep[at + q];
+      std::memcpy(k.len, &t.length[q], sizeof(double));
+      k.parent = static_cast<uint16_t>(t.parent[q]);
+      k.tiprow = -1;
     }
-  }
-  uint8_t *qtip = base + d.off_qtip;
-  uint16_t *qtip16 = reinterpret_cast<uint16_t *>(base + d.off_qtip16);
-  std::memset(qtip, 0, sec.qtip);
-  for (int r = 0; r < N; r++) {
-    const int q = t.tipnode[rowtip[r]];
-    qtip[r] = static_cast<uint8_t>(q);
-    qtip16[r] = static_cast<uint16_t>(q);
-    nodes[q].tiprow = static_cast<int16_t>(r);
+    for (int r = 0; r < N; r++) arena.keep[at + t.tipnode[rowtip[r]]].tiprow = static_cast<int16_t>(r);
   }
   return done(RC_OK);
 }

@@ -29,6 +29,30 @@ struct Tree {
 };
 bool parse_newick(const char *s, Tree &t, std::string &err);
 
+// The anchored null's tree ("Anchored null"): t re-rooted at a new node on the edge of the tip at node refTipNode, at distance 0
+// from it.  Node 0 of `out` is the new root; its children are a copy of the tip with length 0, then the tip's neighbour with the length of the
+// tip's edge.  Every other node keeps its neighbours in t's text order minus the one it is entered from, its former parent last and carrying
+// the node's own former length; the two-child root of a rooted t is dissolved (its branches summed).  `out` is rooted and binary, in text
+// pre-order, 2 * tips - 1 nodes; tips keep their numbers and labels.  false: refTipNode is no tip of t, or t has fewer than two tips.
+bool anchor_tree(const Tree &t, int refTipNode, Tree &out);
+// t as Newick text, "%.17g" lengths (none on the root): parse_newick reads back the same doubles
+std::string tree_text(const Tree &t);
+
+// What re-rooting needs of a block's tree once its thresholds are in the blob: per node 12 bytes in host memory (rc_batch::treeKeep)
+struct TreeKeep {
+  uint32_t len[2];    // the length as parsed, a double's two halves (so that the record packs to 12 bytes)
+  uint16_t parent;
+  int16_t tiprow;     // the row whose tip this node is, -1 for an internal node
+};
+static_assert(sizeof(TreeKeep) == 12, "TreeKeep layout");
+// the tree behind nodes[0 .. nnodes): tip numbers are rows, labels empty
+void tree_of_keep(const TreeKeep *nodes, int nnodes, int N, Tree &t);
+
+// The simulation tables of a tree (seqgen/evolve.c:400-433 in the integer form of threshold_of): NodeRec[t.nnodes], and the node of every
+// row's tip, row r's tip being tip number rowtip[r] -- as bytes (qtip, may be null; meaningful below 256 nodes) and as u16.  Null alignments use
+// the forward frequencies and kappa (score.c:996-998).  The run's tables (prepare_block) and the anchored null's are both made here.
+void fill_sim_tables(const Tree &t, const int *rowtip, int N, const float freqs[4], float kappa, NodeRec *nodes, uint8_t *qtip, uint16_t *qtip16);
+
 // sigma-code space shared by all blocks of a context (depends only on the BLOSUM choice)
 struct PairTable {
   int nB = 0;                 // distinct matrix values
@@ -52,6 +76,9 @@ struct BlobArena {
   std::atomic<size_t> hostUsed{0};
   size_t devCap = 0;
   std::atomic<size_t> devUsed{0};
+  TreeKeep *keep = nullptr;         // where the blocks' trees are kept for re-rooting (null: not kept), keepCap records
+  size_t keepCap = 0;
+  std::atomic<size_t> keepUsed{0};
 };
 
 // what the host keeps per block once the tables are in the blob
@@ -59,6 +86,7 @@ struct BlockMeta {
   int status = RC_OK;
   int N = 0, NK = 0, cols = 0, L = 0;
   int ref_start = 0, ref_length = 0;
+  size_t keepOff = 0;               // the block's tree in BlobArena::keep: DevBlock::nnodes records from here
 };
 
 // upper bounds of a block's share of the two blob parts, from its shape alone (L <= cols, nodes <= 2N-1)

@@ -1085,6 +1085,7 @@ int generic_occupancy(NullKind kind, size_t ldsBytes) {
   switch (kind) {
     case NullKind::GenericSim: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_generic_sim<false>, 64, ldsBytes); break;
     case NullKind::TiledSim: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_generic_sim<true>, 64, ldsBytes); break;
+    case NullKind::GenericSimAnchored: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_generic_sim_anchored, 64, ldsBytes); break;
     case NullKind::GenericDp: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_generic_dp, 64, ldsBytes); break;
     default: break;
   }
@@ -1097,6 +1098,9 @@ void launch_generic(NullKind kind, const NullArgs &a, int grid, size_t ldsBytes,
     hipLaunchKernelGGL(k_generic_sim<true>, dim3(grid), dim3(64), ldsBytes, stream, a, a.blob, a.dblocks, a.classBlocks, a.flags, a.U, a.pair, scratchBytes, a.maxima);
   else
     hipLaunchKernelGGL(k_generic_sim<false>, dim3(grid), dim3(64), ldsBytes, stream, a, a.blob, a.dblocks, a.classBlocks, a.flags, a.U, a.pair, scratchBytes, a.maxima);
+}
+void launch_generic_anchored(const NullArgs &a, int grid, size_t ldsBytes, hipStream_t stream) {
+  hipLaunchKernelGGL(k_generic_sim_anchored, dim3(grid), dim3(64), ldsBytes, stream, a, a.blob, a.dblocks, a.classBlocks, a.flags, a.U, a.pair, a.codesAll, a.maxima);
 }
 void launch_native_dp_generic(const NativeArgs &a, int nblocks, float *scratch, size_t scratchStride, hipStream_t stream) {
   hipLaunchKernelGGL(k_native_dp_generic, dim3(nblocks * 6), dim3(64), 0, stream, a, scratch, scratchStride);

@@ -19,6 +19,14 @@ constexpr bool kProfiling = true;
 constexpr bool kProfiling = false;
 #endif
 
+// k_generic_sim_anchored: the simulation tables of one block's tree re-rooted at its reference tip (rc_host.h, anchor_tree), uploaded by the
+// call; entry p belongs to position p of the launch's classBlocks and stands in for DevBlock::off_nodes, off_qtip16 and nnodes
+struct AnchorRec {
+  const NodeRec *nodes;       // [nnodes]
+  const uint16_t *qtip16;     // [N]
+  int32_t nnodes, pad;
+};
+
 struct NullArgs {
   const uint8_t *blob;
   const DevBlock *dblocks;
@@ -46,7 +54,7 @@ struct NullArgs {
   size_t codesStride;
   int cacheSites;             // codes from L2: the words of the last cacheSites sites of a strand x frame are kept in LDS (0: none)
   uint32_t spillOff;          // two rows per pass: uint32 from a workgroup's scratch to its spill area, the end of its stride (rc_spill_plan.h)
-  int reserved[2];            // unused, zero: keeps the offsets of the fields below (the launch's instantiation is a NullKind, below)
+  const AnchorRec *anchor;    // k_generic_sim_anchored: [nClassBlocks]; null for every other launch (in the place of two unused words: the offsets of the fields below stay)
   int stealWait;              // 1: a workgroup without work waits for owners that are still simulating a late item; 0: it leaves at once (a stream: the next sub-batch's workgroups want its place)
   int simParts, simGrid;      // rows split over workgroups: an item's simulation is cut into simParts site ranges, simGrid workgroups take them (k_null<.., 2>)
   unsigned int *simCounter;   // ... from queues of their own [8]
@@ -202,6 +210,7 @@ enum class NullKind {
   RowSplit,       // k_null<NK, false, false, false, 2> on a.simGrid, then <.., 1>: a part's rows over workgroups (k_null_rowscan follows)
   GenericSim,     // k_generic_sim<false>: the simulation of the blocks of more than 64 rows
   TiledSim,       // k_generic_sim<true>: ... of a tiled class, its codes in k_tiled_dp's layout
+  GenericSimAnchored,   // k_generic_sim_anchored: k_generic_sim<false> on a call's own trees, the root's state from the reference row
   GenericDp,      // k_generic_dp
   TiledDp,        // k_tiled_dp<KT, false>
   TiledDpNan,     // k_tiled_dp<KT, true>: the reference's NaN-order-dependent maxima
@@ -219,6 +228,7 @@ inline std::string null_kernel_name(NullKind kind, int n) {
     case NullKind::RowSplit: return "rc::k_null<" + k + ", false, false, false, 1>";
     case NullKind::GenericSim: return "rc::k_generic_sim<false>";
     case NullKind::TiledSim: return "rc::k_generic_sim<true>";
+    case NullKind::GenericSimAnchored: return "rc::k_generic_sim_anchored";
     case NullKind::GenericDp: return "rc::k_generic_dp";
     case NullKind::TiledDp: return "rc::k_tiled_dp<" + k + ", false>";
     case NullKind::TiledDpNan: return "rc::k_tiled_dp<" + k + ", true>";
@@ -465,6 +475,8 @@ size_t null_generic_state_bytes(int N, int L, int nnodes);
 // k_generic_sim<false / true> and k_generic_dp (GenericSim, TiledSim, GenericDp): occupancy, launch (the DP reads the codes at scratchBytes)
 int generic_occupancy(NullKind kind, size_t ldsBytes);
 void launch_generic(NullKind kind, const NullArgs &a, int grid, size_t ldsBytes, uint8_t *scratchBytes, hipStream_t stream);
+void launch_generic_anchored(const NullArgs &a, int grid, size_t ldsBytes, hipStream_t stream);   // GenericSimAnchored: a.anchor set
+static_assert(sizeof(NullArgs) == 248 && offsetof(NullArgs, stealWait) == 184, "NullArgs layout");
 // blocks of 32 rows and more that are short enough (rc_device.h, block_class) in tiles of KT sequences (rc_null_tiled.h): bytes of an item's
 // codes / of a DP workgroup's row buffer; occupancy and launch of k_tiled_dp<KT, ..> (TiledDp, TiledDpNan)
 size_t null_tiled_codes_bytes(int NK, int KT, int L);

@@ -180,11 +180,17 @@ __host__ __device__ inline size_t generic_lds_bytes(int N, int nn) {
 // in the simulation and in the DP side by side on a CU cost more than the two in turn -- 1024 blocks of 100 x 300: 972 ms against 117 ms
 // + 727 ms alone, 928 ms as two launches per round of 4096 items; 500 blocks of 200 x 90: 225 -> 189 ms; 40 blocks of 500 x 60: 63.5 -> 45.1.)
 // TILED (with SIM): the codes in k_tiled_dp's layout (rc_null_tiled.h) instead, for blocks of up to 64 rows.
-template <bool SIM, bool TILED = false>
+// ANCHOR (with SIM, not TILED): the anchored null's simulation.  The tree is the call's own -- the block's, re-rooted at its reference tip
+// (rc_host.h, anchor_tree): nodes, tip positions and node count come from A.anchor[position in classBlocks] -- and where the reference row holds a
+// nucleotide at the column, the root takes that state: its draw is fetched like every other and dropped, and counts no clamp.  The column's
+// character is the same for every lane: one scalar load per column, in front of the node groups, and one wave-uniform test per group of
+// eight nodes, outside the node body.
+template <bool SIM, bool TILED = false, bool ANCHOR = false>
 __device__ __forceinline__ void generic_body(const NullArgs &A, const uint8_t *__restrict__ blob, const DevBlock *__restrict__ dblocks,
                                              const int *__restrict__ classBlocks, const uint32_t *__restrict__ flags,
                                              const uint32_t *__restrict__ Ustream, const uint8_t *__restrict__ pairTab,
                                              uint8_t *__restrict__ scratch, float *__restrict__ maxima, uint32_t *ldsGeneric) {
+  static_assert(!ANCHOR || (SIM && !TILED), "the anchored simulation writes k_generic_dp's layout");
   const int lane = threadIdx.x;
   uint8_t *__restrict__ mine = scratch + static_cast<size_t>(blockIdx.x) * A.scratchStride;   // scratchStride in bytes here
   unsigned int xcc;
@@ -211,11 +217,12 @@ __device__ __forceinline__ void generic_body(const NullArgs &A, const uint8_t *_
     const int onlyCombo = (A.comboSplit && !SIM) ? sub % parts : -1;
     const DevBlock *__restrict__ db = dblocks + bi;
     const bool nanSem = !SIM && (flags[bi] & kFlagNan) != 0u;   // NaN score tables: every cell through the written-out recurrence with the reference's MAX macro (rc_null_kernel.h, ref_max)
-    const int N = db->N, NK = db->NK, cols = db->cols, L = db->L, nnodes = db->nnodes, L1 = L + 1;
+    const AnchorRec *__restrict__ anchorRec = ANCHOR ? A.anchor + t / perBlock : nullptr;
+    const int N = db->N, NK = db->NK, cols = db->cols, L = db->L, nnodes = ANCHOR ? anchorRec->nnodes : db->nnodes, L1 = L + 1;
     const int NCW = (NK + 4) / 5, ZW = db->zw_words;
     const float Delta = db->Delta, Omega = db->Omega, omega = db->omega, nkf = db->nkf;
-    const NodeRec *__restrict__ nodes = reinterpret_cast<const NodeRec *>(blob + db->off_nodes);
-    const uint16_t *__restrict__ qtip = reinterpret_cast<const uint16_t *>(blob + db->off_qtip16);
+    const NodeRec *__restrict__ nodes = ANCHOR ? anchorRec->nodes : reinterpret_cast<const NodeRec *>(blob + db->off_nodes);
+    const uint16_t *__restrict__ qtip = ANCHOR ? anchorRec->qtip16 : reinterpret_cast<const uint16_t *>(blob + db->off_qtip16);
     const uint16_t *__restrict__ refcol = reinterpret_cast<const uint16_t *>(blob + db->off_refcol);
     const unsigned long long *__restrict__ zw = reinterpret_cast<const unsigned long long *>(blob + db->off_zw);
     const uint32_t *__restrict__ maskw = reinterpret_cast<const uint32_t *>(blob + db->off_mask);
@@ -241,9 +248,12 @@ __device__ __forceinline__ void generic_body(const NullArgs &A, const uint8_t *_
     const int thrLane = lane & 15, thrNode = lane >> 4;
     const size_t qstride = static_cast<size_t>(cols) * A.Spad;
     const int lastNode = nnodes - 1;
+    const uint32_t *__restrict__ refrow = reinterpret_cast<const uint32_t *>(blob + db->off_chars);   // row 0, four columns a word (the section is 16-aligned)
     for (int r = 0; r < N; r++) win[r * kWave] = 0;
     for (int i = 1; i <= L; i++) {
       const uint32_t col = (refw[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+      [[maybe_unused]] uint32_t anchorSt = kSimNoAnchor;   // the root's state where the reference row names it: looked at behind node 0 of the first group, gone behind that group
+      if constexpr (ANCHOR) anchorSt = sim_anchor_state((refrow[col >> 2] >> (8u * (col & 3u))) & 0xffu);
       const uint32_t *__restrict__ up = Ustream + (static_cast<size_t>(col) * A.Spad + sidx);
       uint32_t uu[8], thrA, thrB, ctlV;
       auto fetch = [&](int q0, uint32_t (&u)[8], uint32_t &ta, uint32_t &tb, uint32_t &cv) {
@@ -285,7 +295,19 @@ __device__ __forceinline__ void generic_body(const NullArgs &A, const uint8_t *_
           clamped += sim_clamps(u, thw);
           cur |= (st & 3u) << (2 * t);
         };
-        if (full) {
+        if constexpr (ANCHOR) {
+          // a group's first node by itself: in the first group it is the root, and where the reference row names the root's state the draw's
+          // outcome and its clamp are dropped (anchorSt names nothing behind the first group); then the other seven
+          const unsigned int clampedBefore = clamped;
+          node(std::integral_constant<int, 0>{});
+          if (anchorSt != kSimNoAnchor) { cur = anchorSt; clamped = clampedBefore; }
+          if (full) {
+            static_for<7>([&](auto tc) { node(std::integral_constant<int, decltype(tc)::value + 1>{}); });
+          } else {
+            static_for<7>([&](auto tc) { if (q0 + decltype(tc)::value + 1 < nnodes) node(std::integral_constant<int, decltype(tc)::value + 1>{}); });
+          }
+          anchorSt = kSimNoAnchor;
+        } else if (full) {
           static_for<8>(node);
         } else {
           static_for<8>([&](auto tc) { if (q0 + decltype(tc)::value < nnodes) node(tc); });
@@ -621,6 +643,13 @@ __global__ __launch_bounds__(64) void k_generic_sim(NullArgs A, const uint8_t *_
                                                     uint8_t *__restrict__ scratch, float *__restrict__ maxima) {
   extern __shared__ uint32_t ldsGeneric[];
   generic_body<true, TILED>(A, blob, dblocks, classBlocks, flags, Ustream, pairTab, scratch, maxima, ldsGeneric);
+}
+__global__ __launch_bounds__(64) void k_generic_sim_anchored(NullArgs A, const uint8_t *__restrict__ blob, const DevBlock *__restrict__ dblocks,
+                                                             const int *__restrict__ classBlocks, const uint32_t *__restrict__ flags,
+                                                             const uint32_t *__restrict__ Ustream, const uint8_t *__restrict__ pairTab,
+                                                             uint8_t *__restrict__ scratch, float *__restrict__ maxima) {
+  extern __shared__ uint32_t ldsGeneric[];
+  generic_body<true, false, true>(A, blob, dblocks, classBlocks, flags, Ustream, pairTab, scratch, maxima, ldsGeneric);
 }
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RC_GENERIC_WAVES, RC_GENERIC_WAVES))) void k_generic_dp(NullArgs A, const uint8_t *__restrict__ blob, const DevBlock *__restrict__ dblocks,
                                                    const int *__restrict__ classBlocks, const uint32_t *__restrict__ flags,

@@ -585,8 +585,65 @@ static void seg_pairs_deliver(const SegPairsOut &po, const SegPairsHost &ph, int
   }
 }
 
+// The anchored null (rc_batch_segment_null_anchored and its kin): the simulation tables of a call's distinct blocks on their trees re-rooted at
+// the reference tip (rc_host.h, anchor_tree), made on the host from what the batch keeps of every tree (rc_batch::treeKeep) and the block's
+// forward frequencies and kappa, as prepare_block makes the run's.  One upload: AnchorRec[blocks], then every block's NodeRec[] and u16 tip
+// positions, 16-aligned.  Nothing of it outlives the call.
+struct AnchorHost {
+  std::vector<uint8_t> up;
+  std::vector<size_t> nodesAt, qtipAt;
+  std::vector<int> nnodes;
+  int maxDraws = 0;     // the most (tree nodes x columns) of any of the blocks: what the MT19937 streams must hold
+  double hostMs = 0.0;
+};
+static int anchor_host(const rc_batch *b, const std::vector<int> &blocks, AnchorHost &ah) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t nb = blocks.size();
+  ah.nodesAt.resize(nb); ah.qtipAt.resize(nb); ah.nnodes.resize(nb);
+  size_t at = (nb * sizeof(AnchorRec) + 15) & ~static_cast<size_t>(15);
+  for (size_t p = 0; p < nb; p++) {
+    const BlockMeta &m = b->meta[blocks[p]];
+    ah.nnodes[p] = 2 * m.N - 1;
+    ah.nodesAt[p] = at; at += static_cast<size_t>(ah.nnodes[p]) * sizeof(NodeRec);
+    ah.qtipAt[p] = at; at += (2 * static_cast<size_t>(m.N) + 15) & ~static_cast<size_t>(15);
+    ah.maxDraws = std::max(ah.maxDraws, ah.nnodes[p] * m.cols);
+  }
+  ah.up.assign(at, 0);
+  const uint8_t *hblob = b->hblob.as<uint8_t>();
+  std::atomic<bool> ok{true};
+  parallel_for(static_cast<int>(nb), static_cast<unsigned>(std::max(1, b->ctx->hostThreads)), [&](int p) {
+    static thread_local Tree t, ta;
+    static thread_local std::vector<int> rowtip;
+    const int blk = blocks[p];
+    const BlockMeta &m = b->meta[blk];
+    tree_of_keep(b->treeKeep.data() + m.keepOff, b->db[blk].nnodes, m.N, t);
+    if (t.tipnode[0] < 0 || !anchor_tree(t, t.tipnode[0], ta) || ta.nnodes != ah.nnodes[p]) { ok = false; return; }
+    rowtip.resize(m.N);
+    for (int r = 0; r < m.N; r++) rowtip[r] = r;   // (tree_of_keep numbers the tips by row)
+    const ModelRec *fwd = reinterpret_cast<const ModelRec *>(hblob + b->db[blk].off_models);   // row 0 of the forward strand: the block's frequencies and kappa
+    fill_sim_tables(ta, rowtip.data(), m.N, fwd->freqs, fwd->kappa, reinterpret_cast<NodeRec *>(ah.up.data() + ah.nodesAt[p]), nullptr,
+                    reinterpret_cast<uint16_t *>(ah.up.data() + ah.qtipAt[p]));
+  });
+  if (!ok) return fail(RC_ERR_ARG, "internal: a block's tree could not be re-rooted at its reference tip");
+  ah.hostMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  b->ctx->anchorHostMs.store(ah.hostMs);   // (rc_ctx_anchor_host_ms)
+  return RC_OK;
+}
+// the records' pointers into d, then the upload on st (ah.up must outlive the copy)
+static int anchor_upload(AnchorHost &ah, DevBuf &d, hipStream_t st) {
+  HIP_TRY(d.ensure(ah.up.size()));
+  AnchorRec *rec = reinterpret_cast<AnchorRec *>(ah.up.data());
+  for (size_t p = 0; p < ah.nnodes.size(); p++) {
+    rec[p].nodes = reinterpret_cast<const NodeRec *>(d.as<uint8_t>() + ah.nodesAt[p]);
+    rec[p].qtip16 = reinterpret_cast<const uint16_t *>(d.as<uint8_t>() + ah.qtipAt[p]);
+    rec[p].nnodes = ah.nnodes[p]; rec[p].pad = 0;
+  }
+  HIP_TRY(hipMemcpyAsync(d.p, ah.up.data(), ah.up.size(), hipMemcpyHostToDevice, st));
+  return RC_OK;
+}
+
 static int segment_null_call(const rc_batch *bc, const rc_bt_range *ranges, int32_t n_ranges, float *score_out, int32_t *ge_out, float *null_out,
-                             int64_t cap, const SegPairsOut *po) {
+                             int64_t cap, const SegPairsOut *po, bool anchored) {
   rc_batch *b = const_cast<rc_batch *>(bc);
   if (!b || n_ranges < 0 || (n_ranges > 0 && (!ranges || !score_out || !ge_out))) return fail(RC_ERR_ARG, "bad argument");
   if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
@@ -611,6 +668,8 @@ static int segment_null_call(const rc_batch *bc, const rc_bt_range *ranges, int3
   }
   if (maxItems > static_cast<size_t>(INT32_MAX)) return fail(RC_ERR_ARG, "more than 2^31 - 1 (block, sample group) items in one round");
   for (int blk : pl.blocks) RC_TRY(check_codes_layout(b, blk));
+  AnchorHost ah;
+  if (anchored) RC_TRY(anchor_host(b, pl.blocks, ah));
   // one upload: the distinct blocks, the CSR, the ranges, the native scores
   const size_t nb = pl.blocks.size(), nr = static_cast<size_t>(n_ranges);
   const size_t oStart = nb, oIdx = oStart + nb + 1, oRanges = oIdx + nr, oScores = oRanges + 4 * nr;
@@ -629,8 +688,8 @@ static int segment_null_call(const rc_batch *bc, const rc_bt_range *ranges, int3
   HIP_TRY(hipSetDevice(c->device));
   RC_STREAM_TRY(st, stream_aux(c));
   HIP_TRY(hipEventSynchronize(b->evPrep));   // the tables of the blob are made on the device
-  DevBuf d_up, d_ge, d_cnt, d_codes, d_null, d_pge, d_pnull;
-  adopt_bufs(c, {&d_up, &d_ge, &d_cnt, &d_codes, &d_null, &d_pge, &d_pnull});
+  DevBuf d_up, d_ge, d_cnt, d_codes, d_null, d_pge, d_pnull, d_anchor;
+  adopt_bufs(c, {&d_up, &d_ge, &d_cnt, &d_codes, &d_null, &d_pge, &d_pnull, &d_anchor});
   const uint8_t *blob = b->dblob.as<uint8_t>();
   constexpr size_t kCntWords = 16;   // the simulation's eight work queues, then (8-aligned) its clamp count: this call's own, read by nobody
   bool launched = false;
@@ -647,10 +706,11 @@ static int segment_null_call(const rc_batch *bc, const rc_bt_range *ranges, int3
     launched = true;   // from here on something may be in flight
     // the MT19937 streams of the batch's seeds: the context's cache, or regenerated as a run does (the batch's own record of it stays)
     const bool mtLaunched = b->mtLaunched;
-    const int mt = ensure_mt_stream(c, b, st, b->par.seed_base, Spad, b->maxDraws);
+    const int mt = ensure_mt_stream(c, b, st, b->par.seed_base, Spad, std::max(b->maxDraws, ah.maxDraws));   // (anchored: a node more per block)
     b->mtLaunched = mtLaunched;
     RC_TRY(mt);
     HIP_TRY(hipMemcpyAsync(d_up.p, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (anchored) RC_TRY(anchor_upload(ah, d_anchor, st));
     HIP_TRY(hipMemsetAsync(d_ge.p, 0, nr * sizeof(int32_t), st));
     if (po) HIP_TRY(hipMemsetAsync(d_pge.p, 0, nItems * sizeof(int32_t), st));
     NullArgs sim{};
@@ -673,10 +733,10 @@ static int segment_null_call(const rc_batch *bc, const rc_bt_range *ranges, int3
     for (const SegNullRound &rd : pl.rounds) {
       int maxN = 0, maxNodes = 0;
       for (int p = rd.first; p < rd.first + rd.count; p++) {
-        maxN = std::max(maxN, b->meta[pl.blocks[p]].N); maxNodes = std::max(maxNodes, b->db[pl.blocks[p]].nnodes);
+        maxN = std::max(maxN, b->meta[pl.blocks[p]].N); maxNodes = std::max(maxNodes, anchored ? ah.nnodes[p] : b->db[pl.blocks[p]].nnodes);
       }
       sim.classBlocks = d_up.as<int>() + rd.first; sim.nClassBlocks = rd.count; sim.codesStride = rd.stride;
-      RC_TRY(launch_sim_side(c, sim, static_cast<long long>(rd.count) * groups, maxN, maxNodes, kCntWords, st));
+      RC_TRY(launch_sim_side(c, sim, static_cast<long long>(rd.count) * groups, maxN, maxNodes, kCntWords, st, anchored ? d_anchor.as<AnchorRec>() + rd.first : nullptr));
       sn.blocks = sim.classBlocks; sn.blkStart = d_up.as<int>() + oStart + rd.first; sn.nBlocks = rd.count; sn.codesStride = rd.stride;
       if (po) launch_segment_null_pairs(sn, pa, st); else launch_segment_null(sn, st);
       HIP_TRY(hipGetLastError());
@@ -698,13 +758,25 @@ static int segment_null_call(const rc_batch *bc, const rc_bt_range *ranges, int3
 
 int rc_batch_segment_null(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, float *score_out, int32_t *ge_out, float *null_out,
                           int64_t cap) {
-  return segment_null_call(b, ranges, n_ranges, score_out, ge_out, null_out, cap, nullptr);
+  return segment_null_call(b, ranges, n_ranges, score_out, ge_out, null_out, cap, nullptr, false);
+}
+
+int rc_batch_segment_null_anchored(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, float *score_out, int32_t *ge_out, float *null_out,
+                                   int64_t cap) {
+  return segment_null_call(b, ranges, n_ranges, score_out, ge_out, null_out, cap, nullptr, true);
 }
 
 int rc_batch_segment_null_pairs(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, float *score_out, int32_t *ge_out, float *pair_out,
                                 int32_t *pair_ge_out, int64_t cap, int64_t *offsets, float *pair_null_out, int64_t null_cap) {
   const SegPairsOut po{pair_out, pair_ge_out, cap, offsets, pair_null_out, null_cap};
-  return segment_null_call(b, ranges, n_ranges, score_out, ge_out, nullptr, 0, &po);
+  return segment_null_call(b, ranges, n_ranges, score_out, ge_out, nullptr, 0, &po, false);
+}
+
+int rc_batch_segment_null_pairs_anchored(const rc_batch *b, const rc_bt_range *ranges, int32_t n_ranges, float *score_out, int32_t *ge_out,
+                                         float *pair_out, int32_t *pair_ge_out, int64_t cap, int64_t *offsets, float *pair_null_out,
+                                         int64_t null_cap) {
+  const SegPairsOut po{pair_out, pair_ge_out, cap, offsets, pair_null_out, null_cap};
+  return segment_null_call(b, ranges, n_ranges, score_out, ge_out, nullptr, 0, &po, true);
 }
 
 // The best segment inside named windows and its own null (rc_window_null.hip).  A window's cells are the triangles of rc_window_plan.h; the
@@ -740,7 +812,7 @@ static int window_boxes(const rc_batch *b, const rc_bt_range *windows, int32_t n
   return RC_OK;
 }
 
-static int window_call(const rc_batch *bc, const rc_bt_range *windows, int32_t n_windows, const WinOuts &o, bool withNull) {
+static int window_call(const rc_batch *bc, const rc_bt_range *windows, int32_t n_windows, const WinOuts &o, bool withNull, bool anchored = false) {
   rc_batch *b = const_cast<rc_batch *>(bc);
   if (!b || n_windows < 0 || (n_windows > 0 && (!windows || !o.score || (withNull && !o.ge)))) return fail(RC_ERR_ARG, "bad argument");
   if (b->state != rc_batch::DONE) return fail(RC_ERR_ARG, "batch has not been run");
@@ -761,18 +833,20 @@ static int window_call(const rc_batch *bc, const rc_bt_range *windows, int32_t n
   std::vector<WinFold> folds;
   std::vector<Round> rounds;
   size_t codesNeed = 0, partialNeed = 0, scratchNeed = 0;
+  AnchorHost ah;
   if (withNull) {
     size_t budget = kSegNullMaxBytes;
     if (const char *e = std::getenv("RC_SEGNULL_MAX_BYTES")) budget = static_cast<size_t>(std::max(1ll, std::atoll(e)));
     const auto codes_bytes = [&](int blk) { return null_generic_codes_bytes(b->meta[blk].N, b->meta[blk].L, b->db[blk].nnodes); };
     pl = seg_null_plan(n_windows, [&](int r) { return windows[r].blk; }, codes_bytes, groups, budget);
     for (int blk : pl.blocks) RC_TRY(check_codes_layout(b, blk));
+    if (anchored) RC_TRY(anchor_host(b, pl.blocks, ah));
     for (const SegNullRound &rd : pl.rounds) {
       if (static_cast<size_t>(rd.count) * groups > static_cast<size_t>(INT32_MAX)) return fail(RC_ERR_ARG, "more than 2^31 - 1 (block, sample group) items in one round");
       Round R{items.size(), 0, folds.size(), 0, 0, 0, 0, 0, 0, false};
       for (int p = rd.first; p < rd.first + rd.count; p++) {
         const int blk = pl.blocks[p];
-        R.maxNK = std::max(R.maxNK, b->meta[blk].NK); R.maxN = std::max(R.maxN, b->meta[blk].N); R.maxNodes = std::max(R.maxNodes, b->db[blk].nnodes);
+        R.maxNK = std::max(R.maxNK, b->meta[blk].NK); R.maxN = std::max(R.maxN, b->meta[blk].N); R.maxNodes = std::max(R.maxNodes, anchored ? ah.nnodes[p] : b->db[blk].nnodes);
         for (int q = pl.blkStart[p]; q < pl.blkStart[p + 1]; q++) {
           const int w = pl.rangeIdx[q];
           const size_t slot0 = R.slots;
@@ -805,8 +879,8 @@ static int window_call(const rc_batch *bc, const rc_bt_range *windows, int32_t n
   HIP_TRY(hipSetDevice(c->device));
   RC_STREAM_TRY(st, stream_aux(c));
   HIP_TRY(hipEventSynchronize(b->evPrep));   // the tables of the blob are made on the device
-  DevBuf d_up, d_best, d_ge, d_cnt, d_codes, d_null, d_partial, d_scratch;
-  adopt_bufs(c, {&d_up, &d_best, &d_ge, &d_cnt, &d_codes, &d_null, &d_partial, &d_scratch});
+  DevBuf d_up, d_best, d_ge, d_cnt, d_codes, d_null, d_partial, d_scratch, d_anchor;
+  adopt_bufs(c, {&d_up, &d_best, &d_ge, &d_cnt, &d_codes, &d_null, &d_partial, &d_scratch, &d_anchor});
   const uint8_t *blob = b->dblob.as<uint8_t>();
   constexpr size_t kCntWords = 16;   // the simulation's eight work queues, then (8-aligned) its clamp count: this call's own, read by nobody
   bool launched = false;
@@ -827,11 +901,12 @@ static int window_call(const rc_batch *bc, const rc_bt_range *windows, int32_t n
     if (withNull) {
       // the MT19937 streams of the batch's seeds: the context's cache, or regenerated as a run does (the batch's own record of it stays)
       const bool mtLaunched = b->mtLaunched;
-      const int mt = ensure_mt_stream(c, b, st, b->par.seed_base, Spad, b->maxDraws);
+      const int mt = ensure_mt_stream(c, b, st, b->par.seed_base, Spad, std::max(b->maxDraws, ah.maxDraws));   // (anchored: a node more per block)
       b->mtLaunched = mtLaunched;
       RC_TRY(mt);
     }
     HIP_TRY(hipMemcpyAsync(d_up.p, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (anchored) RC_TRY(anchor_upload(ah, d_anchor, st));
     WinBestArgs wb{};
     wb.blob = blob; wb.dblocks = reinterpret_cast<const DevBlock *>(blob + b->oDblocks); wb.flags = b->dflags.as<uint32_t>();
     wb.boxes = reinterpret_cast<const WinBox *>(d_up.as<int>() + oBoxes);
@@ -854,7 +929,7 @@ static int window_call(const rc_batch *bc, const rc_bt_range *windows, int32_t n
         const SegNullRound &rd = pl.rounds[r];
         const Round &R = rounds[r];
         sim.classBlocks = d_up.as<int>() + oBlocks + rd.first; sim.nClassBlocks = rd.count; sim.codesStride = rd.stride;
-        RC_TRY(launch_sim_side(c, sim, static_cast<long long>(rd.count) * groups, R.maxN, R.maxNodes, kCntWords, st));
+        RC_TRY(launch_sim_side(c, sim, static_cast<long long>(rd.count) * groups, R.maxN, R.maxNodes, kCntWords, st, anchored ? d_anchor.as<AnchorRec>() + rd.first : nullptr));
         wn.blocks = sim.classBlocks; wn.codesStride = rd.stride;
         wn.items = reinterpret_cast<const WinItem *>(d_up.as<int>() + oItems) + R.item0; wn.nItems = static_cast<int>(R.nItems);
         wn.folds = reinterpret_cast<const WinFold *>(d_up.as<int>() + oFolds) + R.fold0; wn.nFolds = static_cast<int>(R.nFolds);
@@ -892,6 +967,13 @@ int rc_batch_window_null(const rc_batch *b, const rc_bt_range *windows, int32_t 
                          int32_t *opt_i_out, int64_t *cells_out, int32_t *ge_out, float *null_out, int64_t cap) {
   return window_call(b, windows, n_windows, WinOuts{score_out, frame_out, opt_b_out, opt_i_out, cells_out, ge_out, null_out, cap}, true);
 }
+
+int rc_batch_window_null_anchored(const rc_batch *b, const rc_bt_range *windows, int32_t n_windows, float *score_out, int32_t *frame_out,
+                                  int32_t *opt_b_out, int32_t *opt_i_out, int64_t *cells_out, int32_t *ge_out, float *null_out, int64_t cap) {
+  return window_call(b, windows, n_windows, WinOuts{score_out, frame_out, opt_b_out, opt_i_out, cells_out, ge_out, null_out, cap}, true, true);
+}
+
+double rc_ctx_anchor_host_ms(const rc_ctx *c) { return c ? c->anchorHostMs.load() : 0.0; }
 
 }  // extern "C"
 

@@ -347,6 +347,7 @@ struct rc_ctx {
   hipStream_t tree = nullptr;      // rc_fit_trees_device: 25-40 ms kernels of a driver's tree-fit thread, kept off the helper stream
   int prioLow = 0, prioHigh = 0;   // stream priorities (compute streams low, the small latency-bound work high)
   int classPrio = 0;               // priority of the class streams
+  std::atomic<double> anchorHostMs{0.0};   // host ms the context's last anchored call spent re-rooting and making its tables (rc_ctx_anchor_host_ms)
   int expMode = 0;                 // the EVD fit's exp: the host C library's algorithm and variant, if it is one the library knows (rc_refexp.h)
   std::mutex streamMutex;          // ctx_stream
   std::vector<hipStream_t> classStreams;   // k_null launches of different row-count classes, when a batch has several: these beside the run's own stream
@@ -450,6 +451,7 @@ struct rc_batch {
   enum State { EMPTY, READY, RUNNING, DONE } state = EMPTY;
   std::vector<BlockMeta> meta;
   std::vector<DevBlock> db;                  // host copies of the block headers (offsets for the accessors)
+  std::vector<TreeKeep> treeKeep;            // every block's tree as parsed, 12 bytes a node (BlockMeta::keepOff): what the anchored null re-roots
   std::map<int, std::string> errs;           // blocks that were rejected: index -> message
   std::vector<int> okBlocks;                 // batch indices with status RC_OK
   std::map<int, std::vector<int>> classes;   // class (N-1, or kGenericClass for blocks of more than 64 rows) -> batch indices
@@ -562,7 +564,9 @@ int launch_native_plan(const NativePlan &pl, const NativeArgs &base, const int *
 int occupancy(rc_ctx *c, NullKind kind, int n, size_t lds);
 // k_generic_sim<false> for a query on a finished batch (rc_batch_segment_null, rc_batch_decoys): sim.workCounter's cntWords words zeroed, then
 // `items` items of blocks of at most maxN rows and maxNodes tree nodes on as many workgroups as stay resident, codes to sim.codesAll
-int launch_sim_side(rc_ctx *c, const NullArgs &sim, long long items, int maxN, int maxNodes, size_t cntWords, hipStream_t st);
+// anchor (rc_launch.h): k_generic_sim_anchored instead, anchor[p] the tables of position p of sim.classBlocks; maxNodes counts their nodes
+int launch_sim_side(rc_ctx *c, const NullArgs &sim, long long items, int maxN, int maxNodes, size_t cntWords, hipStream_t st,
+                    const AnchorRec *anchor = nullptr);
 size_t steal_slots(const rc_ctx *c);
 size_t steal_words(const rc_ctx *c);
 // null sampling of the sample groups [gLo, gHi) of every class: what the round's plan takes -- uint32 of staging scratch, the return value,

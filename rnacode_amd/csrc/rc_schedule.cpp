@@ -101,11 +101,15 @@ int launch_native_plan(const NativePlan &pl, const NativeArgs &base, const int *
 }
 
 // k_generic_sim<false> outside a run: a query's own simulation of blocks of a finished batch
-int launch_sim_side(rc_ctx *c, const NullArgs &sim, long long items, int maxN, int maxNodes, size_t cntWords, hipStream_t st) {
+// (anchor: k_generic_sim_anchored on the call's re-rooted trees)
+int launch_sim_side(rc_ctx *c, const NullArgs &sim, long long items, int maxN, int maxNodes, size_t cntWords, hipStream_t st, const AnchorRec *anchor) {
   const size_t lds = null_generic_lds_bytes(maxN, maxNodes);
-  const int occ = std::max(1, occupancy(c, NullKind::GenericSim, 0, lds));
+  const NullKind kind = anchor ? NullKind::GenericSimAnchored : NullKind::GenericSim;
+  const int occ = std::max(1, occupancy(c, kind, 0, lds));
   HIP_TRY(hipMemsetAsync(sim.workCounter, 0, cntWords * sizeof(uint32_t), st));   // (behind the round before: one stream)
-  launch_generic(NullKind::GenericSim, sim, static_cast<int>(std::min<long long>(items, static_cast<long long>(c->numCU) * occ)), lds, sim.codesAll, st);
+  const int grid = static_cast<int>(std::min<long long>(items, static_cast<long long>(c->numCU) * occ));
+  if (anchor) { NullArgs a = sim; a.anchor = anchor; launch_generic_anchored(a, grid, lds, st); }
+  else launch_generic(NullKind::GenericSim, sim, grid, lds, sim.codesAll, st);
   HIP_TRY(hipGetLastError());
   return RC_OK;
 }

@@ -27,6 +27,14 @@ RC_SIM_HD uint32_t sim_clamps(uint32_t u, uint32_t t3) { return u > t3; }
 constexpr uint32_t kNodeMayClamp = 0x8000u;
 RC_SIM_HD bool sim_may_clamp(uint32_t t3) { return t3 != 0xFFFFFFFFu; }
 
+// The anchored null (k_generic_sim_anchored) takes the root's state from the reference row where that holds a nucleotide: the state 0..3
+// (A, C, G, T or U, either case) of a byte of the alignment, kSimNoAnchor for every other byte (N, IUPAC letters, '-': the root is drawn)
+constexpr uint32_t kSimNoAnchor = 4u;
+RC_SIM_HD uint32_t sim_anchor_state(uint32_t ch) {
+  const uint32_t c = ch & 0xDFu;   // a letter's upper case; no other byte becomes a letter
+  return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : (c == 'T' || c == 'U') ? 3u : kSimNoAnchor;
+}
+
 // a row's window takes in the state of its tip at the new column: the low 6 bits are the codon that ends there (older columns drift
 // out at the top of a 32-bit window; sim_window6 keeps only the codon)
 RC_SIM_HD uint32_t sim_window(uint32_t win, uint32_t state) { return (win << 2) | state; }

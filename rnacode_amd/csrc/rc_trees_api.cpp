@@ -292,6 +292,19 @@ int rc_species_tree_prune(const rc_species_tree *t, const rc_block *blk, char *n
   return RC_OK;
 }
 
+int rc_anchor_newick(const rc_block *blk, char *newick_out, int32_t cap) {
+  if (!blk || !blk->names || !blk->names[0] || !blk->newick || !newick_out || cap < 8) return fail(RC_ERR_ARG, "bad argument");
+  Tree t, ta;
+  std::string err;
+  if (!parse_newick(blk->newick, t, err)) return fail(RC_ERR_ARG, err);
+  int ref = -1;
+  for (int k = 0; k < t.ntips() && ref < 0; k++) if (t.tip_is(k, blk->names[0])) ref = t.tipnode[k];
+  if (ref < 0) return fail(RC_ERR_ARG, std::string("row name not found in tree: ") + blk->names[0]);
+  if (!anchor_tree(t, ref, ta)) return fail(RC_ERR_ARG, "the tree cannot be rooted at the reference tip");
+  if (!put_newick(tree_text(ta), newick_out, cap)) return fail(RC_ERR_ARG, "newick buffer too small");
+  return RC_OK;
+}
+
 int rc_fit_species_trees(const rc_species_tree *t, int32_t mode, const rc_block *blocks, int32_t n_blocks, char *newick_out, int32_t cap,
                          float *kappa_out, double *scale_out, int32_t threads) {
   if (!t || !species_mode_ok(mode) || !blocks || !newick_out || !kappa_out || n_blocks < 0 || cap < 8) return fail(RC_ERR_ARG, "bad argument");

@@ -41,6 +41,8 @@ import numpy as np
 COLUMNS_SUPPORT = ("hss", "name", "strand", "frame", "start", "end", "score", "p", "row", "row_name", "pair_score", "share", "loo_score")
 COLUMNS_NULL = ("null_ge", "p_segment")   # --regions-null: behind COLUMNS_REGIONS
 COLUMNS_SHUFFLE = ("shuffle_ge", "p_segment_shuffled", "movable")   # --regions-shuffle-null: behind COLUMNS_NULL
+COLUMNS_ANCHORED = ("anchored_ge", "p_segment_anchored")   # --regions-anchored-null: behind whichever of the two above are there
+COLUMNS_PAIR_ANCHORED = ("pair_anchored_ge", "p_pair_anchored")   # ... and in --regions-support
 COLUMNS_REGIONS = ("id", "name", "strand", "frame", "from", "to", "start", "end", "score", "p", "support", "rows")
 # --regions-support: the --support table for named segments; behind it --regions-null's pair, then --regions-shuffle-null's
 COLUMNS_REGION_SUPPORT = ("id", "name", "strand", "frame", "from", "to", "start", "end", "score", "row", "row_name", "pair_score", "share", "loo_score")
@@ -58,8 +60,8 @@ def support_header() -> str:
     return "\t".join(COLUMNS_SUPPORT) + "\n"
 
 
-def regions_header(null: bool = False, shuffle: bool = False) -> str:
-    return "\t".join(COLUMNS_REGIONS + (COLUMNS_NULL if null else ()) + (COLUMNS_SHUFFLE if shuffle else ())) + "\n"
+def regions_header(null: bool = False, shuffle: bool = False, anchored: bool = False) -> str:
+    return "\t".join(COLUMNS_REGIONS + (COLUMNS_NULL if null else ()) + (COLUMNS_SHUFFLE if shuffle else ()) + (COLUMNS_ANCHORED if anchored else ())) + "\n"
 
 
 def empirical_p(ge, n):
@@ -194,16 +196,19 @@ def support_lines(counter: int, ref_name: str, h: dict, row_names: Sequence[str]
     return out
 
 
-def region_support_header(null: bool = False, shuffle: bool = False) -> str:
-    return "\t".join(COLUMNS_REGION_SUPPORT + (COLUMNS_PAIR_NULL if null else ()) + (COLUMNS_PAIR_SHUFFLE if shuffle else ())) + "\n"
+def region_support_header(null: bool = False, shuffle: bool = False, anchored: bool = False) -> str:
+    return "\t".join(COLUMNS_REGION_SUPPORT + (COLUMNS_PAIR_NULL if null else ()) + (COLUMNS_PAIR_SHUFFLE if shuffle else ()) +
+                     (COLUMNS_PAIR_ANCHORED if anchored else ())) + "\n"
 
 
 def region_support_lines(region: Region, frame: int, c1: int, c2: int, score, row_names: Sequence[str], pairs, Delta,
-                         null: Optional[Tuple[Sequence[int], int]] = None, shuffle: Optional[Tuple[Sequence[int], int]] = None) -> List[str]:
+                         null: Optional[Tuple[Sequence[int], int]] = None, shuffle: Optional[Tuple[Sequence[int], int]] = None,
+                         anchored: Optional[Tuple[Sequence[int], int]] = None) -> List[str]:
     """The --regions-support lines of one region in one block: one per non-reference row (row_names: the block's row names, the
     reference's first).  null: (pair_ge, n) of --regions-null -- per row how many of the n null alignments have a pair score at least
     the row's own over exactly this segment --, or None: the lines without pair_null_ge and p_pair; shuffle: the same of
-    --regions-shuffle-null.  p = (ge + 1) / (n + 1), `nan` where the row's pair score is NaN."""
+    --regions-shuffle-null, anchored: the same of --regions-anchored-null, behind them.  p = (ge + 1) / (n + 1), `nan` where the row's pair
+    score is NaN."""
     p = np.ascontiguousarray(pairs, dtype=np.float32)
     nkf = np.float32(p.shape[0])
     loo = leave_one_out(p, Delta)
@@ -212,7 +217,7 @@ def region_support_lines(region: Region, frame: int, c1: int, c2: int, score, ro
     with np.errstate(invalid="ignore", over="ignore"):
         for k in range(1, p.shape[0] + 1):
             line = "%s\t%i\t%s\t%s\t%s\t%s" % (head, k, row_names[k], fmt3(p[k - 1]), fmt3(np.float32(p[k - 1] / nkf)), fmt3(loo[k - 1]))
-            for counts in (null, shuffle):
+            for counts in (null, shuffle, anchored):
                 if counts is not None:
                     ge, n = int(counts[0][k - 1]), int(counts[1])
                     line += "\t%i\tnan" % ge if np.isnan(p[k - 1]) else "\t%i\t%.3e" % (ge, (ge + 1.0) / (n + 1.0))
@@ -221,9 +226,9 @@ def region_support_lines(region: Region, frame: int, c1: int, c2: int, score, ro
 
 
 def region_line(region: Region, frame: int, c1: int, c2: int, score, p, pairs, null: Optional[Tuple[int, int]] = None,
-                shuffle: Optional[Tuple[int, int, int]] = None) -> str:
+                shuffle: Optional[Tuple[int, int, int]] = None, anchored: Optional[Tuple[int, int]] = None) -> str:
     """null: (ge, n) of --regions-null, or None: the line without the two columns; shuffle: (ge, n, movable) of --regions-shuffle-null, or
-    None: the line without the three."""
+    None: the line without the three; anchored: (ge, n) of --regions-anchored-null, behind them, or None."""
     pr = np.asarray(pairs, dtype=np.float32)
     line = "%s\t%s\t%s\t%i\t%i\t%i\t%i\t%i\t%s\t%.3e\t%i\t%i" % (region.id, region.name, region.strand, frame + 1, c1 + 1, c2 + 1, region.start,
                                                             region.end, fmt3(score), float(np.float32(p)), int((pr > 0).sum()), pr.shape[0])
@@ -233,4 +238,7 @@ def region_line(region: Region, frame: int, c1: int, c2: int, score, p, pairs, n
     if shuffle is not None:
         ge, n, movable = int(shuffle[0]), int(shuffle[1]), int(shuffle[2])
         line += "\t%i\tnan\t%i" % (ge, movable) if np.isnan(np.float32(score)) else "\t%i\t%.3e\t%i" % (ge, (ge + 1.0) / (n + 1.0), movable)
+    if anchored is not None:
+        ge, n = int(anchored[0]), int(anchored[1])
+        line += "\t%i\tnan" % ge if np.isnan(np.float32(score)) else "\t%i\t%.3e" % (ge, (ge + 1.0) / (n + 1.0))
     return line + "\n"

@@ -41,18 +41,21 @@ from .segments import MALFORMED, NO_BLOCK, OUTSIDE, Region, _int, fmt3
 COLUMNS = ("id", "name", "strand", "lo", "hi", "frame", "from", "to", "start", "end", "score", "p", "cells")
 COLUMNS_NULL = ("null_ge", "p_window")   # --windows-null: behind COLUMNS
 COLUMNS_SHUFFLE = ("shuffle_ge", "p_window_shuffled", "movable")   # --windows-shuffle-null: behind COLUMNS and COLUMNS_NULL
+COLUMNS_ANCHORED = ("anchored_ge", "p_window_anchored")   # --windows-anchored-null: behind whichever of COLUMNS_NULL and COLUMNS_SHUFFLE are there
 COLUMNS_SUMMARY = ("id", "pieces", "score", "null_ge", "p_window")
 COLUMNS_SUMMARY_SHUFFLE = ("shuffle_ge", "p_window_shuffled")      # --windows-summary with --windows-shuffle-null: behind the columns it has
 
 NO_CODON = "no whole codon inside"
 
 
-def header(null: bool = False, shuffle: bool = False) -> str:
-    return "\t".join(COLUMNS + (COLUMNS_NULL if null else ()) + (COLUMNS_SHUFFLE if shuffle else ())) + "\n"
+def header(null: bool = False, shuffle: bool = False, anchored: bool = False) -> str:
+    return "\t".join(COLUMNS + (COLUMNS_NULL if null else ()) + (COLUMNS_SHUFFLE if shuffle else ()) + (COLUMNS_ANCHORED if anchored else ())) + "\n"
 
 
-def summary_header(null: bool = True, shuffle: bool = False) -> str:
-    return "\t".join((COLUMNS_SUMMARY if null else COLUMNS_SUMMARY[:3]) + (COLUMNS_SUMMARY_SHUFFLE if shuffle else ())) + "\n"
+
+def summary_header(null: bool = True, shuffle: bool = False, anchored: bool = False) -> str:
+    return "\t".join((COLUMNS_SUMMARY if null else COLUMNS_SUMMARY[:3]) + (COLUMNS_SUMMARY_SHUFFLE if shuffle else ()) +
+                     (COLUMNS_ANCHORED if anchored else ())) + "\n"
 
 
 def read_windows(lines: Sequence[str]) -> List[Region]:
@@ -126,16 +129,19 @@ def _p_text(score, ge: int, n: int) -> str:
 
 
 def window_line(win: Region, cut_start: int, cut_end: int, frame: int, c1: int, c2: int, seg_start: int, seg_end: int, score, p, n_cells: int,
-                null: Optional[Tuple[int, int]] = None, shuffle: Optional[Tuple[int, int, int]] = None) -> str:
+                null: Optional[Tuple[int, int]] = None, shuffle: Optional[Tuple[int, int, int]] = None,
+                anchored: Optional[Tuple[int, int]] = None) -> str:
     """One --windows-out line.  frame, c1, c2: the best segment's frame and codons (0-based); seg_start / seg_end: its coordinates as the
     listing prints them (track.run_coords); null: (ge, n) of --windows-null, or None: the line without the two columns; shuffle: (ge, N,
-    movable) of --windows-shuffle-null, or None: the line without the three columns."""
+    movable) of --windows-shuffle-null, or None: the line without the three columns; anchored: (ge, n) of --windows-anchored-null, behind them."""
     line = "%s\t%s\t%s\t%i\t%i\t%i\t%i\t%i\t%i\t%i\t%s\t%.3e\t%i" % (win.id, win.name, win.strand, cut_start, cut_end, frame + 1, c1 + 1, c2 + 1,
                                                                     seg_start, seg_end, fmt3(score), float(np.float32(p)), n_cells)
     if null is not None:
         line += _p_text(score, int(null[0]), int(null[1]))
     if shuffle is not None:
         line += _p_text(score, int(shuffle[0]), int(shuffle[1])) + "\t%i" % int(shuffle[2])
+    if anchored is not None:
+        line += _p_text(score, int(anchored[0]), int(anchored[1]))
     return line + "\n"
 
 
@@ -159,11 +165,13 @@ def group_p(scores, null_rows) -> Tuple[np.float32, int, float]:
     return np.float32(score), ge, (ge + 1.0) / (g.shape[0] + 1.0)
 
 
-def summary_line(wid: str, pieces: int, score, ge: Optional[int], n: int, shuffle: Optional[Tuple[int, int]] = None) -> str:
+def summary_line(wid: str, pieces: int, score, ge: Optional[int], n: int, shuffle: Optional[Tuple[int, int]] = None,
+                 anchored: Optional[Tuple[int, int]] = None) -> str:
     """One --windows-summary line: (ge, n) of --windows-null (ge None: without those two columns), shuffle = (ge, N) of
-    --windows-shuffle-null behind them."""
-    return "%s\t%i\t%s%s%s\n" % (wid, pieces, fmt3(score), _p_text(score, int(ge), int(n)) if ge is not None else "",
-                                 _p_text(score, int(shuffle[0]), int(shuffle[1])) if shuffle is not None else "")
+    --windows-shuffle-null behind them, anchored = (ge, n) of --windows-anchored-null behind those."""
+    return "%s\t%i\t%s%s%s%s\n" % (wid, pieces, fmt3(score), _p_text(score, int(ge), int(n)) if ge is not None else "",
+                                   _p_text(score, int(shuffle[0]), int(shuffle[1])) if shuffle is not None else "",
+                                   _p_text(score, int(anchored[0]), int(anchored[1])) if anchored is not None else "")
 
 
 def _reach(vec: np.ndarray, score) -> int:
@@ -176,11 +184,12 @@ class Summary:
     floats, the element-wise fmax of the pieces' vectors (group_p's rule, a piece at a time).  n: the run's null alignments (None: no
     --windows-null); n_shuffles: --windows-shuffle-null's N (None: without it)."""
 
-    def __init__(self, n: Optional[int], n_shuffles: Optional[int] = None):
+    def __init__(self, n: Optional[int], n_shuffles: Optional[int] = None, n_anchored: Optional[int] = None):
         self.n, self.n_shuffles, self.order, self.by_id = (int(n) if n is not None else None), n_shuffles, [], {}
+        self.n_anchored = n_anchored   # --windows-anchored-null: the run's null alignments (None: without it)
 
-    def add(self, wid: str, score, null_row=None, shuffle_row=None) -> None:
-        rows = [np.array(r, dtype=np.float32) if r is not None else None for r in (null_row, shuffle_row)]
+    def add(self, wid: str, score, null_row=None, shuffle_row=None, anchored_row=None) -> None:
+        rows = [np.array(r, dtype=np.float32) if r is not None else None for r in (null_row, shuffle_row, anchored_row)]
         if wid not in self.by_id:
             self.order.append(wid)
             self.by_id[wid] = [1, np.float32(score), *rows]
@@ -194,7 +203,8 @@ class Summary:
     def lines(self) -> List[str]:
         out = []
         for wid in self.order:
-            pieces, score, vec, shf = self.by_id[wid]
+            pieces, score, vec, shf, anc = self.by_id[wid]
             out.append(summary_line(wid, pieces, score, _reach(vec, score) if vec is not None else None, self.n or 0,
-                                    (_reach(shf, score), self.n_shuffles) if shf is not None else None))
+                                    (_reach(shf, score), self.n_shuffles) if shf is not None else None,
+                                    (_reach(anc, score), self.n_anchored) if anc is not None else None))
         return out
